@@ -3,12 +3,14 @@
 solve, temperature to tracers, RK4 advection) at BASELINE config 3 — 2049x2049 nodes
 (2048x2048 cells), 16 markers per node (67.2 M tracers), T-dependent mantle model with heat.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line (rank 0).  `value` = cell-updates/s = cells * steps / time, whole job.
-Extra objects: `roofline` (matrix-free Stokes stencil, algorithmic 64 B/node/apply, timed with
-HIP events on the library's own stream) and `cpu_baseline` (the NumPy/SciPy oracle = numerically
-the reference path, on a bounded sample, rank 0 at N=1 only).
+Prints ONE JSON line (rank 0).  `value` = cell-updates/s = cells * steps / time, whole job;
+`ms_per_step` = milliseconds of one timed step.  A plain run sets up, warms up, times the K steps
+and prints the line.  --full adds the figures that take runs of their own: `roofline` (matrix-free
+Stokes stencil, algorithmic 64 B/node/apply, timed with HIP events on the library's own stream) and
+`cpu_baseline` (the NumPy/SciPy oracle = numerically the reference path, on a bounded sample, rank 0
+at N=1 only).  --dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -23,6 +25,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable
+DUMP_VALUES = 1 << 20          # --dump-outputs: values per array beyond which a fixed seeded sample is written
+DUMP_TRACERS = 1 << 18         # --dump-outputs: tracers written (a fixed seeded sample of the initial IDs)
 
 
 def build_sim(n, tracdens, seed, device, rank, world, scaling, model="mantle"):
@@ -144,6 +148,44 @@ def kernel_roofline(sim, reps):
     return out
 
 
+def stage_roofline(sim, stages, epoch_age):
+    """The marker stages of `roofline`, from the stage times of the timed steps."""
+    # marker stages against the HBM roof: algorithmic bytes of one step (this rank's tracers and nodes) over the stage's
+    # wall time (host-timed with a stream sync each side, so launch gaps are inside -- these stages are 1.7-6 ms long).
+    #   scatter  fused kernel (regular grid): positions 16 B + 7 fields 56 B (+ 4 B slot in the epoch layout) read ONCE per marker,
+    #            13 accumulator planes written and read by the finalisation + 9 result planes written per node (280 B / node);
+    #            the one-set-per-pass kernels (rectilinear grids, several target sets re-reading the positions): 136 B / marker
+    #   rk4      positions read and written, velocities written: 48 B / marker (the 32 velocity gathers per marker hit
+    #            a cache-resident window)
+    #   sort     epoch layout (one rank): key 4 B + destination 4 B + positions, temperature and slot read and written 56 B
+    #            = 64 B / marker, + the re-layout of the 10 constant columns and the index every PYLAMP_EPOCH sorts
+    #            (172 B / marker / epoch length); classic (several ranks): key pass 16 B + placement 12 B + 17 columns
+    #            and the index moved 2 x 144 B = 316 B / marker
+    _, ni_, _, nj_, _, _ = sim.ctx.local_block()
+    nt, nn = float(sim.ntrac), float(ni_ * nj_)
+
+    def stage_roof(ms, nbytes, what):
+        gbs = nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+        return {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                "algorithmic_bytes_per_step": nbytes, "ms": ms, "bytes": what}
+    roof = {}
+    epoch_len = int(os.environ.get("PYLAMP_EPOCH", "64"))
+    fused_scatter = os.environ.get("PYLAMP_SCATTER", "1") != "0"
+    if fused_scatter:
+        per_marker = 72.0 + (4.0 if epoch_age > 0 else 0.0)
+        roof["scatter"] = stage_roof(stages["ms_scatter"], per_marker * nt + 280.0 * nn,
+                                     "%d B/marker + 280 B/node (fused kernel; the reference's four trac2grid calls read 136 B/marker)" % per_marker)
+    else:
+        roof["scatter"] = stage_roof(stages["ms_scatter"], 136.0 * nt + 208.0 * nn, "136 B/marker + 208 B/node")
+    roof["rk4"] = stage_roof(stages["ms_advect"], 48.0 * nt, "48 B/marker")
+    if epoch_age > 0 and epoch_len > 0:
+        per_marker = 64.0 + 172.0 / epoch_len
+        roof["sort"] = stage_roof(stages["ms_sort"], per_marker * nt, "%.1f B/marker (epoch layout: 64 + 172 / %d)" % (per_marker, epoch_len))
+    else:
+        roof["sort"] = stage_roof(stages["ms_sort"], 316.0 * nt, "316 B/marker")
+    return roof
+
+
 def cpu_baseline(n=257, tracdens=16, steps=1):
     """The oracle (NumPy assembly + scipy spsolve + NumPy MIC) on a bounded sample."""
     from oracle import pylamp_oracle as O
@@ -164,6 +206,71 @@ def cpu_baseline(n=257, tracdens=16, steps=1):
                       "%d markers/node, %d step(s), %.1f s; the direct solve is infeasible at 2049^2" %
                       (n, n, tracdens, steps, dt),
             "steps_per_s": round(steps / dt, 5)}
+
+
+def _sample(n, k, seed):
+    """Sorted fixed seeded sample of k of range(n); all of range(n) when n <= k."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def _write_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_outputs_2d(sim, outdir, n_ids, rank, dist):
+    """--dump-outputs of the 2-D step: what the last timed step left for a caller of Simulation.step(), read back the way a
+    caller reads it -- nodal velocities, pressure and temperature (Simulation.field), the tracers' positions, temperature and
+    velocities (Simulation.tracers / tracer_velocity) and the model time -- as float64 .npy files (<= 53 MiB in all).  Fields
+    above DUMP_VALUES nodes are written at a fixed seeded sample of nodes (node_index: flat row-major indices).  The tracers
+    are those of a fixed seeded sample of the n_ids initial IDs (tracer_id), ordered by ID, so that two builds compare entry by
+    entry whatever order each keeps its tracers in.  Collective on several ranks (the field downloads all-reduce, the tracer
+    samples are gathered); rank 0 writes."""
+    from pylamp_amd.pylamp_const import IX, IZ, TR__ID, TR_TMP
+    out = {"time": np.array([sim.totaltime, sim.last["tstep"]])}
+    idx = _sample(sim.nx[0] * sim.nx[1], DUMP_VALUES, 1)
+    out["node_index"] = idx
+    for name in ("velz", "velx", "pres") + (("temp",) if sim.opt.do_heatdiff else ()):
+        out[name] = sim.field(name).ravel()[idx]
+    # injection hands out IDs from the largest initial one up (pylamp2.py:621-622, repeated once per refilled cell): the sample
+    # stays below it
+    want = np.zeros(n_ids - 1, dtype=bool)
+    want[_sample(n_ids - 1, DUMP_TRACERS, 2)] = True
+    tr_x, tr_f = sim.tracers()
+    ids = tr_f[:, TR__ID].astype(np.int64)
+    sel = np.flatnonzero((ids >= 0) & (ids < n_ids - 1))
+    sel = sel[want[ids[sel]]]
+    part = [tr_f[sel, TR__ID], tr_x[sel, IZ], tr_x[sel, IX], tr_f[sel, TR_TMP]]
+    del tr_x, tr_f, ids
+    v = sim.tracer_velocity()
+    part += [v[sel, IZ], v[sel, IX]]
+    del v
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, part)
+        part = [np.concatenate([p[k] for p in parts]) for k in range(len(part))]
+    if rank != 0:
+        return
+    o = np.lexsort((part[2], part[1], part[0]))          # by ID (position breaks a tie)
+    for name, a in zip(("tracer_id", "tracer_z", "tracer_x", "tracer_temp", "tracer_velz", "tracer_velx"), part):
+        out[name] = a[o]
+    _write_outputs(outdir, out)
+
+
+def dump_outputs_3d(A, Ah, outdir):
+    """--dump-outputs of the 3-D configuration (one rank): the resident Stokes solution (pylamp3d.solution: 4 values per node)
+    and temperature of the last timed solve pair, each at a fixed seeded sample of DUMP_VALUES entries (stokes_index /
+    temp_index: indices into the solution vectors), float64 .npy files (32 MiB in all)."""
+    from pylamp_amd import pylamp3d as P3
+    out = {}
+    for name, x, seed in (("stokes", P3.solution(A), 1), ("temp", P3.solution(Ah, heat=True), 2)):
+        i = _sample(x.size, DUMP_VALUES, seed)
+        out[name + "_index"] = i
+        out[name] = x[i]
+    _write_outputs(outdir, out)
 
 
 def layout3(world):
@@ -228,9 +335,9 @@ def bench_3d(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     cells = (n[0] - 1) * (n[1] - 1) * (n[2] - 1)
+    if args.dump_outputs:
+        dump_outputs_3d(A, Ah, args.dump_outputs)
     if rank == 0:
-        ms_s = A.apply_bench(20, True); ms_p = A.apply_bench(20, False)
-        ach = 80.0 * nb ** 3 / (ms_s * 1e-3) / 1e9          # this rank's block
         out = {"metric": "stokes_heat_3d_cell_updates_per_s", "value": round(cells * args.steps / el, 1), "unit": "cell-updates/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -238,10 +345,13 @@ def bench_3d(args):
                                       "device-resident (coefficients uploaded before, solutions left on the GPU: no PCIe in the timed region)" % tuple(n),
                           "parallelism": "1 GPU" if world == 1 else "%d x %d x %d blocks of %d^3 nodes, one-node halos exchanged axis by axis, host all-reduced dot products" % (P + (nb,)),
                           "parity": "unpinned (the reference is 2-D only)"},
-               "stokes_iterations": its, "stokes_converged": conv, "stokes_rel_residual": [float("%.3g" % r) for r in res], "heat_iterations": hits,
-               "roofline": {"kernel": "k3_apply<true> (3-D row-scaled Stokes stencil)", "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
-                            "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "algorithmic_bytes_per_launch": 80.0 * nb ** 3,
-                            "avg_launch_ms": round(ms_s, 5), "plain_operator_ms": round(ms_p, 5)}}
+               "stokes_iterations": its, "stokes_converged": conv, "stokes_rel_residual": [float("%.3g" % r) for r in res], "heat_iterations": hits}
+        if args.full:
+            ms_s = A.apply_bench(20, True); ms_p = A.apply_bench(20, False)
+            ach = 80.0 * nb ** 3 / (ms_s * 1e-3) / 1e9          # this rank's block
+            out["roofline"] = {"kernel": "k3_apply<true> (3-D row-scaled Stokes stencil)", "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "algorithmic_bytes_per_launch": 80.0 * nb ** 3,
+                               "avg_launch_ms": round(ms_s, 5), "plain_operator_ms": round(ms_p, 5)}
         if world > 1:
             hc, rc = ctx.comm_stats()
             out["comm_calls_per_step"] = {"halo_exchanges": round(hc / float(args.steps), 1), "host_allreduces": round(rc / float(args.steps), 1)}
@@ -341,8 +451,8 @@ def main():
     ap.add_argument("--config", default="2d", choices=["2d", "3d257"], help="3d257: BASELINE config 5 on one GPU (3-D Stokes + heat)")
     ap.add_argument("--grid3", dest="n3", type=int, default=257, help="nodes per side of the 3-D configuration")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (ms_per_step = their wall time / steps)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
     ap.add_argument("--grid", dest="n", type=int, default=2049, help="nodes per side (default 2049: BASELINE config 3)")
     ap.add_argument("--tracdens", type=int, default=16)
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
@@ -352,9 +462,19 @@ def main():
                          "(heat off) at the same size -- the slower-converging Stokes problem, a secondary figure")
     ap.add_argument("--transport", choices=["torch", "native"], default="torch",
                     help="N > 1: torch.distributed callbacks (default) or direct RCCL calls on the solver stream (opt-in)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--apply-reps", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: `roofline` (stencil, smoother, stream triad, the 4097^2 point) and "
+                         "`cpu_baseline` (the oracle on a bounded sample); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float64, seeded samples of the "
+                         "larger arrays, < 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
+    ap.add_argument("--apply-reps", type=int, default=50, help="with --full: launches per stencil timing of `roofline`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.config == "3d257" and args.gpus > 1:
+        ap.error("--dump-outputs: the 3-D configuration on one GPU only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
     if args.config == "3d257":
@@ -388,6 +508,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    epoch_age, _lazy = sim.layout()                          # before a dump: a tracer download re-lays the columns out
+    if args.dump_outputs:
+        dump_outputs_2d(sim, args.dump_outputs, sim.nx[0] * sim.nx[1] * args.tracdens, rank, dist)
 
     cells = (sim.nx[0] - 1) * (sim.nx[1] - 1)
     ms_per_step = 1e3 * elapsed / args.steps
@@ -401,42 +524,8 @@ def main():
         dist.all_reduce(t)
         ntrac_global = int(t.item())
     if rank == 0:
-        roof = kernel_roofline(sim, args.apply_reps)
         stage_keys = ["ms_sort", "ms_props", "ms_scatter", "ms_stokes", "ms_heat", "ms_gather", "ms_advect", "ms_total"]
         stages = {k: round(float(np.mean([r[k] for r in timed])), 3) for k in stage_keys}
-        # marker stages against the HBM roof: algorithmic bytes of one step (this rank's tracers and nodes) over the stage's
-        # wall time (host-timed with a stream sync each side, so launch gaps are inside -- these stages are 1.7-6 ms long).
-        #   scatter  fused kernel (regular grid): positions 16 B + 7 fields 56 B (+ 4 B slot in the epoch layout) read ONCE per marker,
-        #            13 accumulator planes written and read by the finalisation + 9 result planes written per node (280 B / node);
-        #            the one-set-per-pass kernels (rectilinear grids, several target sets re-reading the positions): 136 B / marker
-        #   rk4      positions read and written, velocities written: 48 B / marker (the 32 velocity gathers per marker hit
-        #            a cache-resident window)
-        #   sort     epoch layout (one rank): key 4 B + destination 4 B + positions, temperature and slot read and written 56 B
-        #            = 64 B / marker, + the re-layout of the 10 constant columns and the index every PYLAMP_EPOCH sorts
-        #            (172 B / marker / epoch length); classic (several ranks): key pass 16 B + placement 12 B + 17 columns
-        #            and the index moved 2 x 144 B = 316 B / marker
-        _, ni_, _, nj_, _, _ = sim.ctx.local_block()
-        nt, nn = float(sim.ntrac), float(ni_ * nj_)
-
-        def stage_roof(ms, nbytes, what):
-            gbs = nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            return {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                    "algorithmic_bytes_per_step": nbytes, "ms": ms, "bytes": what}
-        epoch_age, _lazy = sim.layout()
-        epoch_len = int(os.environ.get("PYLAMP_EPOCH", "64"))
-        fused_scatter = os.environ.get("PYLAMP_SCATTER", "1") != "0"
-        if fused_scatter:
-            per_marker = 72.0 + (4.0 if epoch_age > 0 else 0.0)
-            roof["scatter"] = stage_roof(stages["ms_scatter"], per_marker * nt + 280.0 * nn,
-                                         "%d B/marker + 280 B/node (fused kernel; the reference's four trac2grid calls read 136 B/marker)" % per_marker)
-        else:
-            roof["scatter"] = stage_roof(stages["ms_scatter"], 136.0 * nt + 208.0 * nn, "136 B/marker + 208 B/node")
-        roof["rk4"] = stage_roof(stages["ms_advect"], 48.0 * nt, "48 B/marker")
-        if epoch_age > 0 and epoch_len > 0:
-            per_marker = 64.0 + 172.0 / epoch_len
-            roof["sort"] = stage_roof(stages["ms_sort"], per_marker * nt, "%.1f B/marker (epoch layout: 64 + 172 / %d)" % (per_marker, epoch_len))
-        else:
-            roof["sort"] = stage_roof(stages["ms_sort"], 316.0 * nt, "316 B/marker")
         out = {
             "metric": "stokes_heat_mic_cell_updates_per_s", "value": round(value, 1), "unit": "cell-updates/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -466,8 +555,10 @@ def main():
             "stokes_error_estimate": [float("%.3g" % r["stokes"]["error_estimate"]) for r in timed],
             "heat_iterations": [r["heat"]["iterations"] for r in timed],
             "tracers_injected": [int(r["ninjected"]) for r in timed],
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = kernel_roofline(sim, args.apply_reps)
+            out["roofline"].update(stage_roofline(sim, stages, epoch_age))
         if world > 1:       # communication calls of rank 0 per timed step (halo exchanges, all-gathers, device / host all-reduces)
             out["comm_calls_per_step"] = [round(c / float(args.steps), 1) for c in comm_calls]
             # rank 0's time inside them per step: [halo exchanges incl. pack / unpack, all-gathers, device all-reduces] between HIP
@@ -476,7 +567,7 @@ def main():
             out["transport"] = ("native RCCL (ncclSend/Recv groups, ncclAllReduce on the solver stream)" if (sim.ctx.comm is not None and sim.ctx.comm.native)
                                 else "torch.distributed callbacks (%s), host-synchronous" % (dist.get_backend() if dist is not None else "-"))
             out["scaling_note"] = "no multi-GPU node was available to the build: N > 1 has only been rehearsed with virtual ranks / gloo on one GPU"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if dist is not None:

@@ -9,7 +9,9 @@ tag=${1:-rXX}
 cd /tmp && export TMPDIR=/tmp && cd "$OLDPWD"
 out=gpurun_out/profiles_$tag
 mkdir -p $out
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_kt -- python3 bench.py --steps 5 --warmup 2 > $out/${tag}_bench_line.json 2> gpurun_out/prof_kt.err
+work=$(dirname "$out")
+# --full: the recorded bench line carries `roofline` and `cpu_baseline`, the kernel statistics their kernels
+rocprofv3 --kernel-trace --stats -d $work/prof_kt -- python3 bench.py --full --steps 5 --warmup 2 > $out/${tag}_bench_line.json 2> $work/prof_kt.err
 echo "kernel trace done"
 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/prof_fetch -- python3 tools/pmc_run.py > gpurun_out/prof_fetch.log 2>&1
 echo "fetch pass done"
