@@ -48,9 +48,11 @@ typedef struct pl_solve_stats {
     double solve_ms;        /* device time of the solve (HIP events)              */
     int    operator_applies;
     int    precond_applies;
-    int    used_direct;     /* 1: the multigrid-preconditioned iteration did not converge and the banded-LU fallback for
-                             * small single-GPU systems finished the solve (indefinite systems: the reference's
-                             * free-surface stabilisation sign at the Courant step, pylamp2.py:387-405) */
+    int    used_direct;     /* 1: the banded LU of one GPU solved the system (pl_direct.hip: blocked LU, sized by the device
+                             * memory budget PYLAMP_DIRECT_MAX_GB) -- up front beyond the viscosity-contrast gate, refined with
+                             * a compensated residual, or after the multigrid-preconditioned iteration did not converge
+                             * (indefinite systems: the reference's free-surface stabilisation sign at the Courant step,
+                             * pylamp2.py:387-405) */
     int    reserved_;       /* 0 */
     double error_estimate;  /* Stokes: estimate of the relative velocity error of the returned iterate from its true residual r
                              * (the residual norm alone does not bound it: error / residual is ~10 on large smooth problems and
@@ -158,6 +160,12 @@ int  pl_stokes_get_scaling(pl_ctx* ctx, double* kcont, double* kbond);
 int  pl_stokes_apply(pl_ctx* ctx, const double* x, double* y);
 /* rhs vector of makeStokesMatrix (pylamp_stokes.py:429,490). */
 int  pl_stokes_rhs(pl_ctx* ctx, double* rhs);
+/* r = rhs - A x in double-double arithmetic from the probed entries of the operator (what A.tocsc() holds), rounded once;
+ * one rank.  The residual of the direct solve's refinement (diagnostic entry). */
+int  pl_stokes_residual_dd(pl_ctx* ctx, const double* rhs, const double* x, double* r);
+/* The last banded LU of this context: storage rows 2 kl + ku + 1, panel width, factorisation ms, triangular-solve ms (summed;
+ * timed under PYLAMP_SOLVER_TRACE only) and the number of solves.  Zeros when there is none. */
+int  pl_stokes_direct_info(pl_ctx* ctx, int* band, int* nb, double* factor_ms, double* solve_ms, int* nsolve);
 /* x = A^-1 rhs by preconditioned BiCGStab (replaces spsolve, pylamp2.py:360,394).
  * rhs == NULL uses the operator's own rhs.  x is output only (initial guess 0) unless
  * use_x0 != 0.

@@ -95,6 +95,8 @@ SIGNATURES = {
     "pl_stokes_get_scaling": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl_stokes_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl_stokes_rhs": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl_stokes_residual_dd": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "pl_stokes_direct_info": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
     "pl_stokes_solve": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int,
                                   C.POINTER(SolveStats)]),
     "pl_stokes_apply_bench": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),

@@ -247,10 +247,13 @@ double* pl_stokes_rhs_buffer_device(pl_ctx* ctx);
 int  pl_heat_solve_device(pl_ctx* ctx, const double* b_dev, double rtol, int maxit, pl_solve_stats* st,
                           double** x_out, const double* x0_dev = nullptr);
 
-// direct fallback for small systems (pl_direct.hip)
-bool pl_direct_possible(pl_ctx* ctx);
-int  pl_direct_factor(pl_ctx* ctx, const PlStokesOp& op_scaled);
+// direct solve: blocked banded LU on one GPU (pl_direct.hip)
+bool pl_direct_possible(pl_ctx* ctx);     // the small-system rule: what a solve keeps for a possible LU (hydrostatic start)
+bool pl_direct_fits(pl_ctx* ctx);         // one rank and the band within the device memory budget (PYLAMP_DIRECT_MAX_GB)
+int  pl_direct_factor(pl_ctx* ctx, const PlStokesOp& op_scaled, const PlStokesOp& op);
 int  pl_direct_solve(pl_ctx* ctx, const double* in, double* out);
+int  pl_direct_residual_dd(pl_ctx* ctx, const double* b, const double* x, double* r);
+void pl_direct_stats(pl_ctx* ctx, int* band, int* nb, double* factor_ms, double* solve_ms, int* nsolve);
 void pl_direct_free(pl_ctx* ctx);
 
 // krylov / MIC / step teardown hooks

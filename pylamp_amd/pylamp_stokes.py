@@ -106,6 +106,25 @@ class StokesOperator:
         self._ctx.check(self._ctx.lib.pl_stokes_rhs(self._ctx.handle(), _lib.dptr(r)))
         return r
 
+    def residual_dd(self, rhs, x):
+        """rhs - A x with the residual accumulated in double-double arithmetic (the direct solve's refinement residual;
+        the entries are those of tocsc()).  One rank."""
+        rhs = _lib.f64(rhs).reshape(-1); x = _lib.f64(x).reshape(-1)
+        if x.size != self.shape[0] or rhs.size != self.shape[0]:
+            raise Exception("dimension mismatch")
+        self._activate()
+        r = np.empty_like(x)
+        self._ctx.check(self._ctx.lib.pl_stokes_residual_dd(self._ctx.handle(), _lib.dptr(rhs), _lib.dptr(x), _lib.dptr(r)))
+        return r
+
+    def direct_info(self):
+        """The last banded LU on this operator's context: {"band", "nb", "factor_ms", "solve_ms", "nsolve"} (storage rows, panel
+        width; solve_ms summed over nsolve triangular-solve pairs, timed only under PYLAMP_SOLVER_TRACE); zeros when there is none."""
+        band = C.c_int(); nb = C.c_int(); fms = C.c_double(); sms = C.c_double(); ns = C.c_int()
+        self._ctx.check(self._ctx.lib.pl_stokes_direct_info(self._ctx.handle(), C.byref(band), C.byref(nb), C.byref(fms), C.byref(sms),
+                                                            C.byref(ns)))
+        return {"band": band.value, "nb": nb.value, "factor_ms": fms.value, "solve_ms": sms.value, "nsolve": ns.value}
+
     def precond(self, r):
         """z = M^-1 r of the solver's preconditioner (diagnostic; r unscaled)."""
         r = _lib.f64(r).reshape(-1)
