@@ -355,13 +355,7 @@ static int line_z_launch(pl_ctx* ctx, const PlVvOp& op, const double* v, const d
     int cols = (LZ_EPT * LZ_NT) / n; if (cols > 16) cols = 16; if (cols > nlines) cols = nlines; if (cols < 1) cols = 1;
     while (cols > 1 && (size_t)32 * n * cols > 150000) cols--;
     a.cols = cols;
-    const size_t lds = (size_t)32 * n * cols;
-    static bool lds_set = false;
-    if (!lds_set) {
-        PL_HIP(ctx, hipFuncSetAttribute((const void*)k_vv_line<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PL_HIP(ctx, hipFuncSetAttribute((const void*)k_vv_line<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        lds_set = true;
-    }
+    const size_t lds = (size_t)32 * n * cols;         // (up to 160 KB: build_hierarchy raised the kernels' limit)
     if (ax == 0) hipLaunchKernelGGL(k_vv_line<0>, dim3((nlines + cols - 1) / cols, 2), dim3(LZ_NT), lds, ctx->stream, a);
     else hipLaunchKernelGGL(k_vv_line<1>, dim3((nlines + cols - 1) / cols, 2), dim3(LZ_NT), lds, ctx->stream, a);
     return 0;
@@ -863,15 +857,78 @@ __global__ __launch_bounds__(256) void k_coarsen_visc(PlGeom gf, const double* _
 // =========================================================================================
 // Vector kernels (nplanes planes; dots over interior nodes only)
 // =========================================================================================
+#define DOT_BLOCKS 1024
+#define PL_PART_N 16            // doubles per block of the partial-sum area behind the scalars
+
+// ---- PlSolver::scal: PL_SCAL_N named device scalars, then the block partials (PL_PART_N * DOT_BLOCKS doubles) ----------------------
+// A one-value reduction through k_sum_partials into slot k also writes 0 into slot k + 1, its SHADOW (the generic kernel always
+// writes a pair).  Where a shadow slot holds a value of its own, that value must be written after the reduction: the order is
+// stated at the call site.  "Several ranks" below means a distributed level with more than one rank (the all-reduces).
+enum PlScal : int {
+    // BiCGStab, first reduction point (dots_dev) -- and the pair of sums of dots() on several ranks
+    SC_SUM_A = 0,           // r~.v (dots_dev); several ranks with the lazy deflation: r~.v_u, corrected to r~.v by k_defl_alpha_ride
+    SC_SUM_B = 1,           // shadow of SC_SUM_A; several ranks with the lazy deflation: the five-cell sum of y_u, all-reduced with it
+    SC_ALPHA = 2,           // alpha = rho / r~.v (k_sum_partials mode 1, k_scalar_alpha, k_defl_alpha_ride)
+    SC_OMEGA = 3,           // omega (bicg_derive)
+    SC_RHO = 4,             // rho of this iteration (written with alpha)
+    SC_RHO_NEXT = 5,        // rho' = r~.r of the updated residual (bicg_derive)
+    SC_RR = 6,              // |r|^2 of the updated residual (bicg_derive)
+    SC_BETA = 7,            // beta of the NEXT iteration (bicg_derive); k_xrp_update_dev writes the next direction with it
+    // second reduction point: the eight k_dot5 sums (k_sum_partials5; several ranks: k_bicg_unpack_defl corrects them)
+    SC_TS = 8, SC_TT = 9, SC_RTS = 10, SC_RTT = 11, SC_SS = 12,    // t.s, t.t, r~.s, r~.t, s.s
+    SC_TS_C = 13, SC_TT_C = 14, SC_SS_C = 15,                     // t.s, t.t, s.s over the continuity planes (planes >= nsplit)
+    // this rank's shares for the error estimate; they ride in the all-reduce of the second reduction point (SC_RED2)
+    SC_XX = 16,             // ||x_vel||^2 (norm2_sum_dev)
+    SC_YS = 17,             // y.s (ysum_dev); also the shadow of SC_XX
+    SC_YT = 18,             // y.t (ysum_dev); also the shadow of SC_YS
+    SC_YT_SHADOW = 19,      // shadow of SC_YT (unused)
+    SC_ZZ = 20,             // ||z_vel||^2 of z = M^-1 s (norm2_sum_dev)
+    SC_ZZ_SHADOW = 21,      // shadow of SC_ZZ (unused)
+    // deflation of the pressure-anchor mode (pl_stokes_solve_device)
+    SC_Y_AW = 24,           // y.(A w), the denominator (k_defl_coef mode 1; all-reduced); written by every solve that deflates before it is read
+    SC_DEFL_C = 25,         // eager correction coefficient of w (k_defl_coef mode 0, k_defl_divide), read by k_axpy_dev_scalar
+    SC_Y_IN = 26,           // y.in of the vector the preconditioner was given (ysum, k_defl_coef_lazy, k_defl_alpha_ride, k_bicg_unpack_defl)
+    SC_Y_NUM = 27,          // shadow of SC_Y_IN; several ranks: this rank's share of y.in - y.(A x) (k_defl_coef mode 2; all-reduced)
+    SC_Y_R = 28,            // y.r for the host (ysum_host)
+    SC_Y_R_SHADOW = 29,     // shadow of SC_Y_R (unused)
+    SC_CY = 30, SC_CZ = 31, // lazy coefficients of w for y and z (k_defl_coef_lazy / k_defl_alpha_ride, k_bicg_unpack_defl); read by the
+                            // operator's epilogue and by k_xrp_update_dev
+    SC_YR = 32,             // lazy recurrences (k_defl_init at a (re)start, k_defl_coef_lazy, bicg_derive): y.r -- written by ysum_dev,
+    SC_YP = 33,             // y.p -- the shadow of SC_YR: k_defl_init writes it after that reduction
+    SC_YSR = 34,            // y.s
+    SC_RT_AW = 35,          // several ranks, lazy deflation: r~.Aw (k_set3, once per solve)
+    SC_FIVE = 36,           // ... this rank's share of the five-cell sum of the last preconditioned vector (k_defl_five_local)
+    SC_AW_AW = 37,          // ... Aw.Aw (k_set3)
+    SC_AW_AW_C = 38,        // ... Aw.Aw over the continuity plane (k_set3)
+    SC_AW_S = 40, SC_AW_T = 41, SC_AW_S_C = 42, SC_AW_T_C = 43,   // ... Aw.s, Aw.t and their continuity parts (k_sum_partials4)
+    SC_STAGE = 44,          // ... all-reduce staging of the second reduction point (k_bicg_pack_defl / k_bicg_unpack_defl):
+    SC_STAGE_FIVE = 57,     //     the SC_RED2 block, SC_FIVE,
+    SC_STAGE_AW = 58,       //     SC_AW_S .. SC_AW_T_C
+    SC_STAGE_N = 18,
+    PL_SCAL_N = 64,         // named scalars in front of the block partials
+    // ranges
+    SC_DOT5 = SC_TS, SC_DOT5_N = 8,     // written by k_sum_partials5
+    SC_RED2 = SC_TS, SC_RED2_N = 13,    // all-reduced on several ranks without the lazy deflation: the k_dot5 sums and the estimate's shares
+    SC_AW_N = 4,
+};
+// block partials behind the scalars (k_dot2 / k_norm2_sum / k_defl_ysum: 2 per block, k_dot5: 8), and the k_dot4w partials (4 per block)
+// in a second area behind the k_dot5 ones; PlSolver::hpart holds the host copy of the partials, then one of the scalars at PL_HSCAL
+constexpr int SC_PART = PL_SCAL_N, SC_PART2 = PL_SCAL_N + 8 * DOT_BLOCKS, PL_HSCAL = PL_PART_N * DOT_BLOCKS;
+static_assert(SC_DOT5 == SC_RED2 && SC_DOT5 + SC_DOT5_N == SC_XX, "the all-reduced block starts with the k_dot5 sums");
+static_assert(SC_RED2 <= SC_TS && SC_SS_C < SC_RED2 + SC_RED2_N && SC_XX >= SC_RED2 && SC_ZZ < SC_RED2 + SC_RED2_N,
+              "bicg_derive and the error estimate read only all-reduced sums");
+static_assert(SC_YS == SC_XX + 1 && SC_YT == SC_YS + 1 && SC_YT_SHADOW == SC_YT + 1 && SC_ZZ_SHADOW == SC_ZZ + 1 && SC_YP == SC_YR + 1 &&
+              SC_SUM_B == SC_SUM_A + 1 && SC_Y_NUM == SC_Y_IN + 1 && SC_Y_R_SHADOW == SC_Y_R + 1, "shadow slots");
+static_assert(SC_SUM_A == 0, "k_sum_partials mode 1 writes SC_ALPHA and SC_RHO relative to its SC_SUM_A output");
+static_assert(SC_STAGE_FIVE == SC_STAGE + SC_RED2_N && SC_STAGE_AW == SC_STAGE_FIVE + 1 && SC_STAGE_N == SC_RED2_N + 1 + SC_AW_N,
+              "staging layout");
+static_assert(SC_AW_T_C == SC_AW_S + SC_AW_N - 1 && SC_AW_T_C < SC_STAGE && SC_STAGE + SC_STAGE_N <= PL_SCAL_N, "staging fits below PL_SCAL_N");
+static_assert(SC_PART2 + 4 * DOT_BLOCKS <= PL_SCAL_N + PL_PART_N * DOT_BLOCKS && 2 * DOT_BLOCKS <= PL_HSCAL,
+              "the partial areas cover the largest layout");
 // Block partials of two dot products over the interior nodes of nplanes planes:
 // part[2*b] = sum a.b, part[2*b+1] = sum c.d (either pair may be NULL).  Grid-stride over rows,
 // no atomics; the host adds the (<= DOT_BLOCKS) partials in a fixed order, so the result is
 // deterministic.
-#define DOT_BLOCKS 1024
-#define PL_SCAL_N 64            // device scalars in front of the dot partials (PlSolver::scal); 32..34: y.r, y.p, y.s of the lazy deflation;
-                                // several ranks (lazy deflation riding in the two reductions): 35 r~.Aw, 36 this rank's share of the five-cell sum,
-                                // 37 Aw.Aw, 38 the same over the continuity plane, 40..43 Aw.s, Aw.t and their continuity parts, 44..63 all-reduce staging
-#define PL_PART_N 16            // doubles per block of the partial-sum area behind the scalars
 template <bool HAS_A, bool HAS_C>
 __global__ __launch_bounds__(256) void k_dot2(PlGeom g, int nplanes, const double* __restrict__ a,
                                               const double* __restrict__ b, const double* __restrict__ cc,
@@ -954,19 +1011,19 @@ __global__ __launch_bounds__(256) void k_dot5(PlGeom g, int nplanes, int nsplit,
     __syncthreads();
     if (threadIdx.x < 8) part[8 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
 }
-// sums of the k_dot5 partials -> out[8..15] (8..12: t.s, t.t, rt.s, rt.t, s.s; 13..15: t.s, t.t, s.s of the continuity planes); derive = 1: also omega -> out[3], rho' -> out[5], |r|^2 -> out[6], next beta -> out[7]
-// (out[2] = alpha and out[4] = rho were left there by the first reduction point of the iteration)
+// sums of the k_dot5 partials -> out[SC_DOT5 ..]; derive = 1: also omega, rho', |r|^2 and the next beta
+// (SC_ALPHA and SC_RHO were left there by the first reduction point of the iteration)
 __device__ inline void bicg_derive(double* __restrict__ out) {
-    const double ts = out[8], tt = out[9], rts = out[10], rtt = out[11], ss = out[12];
+    const double ts = out[SC_TS], tt = out[SC_TT], rts = out[SC_RTS], rtt = out[SC_RTT], ss = out[SC_SS];
     const double om = (tt > 0.0) ? ts / tt : 0.0;       // t = 0: s is already the residual
-    out[3] = om; out[5] = rts - om * rtt;
+    out[SC_OMEGA] = om; out[SC_RHO_NEXT] = rts - om * rtt;
     const double rr = ss - 2.0 * om * ts + om * om * tt;
-    out[6] = rr > 0.0 ? rr : 0.0;
-    out[7] = (out[5] / out[4]) * (out[2] / om);          // beta of the NEXT iteration: (rho' / rho) (alpha / omega)
+    out[SC_RR] = rr > 0.0 ? rr : 0.0;
+    out[SC_BETA] = (out[SC_RHO_NEXT] / out[SC_RHO]) * (out[SC_ALPHA] / om);          // beta of the NEXT iteration: (rho' / rho) (alpha / omega)
     // lazy deflation (k_defl_coef_lazy): y.v = y.p and y.t = y.s hold by construction of the corrected preconditioner, hence
     // y.r' = y.s - omega y.t = (1 - omega) y.s  and  y.p' = y.r' + beta (y.p - omega y.v) = y.r' + beta (1 - omega) y.p
-    out[32] = (1.0 - om) * out[34];
-    out[33] = out[32] + out[7] * (1.0 - om) * out[33];
+    out[SC_YR] = (1.0 - om) * out[SC_YSR];
+    out[SC_YP] = out[SC_YR] + out[SC_BETA] * (1.0 - om) * out[SC_YP];
 }
 __global__ __launch_bounds__(256) void k_sum_partials5(int nb, const double* __restrict__ part, double* __restrict__ out, int derive) {
     __shared__ double sh[8][4];
@@ -981,7 +1038,7 @@ __global__ __launch_bounds__(256) void k_sum_partials5(int nb, const double* __r
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int q = 0; q < 8; q++) out[8 + q] = sh[q][0] + sh[q][1] + sh[q][2] + sh[q][3];
+        for (int q = 0; q < SC_DOT5_N; q++) out[SC_DOT5 + q] = sh[q][0] + sh[q][1] + sh[q][2] + sh[q][3];
         if (derive) bicg_derive(out);
     }
 }
@@ -1002,17 +1059,17 @@ __global__ void k_bicg_derive(double* __restrict__ out) { bicg_derive(out); }
 __global__ void k_defl_five_local(PlStokesOp op, const double* __restrict__ x, double* __restrict__ dst);
 __global__ void k_set3(double* __restrict__ a, double va, double* __restrict__ b, double vb, double* __restrict__ c, double vc) { *a = va; *b = vb; *c = vc; }
 __global__ void k_defl_alpha_ride(double* __restrict__ sc, double rho_new) {
-    const double five = sc[1];                                   // summed over the ranks next to r~.v_u
-    const double cy = (sc[24] != 0.0 && isfinite(sc[24])) ? (sc[33] + five) / sc[24] : 0.0;
-    sc[30] = cy; sc[26] = sc[33];
-    const double rtv = sc[0] + cy * sc[35];
-    sc[0] = rtv; sc[2] = rho_new / rtv; sc[4] = rho_new;
+    const double five = sc[SC_SUM_B];                            // summed over the ranks next to r~.v_u
+    const double cy = (sc[SC_Y_AW] != 0.0 && isfinite(sc[SC_Y_AW])) ? (sc[SC_YP] + five) / sc[SC_Y_AW] : 0.0;
+    sc[SC_CY] = cy; sc[SC_Y_IN] = sc[SC_YP];
+    const double rtv = sc[SC_SUM_A] + cy * sc[SC_RT_AW];
+    sc[SC_SUM_A] = rtv; sc[SC_ALPHA] = rho_new / rtv; sc[SC_RHO] = rho_new;
 }
-__global__ void k_defl_pack_first(double* __restrict__ sc) { sc[1] = sc[36]; }
+__global__ void k_defl_pack_first(double* __restrict__ sc) { sc[SC_SUM_B] = sc[SC_FIVE]; }
 // s = r - alpha (v + c_y Aw), v += c_y Aw
 __global__ void k_s_update_defl(long long n, double* __restrict__ s, const double* __restrict__ r, double* __restrict__ v, const double* __restrict__ aw,
                                 const double* __restrict__ sc) {
-    const double alpha = sc[2], cy = sc[30];
+    const double alpha = sc[SC_ALPHA], cy = sc[SC_CY];
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) { const double vv = v[k] + cy * aw[k]; v[k] = vv; s[k] = r[k] - alpha * vv; }
 }
@@ -1050,25 +1107,27 @@ __global__ __launch_bounds__(256) void k_sum_partials4(int nb, const double* __r
     __syncthreads();
     if (threadIdx.x == 0) for (int q = 0; q < 4; q++) out[q] = sh[q][0] + sh[q][1] + sh[q][2] + sh[q][3];
 }
-// staging block of the second reduction: [0..7] the k_dot5 sums, [8..12] slots 16..20, [13] five(z_u) share, [14..17] the Aw sums
+// staging block of the second reduction (SC_STAGE_N values from SC_STAGE): the SC_RED2 block, five(z_u) share, the Aw sums
+__host__ __device__ constexpr int sc_staged_aw(int slot) { return SC_STAGE_AW + (slot - SC_AW_S); }      // where an Aw sum is staged
 __global__ void k_bicg_pack_defl(double* __restrict__ sc) {
     const int k = threadIdx.x;
-    if (k < 13) sc[44 + k] = sc[8 + k];
-    else if (k == 13) sc[44 + 13] = sc[36];
-    else if (k < 18) sc[44 + k] = sc[40 + (k - 14)];
+    if (k < SC_RED2_N) sc[SC_STAGE + k] = sc[SC_RED2 + k];
+    else if (k == SC_STAGE_FIVE - SC_STAGE) sc[SC_STAGE_FIVE] = sc[SC_FIVE];
+    else if (k < SC_STAGE_N) sc[SC_STAGE + k] = sc[SC_AW_S + (k - (SC_STAGE_AW - SC_STAGE))];
 }
 __global__ void k_bicg_unpack_defl(double* __restrict__ sc) {
-    for (int k = 0; k < 13; k++) sc[8 + k] = sc[44 + k];
-    const double five = sc[44 + 13], aws = sc[44 + 14], awt = sc[44 + 15], aws_c = sc[44 + 16], awt_c = sc[44 + 17];
-    const double ys = sc[32] - sc[2] * sc[33];                   // y.s = y.r - alpha y.v, y.v = y.p
-    sc[34] = ys; sc[26] = ys;
-    const double cz = (sc[24] != 0.0 && isfinite(sc[24])) ? (ys + five) / sc[24] : 0.0;
-    sc[31] = cz;
-    sc[8] += cz * aws;                                           // t.s
-    sc[9] += 2.0 * cz * awt + cz * cz * sc[37];                  // t.t
-    sc[11] += cz * sc[35];                                       // r~.t
-    sc[13] += cz * aws_c;                                        // continuity parts
-    sc[14] += 2.0 * cz * awt_c + cz * cz * sc[38];
+    for (int k = 0; k < SC_RED2_N; k++) sc[SC_RED2 + k] = sc[SC_STAGE + k];
+    const double five = sc[SC_STAGE_FIVE], aws = sc[sc_staged_aw(SC_AW_S)], awt = sc[sc_staged_aw(SC_AW_T)],
+                 aws_c = sc[sc_staged_aw(SC_AW_S_C)], awt_c = sc[sc_staged_aw(SC_AW_T_C)];
+    const double ys = sc[SC_YR] - sc[SC_ALPHA] * sc[SC_YP];      // y.s = y.r - alpha y.v, y.v = y.p
+    sc[SC_YSR] = ys; sc[SC_Y_IN] = ys;
+    const double cz = (sc[SC_Y_AW] != 0.0 && isfinite(sc[SC_Y_AW])) ? (ys + five) / sc[SC_Y_AW] : 0.0;
+    sc[SC_CZ] = cz;
+    sc[SC_TS] += cz * aws;                                       // t.s
+    sc[SC_TT] += 2.0 * cz * awt + cz * cz * sc[SC_AW_AW];        // t.t
+    sc[SC_RTT] += cz * sc[SC_RT_AW];                             // r~.t
+    sc[SC_TS_C] += cz * aws_c;                                   // continuity parts
+    sc[SC_TT_C] += 2.0 * cz * awt_c + cz * cz * sc[SC_AW_AW_C];
     bicg_derive(sc);
 }
 
@@ -1098,10 +1157,6 @@ __global__ void k_xr_update(long long n, double* __restrict__ x, const double* _
 __global__ void k_add_inplace(long long n, double* __restrict__ x, const double* __restrict__ d) {
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) x[k] += d[k];
-}
-__global__ void k_scale(long long n, double* __restrict__ x, double a) {
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; k < n; k += (long long)gridDim.x * blockDim.x) x[k] *= a;
 }
 // seeded pseudo-random values in [-1,1) on interior nodes (shadow residual, power iteration)
 __global__ __launch_bounds__(256) void k_random_interior(PlGeom g, int nplanes, double* __restrict__ v, unsigned seed) {
@@ -1435,7 +1490,6 @@ struct MgLevel {
     bool own_rho = false;
     double* v[3] = {nullptr, nullptr, nullptr};      // rotating Chebyshev buffers (2 planes each)
     double *f = nullptr, *r = nullptr;
-    double* fe = nullptr;        // early coarse branch: R^l f of the finest level (levels 1 .. early_K-1)
     double lmax = 3.0;
     bool line_z = false;         // line relaxation instead of point Jacobi (k_vv_line): cells of this level at least 6 x wider than high (or
     int line_ax = 0;             // higher than wide) somewhere; line_ax 0: z-lines, 1: x-lines
@@ -1472,7 +1526,7 @@ struct PlSolver {
     double *r = nullptr, *rt = nullptr, *p = nullptr, *v = nullptr, *s = nullptr, *t = nullptr, *y = nullptr,
            *z = nullptr, *b = nullptr, *x = nullptr, *xb = nullptr, *dx = nullptr, *r0 = nullptr, *xh = nullptr,
            *bu = nullptr;      // bu: the unscaled right-hand side, kept where the LU solves up front (compensated residual)
-    double* scal = nullptr;     // device scalars [0..PL_SCAL_N) + dot partials [PL_SCAL_N .. PL_SCAL_N + 8*DOT_BLOCKS)
+    double* scal = nullptr;     // device scalars (PlScal) + block partials (SC_PART, SC_PART2)
     double* hpart = nullptr;    // pinned host copy of the dot partials
     int nu_pre = 2, nu_post = 2, coarse_sweeps = 12;
     int nu0_pre = -1, nu0_post = -1;                    // finest level only (PYLAMP_MG_NU0), -1: as the other levels
@@ -1485,10 +1539,6 @@ struct PlSolver {
     long long tail_knob = 0;                            // PYLAMP_MG_TAIL_NODES (0: automatic)
     long long tail_max_nodes = 33 * 33;                 // levels up to this size run in the fused tail kernel
     int min_cells = 4;                                  // coarsest grid has >= min_cells cells per side 
-    // halo policy inside the V-cycle on distributed levels: 2 = exchange before every sweep / residual /
-    // transfer (identical numerics to one rank); 1 = once per level and direction; 0 = none (slab-local
-    // smoothing with frozen zero halos; only the replicated coarse tail couples the slabs)
-    int mg_halo = 2;
     // FP32 multigrid levels: OFF by default (PYLAMP_MG_FP32=1 / pl_stokes_set_mg_precision switch them on;
     // PYLAMP_MG_FP32_NODES: smallest level, in local nodes, that is worth it -- the smaller ones are launch-latency bound).
     // Measured at 2049^2: the FP32 sweep takes 40 instead of 75 us, an iteration 1.79 instead of 2.08 ms -- but storing the
@@ -1529,20 +1579,6 @@ struct PlSolver {
     double* hc3 = nullptr;                    // several ranks: the three Chebyshev iterates of the heat solve, contiguous (one halo exchange)
     double* hc[9] = {nullptr}; double* hc_part = nullptr; int hc_nb = 0, hc_last_its = 0;      // CG work planes (wall entries of d, r, z, p, q stay 0)
     int napply = 0, nprec = 0;
-    // Early coarse branch (single rank): the levels >= early_K get R^K f -- the right-hand side itself, restricted K
-    // times -- instead of the restricted residual of level K-1, which makes them independent of the pre-smoothing of the
-    // fine levels: they run on a second stream, concurrently with it.  The coarse levels are pure launch latency
-    // (~235 us of a 730 us preconditioner application at 2049^2 with the GPU idle), the fine ones pure bandwidth.
-    // The NumPy prototype needs the same number of BiCGStab iterations either way (tools/early_coarse.py: mantle model,
-    // 129^2: 33 / 33 / 32 for K = off / 2 / 3; 257^2: 36 / 37 / 35 / 36 for off / 2 / 3 / 4).
-    // On the GPU (2049^2, K = 2 / 3 / 4) the branch costs 2-4 more iterations than the standard cycle (V(1,1) + V(3,3) smooth
-    // harder than the prototype's V(2,2), so more of what the coarse levels are asked to remove is already gone), the
-    // coarse kernels run 1.5-3 x slower while the bandwidth-bound fine kernels are in flight, and the 100 us tail kernel
-    // stays on the critical path: 74-78 ms per solve against 73-74.  OFF by default.
-    // PYLAMP_MG_EARLY=K switches it on (-1: automatic K, the first level of <= early_max_nodes nodes on large grids).
-    int early_knob = 0; long long early_max_nodes = 300000;
-    int early_K = 0;                         // decided by build_hierarchy
-    hipStream_t stream2 = nullptr; hipEvent_t ev_f = nullptr, ev_b = nullptr;
 };
 
 static PlSolver* solver_of(pl_ctx* ctx) {
@@ -1556,9 +1592,7 @@ static PlSolver* solver_of(pl_ctx* ctx) {
         if (const char* e = getenv("PYLAMP_MG_TAIL")) S->use_tail = atoi(e) != 0;
         if (const char* e = getenv("PYLAMP_MG_REPL_NODES")) { long long v = atoll(e); if (v >= 25) S->repl_max_nodes = v; }
         if (const char* e = getenv("PYLAMP_MG_TAIL_NODES")) { long long v = atoll(e); if (v >= 25 && v <= PL_TAIL_MAX_NODES) S->tail_knob = v; }
-        if (const char* e = getenv("PYLAMP_MG_HALO")) S->mg_halo = atoi(e);
         if (const char* e = getenv("PYLAMP_MG_DEEP")) S->deep = atoi(e) != 0;
-        if (const char* e = getenv("PYLAMP_MG_EARLY")) S->early_knob = atoi(e);
         if (const char* e = getenv("PYLAMP_DEFLATE")) S->defl_enable = atoi(e) != 0;
         if (const char* e = getenv("PYLAMP_STOKES_ETOL")) { const double v = atof(e); if (v >= 0.0) S->etol = v; }
         if (const char* e = getenv("PYLAMP_MG_FP32")) S->f32_enable = atoi(e) != 0;
@@ -1582,7 +1616,7 @@ static void free_levels(PlSolver* S) {
         if (L->own_visc) { (void)hipFree(L->etas); (void)hipFree(L->etan); }
         if (L->own_rho && L->rho) (void)hipFree(L->rho);
         for (double* q : {L->szz, L->szx, L->eig}) if (q) (void)hipFree(q);
-        for (double* q : {L->v[0], L->v[1], L->v[2], L->f, L->r, L->fe}) if (q) (void)hipFree(q);
+        for (double* q : {L->v[0], L->v[1], L->v[2], L->f, L->r}) if (q) (void)hipFree(q);
         for (float* q : {L->etas_f, L->etan_f, L->tab_f, L->vf[0], L->vf[1], L->vf[2], L->ff, L->rf}) if (q) (void)hipFree(q);
         pl_geom_free(L->gh);
         delete L;
@@ -1601,9 +1635,6 @@ void pl_solver_free(pl_ctx* ctx) {
     if (S->hc_part) (void)hipFree(S->hc_part);
     if (S->hc3) (void)hipFree(S->hc3);
     if (S->hpart) (void)hipHostFree(S->hpart);
-    if (S->stream2) (void)hipStreamDestroy(S->stream2);
-    if (S->ev_f) (void)hipEventDestroy(S->ev_f);
-    if (S->ev_b) (void)hipEventDestroy(S->ev_b);
     delete S;
     ctx->krylov = nullptr;
 }
@@ -1613,30 +1644,35 @@ static int dmalloc0(pl_ctx* ctx, double** p, size_t bytes) {
     PL_HIP(ctx, hipMemsetAsync(*p, 0, bytes, ctx->stream));
     return 0;
 }
+// the scalar block with its partial-sum areas, and its pinned host copy
+static int scal_alloc(pl_ctx* ctx, PlSolver* S) {
+    if (S->scal) return 0;
+    PL_TRY(dmalloc0(ctx, &S->scal, (PL_SCAL_N + PL_PART_N * DOT_BLOCKS) * sizeof(double)));
+    PL_HIP(ctx, hipHostMalloc((void**)&S->hpart, (PL_HSCAL + PL_SCAL_N) * sizeof(double)));
+    return 0;
+}
 
 // ---- BiCGStab scalars kept on the device -------------------------------------------------------------
-// alpha and omega are produced and consumed on the device (sc[0], sc[1] hold the two sums of the last
-// dots_dev call; sc[2] = alpha, sc[3] = omega): two of the three host round trips per iteration (~30 us of
-// idle GPU each) disappear; the third (rho, ||r||) stays because the host decides whether to go on.
-__global__ void k_scalar_alpha(double* __restrict__ sc, double rho_new) { sc[2] = rho_new / sc[0]; sc[4] = rho_new; }
-__global__ void k_scalar_omega(double* __restrict__ sc) { sc[3] = (sc[1] > 0.0) ? sc[0] / sc[1] : 0.0; }   // t = 0: s is already the residual
+// alpha and omega are produced and consumed on the device (SC_ALPHA, SC_OMEGA): two of the three host round trips per
+// iteration (~30 us of idle GPU each) disappear; the third (rho, ||r||) stays because the host decides whether to go on.
+__global__ void k_scalar_alpha(double* __restrict__ sc, double rho_new) { sc[SC_ALPHA] = rho_new / sc[SC_SUM_A]; sc[SC_RHO] = rho_new; }
 // y = a - alpha b
 __global__ void k_s_update_dev(long long n, double* __restrict__ y, const double* __restrict__ a, const double* __restrict__ b,
                                const double* __restrict__ sc) {
-    const double alpha = sc[2];
+    const double alpha = sc[SC_ALPHA];
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) y[k] = a[k] - alpha * b[k];
 }
 // x += alpha y + omega z ; r = s - omega t
 // x += alpha y + omega z ; r = s - omega t ; and the NEXT iteration's direction p = r + beta (p - omega v) in the same
-// pass (beta from the fused reduction, sc[7]): r is not read back, 10 instead of 13 vector passes
+// pass (beta from the fused reduction, SC_BETA): r is not read back, 10 instead of 13 vector passes
 __global__ void k_xrp_update_dev(long long n, double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
                                  double* __restrict__ r, const double* __restrict__ s, const double* __restrict__ t,
                                  double* __restrict__ p, const double* __restrict__ v, const double* __restrict__ sc,
                                  const double* __restrict__ wd, const double* __restrict__ awd) {
-    const double alpha = sc[2], omega = sc[3], beta = sc[7];
-    const double cw = wd ? alpha * sc[30] + omega * sc[31] : 0.0;      // lazy deflation: y and z stand for y + c_y w and z + c_z w
-    const double cz = awd ? sc[31] : 0.0;                              // ... and (several ranks) t for t + c_z A w
+    const double alpha = sc[SC_ALPHA], omega = sc[SC_OMEGA], beta = sc[SC_BETA];
+    const double cw = wd ? alpha * sc[SC_CY] + omega * sc[SC_CZ] : 0.0;    // lazy deflation: y and z stand for y + c_y w and z + c_z w
+    const double cz = awd ? sc[SC_CZ] : 0.0;                               // ... and (several ranks) t for t + c_z A w
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) {
         double xn = x[k] + alpha * y[k] + omega * z[k];
@@ -1650,13 +1686,13 @@ __global__ void k_xrp_update_dev(long long n, double* __restrict__ x, const doub
 __global__ void k_xr_update_dev(long long n, double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
                                 double* __restrict__ r, const double* __restrict__ s, const double* __restrict__ t,
                                 const double* __restrict__ sc) {
-    const double alpha = sc[2], omega = sc[3];
+    const double alpha = sc[SC_ALPHA], omega = sc[SC_OMEGA];
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) { x[k] += alpha * y[k] + omega * z[k]; r[k] = s[k] - omega * t[k]; }
 }
 
-// sum the block partials on the device (one workgroup): out[0], out[1]
-// mode 1 / 2 (single rank): also derive alpha = rho_new / out[0] -> out[2], resp. omega = out[0] / out[1] -> out[3]
+// sum the block partials on the device (one workgroup): out[0], out[1] -- always BOTH, so a one-value reduction into slot k also
+// writes its shadow k + 1 (see PlScal).  mode 1 (single rank, out = the scalar block): also alpha = rho_new / out[0] and rho_new
 __global__ __launch_bounds__(256) void k_sum_partials(int nb, const double* __restrict__ part, double* __restrict__ out,
                                                       int mode = 0, double rho_new = 0.0) {
     double s0 = 0.0, s1 = 0.0;
@@ -1669,8 +1705,7 @@ __global__ __launch_bounds__(256) void k_sum_partials(int nb, const double* __re
     if (threadIdx.x == 0) {
         const double a0 = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3], a1 = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
         out[0] = a0; out[1] = a1;
-        if (mode == 1) { out[2] = rho_new / a0; out[4] = rho_new; }
-        if (mode == 2) out[3] = (a1 > 0.0) ? a0 / a1 : 0.0;
+        if (mode == 1) { out[SC_ALPHA] = rho_new / a0; out[SC_RHO] = rho_new; }
     }
 }
 
@@ -1678,19 +1713,19 @@ static int dots(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const double*
                 const double* d, double* out2) {
     long long rows = (long long)g.lnz * np;
     const int nb = (int)(rows < DOT_BLOCKS ? rows : DOT_BLOCKS);
-    if (a && c) hipLaunchKernelGGL((k_dot2<true, true>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + PL_SCAL_N);
-    else if (a) hipLaunchKernelGGL((k_dot2<true, false>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + PL_SCAL_N);
-    else hipLaunchKernelGGL((k_dot2<false, true>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + PL_SCAL_N);
+    if (a && c) hipLaunchKernelGGL((k_dot2<true, true>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + SC_PART);
+    else if (a) hipLaunchKernelGGL((k_dot2<true, false>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + SC_PART);
+    else hipLaunchKernelGGL((k_dot2<false, true>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + SC_PART);
     if (ctx->nranks > 1 && pl_geom_is_dist(g)) {
         // several ranks: reduce on the device, all-reduce 2 doubles (stream-ordered over xGMI on the native transport), one 16-byte copy back
-        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + PL_SCAL_N, S->scal);
-        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal, 2));
-        PL_HIP(ctx, hipMemcpyAsync(S->hpart, S->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + SC_PART, S->scal + SC_SUM_A);
+        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_SUM_A, 2));
+        PL_HIP(ctx, hipMemcpyAsync(S->hpart, S->scal + SC_SUM_A, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         out2[0] = S->hpart[0]; out2[1] = S->hpart[1];
         return 0;
     }
-    PL_HIP(ctx, hipMemcpyAsync(S->hpart, S->scal + PL_SCAL_N, (size_t)2 * nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipMemcpyAsync(S->hpart, S->scal + SC_PART, (size_t)2 * nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     double s0 = 0.0, s1 = 0.0;
     for (int k = 0; k < nb; k++) { s0 += S->hpart[2 * k]; s1 += S->hpart[2 * k + 1]; }
@@ -1698,35 +1733,31 @@ static int dots(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const double*
     return 0;
 }
 
-// the device-scalar path needs the global sums on the device: one rank, or the native (stream-ordered) all-reduce
-static bool dots_on_device(pl_ctx* ctx, const PlGeom& g) {
-    (void)ctx; (void)g;
-    return true;       // pl_comm_allreduce_dev stages through the host on the non-native transports
-}
-// second reduction point of BiCGStab: omega -> scal[3], rho' -> scal[5], |r|^2 -> scal[6] (ONE all-reduce of 5 doubles)
+// second reduction point of BiCGStab: the SC_DOT5 sums, and from them omega, rho', |r|^2 and the next beta (bicg_derive);
+// several ranks: ONE all-reduce (SC_RED2, or the SC_STAGE block with the lazy deflation)
 static int dots5_dev(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, int nsplit, const double* t, const double* sv, const double* rt,
                      const double* aw_ride = nullptr) {
     long long rows = (long long)g.lnz * np;
     const int nb = (int)(rows < DOT_BLOCKS ? rows : DOT_BLOCKS);
-    hipLaunchKernelGGL(k_dot5, dim3(nb), dim3(256), 0, ctx->stream, g, np, nsplit, t, sv, rt, S->scal + PL_SCAL_N);
+    hipLaunchKernelGGL(k_dot5, dim3(nb), dim3(256), 0, ctx->stream, g, np, nsplit, t, sv, rt, S->scal + SC_PART);
     const bool reduce = ctx->nranks > 1 && pl_geom_is_dist(g);
-    hipLaunchKernelGGL(k_sum_partials5, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + PL_SCAL_N, S->scal, reduce ? 0 : 1);
+    hipLaunchKernelGGL(k_sum_partials5, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + SC_PART, S->scal, reduce ? 0 : 1);
     if (reduce && aw_ride) {          // lazy deflation on several ranks: its sums and the five-cell share ride in this ONE all-reduce (18 values)
-        double* part2 = S->scal + PL_SCAL_N + 8 * DOT_BLOCKS;
+        double* part2 = S->scal + SC_PART2;
         hipLaunchKernelGGL(k_dot4w, dim3(nb), dim3(256), 0, ctx->stream, g, np, nsplit, aw_ride, sv, t, part2);
-        hipLaunchKernelGGL(k_sum_partials4, dim3(1), dim3(256), 0, ctx->stream, nb, (const double*)part2, S->scal + 40);
+        hipLaunchKernelGGL(k_sum_partials4, dim3(1), dim3(256), 0, ctx->stream, nb, (const double*)part2, S->scal + SC_AW_S);
         hipLaunchKernelGGL(k_bicg_pack_defl, dim3(1), dim3(64), 0, ctx->stream, S->scal);
-        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 44, 18));
+        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_STAGE, SC_STAGE_N));
         hipLaunchKernelGGL(k_bicg_unpack_defl, dim3(1), dim3(1), 0, ctx->stream, S->scal);
         return 0;
     }
     if (reduce) {
-        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 8, 13));        // scal[16..20]: the local ||x_vel||^2, y.s, y.t, (unused) and ||z_vel||^2 ride along
+        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_RED2, SC_RED2_N));      // the local SC_XX .. SC_ZZ ride along
         hipLaunchKernelGGL(k_bicg_derive, dim3(1), dim3(1), 0, ctx->stream, S->scal);
     }
     return 0;
 }
-// ||a + b||^2 over the interior nodes of the first nplanes planes -> S->scal[0] (b may be NULL)
+// block partials of ||a + b||^2 over the interior nodes of the first nplanes planes, in k_dot2's layout (b may be NULL)
 __global__ __launch_bounds__(256) void k_norm2_sum(PlGeom g, int nplanes, const double* __restrict__ a, const double* __restrict__ b,
                                                    double* __restrict__ part) {
     double s0 = 0.0;
@@ -1743,37 +1774,31 @@ __global__ __launch_bounds__(256) void k_norm2_sum(PlGeom g, int nplanes, const 
     __syncthreads();
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3]; part[2 * blockIdx.x + 1] = 0.0; }
 }
-// -> S->scal[16] (this rank's share when reduce = false: the fused reduction of the iteration all-reduces it)
-static int norm2_sum_dev(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const double* a, const double* b, bool reduce, int slot = 16) {
+// -> S->scal[slot], and 0 into its shadow slot + 1 (this rank's share when reduce = false: the fused reduction of the iteration
+// all-reduces it)
+static int norm2_sum_dev(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const double* a, const double* b, bool reduce, int slot = SC_XX) {
     long long rows = (long long)g.lnz * np;
     const int nb = (int)(rows < DOT_BLOCKS ? rows : DOT_BLOCKS);
-    hipLaunchKernelGGL(k_norm2_sum, dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, S->scal + PL_SCAL_N);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + PL_SCAL_N, S->scal + slot, 0, 0.0);
+    hipLaunchKernelGGL(k_norm2_sum, dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, S->scal + SC_PART);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + SC_PART, S->scal + slot, 0, 0.0);
     if (reduce && ctx->nranks > 1 && pl_geom_is_dist(g)) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + slot, 2));
     return 0;
 }
-// sums of the two dot products into S->scal[0..1], no host synchronisation
-// mode 1 / 2: alpha resp. omega are derived in the same pass (see k_sum_partials); with several ranks the sums
-// are all-reduced first and a one-thread kernel derives the scalar
-static int dots_dev(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const double* a, const double* b, const double* c,
-                    const double* d, int mode, double rho_new, bool ride = false) {
+// first reduction point of BiCGStab: r~.v -> SC_SUM_A, alpha = rho_new / r~.v -> SC_ALPHA and rho_new -> SC_RHO, no host
+// synchronisation.  Several ranks: the sum is all-reduced first and a one-thread kernel derives alpha; with ride (lazy deflation)
+// the five-cell share of y_u travels in the same all-reduce
+static int dots_dev(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const double* a, const double* b, double rho_new, bool ride) {
     long long rows = (long long)g.lnz * np;
     const int nb = (int)(rows < DOT_BLOCKS ? rows : DOT_BLOCKS);
-    if (a && c) hipLaunchKernelGGL((k_dot2<true, true>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + PL_SCAL_N);
-    else if (a) hipLaunchKernelGGL((k_dot2<true, false>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + PL_SCAL_N);
-    else hipLaunchKernelGGL((k_dot2<false, true>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, c, d, S->scal + PL_SCAL_N);
+    hipLaunchKernelGGL((k_dot2<true, false>), dim3(nb), dim3(256), 0, ctx->stream, g, np, a, b, (const double*)nullptr, (const double*)nullptr,
+                       S->scal + SC_PART);
     const bool reduce = ctx->nranks > 1 && pl_geom_is_dist(g);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + PL_SCAL_N, S->scal, reduce ? 0 : mode, rho_new);
-    if (reduce && ride && mode == 1) {                  // lazy deflation on several ranks: the five-cell share of y_u travels with r~.v_u
-        hipLaunchKernelGGL(k_defl_pack_first, dim3(1), dim3(1), 0, ctx->stream, S->scal);
-        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal, 2));
-        hipLaunchKernelGGL(k_defl_alpha_ride, dim3(1), dim3(1), 0, ctx->stream, S->scal, rho_new);
-        return 0;
-    }
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + SC_PART, S->scal + SC_SUM_A, reduce ? 0 : 1, rho_new);
     if (reduce) {
-        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal, 2));
-        if (mode == 1) hipLaunchKernelGGL(k_scalar_alpha, dim3(1), dim3(1), 0, ctx->stream, S->scal, rho_new);
-        if (mode == 2) hipLaunchKernelGGL(k_scalar_omega, dim3(1), dim3(1), 0, ctx->stream, S->scal);
+        if (ride) hipLaunchKernelGGL(k_defl_pack_first, dim3(1), dim3(1), 0, ctx->stream, S->scal);
+        PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_SUM_A, 2));
+        if (ride) hipLaunchKernelGGL(k_defl_alpha_ride, dim3(1), dim3(1), 0, ctx->stream, S->scal, rho_new);
+        else hipLaunchKernelGGL(k_scalar_alpha, dim3(1), dim3(1), 0, ctx->stream, S->scal, rho_new);
     }
     return 0;
 }
@@ -1938,6 +1963,10 @@ static int build_hierarchy(pl_ctx* ctx, PlSolver* S) {
                 L->line_z = false; L->line_ax = 0;
                 if (knob == 1 || (knob < 0 && wide >= 6.0 && wide >= high)) { L->line_z = line_z_possible(ctx, nz); L->line_ax = 0; }
                 else if (knob == 2 || (knob < 0 && high >= 6.0)) { L->line_z = line_z_possible(ctx, nx); L->line_ax = 1; }
+                if (L->line_z && !S->any_line) {            // the first line level of this hierarchy: allow k_vv_line its dynamic LDS
+                    PL_HIP(ctx, hipFuncSetAttribute((const void*)k_vv_line<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    PL_HIP(ctx, hipFuncSetAttribute((const void*)k_vv_line<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                }
                 if (L->line_z) S->any_line = true;
             }
             S->levels.push_back(L);
@@ -2059,26 +2088,6 @@ static int build_hierarchy(pl_ctx* ctx, PlSolver* S) {
         L->eig_confirm = (L->eig_valid && lam_before > 0.0 && std::fabs(lam - lam_before) < 0.002 * lam) ? L->eig_confirm + 1 : 0;
     }
     PL_TRY(setup_f32_levels(ctx, S));
-    // early coarse branch: first level of at most early_max_nodes nodes, on one rank, when at least two levels lie above it
-    S->early_K = 0;
-    if (ctx->nranks == 1 && S->early_knob != 0 && !S->levels[0]->f32 && S->levels.size() > 2) {
-        int K = S->early_knob > 0 ? S->early_knob : 0;
-        if (K == 0 && (long long)ctx->nz * ctx->nx >= 1000000LL)
-            for (size_t l = 2; l < S->levels.size(); l++)
-                if ((long long)S->levels[l]->gh.d.nz * S->levels[l]->gh.d.nx <= S->early_max_nodes) { K = (int)l; break; }
-        if (K >= 1 && K + 1 <= (int)S->levels.size() - 0 && K < (int)S->levels.size() && S->nu_pre >= 1) {
-            S->early_K = K;
-            if (!S->stream2) {
-                PL_HIP(ctx, hipStreamCreateWithFlags(&S->stream2, hipStreamNonBlocking));
-                PL_HIP(ctx, hipEventCreateWithFlags(&S->ev_f, hipEventDisableTiming));
-                PL_HIP(ctx, hipEventCreateWithFlags(&S->ev_b, hipEventDisableTiming));
-            }
-            for (int l = 1; l < K; l++) {
-                MgLevel* L = S->levels[l];
-                if (!L->fe) PL_TRY(dmalloc0(ctx, &L->fe, (size_t)2 * L->gh.d.plane * sizeof(double)));
-            }
-        }
-    }
     return 0;
 }
 
@@ -2112,12 +2121,12 @@ static ExtViewT<T> ext_view(pl_ctx* ctx, const MgLevel* L, int e) {
 }
 // nsweep Chebyshev-Jacobi sweeps on level L; buf[0] is the current iterate on entry and on exit.
 // ext_first >= 0 (deep mode): sweep k runs on the block extended by ext_first - k nodes, no exchanges in here;
-// ext_first < 0: one halo exchange before every sweep that needs one (halo policy `halo`).
+// ext_first < 0: one halo exchange before every sweep that needs one.
 // final_out: the LAST sweep writes its result there -- always an FP64 Krylov vector -- times final_scale, and buf is
 // left as it was before that sweep.  Returns true when it did.
 template <typename T>
 static bool smooth(pl_ctx* ctx, MgLevel* L, T* buf[3], const T* f, int nsweep, double ratio,
-                   double* final_out = nullptr, double final_scale = 1.0, bool zero_guess = false, int halo = 2,
+                   double* final_out = nullptr, double final_scale = 1.0, bool zero_guess = false,
                    bool first_halo_valid = false, int ext_first = -1, const int* first_done_anchor = nullptr) {
     const double lmax = L->lmax, lmin = lmax / ratio;
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
@@ -2127,7 +2136,7 @@ static bool smooth(pl_ctx* ctx, MgLevel* L, T* buf[3], const T* f, int nsweep, d
         double c1, c2;
         if (k == 0) { c1 = 0.0; c2 = 1.0 / theta; }
         else { const double rho = 1.0 / (2.0 * sigma - rho_old); c1 = rho * rho_old; c2 = 2.0 * rho / delta; rho_old = rho; }
-        if (ext_first < 0 && L->dist && !(k == 0 && (zero_guess || first_halo_valid)) && (halo == 2 || (halo == 1 && k == 0)))
+        if (ext_first < 0 && L->dist && !(k == 0 && (zero_guess || first_halo_valid)))
             (void)pl_halo(ctx, L->gh.d, buf[0], 2, L->gh.d.plane);
         const ExtViewT<T> V = ext_view<T>(ctx, L, ext_first < 0 ? 0 : std::max(ext_first - k, 0));
         const long long sh = V.sh;
@@ -2220,7 +2229,7 @@ static void vcycle_fused_level(pl_ctx* ctx, PlSolver* S, size_t l, const double*
                                const PlStokesOp* sop, const double* rs, double* z);
 
 template <typename T, typename TC>
-static void coarse_correction(pl_ctx* ctx, PlSolver* S, size_t l, MgLevel* L, MgLevel* C, T* buf[3], bool deep, int npost, int hp) {
+static void coarse_correction(pl_ctx* ctx, PlSolver* S, size_t l, MgLevel* L, MgLevel* C, T* buf[3], bool deep, int npost) {
     const PlGeom& g = L->gh.d;
     T* r = LevelT<T>::r(L);
     TC* cf = LevelT<TC>::f(C);
@@ -2241,8 +2250,8 @@ static void coarse_correction(pl_ctx* ctx, PlSolver* S, size_t l, MgLevel* L, Mg
     // ---- way up.  The correction is prolonged into the halo as well -- `pe` nodes deep -- so that the post-smoothing
     // sequence needs no exchange of its own; the coarse correction must then be known (pe+1)/2 + 1 coarse nodes deep
     // (ONE exchange, none when the coarse level is replicated).
-    const int pe = deep ? npost : ((L->dist && hp == 2) ? 1 : 0);
-    if (C->dist && (deep || hp >= 1))
+    const int pe = deep ? npost : (L->dist ? 1 : 0);
+    if (C->dist)
         (void)pl_halo(ctx, C->gh.d, ec, 2, C->gh.d.plane, std::min(std::max((pe + 1) / 2 + 1, 2), std::min(PL_RING, std::min(C->gh.d.lnz, C->gh.d.lnx))));
     ExtViewT<T> V = ext_view<T>(ctx, L, pe);
     if (!deep && pe == 1) {            // legacy extension by exactly one node (no rounding: the prolongation kernel is scalar)
@@ -2253,31 +2262,6 @@ static void coarse_correction(pl_ctx* ctx, PlSolver* S, size_t l, MgLevel* L, Mg
     }
     hipLaunchKernelGGL((k_vv_prolong_add<T, TC>), grid2d(V.op.g), dim3(64, 4), 0, ctx->stream, V.op, C->gh.d, (const TC*)ec, (const T*)(buf[0] - V.sh),
                        buf[2] - V.sh);
-}
-
-// Early coarse branch (PlSolver::early_K), level l = K-1 of the fine branch: on the second stream, as soon as stage 1 has
-// written the right-hand side of level 0, restrict IT down to level K and solve there; the fine branch (this stream) has
-// meanwhile pre-smoothed levels 0 .. K-1 and now waits for the correction, which it prolongs as usual.
-static void early_coarse_branch(pl_ctx* ctx, PlSolver* S, size_t l, MgLevel* L, MgLevel* C, double* buf[3]) {
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = S->stream2;                       // everything below is enqueued on the second stream
-    (void)hipStreamWaitEvent(S->stream2, S->ev_f, 0);
-    const double* src = S->levels[0]->f;
-    for (size_t q = 1; q <= l + 1; q++) {
-        MgLevel* F = S->levels[q - 1];
-        MgLevel* Q = S->levels[q];
-        double* dst = (q == l + 1) ? Q->f : Q->fe;
-        hipLaunchKernelGGL((k_vv_restrict<double, double>), grid2d(Q->gh.d), dim3(64, 4), 0, ctx->stream, F->gh.d, Q->op, src, dst, 1.0);
-        src = dst;
-    }
-    double* ec = nullptr;
-    bool wf = false;
-    vcycle<double>(ctx, S, l + 1, C->f, &ec, &wf, nullptr, 1.0, 0, nullptr);
-    (void)hipEventRecord(S->ev_b, S->stream2);
-    ctx->stream = main_stream;
-    (void)hipStreamWaitEvent(main_stream, S->ev_b, 0);
-    hipLaunchKernelGGL((k_vv_prolong_add<double, double>), grid2d(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, C->gh.d, (const double*)ec,
-                       (const double*)buf[0], buf[2]);
 }
 
 // solves A_vv e = f(level l) approximately; result in *out (one of the level's v buffers)
@@ -2324,25 +2308,20 @@ static void vcycle(pl_ctx* ctx, PlSolver* S, size_t l, const T* f, T** out, bool
         (void)hipMemsetAsync(buf[0], 0, (size_t)2 * g.plane * sizeof(T), ctx->stream);
     if (coarsest) {
         double ratio = 0.4 * g.nz * g.nx; if (ratio < 30.0) ratio = 30.0;
-        smooth<T>(ctx, L, buf, f, coarsest_sweeps(S, g), ratio, nullptr, 1.0, true, S->mg_halo);
+        smooth<T>(ctx, L, buf, f, coarsest_sweeps(S, g), ratio, nullptr, 1.0, true);
         *out = buf[0];
         return;
     }
-    const int hp = S->mg_halo;
     int npre, npost, e_last, f_depth;
     level_nu(S, l, npre, npost);
     const bool deep = level_deep_plan(S, L, l, e_last, f_depth);
     MgLevel* C = S->levels[l + 1];
     T* r = LevelT<T>::r(L);
-    // early coarse branch: the coarse levels do not see this level's residual (see PlSolver::early_K)
-    const bool early_here = std::is_same<T, double>::value && S->early_K > 0 && (int)l + 1 == S->early_K && !L->dist;
-    if (early_here) {
-        smooth<T>(ctx, L, buf, f, npre, S->cheb_ratio, nullptr, 1.0, true, hp, false, -1, first_done_anchor);
-    } else if (deep) {
+    if (deep) {
         // ---- ONE exchange on the way down: the right-hand side, deep enough for the whole pre-smoothing sequence,
         //      the residual and (later) the post-smoothing sequence
         if (f_valid_depth < f_depth) (void)pl_halo(ctx, g, (T*)f, 2, g.plane, f_depth);
-        smooth<T>(ctx, L, buf, f, npre, S->cheb_ratio, nullptr, 1.0, true, hp, false, e_last + npre - 1, first_done_anchor);      // iterate valid e_last deep
+        smooth<T>(ctx, L, buf, f, npre, S->cheb_ratio, nullptr, 1.0, true, false, e_last + npre - 1, first_done_anchor);      // iterate valid e_last deep
         const ExtViewT<T> V = ext_view<T>(ctx, L, e_last - 1);
         if (g_vv_vec)
             hipLaunchKernelGGL((k_vv_sweep2<1, T, T>), pl_grid_rows2(V.op.g), dim3(64, 4), 0, ctx->stream, V.op, (const T*)(buf[0] - V.sh),
@@ -2351,26 +2330,24 @@ static void vcycle(pl_ctx* ctx, PlSolver* S, size_t l, const T* f, T** out, bool
             hipLaunchKernelGGL(k_vv_residual<T>, pl_grid_rows(V.op.g), dim3(64, 4), 0, ctx->stream, V.op, (const T*)(buf[0] - V.sh), f - V.sh,
                                r - V.sh, pl_row_iters(V.op.g));
     } else {
-        smooth<T>(ctx, L, buf, f, npre, S->cheb_ratio, nullptr, 1.0, true, hp, false, -1, first_done_anchor);
-        if (L->dist && hp >= 1) (void)pl_halo(ctx, g, buf[0], 2, g.plane);
+        smooth<T>(ctx, L, buf, f, npre, S->cheb_ratio, nullptr, 1.0, true, false, -1, first_done_anchor);
+        if (L->dist) (void)pl_halo(ctx, g, buf[0], 2, g.plane);
         if (g_vv_vec)
             hipLaunchKernelGGL((k_vv_sweep2<1, T, T>), pl_grid_rows2(g), dim3(64, 4), 0, ctx->stream, LevelT<T>::op(L), (const T*)buf[0], (const T*)nullptr, f,
                                r, T(0), T(0), T(1));
         else
             hipLaunchKernelGGL(k_vv_residual<T>, pl_grid_rows(g), dim3(64, 4), 0, ctx->stream, LevelT<T>::op(L), (const T*)buf[0], f, r, pl_row_iters(g));
-        if (L->dist && hp >= 1) (void)pl_halo(ctx, g, r, 2, g.plane, 2);
+        if (L->dist) (void)pl_halo(ctx, g, r, 2, g.plane, 2);
     }
     if constexpr (std::is_same<T, float>::value) {
-        if (C->f32) coarse_correction<float, float>(ctx, S, l, L, C, buf, deep, npost, hp);
-        else coarse_correction<float, double>(ctx, S, l, L, C, buf, deep, npost, hp);
+        if (C->f32) coarse_correction<float, float>(ctx, S, l, L, C, buf, deep, npost);
+        else coarse_correction<float, double>(ctx, S, l, L, C, buf, deep, npost);
     } else {
-        if (early_here) early_coarse_branch(ctx, S, l, L, C, buf);
-        else coarse_correction<double, double>(ctx, S, l, L, C, buf, deep, npost, hp);
+        coarse_correction<double, double>(ctx, S, l, L, C, buf, deep, npost);
     }
     std::swap(buf[0], buf[2]);
-    const int pe = deep ? npost : ((L->dist && hp == 2) ? 1 : 0);
-    if (deep) *wrote_final = smooth<T>(ctx, L, buf, f, npost, S->cheb_ratio, final_out, final_scale, false, hp, true, npost - 1);
-    else *wrote_final = smooth<T>(ctx, L, buf, f, npost, S->cheb_ratio, final_out, final_scale, false, hp, pe == 1);
+    if (deep) *wrote_final = smooth<T>(ctx, L, buf, f, npost, S->cheb_ratio, final_out, final_scale, false, true, npost - 1);
+    else *wrote_final = smooth<T>(ctx, L, buf, f, npost, S->cheb_ratio, final_out, final_scale, false, L->dist);
     *out = buf[0];
 }
 
@@ -3060,7 +3037,7 @@ static void cheb_coeffs(double lmax, double ratio, int n, double* c1, double* c2
     }
 }
 static bool mg_fused_level_ok(pl_ctx* ctx, const PlSolver* S, size_t l) {
-    if (!S->fused || l + 1 >= S->levels.size() || S->early_K > 0 || S->any_line) return false;
+    if (!S->fused || l + 1 >= S->levels.size() || S->any_line) return false;
     const MgLevel* L = S->levels[l];
     // several ranks: the REPLICATED levels (every rank holds and computes the whole level) run the tile kernels like one rank does --
     // they are the latency-bound ones; a level whose own or whose coarse grid is distributed keeps the staged path with its exchanges
@@ -3212,7 +3189,7 @@ static int stokes_precond_t(pl_ctx* ctx, PlSolver* S, const double* rs, double* 
         const double sig = ctx->sop.Kc / hmean, ik = 1.0 / S->kappa;            // ~ eta_min / h^2 and the typical entry of the scaled residual
         const bool range_ok = std::isfinite(sig) && sig > 0.0 && ik * std::min(1.0, sig) > 1e-30 && ik * std::max(1.0, sig) < 1e22;
         if (S->l0_mixed && S->l0_mixed_now && !S->any_line && range_ok && !L0->dist && !L0->op.szz && g_vv_vec && (g.plane % 2) == 0 && S->levels.size() > 1 && npre0 == 1 && npost0 == 1 &&
-            S->fuse_first && S->early_K == 0 && ctx->nranks == 1 && !S->levels[1]->dist && !S->levels[1]->f32) {
+            S->fuse_first && ctx->nranks == 1 && !S->levels[1]->dist && !S->levels[1]->f32) {
             MgLevel* C = S->levels[1];
             // (planes of their own, zero-initialised: the ring around the block must read as zero, which a view of an FP64 buffer
             //  that an all-FP64 solve has used before does not)
@@ -3227,16 +3204,9 @@ static int stokes_precond_t(pl_ctx* ctx, PlSolver* S, const double* rs, double* 
             hipLaunchKernelGGL(k_prec_stage1_v2<float>, rows2, bl, 0, ctx->stream, op, cls, rs, z, ff, v1f, c2, 1.0, 1.0);
             hipLaunchKernelGGL((k_vv_first2<double, float, float>), dim3(3 * rows2.x + 3 * rows2.y + 2), bl, 0, ctx->stream, L0->op, (const float*)ff, v1f, c2, 2,
                                ctx->sop.anchor_i, ctx->sop.anchor_j, ctx->sop.wall_ps);
-            static const bool r_double = getenv("PYLAMP_L0_MIXED") && atoi(getenv("PYLAMP_L0_MIXED")) == 2;      // experiment: residual kept in FP64
-            if (r_double) {
-                hipLaunchKernelGGL((k_vv_sweep2<1, double, double, float, float>), rows2, bl, 0, ctx->stream, L0->op, (const float*)v1f, (const float*)nullptr,
-                                   (const float*)ff, L0->r, 0.0, 0.0, 1.0);
-                hipLaunchKernelGGL((k_vv_restrict<double, double>), grid2d(C->gh.d), bl, 0, ctx->stream, g, C->op, (const double*)L0->r, C->f, 1.0);
-            } else {
             hipLaunchKernelGGL((k_vv_sweep2<1, double, float, float, float>), rows2, bl, 0, ctx->stream, L0->op, (const float*)v1f, (const float*)nullptr,
                                (const float*)ff, rf, 0.0, 0.0, 1.0f);
             hipLaunchKernelGGL((k_vv_restrict<float, double>), grid2d(C->gh.d), bl, 0, ctx->stream, g, C->op, (const float*)rf, C->f, 1.0);
-            }
             double* ec = nullptr; bool wf = false;
             vcycle<double>(ctx, S, 1, C->f, &ec, &wf, nullptr, 1.0, 0, nullptr);
             // (Round 3: prolongation + correction + post-sweep in ONE kernel -- v never written, P e evaluated in registers from the coarse
@@ -3260,7 +3230,6 @@ static int stokes_precond_t(pl_ctx* ctx, PlSolver* S, const double* rs, double* 
     } else
         hipLaunchKernelGGL(k_prec_stage1<T>, pl_grid_rows(op.g), dim3(64, 4), 0, ctx->stream, op, V.op, rs - V.sh, z - V.sh, f0 - V.sh,
                            pl_row_iters(op.g), fscale);
-    if (S->early_K > 0 && !f32) (void)hipEventRecord(S->ev_f, ctx->stream);        // level 0's right-hand side is complete
     T* e = nullptr;
     bool wrote = false;
     const bool direct = S->levels.size() > 1 && S->nu_post > 0;     // last sweep writes into z
@@ -3351,14 +3320,14 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
         PL_HIP(ctx, hipMemsetAsync(w.rt, 0, bytes, ctx->stream));
         hipLaunchKernelGGL(k_random_interior, grid2d(g), dim3(64, 4), 0, ctx->stream, g, np, w.rt, 1234u);
     }
-    const bool on_device = dots_on_device(ctx, g) && !getenv("PYLAMP_HOST_SCALARS");
+    const bool on_device = !getenv("PYLAMP_HOST_SCALARS");
     // lazy deflation on several ranks: its coefficients ride in the two reductions of an iteration (k_defl_alpha_ride ...)
     const bool ride = S->defl_lazy && S->defl_active && np == 3 && M && on_device && ctx->nranks > 1 && pl_geom_is_dist(g);
     if (ride) {                                          // r~.Aw, Aw.Aw and its continuity part: constant during this solve
         double c1[2], c2[2];
         PL_TRY(dots(ctx, S, g, 3, w.rt, S->Awdefl, S->Awdefl, S->Awdefl, c1));
         PL_TRY(dots(ctx, S, g, 1, S->Awdefl + 2 * g.plane, S->Awdefl + 2 * g.plane, nullptr, nullptr, c2));
-        hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, ctx->stream, S->scal + 35, c1[0], S->scal + 37, c1[1], S->scal + 38, c2[0]);
+        hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, ctx->stream, S->scal + SC_RT_AW, c1[0], S->scal + SC_AW_AW, c1[1], S->scal + SC_AW_AW_C, c2[0]);
     }
     static const bool trace = getenv("PYLAMP_SOLVER_TRACE") != nullptr;        // residual history on stderr
     int it = 0, restarts = 0;
@@ -3401,17 +3370,18 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
         if (anchor_term) e += std::fabs(yr / S->defl_yAw) * std::sqrt(S->defl_wvel2 / xx);
         return e;
     };
-    auto ysum_dev = [&](const double* rp, double* out_slot) {       // y . r over the continuity rows -> *out_slot (this rank's share)
+    // y . r over the continuity rows -> scal[slot] (this rank's share), and 0 into its shadow slot + 1
+    auto ysum_dev = [&](const double* rp, int slot) {
         const int nb = g.lnz < DOT_BLOCKS ? g.lnz : DOT_BLOCKS;
-        hipLaunchKernelGGL(k_defl_ysum, dim3(nb), dim3(256), 0, ctx->stream, ctx->sop, rp, S->scal + PL_SCAL_N);
-        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + PL_SCAL_N, out_slot, 0, 0.0);
+        hipLaunchKernelGGL(k_defl_ysum, dim3(nb), dim3(256), 0, ctx->stream, ctx->sop, rp, S->scal + SC_PART);
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + SC_PART, S->scal + slot, 0, 0.0);
     };
     auto ysum_host = [&](const double* rp, double& yr) -> int {     // the same, reduced over the ranks, on the host
-        ysum_dev(rp, S->scal + 28);
-        if (ctx->nranks > 1 && pl_geom_is_dist(g)) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 28, 1));
-        PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_PART_N * DOT_BLOCKS, S->scal + 28, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        ysum_dev(rp, SC_Y_R);
+        if (ctx->nranks > 1 && pl_geom_is_dist(g)) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_Y_R, 1));
+        PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_HSCAL, S->scal + SC_Y_R, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        yr = S->hpart[PL_PART_N * DOT_BLOCKS];
+        yr = S->hpart[PL_HSCAL];
         return 0;
     };
     bool resume = false;                            // continue the running iteration instead of restarting it
@@ -3434,8 +3404,8 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
             set_kappa(rnorm);
             broke = false;
             if (S->defl_lazy && S->defl_active && np == 3 && M) {       // y.r of the (re)start residual; p = r
-                ysum_dev(w.r + 2 * g.plane, S->scal + 32);
-                if (ride) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 32, 1));
+                ysum_dev(w.r + 2 * g.plane, SC_YR);                     // (clears SC_YP, which k_defl_init then sets)
+                if (ride) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_YR, 1));
                 hipLaunchKernelGGL(k_defl_init, dim3(1), dim3(1), 0, ctx->stream, S->scal);
             }
         }
@@ -3451,12 +3421,12 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
             const double* zv = w.s;
             if (on_device) {
                 // alpha, omega stay on the device; a breakdown (rt.v = 0) shows up as a non-finite alpha / ||r|| below
-                PL_TRY(dots_dev(ctx, S, g, np, w.rt, w.v, nullptr, nullptr, 1, rho_new, ride));
+                PL_TRY(dots_dev(ctx, S, g, np, w.rt, w.v, rho_new, ride));
                 if (ride) hipLaunchKernelGGL(k_s_update_defl, grid1d(n), dim3(256), 0, ctx->stream, n, w.s, (const double*)w.r, w.v, (const double*)S->Awdefl, (const double*)S->scal);
                 else hipLaunchKernelGGL(k_s_update_dev, grid1d(n), dim3(256), 0, ctx->stream, n, w.s, w.r, w.v, S->scal);
                 if (M) { PL_TRY((*M)(w.s, w.z)); zv = w.z; }
                 PL_TRY(A(zv, w.t));
-                // near the end: ||x_vel||^2 for the error estimate (-> scal[16]; of the iterate BEFORE this update, so that
+                // near the end: ||x_vel||^2 for the error estimate (-> SC_XX; of the iterate BEFORE this update, so that
                 // it can ride along in the fused reduction -- the estimate needs it to ~10 %)
                 const bool want_xx = use_est && rnorm <= 1e3 * tol * bnorm;
                 // (warm start: ||x0_vel|| stands for ||x_vel|| in the per-iteration estimate -- they differ by the relative size of the
@@ -3465,11 +3435,12 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
                 // (the amplification moves slowly: measured in the first two late iterations, then in every third)
                 const bool amom_now = want_xx && M && (amom_count < 2 || amom_count % 3 == 0);
                 if (want_xx && M) amom_count++;
-                if (amom_now) PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, zv, nullptr, false, 20));      // ||z_vel||^2 of z = M^-1 s -> scal[20] (k_sum_partials also clears the slot behind its target: 19 belongs to y.t)
-                const bool y_recur = S->defl_lazy && S->defl_active && np == 3 && M;       // y.r of the updated residual comes out of bicg_derive (sc[32])
+                if (amom_now) PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, zv, nullptr, false, SC_ZZ));      // ||z_vel||^2 of z = M^-1 s
+                const bool y_recur = S->defl_lazy && S->defl_active && np == 3 && M;       // y.r of the updated residual comes out of bicg_derive (SC_YR)
                 if (want_xx && anchor_term && !y_recur) {            // y.r of the updated residual = y.s - omega y.t: both ride in the reduction as well
-                    ysum_dev(w.s + (long long)np_vel * g.plane, S->scal + 17);
-                    ysum_dev(w.t + (long long)np_vel * g.plane, S->scal + 18);
+                    // (in this order, after SC_XX: each reduction clears the slot behind its own; SC_YS is the shadow of SC_XX, SC_YT of SC_YS)
+                    ysum_dev(w.s + (long long)np_vel * g.plane, SC_YS);
+                    ysum_dev(w.t + (long long)np_vel * g.plane, SC_YT);
                 }
                 PL_TRY(dots5_dev(ctx, S, g, np, use_est ? np_vel : np, w.t, w.s, w.rt, ride ? (const double*)S->Awdefl : (const double*)nullptr));       // omega, rho' and |r|^2 from ONE reduction
                 // ... and the next direction in the same pass (the host's beta above is then only the breakdown test)
@@ -3480,19 +3451,19 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
                     p_fused = true;
                 } else            // no preconditioner: y IS p
                     hipLaunchKernelGGL(k_xr_update_dev, grid1d(n), dim3(256), 0, ctx->stream, n, dx, yv, zv, w.r, w.s, w.t, S->scal);
-                double* hs = S->hpart + PL_PART_N * DOT_BLOCKS;
+                double* hs = S->hpart + PL_HSCAL;
                 PL_HIP(ctx, hipMemcpyAsync(hs, S->scal, PL_SCAL_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
                 PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 rho = rho_new;
-                alpha = hs[2]; omega = hs[3];
-                rho_new = hs[5]; rnorm = std::sqrt(hs[6]);
+                alpha = hs[SC_ALPHA]; omega = hs[SC_OMEGA];
+                rho_new = hs[SC_RHO_NEXT]; rnorm = std::sqrt(hs[SC_RR]);
                 if (!std::isfinite(alpha)) { broke = true; break; }
                 if (amom_now) {
-                    const double ss_mom = hs[12] - hs[15];
-                    if (ss_mom > 0.0 && hs[20] > 0.0) { a_mom = std::min(std::max(std::sqrt(hs[20] / ss_mom), 1.0), n_amp * n_amp); a_mom_measured = true; }
+                    const double ss_mom = hs[SC_SS] - hs[SC_SS_C];
+                    if (ss_mom > 0.0 && hs[SC_ZZ] > 0.0) { a_mom = std::min(std::max(std::sqrt(hs[SC_ZZ] / ss_mom), 1.0), n_amp * n_amp); a_mom_measured = true; }
                 }
-                if (want_xx) est_rec = estimate(hs[15] - 2.0 * omega * hs[13] + omega * omega * hs[14], hs[6], xx_guess > 0.0 ? xx_guess : hs[16],
-                                                y_recur ? hs[32] : hs[17] - omega * hs[18]);
+                if (want_xx) est_rec = estimate(hs[SC_SS_C] - 2.0 * omega * hs[SC_TS_C] + omega * omega * hs[SC_TT_C], hs[SC_RR], xx_guess > 0.0 ? xx_guess : hs[SC_XX],
+                                                y_recur ? hs[SC_YR] : hs[SC_YS] - omega * hs[SC_YT]);
                 else est_rec = 0.0;
             } else {
                 PL_TRY(dots(ctx, S, g, np, w.rt, w.v, nullptr, nullptr, d2));
@@ -3516,9 +3487,9 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
                     double dc[2];
                     PL_TRY(dots(ctx, S, g, np - np_vel, w.r + (long long)np_vel * g.plane, w.r + (long long)np_vel * g.plane, nullptr, nullptr, dc));
                     PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, dx, dx != x ? (const double*)x : (const double*)nullptr, true));
-                    PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_PART_N * DOT_BLOCKS, S->scal + 16, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                    PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_HSCAL, S->scal + SC_XX, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
                     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    const double xxh = S->hpart[PL_PART_N * DOT_BLOCKS];
+                    const double xxh = S->hpart[PL_HSCAL];
                     double yr = 0.0;
                     if (anchor_term) PL_TRY(ysum_host(w.r + (long long)np_vel * g.plane, yr));
                     est_rec = estimate(dc[0], d2[1], xxh, yr);
@@ -3563,10 +3534,10 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
                 PL_TRY(dots(ctx, S, g, np_vel, w.z, w.z, nullptr, nullptr, dz));
             }
             PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, dx, dx != x ? (const double*)x : (const double*)nullptr, true));
-            PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_PART_N * DOT_BLOCKS, S->scal + 16, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_HSCAL, S->scal + SC_XX, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
             est_checks++;
-            const double xx = S->hpart[PL_PART_N * DOT_BLOCKS];
+            const double xx = S->hpart[PL_HSCAL];
             if (xx_guess > 0.0 && xx > 0.0) xx_guess = xx;               // (the exact norm of this iterate from here on)
             const double rc = dc[0] > 0.0 ? dc[0] : 0.0, rm = true_norm * true_norm - rc;
             if (!exact) dz[0] = a_mom * a_mom * (rm > 0.0 ? rm : 0.0);            // the response the last iteration measured, scaled to this residual
@@ -3617,10 +3588,7 @@ static int stokes_alloc(pl_ctx* ctx, PlSolver* S) {
     size_t vb = (size_t)3 * ctx->geom.d.plane * sizeof(double);
     for (double** q : {&S->r, &S->rt, &S->p, &S->v, &S->s, &S->t, &S->y, &S->z, &S->b, &S->x, &S->xb, &S->dx, &S->r0})
         PL_TRY(dmalloc0(ctx, q, vb));
-    if (!S->scal) {
-        PL_TRY(dmalloc0(ctx, &S->scal, (PL_SCAL_N + PL_PART_N * DOT_BLOCKS) * sizeof(double)));
-        PL_HIP(ctx, hipHostMalloc((void**)&S->hpart, (PL_PART_N * DOT_BLOCKS + PL_SCAL_N) * sizeof(double)));
-    }
+    PL_TRY(scal_alloc(ctx, S));
     return 0;
 }
 
@@ -3669,25 +3637,25 @@ __global__ __launch_bounds__(256) void k_defl_ysum(PlStokesOp op, const double* 
     __syncthreads();
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3]; part[2 * blockIdx.x + 1] = 0.0; }
 }
-// y . (D_r A x) from the five cells without a continuity row.  mode 1: sc[24] = y.(A x) (the denominator, x = w);
-// mode 0: sc[25] = (sc[26] - y.(A x)) / sc[24]  (sc[26] = y . r, x = z); mode 2 + k_defl_divide: the same with an all-reduce in between
+// y . (D_r A x) from the five cells without a continuity row.  mode 1: SC_Y_AW = y.(A x) (the denominator, x = w);
+// mode 0: SC_DEFL_C = (SC_Y_IN - y.(A x)) / SC_Y_AW  (SC_Y_IN = y . r, x = z); mode 2 + k_defl_divide: the same with an all-reduce in between
 __device__ inline double defl_five_cells(const PlStokesOp& op, const double* __restrict__ x);
-// lazy correction (one rank): sc[slot] = (y.in - y.(A x)) / sc[24] for x = M^-1 in.  y.in is NOT reduced: the corrected
-// preconditioner makes y.(A M~^-1 r) = y.r an identity, so y.p and y.s follow from scalar recurrences (sc[32] = y.r, sc[33] = y.p,
-// sc[34] = y.s; initialised by k_defl_init at every (re)start, advanced here and in bicg_derive) -- no pass over the vector
+// lazy correction (one rank): sc[slot] = (y.in - y.(A x)) / SC_Y_AW for x = M^-1 in.  y.in is NOT reduced: the corrected
+// preconditioner makes y.(A M~^-1 r) = y.r an identity, so y.p and y.s follow from scalar recurrences (SC_YR, SC_YP, SC_YSR;
+// initialised by k_defl_init at every (re)start, advanced here and in bicg_derive) -- no pass over the vector
 __global__ void k_defl_coef_lazy(PlStokesOp op, const double* __restrict__ x, double* __restrict__ sc, int slot, int for_s) {
-    double yin = sc[33];                                        // in = p
-    if (for_s) { yin = sc[32] - sc[2] * sc[33]; sc[34] = yin; }  // in = s = r - alpha v,  y.v = y.p
+    double yin = sc[SC_YP];                                                  // in = p
+    if (for_s) { yin = sc[SC_YR] - sc[SC_ALPHA] * sc[SC_YP]; sc[SC_YSR] = yin; }   // in = s = r - alpha v,  y.v = y.p
     const double yAx = -defl_five_cells(op, x);
-    sc[26] = yin;
-    sc[slot] = (sc[24] != 0.0 && isfinite(sc[24])) ? (yin - yAx) / sc[24] : 0.0;
+    sc[SC_Y_IN] = yin;
+    sc[slot] = (sc[SC_Y_AW] != 0.0 && isfinite(sc[SC_Y_AW])) ? (yin - yAx) / sc[SC_Y_AW] : 0.0;
 }
-__global__ void k_defl_init(double* __restrict__ sc) { sc[33] = sc[32]; sc[34] = sc[32]; }     // p = r at a (re)start
+__global__ void k_defl_init(double* __restrict__ sc) { sc[SC_YP] = sc[SC_YR]; sc[SC_YSR] = sc[SC_YR]; }     // p = r at a (re)start
 __global__ void k_defl_coef(PlStokesOp op, const double* __restrict__ x, double* __restrict__ sc, int mode) {
     const double yAx = -defl_five_cells(op, x);
-    if (mode == 1) sc[24] = yAx;                                                                  // (this rank's share on several ranks)
-    else if (mode == 2) sc[27] = sc[26] - yAx;                                                    // this rank's share of the numerator
-    else sc[25] = (sc[24] != 0.0 && isfinite(sc[24])) ? (sc[26] - yAx) / sc[24] : 0.0;
+    if (mode == 1) sc[SC_Y_AW] = yAx;                                                             // (this rank's share on several ranks)
+    else if (mode == 2) sc[SC_Y_NUM] = sc[SC_Y_IN] - yAx;                                         // this rank's share of the numerator
+    else sc[SC_DEFL_C] = (sc[SC_Y_AW] != 0.0 && isfinite(sc[SC_Y_AW])) ? (sc[SC_Y_IN] - yAx) / sc[SC_Y_AW] : 0.0;
 }
 __device__ inline double defl_five_cells(const PlStokesOp& op, const double* __restrict__ x) {
     const PlGeom& g = op.g;
@@ -3705,9 +3673,10 @@ __device__ inline double defl_five_cells(const PlStokesOp& op, const double* __r
     return five;
 }
 __global__ void k_defl_five_local(PlStokesOp op, const double* __restrict__ x, double* __restrict__ dst) { *dst = defl_five_cells(op, x); }
-__global__ void k_defl_divide(double* __restrict__ sc) { sc[25] = (sc[24] != 0.0 && isfinite(sc[24])) ? sc[27] / sc[24] : 0.0; }
-__global__ void k_axpy_dev_scalar(long long n, double* __restrict__ z, const double* __restrict__ w, const double* __restrict__ sc) {
-    const double a = sc[0];
+__global__ void k_defl_divide(double* __restrict__ sc) { sc[SC_DEFL_C] = (sc[SC_Y_AW] != 0.0 && isfinite(sc[SC_Y_AW])) ? sc[SC_Y_NUM] / sc[SC_Y_AW] : 0.0; }
+// z += a w, a read on the device
+__global__ void k_axpy_dev_scalar(long long n, double* __restrict__ z, const double* __restrict__ w, const double* __restrict__ a_dev) {
+    const double a = *a_dev;
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) z[k] += a * w[k];
 }
@@ -3746,13 +3715,13 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
     S->napply = 0; S->nprec = 0;
     S->l0_mixed_now = rtol >= 1e-8 && use_x0;                // warm-started solves of a time loop (see stokes_precond_t)
     // one rank with the scalars on the device: the deflation correction is applied lazily (PlSolver::Awdefl)
-    S->defl_lazy = dots_on_device(ctx, g) && !getenv("PYLAMP_HOST_SCALARS") &&
+    S->defl_lazy = !getenv("PYLAMP_HOST_SCALARS") &&
                    !(getenv("PYLAMP_DEFL_LAZY") && atoi(getenv("PYLAMP_DEFL_LAZY")) == 0);
     VecOp A = [&](const double* in, double* out) -> int {
         PL_TRY(pl_halo(ctx, g, (double*)in, 3, g.plane));
         // y = D_r A x in one pass; for a vector the preconditioner has just produced: + c A w (its lazy deflation correction)
         if (S->defl_lazy && S->defl_active && ctx->nranks == 1 && (in == S->y || in == S->z))
-            pl_launch_stokes_apply(ctx, sop_scaled, in, out, S->Awdefl, S->scal + (in == S->y ? 30 : 31));
+            pl_launch_stokes_apply(ctx, sop_scaled, in, out, S->Awdefl, S->scal + (in == S->y ? SC_CY : SC_CZ));
         else pl_launch_stokes_apply(ctx, sop_scaled, in, out);
         S->napply++;
         return 0;
@@ -3762,23 +3731,23 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
         PL_TRY(stokes_precond(ctx, S, in, out));
         if (S->defl_active) {                               // z += w y.(r - A z) / y.(A w), all scalars on the device
             if (S->defl_lazy && ctx->nranks > 1 && (out == S->y || out == S->z)) {   // several ranks: this rank's share of the five-cell sum; it rides in
-                hipLaunchKernelGGL(k_defl_five_local, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)out, S->scal + 36);      // the reduction that follows
+                hipLaunchKernelGGL(k_defl_five_local, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)out, S->scal + SC_FIVE);   // the reduction that follows
                 return 0;
             }
             if (S->defl_lazy && (out == S->y || out == S->z)) {       // the coefficient only: A and the iterate update do the rest
-                hipLaunchKernelGGL(k_defl_coef_lazy, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)out, S->scal, out == S->y ? 30 : 31, out == S->z ? 1 : 0);
+                hipLaunchKernelGGL(k_defl_coef_lazy, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)out, S->scal, out == S->y ? SC_CY : SC_CZ, out == S->z ? 1 : 0);
                 return 0;
             }
             const int nb = g.lnz < DOT_BLOCKS ? g.lnz : DOT_BLOCKS;
-            hipLaunchKernelGGL(k_defl_ysum, dim3(nb), dim3(256), 0, ctx->stream, sop, in + 2 * g.plane, S->scal + PL_SCAL_N);
-            hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + PL_SCAL_N, S->scal + 26, 0, 0.0);
+            hipLaunchKernelGGL(k_defl_ysum, dim3(nb), dim3(256), 0, ctx->stream, sop, in + 2 * g.plane, S->scal + SC_PART);
+            hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, nb, S->scal + SC_PART, S->scal + SC_Y_IN, 0, 0.0);   // (clears SC_Y_NUM)
             if (ctx->nranks > 1) {                          // one scalar per application: y.r and the five cells live on different ranks
                 hipLaunchKernelGGL(k_defl_coef, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)out, S->scal, 2);
-                PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 27, 1));
+                PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_Y_NUM, 1));
                 hipLaunchKernelGGL(k_defl_divide, dim3(1), dim3(1), 0, ctx->stream, S->scal);
             } else
                 hipLaunchKernelGGL(k_defl_coef, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)out, S->scal, 0);
-            hipLaunchKernelGGL(k_axpy_dev_scalar, grid1d(n3v), dim3(256), 0, ctx->stream, n3v, out, (const double*)S->wdefl, (const double*)(S->scal + 25));
+            hipLaunchKernelGGL(k_axpy_dev_scalar, grid1d(n3v), dim3(256), 0, ctx->stream, n3v, out, (const double*)S->wdefl, (const double*)(S->scal + SC_DEFL_C));
         }
         return 0;
     };
@@ -3806,7 +3775,7 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
         const bool reuse = S->defl_valid && q < std::max(0.5, q_refresh);
         if (reuse) {                                        // denominator y.(A w) of the old w under the new coefficients
             hipLaunchKernelGGL(k_defl_coef, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)S->wdefl, S->scal, 1);
-            if (ctx->nranks > 1) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 24, 1));
+            if (ctx->nranks > 1) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_Y_AW, 1));
             S->defl_active = true;
         }
         if (!reuse || q > q_refresh) {
@@ -3816,7 +3785,7 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
             S->defl_valid = st2.rel_residual < 0.05 && std::isfinite(st2.rel_residual);
             if (S->defl_valid) {
                 hipLaunchKernelGGL(k_defl_coef, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)S->wdefl, S->scal, 1);
-                if (ctx->nranks > 1) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + 24, 1));
+                if (ctx->nranks > 1) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_Y_AW, 1));
                 S->defl_active = false;                     // (A below must not take w for a preconditioned vector)
                 PL_TRY(A(S->wdefl, S->Awdefl));
             }
@@ -3827,9 +3796,9 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
         double dw[2];
         PL_TRY(dots(ctx, S, g, 2, S->wdefl, S->wdefl, nullptr, nullptr, dw));
         S->defl_wvel2 = dw[0];
-        PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_PART_N * DOT_BLOCKS, S->scal + 24, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_HSCAL, S->scal + SC_Y_AW, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        S->defl_yAw = S->hpart[PL_PART_N * DOT_BLOCKS];
+        S->defl_yAw = S->hpart[PL_HSCAL];
     }
     if (trace_t) tph[2] = now();
     // Viscosity contrast beyond the validated envelope (smooth variations over 1e3..1e6, jumps of 1e3): the row scaling divides a
@@ -4018,7 +3987,7 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
             PL_HIP(ctx, hipMemcpyAsync(S->x, S->xh, (size_t)3 * g.plane * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         else PL_HIP(ctx, hipMemsetAsync(S->x, 0, (size_t)3 * g.plane * sizeof(double), ctx->stream));
         hipLaunchKernelGGL(k_close_constraints, grid2d(g), dim3(64, 4), 0, ctx->stream, sop, S->levels[0]->op, S->b, S->x);
-        // MD never computes the lazy deflation coefficients (scal[30], scal[31]): with the deflation left active, A and the iterate
+        // MD never computes the lazy deflation coefficients (SC_CY, SC_CZ): with the deflation left active, A and the iterate
         // update would keep adding stale -- after a breakdown possibly non-finite -- multiples of w.  The LU needs no deflation.
         const bool defl_was = S->defl_active;
         S->defl_active = false;
@@ -4272,7 +4241,22 @@ __global__ __launch_bounds__(256) void k_heat_cg_residual(PlHeatOp op, const dou
     }
     heat_block_sum3(s0, s1, s2, part);
 }
-// p_new = z + beta p_old at the node and its four neighbours (beta = sc[3]; first iteration: use_beta = 0, p_old holds z), q = A_red p_new
+// Device scalars of the heat CG / Chebyshev solve: the first HC_N slots of PlSolver::scal, with meanings of their own.  Nothing of the
+// Stokes block needs to survive a heat solve (SC_Y_AW, the one deflation value kept across iterations, is recomputed by every Stokes
+// solve that deflates); the heat slots lie below it all the same.
+enum PlHeatScal : int {
+    HC_RZ = 0,              // r.z of the current residual
+    HC_ZZ = 1,              // z.z
+    HC_ALPHA = 2,           // CG alpha; several ranks: HC_REF is staged here for the all-reduce of HC_RZ .. HC_ALPHA
+    HC_BETA = 3,            // CG beta
+    HC_PQ = 4,              // p.q; k_heat_mass_norm: the mass-weighted norm of x
+    HC_REF = 5,             // reference norm of the start residual
+    HC_HS = 6,              // alpha times the old r.z (Hestenes-Stiefel term of the error estimate)
+    HC_RAD = 7,             // k_heat_mass_norm: the maximum Gershgorin radius of D^-1 A_red
+    HC_N = 8,
+};
+static_assert((int)HC_N <= (int)SC_Y_AW, "the heat solve leaves the deflation slots alone");
+// p_new = z + beta p_old at the node and its four neighbours (beta = HC_BETA; first iteration: use_beta = 0, p_old holds z), q = A_red p_new
 __global__ __launch_bounds__(256) void k_heat_cg_apply(PlHeatOp op, const double* __restrict__ z, const double* __restrict__ pold, double* __restrict__ pnew,
                                                        double* __restrict__ q, const double* __restrict__ sc, int use_beta, double* __restrict__ part) {
     const PlGeom& g = op.g;
@@ -4281,7 +4265,7 @@ __global__ __launch_bounds__(256) void k_heat_cg_apply(PlHeatOp op, const double
     if (i >= 1 && i <= g.nz - 2 && j >= 1 && j <= g.nx - 2) {
         const long long c = pl_idx(g, i, j);
         const int p = g.pitch;
-        const double beta = use_beta ? sc[3] : 0.0;
+        const double beta = use_beta ? sc[HC_BETA] : 0.0;
         auto pv = [&](long long k) { return use_beta ? z[k] + beta * pold[k] : pold[k]; };     // wall entries of z and p are 0 and stay 0
         const double pc = pv(c);
         const HeatRed h = heat_red(op, i, j, c);
@@ -4291,7 +4275,7 @@ __global__ __launch_bounds__(256) void k_heat_cg_apply(PlHeatOp op, const double
     }
     heat_block_sum3(s0, 0.0, 0.0, part);
 }
-// alpha = sc[2]:  d += alpha p,  r -= alpha q,  z = r dinv;  partials r.z, z.z
+// alpha = HC_ALPHA:  d += alpha p,  r -= alpha q,  z = r dinv;  partials r.z, z.z
 __global__ __launch_bounds__(256) void k_heat_cg_update(PlGeom g, const double* __restrict__ pdir, const double* __restrict__ q, const double* __restrict__ dinv,
                                                         double* __restrict__ d, double* __restrict__ r, double* __restrict__ z, const double* __restrict__ sc,
                                                         double* __restrict__ part) {
@@ -4299,7 +4283,7 @@ __global__ __launch_bounds__(256) void k_heat_cg_update(PlGeom g, const double* 
     double s0 = 0.0, s1 = 0.0;
     if (i >= 1 && i <= g.nz - 2 && j >= 1 && j <= g.nx - 2) {
         const long long c = pl_idx(g, i, j);
-        const double alpha = sc[2];
+        const double alpha = sc[HC_ALPHA];
         d[c] += alpha * pdir[c];
         const double rn = r[c] - alpha * q[c];
         r[c] = rn;
@@ -4309,11 +4293,11 @@ __global__ __launch_bounds__(256) void k_heat_cg_update(PlGeom g, const double* 
     }
     heat_block_sum3(s0, s1, 0.0, part);
 }
-// sums of the block partials and the CG scalars: sc[0] = r.z (current), sc[1] = z.z, sc[2] = alpha, sc[3] = beta, sc[4] = p.q, sc[5] = reference
-// what 0: start (sc[0] = r.z, sc[1] = z.z, sc[5] = ref);  1: after apply (sc[4] = p.q, alpha = sc[0] / p.q);
-//      2: after update (beta = r.z_new / sc[0], sc[6] = alpha * old r.z (Hestenes-Stiefel term), sc[0] = r.z_new, sc[1] = z.z);  3: check (sc[1] = z.z)
+// sums of the block partials and the CG scalars (PlHeatScal)
+// what 0: start (HC_RZ, HC_ZZ, HC_REF);  1: after apply (HC_PQ, alpha = r.z / p.q);
+//      2: after update (beta = r.z_new / r.z, HC_HS = alpha * old r.z, then HC_RZ = r.z_new, HC_ZZ);  3: check (HC_ZZ)
 // (1024 threads: at 2049^2 there are 17 000 partials per sum, which one 256-thread block took 19 us to add -- twice per iteration)
-//      4: sc[4] = sum of slot 0, sc[7] = MAXIMUM of slot 1 (k_heat_mass_norm)
+//      4: HC_PQ = sum of slot 0, HC_RAD = MAXIMUM of slot 1 (k_heat_mass_norm)
 __global__ __launch_bounds__(1024) void k_heat_cg_scalars(int nb, const double* __restrict__ part, double* __restrict__ sc, int what) {
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     if (what == 4) for (int k = threadIdx.x; k < nb; k += 1024) { a0 += part[3 * k]; a1 = fmax(a1, part[3 * k + 1]); }
@@ -4329,11 +4313,11 @@ __global__ __launch_bounds__(1024) void k_heat_cg_scalars(int nb, const double* 
     if (threadIdx.x == 0) {
         a0 = a1 = a2 = 0.0;
         for (int w = 0; w < 16; w++) { a0 += sh[0][w]; a1 = what == 4 ? fmax(a1, sh[1][w]) : a1 + sh[1][w]; a2 += sh[2][w]; }
-        if (what == 4) { sc[4] = a0; sc[7] = a1; }
-        else if (what == 0) { sc[0] = a0; sc[1] = a1; sc[5] = a2; }
-        else if (what == 1) { sc[4] = a0; sc[2] = (a0 > 0.0) ? sc[0] / a0 : 0.0; }
-        else if (what == 2) { sc[3] = (sc[0] > 0.0) ? a0 / sc[0] : 0.0; sc[6] = sc[2] * sc[0]; sc[0] = a0; sc[1] = a1; }
-        else sc[1] = a1;
+        if (what == 4) { sc[HC_PQ] = a0; sc[HC_RAD] = a1; }
+        else if (what == 0) { sc[HC_RZ] = a0; sc[HC_ZZ] = a1; sc[HC_REF] = a2; }
+        else if (what == 1) { sc[HC_PQ] = a0; sc[HC_ALPHA] = (a0 > 0.0) ? sc[HC_RZ] / a0 : 0.0; }
+        else if (what == 2) { sc[HC_BETA] = (sc[HC_RZ] > 0.0) ? a0 / sc[HC_RZ] : 0.0; sc[HC_HS] = sc[HC_ALPHA] * sc[HC_RZ]; sc[HC_RZ] = a0; sc[HC_ZZ] = a1; }
+        else sc[HC_ZZ] = a1;
     }
 }
 // slot 0: mass-weighted norm of x; slot 1: the block's MAXIMUM of (sum of the off-diagonal couplings) / diagonal of the reduced
@@ -4400,10 +4384,7 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
     const bool multi = ctx->nranks > 1;
     for (int k = 0; k < 9; k++) if (!S->hc[k]) PL_TRY(dmalloc0(ctx, &S->hc[k], pb));
     if (multi && !S->hc3) PL_TRY(dmalloc0(ctx, &S->hc3, 3 * pb));            // the three Chebyshev iterates as ONE allocation: one exchange for all
-    if (!S->scal) {
-        PL_TRY(dmalloc0(ctx, &S->scal, (PL_SCAL_N + PL_PART_N * DOT_BLOCKS) * sizeof(double)));
-        PL_HIP(ctx, hipHostMalloc((void**)&S->hpart, (PL_PART_N * DOT_BLOCKS + PL_SCAL_N) * sizeof(double)));
-    }
+    PL_TRY(scal_alloc(ctx, S));
     // deepest extension a kernel of this solve runs on: it reads the coefficient planes one node further (ring PL_RING deep)
     const int E = multi ? std::min(PL_RING - 1, std::min(g.lnz, g.lnx)) : 0;
     const HeatExt X = heat_ext(ctx, ctx->hop, E > 0 ? E - 1 : 0);             // residual / first sweep: extended by E - 1
@@ -4428,21 +4409,21 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
         hipLaunchKernelGGL(k_heat_close_walls, dim3((2 * g.nx + 255) / 256), dim3(256), 0, ctx->stream, hop, bv[0], bv[1], bv[2], bv[3], v, 1);
     };
     auto fetch = [&]() -> int {
-        PL_HIP(ctx, hipMemcpyAsync(hs, sc, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PL_HIP(ctx, hipMemcpyAsync(hs, sc, HC_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return 0;
     };
     close_walls(x);
     hipLaunchKernelGGL(k_heat_mass_norm, gr, bl, 0, ctx->stream, hop, (const double*)x, S->hc_part);
-    hipLaunchKernelGGL(k_heat_cg_scalars, dim3(1), dim3(1024), 0, ctx->stream, (int)(gr.x * gr.y), (const double*)S->hc_part, sc, 4);     // -> sc[4], sc[7]
-    if (multi) { PL_TRY(pl_comm_allreduce_dev(ctx, sc + 4, 1, 0)); PL_TRY(pl_comm_allreduce_dev(ctx, sc + 7, 1, 2)); }
+    hipLaunchKernelGGL(k_heat_cg_scalars, dim3(1), dim3(1024), 0, ctx->stream, (int)(gr.x * gr.y), (const double*)S->hc_part, sc, 4);     // -> HC_PQ, HC_RAD
+    if (multi) { PL_TRY(pl_comm_allreduce_dev(ctx, sc + HC_PQ, 1, 0)); PL_TRY(pl_comm_allreduce_dev(ctx, sc + HC_RAD, 1, 2)); }
     PL_TRY(fetch());
-    const double xmass = hs[4];
+    const double xmass = hs[HC_PQ];
     // Chebyshev iteration instead of CG where its sweep count is known to be small: the eigenvalues of D^-1 A_red lie in
     // [1 - rho, 1 + rho] (Gershgorin; rho = 1 / (1 + m / sum w) < 1 for a backward-Euler step), so k sweeps reduce the residual by
     // 1 / T_k(1 / rho) -- with NO reduction and ONE launch per sweep (CG: 4 launches and 2 reductions per iteration, which is what the
     // 2.2 ms of a 12-iteration solve at 2049^2 were made of).  The true residual is confirmed afterwards as before.
-    const double rho_g = hs[7];
+    const double rho_g = hs[HC_RAD];
     const int cheb_env = getenv("PYLAMP_HEAT_CHEB") ? atoi(getenv("PYLAMP_HEAT_CHEB")) : 1;         // (read per solve: tests switch it)
     const bool cheb_ok = cheb_env != 0 && rho_g > 0.0 && rho_g < 0.97 && std::isfinite(rho_g);
     if (unsuited) *unsuited = false;
@@ -4464,12 +4445,15 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
         hipLaunchKernelGGL(k_heat_cg_residual, grX, bl, 0, ctx->stream, X.op, b_dev - X.sh, (const double*)(x - X.sh), r - X.sh, dinv - X.sh, z - X.sh, pa - X.sh,
                            d - X.sh, 0, S->hc_part, own);
         hipLaunchKernelGGL(k_heat_cg_scalars, dim3(1), dim3(1024), 0, ctx->stream, nb, (const double*)S->hc_part, sc, 0);
-        if (multi) { PL_HIP(ctx, hipMemcpyAsync(sc + 2, sc + 5, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream)); PL_TRY(pl_comm_allreduce_dev(ctx, sc, 3, 0));
-                     PL_HIP(ctx, hipMemcpyAsync(sc + 5, sc + 2, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream)); }
+        if (multi) {                                     // HC_RZ, HC_ZZ and HC_REF (staged in HC_ALPHA) in one all-reduce
+            PL_HIP(ctx, hipMemcpyAsync(sc + HC_ALPHA, sc + HC_REF, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+            PL_TRY(pl_comm_allreduce_dev(ctx, sc + HC_RZ, 3, 0));
+            PL_HIP(ctx, hipMemcpyAsync(sc + HC_REF, sc + HC_ALPHA, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        }
         S->napply++;
         PL_TRY(fetch());
-        if (pass == 0) ref = std::sqrt(hs[5]);
-        double znorm = std::sqrt(hs[1]);
+        if (pass == 0) ref = std::sqrt(hs[HC_REF]);
+        double znorm = std::sqrt(hs[HC_ZZ]);
         if (!(ref > 0.0)) { st->converged = 1; break; }      // b = 0 on the interior: x0 with closed walls is the answer
         st->rel_residual = znorm / ref;
         if (znorm <= rtol * ref || it >= maxit || pass == 4) { st->converged = znorm <= rtol * ref ? 1 : 0; break; }
@@ -4517,9 +4501,9 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
             // before the previous solve's count on (consecutive time steps need the same number to within one or two)
             if (it + 3 < S->hc_last_its && it < maxit) continue;
             PL_TRY(fetch());
-            hist[it & 3] = hs[6];
-            znorm = std::sqrt(hs[1]);
-            if (!std::isfinite(znorm) || !(hs[4] > 0.0)) { ok = false; break; }
+            hist[it & 3] = hs[HC_HS];
+            znorm = std::sqrt(hs[HC_ZZ]);
+            if (!std::isfinite(znorm) || !(hs[HC_PQ] > 0.0)) { ok = false; break; }
             if (znorm <= rtol * ref) break;
         }
         // x = x0 + d with its wall nodes re-closed; the next pass confirms the TRUE residual (and restarts from it if need be)
@@ -4532,7 +4516,7 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
     S->hc_last_its = st->converged ? it : 0;
     if (xmass > 0.0) st->error_estimate = std::sqrt(std::fabs(hist[0]) + std::fabs(hist[1]) + std::fabs(hist[2]) + std::fabs(hist[3])) / std::sqrt(xmass);
     // Chebyshev: the energy norm of the error is r.A^-1 r <= r.D^-1 r / lambda_min = (r.z) / (1 - rho), with r.z of the confirmed residual
-    if (cheb_ok && xmass > 0.0 && hs[0] >= 0.0) st->error_estimate = std::sqrt(hs[0] / (1.0 - rho_g)) / std::sqrt(xmass);
+    if (cheb_ok && xmass > 0.0 && hs[HC_RZ] >= 0.0) st->error_estimate = std::sqrt(hs[HC_RZ] / (1.0 - rho_g)) / std::sqrt(xmass);
     double ms = 0;
     PL_TRY(pl_timer_stop_ms(ctx, &ms));
     st->solve_ms = ms; st->operator_applies = S->napply; st->precond_applies = 0;
@@ -4543,9 +4527,8 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
 int pl_heat_solve_device(pl_ctx* ctx, const double* b_dev, double rtol, int maxit, pl_solve_stats* st,
                          double** x_out, const double* x0_dev) {
     PlSolver* S = solver_of(ctx);
-    // one rank: CG on the symmetrised system (PYLAMP_HEAT_CG=0: the Jacobi-scaled BiCGStab below, which several ranks still use)
-    static const bool use_cg = !(getenv("PYLAMP_HEAT_CG") && atoi(getenv("PYLAMP_HEAT_CG")) == 0);
-    if (use_cg && ctx->nz >= 3 && ctx->nx >= 3 && (ctx->nranks == 1 || std::min(ctx->geom.d.lnz, ctx->geom.d.lnx) >= 2)) {
+    // CG / Chebyshev on the symmetrised system first (several ranks may fall back to the Jacobi-scaled BiCGStab below)
+    if (ctx->nz >= 3 && ctx->nx >= 3 && (ctx->nranks == 1 || std::min(ctx->geom.d.lnz, ctx->geom.d.lnx) >= 2)) {
         bool unsuited = false;
         PL_TRY(heat_solve_cg(ctx, S, b_dev, rtol, maxit, st, x_out, x0_dev, &unsuited));
         if (!unsuited) return 0;             // (several ranks and a Gershgorin radius >= 0.97: the Jacobi-scaled BiCGStab below)
@@ -4553,10 +4536,7 @@ int pl_heat_solve_device(pl_ctx* ctx, const double* b_dev, double rtol, int maxi
     const PlGeom& g = ctx->geom.d;
     size_t pb = (size_t)g.plane * sizeof(double);
     for (int k = 0; k < 11; k++) if (!S->h[k]) PL_TRY(dmalloc0(ctx, &S->h[k], pb));
-    if (!S->scal) {
-        PL_TRY(dmalloc0(ctx, &S->scal, (PL_SCAL_N + PL_PART_N * DOT_BLOCKS) * sizeof(double)));
-        PL_HIP(ctx, hipHostMalloc((void**)&S->hpart, (PL_PART_N * DOT_BLOCKS + PL_SCAL_N) * sizeof(double)));
-    }
+    PL_TRY(scal_alloc(ctx, S));
     PL_TRY(pl_timer_start(ctx));
     PlHeatOp hop = ctx->hop;
     S->napply = 0;

@@ -169,8 +169,8 @@ def test_unattainable_tolerance_returns_best_iterate():
 def test_cross_check_kernel_variants(oracle):
     """The scalar one-column-per-lane multigrid kernels (PYLAMP_VV_VEC=0) and the host-scalar BiCGStab loop
     (PYLAMP_HOST_SCALARS=1) are kept as cross-checks of the vectorised / device-scalar defaults, and the optional FP32
-    multigrid levels and early coarse branch must not change the answer either: same problem, every variant must
-    reach the oracle's direct solution, with iteration counts in the same range."""
+    multigrid levels must not change the answer either: same problem, every variant must reach the oracle's direct
+    solution, with iteration counts in the same range."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = r'''
@@ -198,10 +198,9 @@ print("RESULT", json.dumps(dict(its=A.last_stats["iterations"], conv=A.last_stat
     res = {}
     variants = (("default", {}), ("scalar_kernels", {"PYLAMP_VV_VEC": "0"}), ("host_scalars", {"PYLAMP_HOST_SCALARS": "1"}),
                 # optional paths (off by default): FP32 multigrid levels under the FP64 BiCGStab, with the
-                # vectorised and with the scalar kernels; the early coarse branch on a second stream
+                # vectorised and with the scalar kernels
                 ("fp32_levels", {"PYLAMP_MG_FP32": "1", "PYLAMP_MG_FP32_NODES": "1000"}),
                 ("fp32_levels_scalar_kernels", {"PYLAMP_MG_FP32": "1", "PYLAMP_MG_FP32_NODES": "1000", "PYLAMP_VV_VEC": "0"}),
-                ("early_coarse_branch", {"PYLAMP_MG_EARLY": "1"}),
                 # every multigrid stage as a kernel of its own instead of the fused tile kernels (k_mg_pre / k_mg_post)
                 ("staged_levels", {"PYLAMP_MG_FUSED": "0"}), ("staged_levels_scalar", {"PYLAMP_MG_FUSED": "0", "PYLAMP_VV_VEC": "0"}))
     for name, env in variants:
@@ -430,7 +429,7 @@ def test_stock_model5_sphere_contrast_1e10(oracle):
 
 @pytest.mark.parametrize("nx,forced", [([513, 33], 0), ([129, 129], 1), ([33, 513], 0), ([129, 129], 2)])
 def test_z_line_relaxation_vs_direct_solve(oracle, nx, forced):
-    """Stretched grids (pl_solver.hip, k_vv_line_z): 513 x 33 nodes on a square domain -- cells 16 times wider than high, where the
+    """Stretched grids (pl_solver.hip, k_vv_line): 513 x 33 nodes on a square domain -- cells 16 times wider than high, where the
     point-Jacobi multigrid stalls -- take the z-line smoother by themselves; the isotropic 129^2 case forces it on every level
     (PYLAMP_MG_LINE=1) so that the kernel is checked where the point smoother's answer is known to be good.  Both against the
     oracle's direct solve at the north-star tolerance."""
