@@ -372,6 +372,49 @@ int  pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double rtol, int
 /* solution of the last solve of this context: which = 0 Stokes (nz, nx, ny, 4), 1 heat (nz, nx, ny) */
 int  pl3_get_solution(pl3_ctx* ctx, int which, double* out);
 
+/* ---- 3-D marker-in-cell (one rank; every entry point fails on a context that has pl3_set_comm attached) -------------
+ * The dimension-by-dimension extension of pylamp_trac.py:30-388.  tr_x is (n, 3) in [z, x, y] order, tr_f is (n, ld_f) with the
+ * 2-D columns of pylamp_const.py, grid arrays are C-order (nz, nx, ny).  Cells are found per axis by the regular-grid formula
+ * floor((n-1)(x-x0)/L).
+ * pl3_trac2grid: averages nf <= 8 tracer fields (the first nf columns of tr_f) onto the node set given by its three coordinate
+ * arrays; the four PL_AVG_* schemes, trilinear weights, auto-extension and crop as in 2-D (a contribution to a node outside the
+ * set is dropped, a node that receives nothing is NaN).  Built as a gather over cell-sorted tracers without floating-point
+ * atomics: two calls with the same input give bitwise the same output.
+ * pl3_grid2trac: PL_INTERP_LINEAR (trilinear), PL_INTERP_NEAREST (nearest of the eight corners, ties by corner index
+ * (di 2 + dj) 2 + dk) or PL_INTERP_VELDIV (divergence-conserving, exactly the three fields vz, vx, vy).  A tracer outside the grid
+ * gets defval in EVERY column -- the 2-D quirk that leaves vz extrapolated under VELDIV is deliberately not copied.
+ * pl3_rk4: four VELDIV evaluations on the padded (nz+1, nx+1, ny+1) centre grid, out-of-grid velocity 0, the reference's weights
+ * (1,1,1,1)/6; v_out = (x_new - x)/tstep and x_out, both (n, 3). */
+int  pl3_trac2grid(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f, int64_t ld_f, int nf, const int* avgscheme,
+                   const double* zc, int nzc, const double* xc, int nxc, const double* yc, int nyc, double* const* out);
+int  pl3_grid2trac(pl3_ctx* ctx, int64_t n, const double* tr_x, int nf, const double* const* fields, int gnz, int gnx, int gny,
+                   const double* gz, const double* gx, const double* gy, int method, double defval, int stop_on_error, double* out,
+                   int64_t ld_out, int64_t* n_outside);
+int  pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int gnx, int gny, const double* gz, const double* gx, const double* gy,
+             const double* vz, const double* vx, const double* vy, double tstep, double* v_out, double* x_out);
+/* Resident tracers of a context: (n, 3) positions and (n, 13) fields, kept on the device sorted by cell of the context's node grid
+ * (tracers outside it count to the nearest cell).  Download returns them in the resident order: TR__ID identifies a tracer.
+ * Census: tracers per cell, (nz-1, nx-1, ny-1) int32, a by-product of the sort. */
+int  pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f);
+int  pl3_tracers_download(pl3_ctx* ctx, int64_t n, double* tr_x, double* tr_f);
+int  pl3_tracers_count(pl3_ctx* ctx, int64_t* n);
+int  pl3_tracers_census(pl3_ctx* ctx, int64_t ncell, int32_t* counts);
+/* Stages of a time step on the resident tracers -- the same kernels as the host-array calls; only grid fields cross PCIe.
+ * props: rho(T) and eta(T) with clamps (pylamp2.py:291-303).  trac2grid: tracer columns `columns` onto a node set, to host arrays.
+ * temp_to_tracers: field (nz, nx, ny) = the new nodal temperature (absolute != 0, first step) or its increment, then with
+ * subgrid != 0 the subgrid-diffusion update of pylamp2.py:471-480 with (2/dz)^2 + (2/dx)^2 + (2/dy)^2 in the time scale; a tracer
+ * outside the grid is an error.  rk4: advection on the padded centre grid, fence != 0: x <= 0 -> EPS, x >= L -> L - EPS per axis
+ * (pylamp2.py:558-572), then the re-sort; the tracer velocities of the last call stay retrievable (n, 3).
+ * times: device milliseconds of the last resident scatter, temperature stage, RK4 kernel and sort. */
+int  pl3_resident_props(pl3_ctx* ctx, int tdep_rho, int tdep_eta, double tref, double etamin, double etamax);
+int  pl3_resident_trac2grid(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* zc, int nzc, const double* xc,
+                            int nxc, const double* yc, int nyc, double* const* out);
+int  pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* field, int subgrid, double tstep);
+int  pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
+                      const double* vy, double tstep, int fence);
+int  pl3_get_tracer_velocity(pl3_ctx* ctx, int64_t n, double* out);
+int  pl3_resident_times(pl3_ctx* ctx, double ms[4]);
+
 /* sizeof / offsetof of the structs above as compiled into the library: out = { sizeof(pl_solve_stats),
  * sizeof(pl_step_config), sizeof(pl_step_report), offsetof(config.length), offsetof(config.inject_seed),
  * offsetof(config.tracs_fence_disabled), offsetof(report.ntrac), offsetof(report.nremoved) } -- lets a binding

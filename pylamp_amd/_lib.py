@@ -71,6 +71,24 @@ SIGNATURES = {
     "pl3_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_heat_solve": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int, C.POINTER(SolveStats)]),
     "pl3_get_solution": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "pl3_trac2grid": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int, c_int_p, c_double_p, C.c_int,
+                                c_double_p, C.c_int, c_double_p, C.c_int, C.POINTER(c_double_p)]),
+    "pl3_grid2trac": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, C.c_int, C.POINTER(c_double_p), C.c_int, C.c_int, C.c_int,
+                                c_double_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, c_double_p, C.c_int64,
+                                C.POINTER(C.c_int64)]),
+    "pl3_rk4": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, C.c_int, C.c_int, C.c_int] + [c_double_p] * 6 +
+                [C.c_double, c_double_p, c_double_p]),
+    "pl3_tracers_upload": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
+    "pl3_tracers_download": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
+    "pl3_tracers_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "pl3_tracers_census": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "pl3_resident_props": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "pl3_resident_trac2grid": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int, c_double_p, C.c_int,
+                                         c_double_p, C.c_int, C.POINTER(c_double_p)]),
+    "pl3_resident_temp_to_tracers": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int, C.c_double]),
+    "pl3_resident_rk4": (C.c_int, [C.c_void_p] + [c_double_p] * 6 + [C.c_double, C.c_int]),
+    "pl3_get_tracer_velocity": (C.c_int, [C.c_void_p, C.c_int64, c_double_p]),
+    "pl3_resident_times": (C.c_int, [C.c_void_p, c_double_p]),
     "pl_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, c_int_p, C.POINTER(C.c_size_t)]),
     "pl_set_comm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pl_set_comm_2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -14,6 +14,7 @@
 // preconditioner [[A_vv, A_vp],[0, S^]] with one geometric-multigrid V-cycle (Chebyshev-Jacobi smoothing, rediscretised
 // coarse operators with natural wall rows, arithmetic viscosity coarsening) for A_vv.  One GPU per problem.
 #include "pl_internal.h"
+#include "pl_mic3.h"
 #include <algorithm>
 #include <cmath>
 #include <functional>
@@ -1050,6 +1051,7 @@ struct pl3_ctx {
     double *dfl_y = nullptr, *dfl_t = nullptr; bool dfl_valid = false;
     bool dfl_active = false; double dfl_yAw = 0.0, dfl_wvel2 = 0.0;      // of the running solve: the anchor-mode term of the error estimate
     double etol = 3e-8;                     // bound on the velocity-error estimate of a converged Stokes solve (PYLAMP_STOKES_ETOL)
+    void* mic3 = nullptr;                   // pl_mic3.hip: resident tracers and the work buffers of the 3-D marker kernels
 };
 static thread_local std::string p3_tls_error;
 static int p3_fail(pl3_ctx* ctx, const std::string& m) { if (ctx) ctx->err = m; p3_tls_error = m; return 1; }
@@ -1095,6 +1097,15 @@ static dim3 g1(long long n) { long long b = (n + 255) / 256; return dim3((unsign
 
 extern "C" const char* pl3_last_error(const pl3_ctx* ctx) { return ctx ? ctx->err.c_str() : p3_tls_error.c_str(); }
 
+// what the marker-in-cell unit (pl_mic3.hip) needs of a context
+int pl3_fail(pl3_ctx* ctx, const std::string& m) { return p3_fail(ctx, m); }
+int pl3_host_view(pl3_ctx* ctx, Pl3HostView* v) {
+    if (!ctx) return p3_fail(nullptr, "3-D marker-in-cell: NULL context");
+    v->device = ctx->device; v->stream = ctx->stream; v->nranks = ctx->nranks; v->slot = &ctx->mic3;
+    for (int a = 0; a < 3; a++) { v->gn[a] = ctx->gn[a]; v->coord[a] = ctx->gcoord[a].data(); }
+    return 0;
+}
+
 extern "C" int pl3_create(pl3_ctx** out, int device, int nz, int nx, int ny, const double* zc, const double* xc, const double* yc) {
     if (!out) return p3_fail(nullptr, "pl3_create: out is NULL");
     *out = nullptr;
@@ -1128,6 +1139,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
     for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf}) if (q) (void)hipFree(q);
     for (auto& v : ctx->vec) if (v[0]) (void)hipFree(v[0]);

@@ -1,0 +1,810 @@
+// 3-D marker-in-cell: tracer->grid, grid->tracer, RK4 advection and the resident tracer state of a pl3_ctx.
+// The dimension-by-dimension extension of pylamp_trac.py:30-388 (the reference is 2-D only); conventions: positions (n,3) in
+// [z, x, y] order, tracer fields with the 2-D columns of pylamp_const.py, grid arrays C-order (nz, nx, ny).  One rank only.
+//
+// Tracer -> grid is a GATHER: the tracers are sorted by cell (counting sort, made stable by ordering every cell's slice by the
+// previous index), the start offset of every cell is kept, and each target node sums the tracers of the cells around it in a fixed
+// order.  No floating-point atomics anywhere, so a scatter is bitwise the same from run to run.  Whether a tracer contributes to a
+// node is decided by the tracer's own cell on the TARGET node set (the reference's regular-grid formula); the sort cells only
+// bound the search, so a tracer on an exact cell face cannot be lost or counted twice.
+//
+// Grid -> tracer: out-of-grid tracers get defval in EVERY column.  This deliberately does not copy the 2-D quirk of
+// pylamp_trac.py:83-156 (which leaves vz extrapolated under VELDIV): it has no meaning with three components.
+#include "pl_internal.h"
+#include "pl_mic3.h"
+#include <algorithm>
+#include <cmath>
+
+#define M3_MAXF 8
+#define M3_NFTRAC 13
+enum { M3_RHO = 0, M3_ETA = 1, M3_TMP = 3, M3_HCD = 4, M3_HCP = 5, M3_RH0 = 6, M3_ALP = 7, M3_ACE = 9, M3_ET0 = 10 };
+#define M3_GASR 8.31446
+
+// one axis of a regular node set: n coordinates c[], cell = floor((n-1)(x - c0)/L) (pylamp_trac.py:42-47,222-227)
+struct M3Axis { int n; double c0, L, h0, h1; const double* c; };
+struct M3Grid { M3Axis a[3]; };
+
+__device__ inline double m3_cellf(const M3Axis& a, double p) { return floor((double)(a.n - 1) * (p - a.c0) / a.L); }
+// coordinate of node i of the auto-extended node set (pylamp_trac.py:207-220): beyond the ends it continues with the end spacing
+__device__ inline double m3_coord(const M3Axis& a, int i) {
+    if (i < 0) return a.c0 + (double)i * a.h0;
+    if (i > a.n - 1) return a.c[a.n - 1] + (double)(i - (a.n - 1)) * a.h1;
+    return a.c[i];
+}
+__device__ inline int m3_sort_cell(const M3Axis& a, double p) {
+    const double f = m3_cellf(a, p);
+    return f >= (double)(a.n - 2) ? a.n - 2 : (f > 0.0 ? (int)f : 0);       // clamped into the node set (NaN -> 0)
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sort by cell
+// ---------------------------------------------------------------------------------------------------------------------
+// position of tracer t along axis a is x[a][t * xs]: xs = 1 for the resident SoA columns, 3 for a host (n,3) array
+struct M3Pos { const double* x[3]; long long xs; };
+
+__global__ __launch_bounds__(256) void k_m3_key(long long n, M3Pos p, M3Grid s, int* __restrict__ key, int* __restrict__ count) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int ci = m3_sort_cell(s.a[0], p.x[0][t * p.xs]), cj = m3_sort_cell(s.a[1], p.x[1][t * p.xs]), ck = m3_sort_cell(s.a[2], p.x[2][t * p.xs]);
+    const int c = (ci * (s.a[1].n - 1) + cj) * (s.a[2].n - 1) + ck;
+    key[t] = c;
+    atomicAdd(&count[c], 1);                      // integer: the counts do not depend on the order of arrival
+}
+// exclusive prefix sum of count[0..m) into start[0..m] and cursor[0..m): one workgroup, each thread a contiguous chunk
+__global__ __launch_bounds__(1024) void k_m3_scan(int m, const int* __restrict__ count, int* __restrict__ start, int* __restrict__ cursor) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x, chunk = (m + 1023) / 1024, b = tid * chunk, e = min(b + chunk, m);
+    int s = 0;
+    for (int i = b; i < e; i++) s += count[i];
+    part[tid] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = part[tid] - s;
+    for (int i = b; i < e; i++) { start[i] = run; cursor[i] = run; run += count[i]; }
+    if (tid == 1023) start[m] = part[1023];
+}
+__global__ __launch_bounds__(256) void k_m3_place(long long n, const int* __restrict__ key, int* __restrict__ cursor, int* __restrict__ perm) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    perm[atomicAdd(&cursor[key[t]], 1)] = (int)t;
+}
+// the slots inside a cell were handed out in order of arrival: order every cell's slice by the previous index, which makes the
+// sort stable and its result independent of the scheduling
+__global__ __launch_bounds__(256) void k_m3_cell_order(int m, const int* __restrict__ start, int* __restrict__ perm) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= m) return;
+    int* a = perm + start[c];
+    const int k = start[c + 1] - start[c];
+    if (k <= 32) {
+        for (int i = 1; i < k; i++) { const int v = a[i]; int j = i - 1; while (j >= 0 && a[j] > v) { a[j + 1] = a[j]; j--; } a[j + 1] = v; }
+        return;
+    }
+    for (int top = k / 2 - 1, end = k; end > 1;) {            // heap sort: a crowded cell must not cost k^2
+        int root, v;
+        if (top >= 0) { root = top; v = a[top]; top--; }
+        else { end--; v = a[end]; a[end] = a[0]; root = 0; }
+        for (;;) {
+            int ch = 2 * root + 1;
+            if (ch >= end) break;
+            if (ch + 1 < end && a[ch + 1] > a[ch]) ch++;
+            if (a[ch] <= v) break;
+            a[root] = a[ch]; root = ch;
+        }
+        a[root] = v;
+    }
+}
+// dst[j * dstride + p] = g(src[perm[p] * ts + j * cs]) for ncol columns; bit j of logmask: g = log (geometric averaging)
+__global__ __launch_bounds__(256) void k_m3_take(long long n, const double* __restrict__ src, long long ts, long long cs, int ncol,
+                                                 const int* __restrict__ perm, double* __restrict__ dst, long long dstride, unsigned logmask) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const long long t = perm ? (long long)perm[p] : p;
+    for (int j = 0; j < ncol; j++) {
+        const double v = src[t * ts + j * cs];
+        dst[j * dstride + p] = ((logmask >> j) & 1u) ? log(v) : v;
+    }
+}
+// SoA -> (n, ncol) host layout
+__global__ __launch_bounds__(256) void k_m3_to_aos(long long n, const double* __restrict__ src, long long cs, int ncol, double* __restrict__ dst) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    for (int j = 0; j < ncol; j++) dst[t * ncol + j] = src[j * cs + t];
+}
+__global__ __launch_bounds__(256) void k_m3_census(int m, const int* __restrict__ start, int* __restrict__ cnt) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < m) cnt[c] = start[c + 1] - start[c];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// tracer -> grid
+// ---------------------------------------------------------------------------------------------------------------------
+struct M3Scatter {
+    const double* x[3];                  // cell-sorted positions
+    int nf; const double* val[M3_MAXF]; int scheme[M3_MAXF];     // values in the form that is summed (logarithm taken for GEOMETRIC)
+    M3Grid t;                            // target node set
+    int ncs[3];                          // sort cells per axis
+    const int* lo[3]; const int* hi[3];  // per target node and axis: the range of sort cells that can hold a contributing tracer
+    const int* start;
+    double* out[M3_MAXF];
+};
+
+// One thread per target node; lanes run along y, so neighbouring lanes read neighbouring cells' slices of the sorted arrays.
+// NF > 0: field count known at compile time (accumulators stay in registers); 0: generic.
+template <int NF>
+__global__ __launch_bounds__(256) void k_m3_scatter(M3Scatter a) {
+    const int nz = a.t.a[0].n, nx = a.t.a[1].n, ny = a.t.a[2].n;
+    const long long node = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (node >= (long long)nz * nx * ny) return;
+    const int nf = NF > 0 ? NF : a.nf;
+    const int k = (int)(node % ny), j = (int)((node / ny) % nx), i = (int)(node / ((long long)ny * nx));
+    const int idx[3] = {i, j, k};
+    double wsum = 0.0, cnt = 0.0, acc[NF > 0 ? NF : M3_MAXF];
+    for (int q = 0; q < nf; q++) acc[q] = 0.0;
+    const int lo2 = a.lo[2][k], hi2 = a.hi[2][k];
+    for (int cz = a.lo[0][i]; cz <= a.hi[0][i]; cz++)
+        for (int cx = a.lo[1][j]; cx <= a.hi[1][j]; cx++) {
+            const long long row = ((long long)cz * a.ncs[1] + cx) * a.ncs[2];
+            const int t0 = a.start[row + lo2], t1 = a.start[row + hi2 + 1];        // the cells of a y-row are contiguous
+            for (int t = t0; t < t1; t++) {
+                double w = 1.0; bool mine = true;
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    const M3Axis& ax = a.t.a[d];
+                    const double p = a.x[d][t];
+                    double f = m3_cellf(ax, p);
+                    f = fmin(fmax(f, -4.0), (double)ax.n + 2.0);
+                    const int ie = (int)f, dn = idx[d] - ie;             // the tracer's corners along this axis are ie, ie + 1
+                    if (dn != 0 && dn != 1) { mine = false; break; }
+                    const double c0 = m3_coord(ax, ie), c1 = m3_coord(ax, ie + 1), tt = (p - c0) / (c1 - c0);
+                    w *= dn ? tt : 1.0 - tt;
+                }
+                if (!mine) continue;
+                wsum += w; cnt += 1.0;
+                for (int q = 0; q < nf; q++) { const double v = a.val[q][t]; acc[q] += (a.scheme[q] & PL_AVG_WEIGHTED) ? v * w : v; }
+            }
+        }
+    for (int q = 0; q < nf; q++) {
+        const double den = (a.scheme[q] & PL_AVG_WEIGHTED) ? wsum : cnt;
+        double s = acc[q], r;
+        if (a.scheme[q] & PL_AVG_ARITHMETIC) r = s / den;                // nothing received: 0/0 = NaN, as in 2-D
+        else { if (isinf(s)) s = 0.0; r = exp(s / den); }                // pylamp_trac.py:301
+        a.out[q][node] = r;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// grid -> tracer, RK4
+// ---------------------------------------------------------------------------------------------------------------------
+struct M3Loc { int ie[3]; double t[3], h[3], d0[3], d1[3]; bool bad; long long o; };
+
+__device__ inline M3Loc m3_locate(const M3Grid& g, const double p[3]) {
+    M3Loc c; c.bad = false;
+    double f[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) { f[d] = m3_cellf(g.a[d], p[d]); c.bad = c.bad || !(f[d] >= 0.0 && f[d] <= (double)(g.a[d].n - 2)); }
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const int ie = c.bad ? 0 : (int)f[d];
+        const double lo = g.a[d].c[ie], hi = g.a[d].c[ie + 1];
+        c.ie[d] = ie; c.d0[d] = p[d] - lo; c.d1[d] = hi - p[d]; c.h[d] = hi - lo;
+        c.t[d] = c.d0[d] / (c.d0[d] + c.d1[d]);                          // pylamp_trac.py:89-90
+    }
+    c.o = ((long long)c.ie[0] * g.a[1].n + c.ie[1]) * g.a[2].n + c.ie[2];
+    return c;
+}
+// the eight corners of a cell, corner index (di 2 + dj) 2 + dk
+__device__ inline void m3_corners(const double* __restrict__ F, const M3Grid& g, const M3Loc& c, double v[8]) {
+    const long long sy = g.a[2].n, sx = (long long)g.a[1].n * sy;
+#pragma unroll
+    for (int q = 0; q < 8; q++) v[q] = F[c.o + (q >> 2) * sx + ((q >> 1) & 1) * sy + (q & 1)];
+}
+__device__ inline double m3_trilinear(const double v[8], const double t[3]) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) s += ((q >> 2) ? t[0] : 1 - t[0]) * (((q >> 1) & 1) ? t[1] : 1 - t[1]) * ((q & 1) ? t[2] : 1 - t[2]) * v[q];
+    return s;
+}
+// delta_d delta_e F on the faces f = 0 and f = 1 of the cell, interpolated along f at s  (D, E, F: corner-index bits of the axes)
+template <int D, int E, int Fb>
+__device__ inline double m3_mixed(const double v[8], double s) {
+    const double f0 = v[0] - v[E] - v[D] + v[D + E], f1 = v[Fb] - v[E + Fb] - v[D + Fb] + v[D + E + Fb];
+    return (1 - s) * f0 + s * f1;
+}
+// Divergence-conserving interpolation in 3-D: trilinear plus t_d (1 - t_d) (h_d / 2) [M_de / h_e + M_df / h_f],
+// the symmetric extension of pylamp_trac.py:98-154.  Out of grid: all three components = defval.
+__device__ inline void m3_veldiv(const M3Grid& g, const double* __restrict__ Vz, const double* __restrict__ Vx, const double* __restrict__ Vy,
+                                 const double p[3], double defval, double u[3], bool& bad) {
+    const M3Loc c = m3_locate(g, p);
+    double vz[8], vx[8], vy[8];
+    m3_corners(Vz, g, c, vz); m3_corners(Vx, g, c, vx); m3_corners(Vy, g, c, vy);
+    const double* t = c.t; const double* h = c.h;
+    // corner-index bits: z = 4, x = 2, y = 1
+    const double Gz = 0.5 * h[0] * (m3_mixed<4, 2, 1>(vx, 0.25 + 0.5 * t[2]) / h[1] + m3_mixed<4, 1, 2>(vy, 0.25 + 0.5 * t[1]) / h[2]);
+    const double Gx = 0.5 * h[1] * (m3_mixed<2, 4, 1>(vz, 0.25 + 0.5 * t[2]) / h[0] + m3_mixed<2, 1, 4>(vy, 0.25 + 0.5 * t[0]) / h[2]);
+    const double Gy = 0.5 * h[2] * (m3_mixed<1, 4, 2>(vz, 0.25 + 0.5 * t[1]) / h[0] + m3_mixed<1, 2, 4>(vx, 0.25 + 0.5 * t[0]) / h[1]);
+    u[0] = m3_trilinear(vz, t) + t[0] * (1 - t[0]) * Gz;
+    u[1] = m3_trilinear(vx, t) + t[1] * (1 - t[1]) * Gx;
+    u[2] = m3_trilinear(vy, t) + t[2] * (1 - t[2]) * Gy;
+    if (c.bad) { u[0] = defval; u[1] = defval; u[2] = defval; }
+    bad = c.bad;
+}
+
+struct M3Gather {
+    long long n; M3Pos p; M3Grid g;
+    int nf; const double* f[M3_MAXF]; double* out[M3_MAXF]; long long os;     // out[k][t * os]
+    int method; double defval; int accumulate;                               // LINEAR only: out += value
+    unsigned long long* nout;
+};
+__global__ __launch_bounds__(256) void k_m3_gather(M3Gather a) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n) return;
+    const double p[3] = {a.p.x[0][t * a.p.xs], a.p.x[1][t * a.p.xs], a.p.x[2][t * a.p.xs]};
+    bool bad;
+    if (a.method & PL_INTERP_NEAREST) {
+        const M3Loc c = m3_locate(a.g, p);
+        int m = 0; double dm = 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) {       // exactly rounded products and sums in a fixed order: ties break as np.argmin does
+            const double dz = (q >> 2) ? c.d1[0] : c.d0[0], dx = ((q >> 1) & 1) ? c.d1[1] : c.d0[1], dy = (q & 1) ? c.d1[2] : c.d0[2];
+            const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dz, dz), __dmul_rn(dx, dx)), __dmul_rn(dy, dy));
+            if (q == 0 || d2 < dm) { m = q; dm = d2; }
+        }
+        const long long sy = a.g.a[2].n, sx = (long long)a.g.a[1].n * sy, o = c.o + (m >> 2) * sx + ((m >> 1) & 1) * sy + (m & 1);
+        for (int k = 0; k < a.nf; k++) a.out[k][t * a.os] = c.bad ? a.defval : a.f[k][o];
+        bad = c.bad;
+    } else if (a.method & PL_INTERP_LINEAR) {
+        const M3Loc c = m3_locate(a.g, p);
+        for (int k = 0; k < a.nf; k++) {
+            double v[8];
+            m3_corners(a.f[k], a.g, c, v);
+            const double r = m3_trilinear(v, c.t);
+            a.out[k][t * a.os] = c.bad ? a.defval : (a.accumulate ? a.out[k][t * a.os] + r : r);
+        }
+        bad = c.bad;
+    } else {
+        double u[3];
+        m3_veldiv(a.g, a.f[0], a.f[1], a.f[2], p, a.defval, u, bad);
+        for (int k = 0; k < 3; k++) a.out[k][t * a.os] = u[k];
+    }
+    if (bad) atomicAdd(a.nout, 1ull);
+}
+
+// RK4 with the reference's weights (1,1,1,1)/6 (pylamp_trac.py:385) and v = (x_new - x)/dt; the four stages of a tracer run in
+// registers.  72 B/tracer: read the position, write the new one and the velocity; the velocity grid is read through the caches.
+struct M3Rk4 {
+    long long n; M3Pos p; M3Grid g; const double* V[3]; double dt;
+    double* xo[3]; double* vo[3]; long long os;
+    int fence; double eps, L[3];                   // pylamp2.py:558-572 per axis
+};
+__global__ __launch_bounds__(256) void k_m3_rk4(M3Rk4 a) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.n) return;
+    const double x[3] = {a.p.x[0][t * a.p.xs], a.p.x[1][t * a.p.xs], a.p.x[2][t * a.p.xs]};
+    const double dt = a.dt;
+    double k1[3], k2[3], k3[3], k4[3], q[3]; bool bad;
+    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], x, 0.0, k1, bad);
+    for (int d = 0; d < 3; d++) q[d] = x[d] + 0.5 * dt * k1[d];
+    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k2, bad);
+    for (int d = 0; d < 3; d++) q[d] = x[d] + 0.5 * dt * k2[d];
+    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k3, bad);
+    for (int d = 0; d < 3; d++) q[d] = x[d] + dt * k3[d];
+    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k4, bad);
+    for (int d = 0; d < 3; d++) {
+        const double xn = x[d] + (1.0 / 6.0) * dt * (k1[d] + k2[d] + k3[d] + k4[d]);
+        a.vo[d][t * a.os] = (xn - x[d]) / dt;
+        double xf = xn;
+        if (a.fence) { if (xf <= 0.0) xf = a.eps; if (xf >= a.L[d]) xf = a.L[d] - a.eps; }
+        a.xo[d][t * a.os] = xf;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// per-tracer properties and subgrid diffusion
+// ---------------------------------------------------------------------------------------------------------------------
+// pylamp2.py:291-303; f = SoA columns with stride cs
+__global__ __launch_bounds__(256) void k_m3_props(long long n, double* __restrict__ f, long long cs, int tdep_rho, int tdep_eta, double tref,
+                                                  double etamin, double etamax) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const double T = f[M3_TMP * cs + t], rh0 = f[M3_RH0 * cs + t], et0 = f[M3_ET0 * cs + t];
+    f[M3_RHO * cs + t] = tdep_rho ? 1.0 / ((f[M3_ALP * cs + t] * (T - tref) + 1.0) / rh0) : rh0;
+    if (tdep_eta) {
+        const double ace = f[M3_ACE * cs + t], e = et0 * exp(ace / (M3_GASR * T) - ace / (M3_GASR * tref));
+        f[M3_ETA * cs + t] = fmin(fmax(e, etamin), etamax);
+    } else f[M3_ETA * cs + t] = et0;
+}
+// pylamp2.py:471-480 with the third axis in the time scale: T holds T_old + dT; Tsub and dTs = Tsub - T are written
+__global__ __launch_bounds__(256) void k_m3_subgrid(long long n, const double* __restrict__ f, long long cs, const double* __restrict__ Told,
+                                                    double inv2, double dt, double* __restrict__ Tsub, double* __restrict__ dTs) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const double Tn = f[M3_TMP * cs + t], To = Told[t];
+    const double dt0 = f[M3_HCP * cs + t] * f[M3_RHO * cs + t] / (f[M3_HCD * cs + t] * inv2);
+    const double ts = To - (To - Tn) * exp(-0.5 * dt / dt0);
+    Tsub[t] = ts; dTs[t] = ts - Tn;
+}
+__global__ __launch_bounds__(256) void k_m3_sub(long long n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ o) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) o[t] = a[t] - b[t];
+}
+
+// =====================================================================================================================
+// host side
+// =====================================================================================================================
+struct Mic3 {
+    std::map<std::string, void*> bufs; std::map<std::string, size_t> bytes;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // resident tracers: SoA columns of `cap` doubles, cell-sorted on the context's node grid
+    long long n = 0, cap = 0; bool have = false;
+    double *x = nullptr, *f = nullptr, *v = nullptr;
+    double ms[4] = {0, 0, 0, 0};         // device time of the last resident scatter / temperature gather / RK4 / sort
+};
+#define M3_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return pl3_fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
+#define M3_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+void pl3_mic_free(void** slot) {
+    Mic3* M = (Mic3*)*slot;
+    if (!M) return;
+    for (auto& b : M->bufs) (void)hipFree(b.second);
+    if (M->ev0) (void)hipEventDestroy(M->ev0);
+    if (M->ev1) (void)hipEventDestroy(M->ev1);
+    delete M;
+    *slot = nullptr;
+}
+static int m3_open(pl3_ctx* ctx, const char* who, Pl3HostView& v, Mic3** out) {
+    M3_TRY(pl3_host_view(ctx, &v));
+    if (v.nranks > 1) return pl3_fail(ctx, std::string(who) + ": the 3-D marker-in-cell entry points run on one rank (this context has pl3_set_comm attached)");
+    M3_HIP(ctx, hipSetDevice(v.device));
+    if (!*v.slot) {
+        Mic3* M = new Mic3();
+        if (hipEventCreate(&M->ev0) != hipSuccess || hipEventCreate(&M->ev1) != hipSuccess) { delete M; return pl3_fail(ctx, "3-D marker-in-cell: event creation failed"); }
+        *v.slot = M;
+    }
+    *out = (Mic3*)*v.slot;
+    return 0;
+}
+template <typename T>
+static int m3_buf(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, size_t count, T** out) {
+    const size_t need = std::max<size_t>(count, 1) * sizeof(T);
+    auto it = M->bufs.find(name);
+    if (it == M->bufs.end() || M->bytes[name] < need) {
+        if (it != M->bufs.end()) { M3_HIP(ctx, hipStreamSynchronize(v.stream)); (void)hipFree(it->second); M->bufs.erase(it); }
+        void* p = nullptr;
+        M3_HIP(ctx, hipMalloc(&p, need));
+        M->bufs[name] = p; M->bytes[name] = need;
+    }
+    *out = (T*)M->bufs[name];
+    return 0;
+}
+static inline dim3 m3_blocks(long long n) { return dim3((unsigned)((std::max<long long>(n, 1) + 255) / 256)); }
+
+// a node set given by three host coordinate arrays -> device axes (coordinates in the buffer `name`)
+static int m3_grid(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, const double* const c[3], const int n[3], M3Grid& g) {
+    double* d;
+    M3_TRY(m3_buf(ctx, v, M, name, (size_t)n[0] + n[1] + n[2], &d));
+    size_t off = 0;
+    for (int a = 0; a < 3; a++) {
+        if (n[a] < 2) return pl3_fail(ctx, "3-D marker-in-cell: a node set needs at least 2 coordinates per axis");
+        for (int i = 0; i + 1 < n[a]; i++) if (!(c[a][i + 1] > c[a][i])) return pl3_fail(ctx, "3-D marker-in-cell: coordinates must increase");
+        M3_HIP(ctx, hipMemcpyAsync(d + off, c[a], (size_t)n[a] * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        g.a[a].n = n[a]; g.a[a].c0 = c[a][0]; g.a[a].L = c[a][n[a] - 1] - c[a][0]; g.a[a].h0 = c[a][1] - c[a][0];
+        g.a[a].h1 = c[a][n[a] - 1] - c[a][n[a] - 2]; g.a[a].c = d + off;
+        off += n[a];
+    }
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));          // the host arrays may be temporaries of the caller
+    return 0;
+}
+static long long m3_ncells(const M3Grid& s) { return (long long)(s.a[0].n - 1) * (s.a[1].n - 1) * (s.a[2].n - 1); }
+
+// counting sort by cell of the node set s: perm (sorted slot -> previous index) and start (ncell + 1)
+static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long long n, const M3Pos& p, const M3Grid& s, int** perm_out, int** start_out) {
+    const long long m = m3_ncells(s);
+    if (m >= (1ll << 31) - 1 || n >= (1ll << 31) - 1) return pl3_fail(ctx, "3-D marker-in-cell: more than 2^31 cells or tracers");
+    int *key, *perm, *cnt, *start, *cur;
+    const std::string t(tag);
+    M3_TRY(m3_buf(ctx, v, M, (t + "_key").c_str(), (size_t)n, &key));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_perm").c_str(), (size_t)n, &perm));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_cnt").c_str(), (size_t)m, &cnt));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_start").c_str(), (size_t)m + 1, &start));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_cur").c_str(), (size_t)m, &cur));
+    M3_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(int), v.stream));
+    if (n > 0) hipLaunchKernelGGL(k_m3_key, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
+    hipLaunchKernelGGL(k_m3_scan, dim3(1), dim3(1024), 0, v.stream, (int)m, (const int*)cnt, start, cur);
+    if (n > 0) {
+        hipLaunchKernelGGL(k_m3_place, m3_blocks(n), dim3(256), 0, v.stream, n, (const int*)key, cur, perm);
+        hipLaunchKernelGGL(k_m3_cell_order, m3_blocks(m), dim3(256), 0, v.stream, (int)m, (const int*)start, perm);
+    }
+    M3_HIP(ctx, hipGetLastError());
+    *perm_out = perm; *start_out = start;
+    return 0;
+}
+
+// tracer -> grid on cell-sorted device tracers: tc = host coordinates of the target node set, sc = of the node set whose cells the
+// tracers are sorted by (sort == target: pass the same arrays); out[k] device arrays of the target size
+static int m3_scatter_device(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Scatter& a, const double* const tc[3], const int tn[3],
+                             const double* const sc[3], const int sn[3], const int* start) {
+    if (a.nf < 1 || a.nf > M3_MAXF) return pl3_fail(ctx, "trac2grid (3-D): 1..8 fields per call");
+    for (int k = 0; k < a.nf; k++)
+        if (!(a.scheme[k] & (PL_AVG_ARITHMETIC | PL_AVG_GEOMETRIC))) return pl3_fail(ctx, "!!! ERROR INVALID AVERAGING SCHEME");
+    M3_TRY(m3_grid(ctx, v, M, "sc_tgrid", tc, tn, a.t));
+    // sort cells that can hold a tracer with target node i among its corners: the node's support reaches from its lower to its upper
+    // neighbour (extended by one spacing at the ends; everything beyond sits in the end cells of the sort, which are clamped)
+    std::vector<int> tab((size_t)2 * (tn[0] + tn[1] + tn[2]));
+    size_t off = 0; int* d_tab;
+    M3_TRY(m3_buf(ctx, v, M, "sc_ranges", tab.size(), &d_tab));
+    for (int d = 0; d < 3; d++) {
+        const int n = tn[d], ns = sn[d], nc = ns - 1;
+        a.ncs[d] = nc;
+        const bool same = n == ns && tc[d][0] == sc[d][0] && tc[d][n - 1] == sc[d][ns - 1];
+        const double s0 = sc[d][0], Ls = sc[d][ns - 1] - sc[d][0];
+        for (int i = 0; i < n; i++) {
+            int lo, hi;
+            if (same) { lo = i - 1; hi = i; }                      // the tracer's cell and the sort cell come from the same expression
+            else {
+                const double pl = i > 0 ? tc[d][i - 1] : tc[d][0] - (tc[d][1] - tc[d][0]);
+                const double ph = i < n - 1 ? tc[d][i + 1] : tc[d][n - 1] + (tc[d][n - 1] - tc[d][n - 2]);
+                lo = (int)std::floor(std::min(std::max((ns - 1) * (pl - s0) / Ls - 1e-6, -1.0), (double)ns));
+                hi = (int)std::floor(std::min(std::max((ns - 1) * (ph - s0) / Ls + 1e-6, -1.0), (double)ns));
+            }
+            tab[off + i] = std::min(std::max(lo, 0), nc - 1);
+            tab[off + n + i] = std::min(std::max(hi, 0), nc - 1);
+        }
+        a.lo[d] = d_tab + off; a.hi[d] = d_tab + off + n;
+        off += 2 * (size_t)n;
+    }
+    M3_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    a.start = start;
+    const long long N = (long long)tn[0] * tn[1] * tn[2];
+    if (a.nf == 1) hipLaunchKernelGGL(k_m3_scatter<1>, m3_blocks(N), dim3(256), 0, v.stream, a);
+    else if (a.nf == 2) hipLaunchKernelGGL(k_m3_scatter<2>, m3_blocks(N), dim3(256), 0, v.stream, a);
+    else if (a.nf == 6) hipLaunchKernelGGL(k_m3_scatter<6>, m3_blocks(N), dim3(256), 0, v.stream, a);
+    else hipLaunchKernelGGL(k_m3_scatter<0>, m3_blocks(N), dim3(256), 0, v.stream, a);
+    M3_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+static unsigned m3_logmask(int nf, const int* scheme) {
+    unsigned m = 0;
+    for (int k = 0; k < nf; k++) if ((scheme[k] & PL_AVG_GEOMETRIC) && !(scheme[k] & PL_AVG_ARITHMETIC)) m |= 1u << k;
+    return m;
+}
+
+// ---- host-array entry points ----------------------------------------------------------------------------------------
+extern "C" int pl3_trac2grid(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f, int64_t ld_f, int nf, const int* avgscheme,
+                             const double* zc, int nzc, const double* xc, int nxc, const double* yc, int nyc, double* const* out) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_trac2grid", v, &M));
+    if (n < 0 || (n > 0 && (!tr_x || !tr_f)) || !avgscheme || !zc || !xc || !yc || !out || ld_f < nf) return pl3_fail(ctx, "pl3_trac2grid: bad argument");
+    if (nf < 1 || nf > M3_MAXF) return pl3_fail(ctx, "pl3_trac2grid: 1..8 fields per call");
+    const double* tc[3] = {zc, xc, yc}; const int tn[3] = {nzc, nxc, nyc};
+    const size_t N = (size_t)nzc * nxc * nyc, nn = (size_t)std::max<int64_t>(n, 1);
+    double *aos, *xs, *vals, *dout;
+    M3_TRY(m3_buf(ctx, v, M, "h_aos", nn * (size_t)(3 + ld_f), &aos));
+    M3_TRY(m3_buf(ctx, v, M, "h_x", nn * 3, &xs));
+    M3_TRY(m3_buf(ctx, v, M, "h_val", nn * (size_t)nf, &vals));
+    M3_TRY(m3_buf(ctx, v, M, "h_out", N * (size_t)nf, &dout));
+    M3Grid sg;
+    M3_TRY(m3_grid(ctx, v, M, "h_sgrid", tc, tn, sg));
+    if (n > 0) {
+        M3_HIP(ctx, hipMemcpyAsync(aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, hipMemcpyAsync(aos + 3 * nn, tr_f, (size_t)n * ld_f * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    }
+    M3Pos p{{aos, aos + 1, aos + 2}, 3};
+    int *perm, *start;
+    M3_TRY(m3_sort(ctx, v, M, "h", n, p, sg, &perm, &start));
+    if (n > 0) {
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, (long long)n, (const double*)aos, 3ll, 1ll, 3, (const int*)perm, xs, (long long)nn, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, (long long)n, (const double*)(aos + 3 * nn), (long long)ld_f, 1ll, nf,
+                           (const int*)perm, vals, (long long)nn, m3_logmask(nf, avgscheme));
+    }
+    M3Scatter a{};
+    for (int d = 0; d < 3; d++) a.x[d] = xs + d * nn;
+    a.nf = nf;
+    for (int k = 0; k < nf; k++) { a.val[k] = vals + k * nn; a.scheme[k] = avgscheme[k]; a.out[k] = dout + k * N; }
+    M3_TRY(m3_scatter_device(ctx, v, M, a, tc, tn, tc, tn, start));
+    for (int k = 0; k < nf; k++) M3_HIP(ctx, hipMemcpyAsync(out[k], dout + k * N, N * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    return 0;
+}
+
+static int m3_fields_up(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, int nf, const double* const* fields, size_t GN, double** d) {
+    M3_TRY(m3_buf(ctx, v, M, name, GN * (size_t)nf, d));
+    for (int k = 0; k < nf; k++) M3_HIP(ctx, hipMemcpyAsync(*d + k * GN, fields[k], GN * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    return 0;
+}
+
+extern "C" int pl3_grid2trac(pl3_ctx* ctx, int64_t n, const double* tr_x, int nf, const double* const* fields, int gnz, int gnx, int gny,
+                             const double* gz, const double* gx, const double* gy, int method, double defval, int stop_on_error, double* out,
+                             int64_t ld_out, int64_t* n_outside) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_grid2trac", v, &M));
+    if (n < 0 || (n > 0 && (!tr_x || !out)) || !fields || !gz || !gx || !gy || ld_out < nf) return pl3_fail(ctx, "pl3_grid2trac: bad argument");
+    if (nf < 1 || nf > M3_MAXF) return pl3_fail(ctx, "pl3_grid2trac: 1..8 fields per call");
+    if (!(method & (PL_INTERP_LINEAR | PL_INTERP_NEAREST | PL_INTERP_VELDIV))) return pl3_fail(ctx, "pl3_grid2trac: unknown interpolation method");
+    if (!(method & (PL_INTERP_LINEAR | PL_INTERP_NEAREST)) && nf != 3) return pl3_fail(ctx, "grid2trac(): method INTERP_METHOD_VELDIV expects the fields (vz, vx, vy)");
+    const double* gc[3] = {gz, gx, gy}; const int gn[3] = {gnz, gnx, gny};
+    const size_t GN = (size_t)gnz * gnx * gny, nn = (size_t)std::max<int64_t>(n, 1);
+    double *dx, *df, *dout; unsigned long long* cnt;
+    M3_TRY(m3_buf(ctx, v, M, "h_aos", nn * 3, &dx));
+    M3_TRY(m3_buf(ctx, v, M, "h_gout", nn * (size_t)nf, &dout));
+    M3_TRY(m3_buf(ctx, v, M, "h_counter", (size_t)8, &cnt));
+    M3_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(*cnt), v.stream));
+    M3Gather a{};
+    M3_TRY(m3_grid(ctx, v, M, "h_ggrid", gc, gn, a.g));
+    M3_TRY(m3_fields_up(ctx, v, M, "h_gfields", nf, fields, GN, &df));
+    if (n > 0) M3_HIP(ctx, hipMemcpyAsync(dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.nf = nf; a.os = nf; a.method = method; a.defval = defval; a.accumulate = 0; a.nout = cnt;
+    for (int k = 0; k < nf; k++) { a.f[k] = df + k * GN; a.out[k] = dout + k; }
+    if (n > 0) hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
+    M3_HIP(ctx, hipGetLastError());
+    unsigned long long nout = 0;
+    M3_HIP(ctx, hipMemcpyAsync(&nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    if (n_outside) *n_outside = (int64_t)nout;
+    if (stop_on_error && nout > 0) return pl3_fail(ctx, "stopOnError in grid2trac");
+    if (n > 0) {
+        M3_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ld_out * sizeof(double), dout, (size_t)nf * sizeof(double), (size_t)nf * sizeof(double), (size_t)n,
+                                     hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    }
+    return 0;
+}
+
+extern "C" int pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int gnx, int gny, const double* gz, const double* gx, const double* gy,
+                       const double* vz, const double* vx, const double* vy, double tstep, double* v_out, double* x_out) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_rk4", v, &M));
+    if (n < 0 || (n > 0 && (!tr_x || !v_out || !x_out)) || !gz || !gx || !gy || !vz || !vx || !vy) return pl3_fail(ctx, "pl3_rk4: bad argument");
+    const double* gc[3] = {gz, gx, gy}; const int gn[3] = {gnz, gnx, gny}; const double* vel[3] = {vz, vx, vy};
+    const size_t GN = (size_t)gnz * gnx * gny, nn = (size_t)std::max<int64_t>(n, 1);
+    double *dx, *df;
+    M3_TRY(m3_buf(ctx, v, M, "h_aos", nn * 9, &dx));
+    M3Rk4 a{};
+    M3_TRY(m3_grid(ctx, v, M, "h_ggrid", gc, gn, a.g));
+    M3_TRY(m3_fields_up(ctx, v, M, "h_gfields", 3, vel, GN, &df));
+    if (n > 0) M3_HIP(ctx, hipMemcpyAsync(dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.dt = tstep; a.os = 3; a.fence = 0;
+    for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = dx + 3 * nn + d; a.vo[d] = dx + 6 * nn + d; }
+    if (n > 0) {
+        hipLaunchKernelGGL(k_m3_rk4, m3_blocks(n), dim3(256), 0, v.stream, a);
+        M3_HIP(ctx, hipGetLastError());
+        M3_HIP(ctx, hipMemcpyAsync(x_out, dx + 3 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, hipMemcpyAsync(v_out, dx + 6 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    }
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    return 0;
+}
+
+// ---- resident tracers -----------------------------------------------------------------------------------------------
+static int m3_node_grid(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Grid& g) { return m3_grid(ctx, v, M, "r_ngrid", v.coord, v.gn, g); }
+static int m3_need_tracers(pl3_ctx* ctx, Mic3* M, const char* who) {
+    return M->have ? 0 : pl3_fail(ctx, std::string(who) + ": no resident tracers (pl3_tracers_upload first)");
+}
+// (re-)sort the resident columns x | f | v by cell into the other of two buffers, which then becomes the resident one
+static int m3_resort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M) {
+    M3Grid sg;
+    M3_TRY(m3_node_grid(ctx, v, M, sg));
+    const long long n = M->n, cap = M->cap;
+    M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
+    M3Pos p{{M->x, M->x + cap, M->x + 2 * cap}, 1};
+    int *perm, *start;
+    M3_TRY(m3_sort(ctx, v, M, "r", n, p, sg, &perm, &start));
+    double* alt;
+    M3_TRY(m3_buf(ctx, v, M, M->x == (double*)M->bufs["r_a"] ? "r_b" : "r_a", (size_t)cap * (6 + M3_NFTRAC), &alt));
+    if (n > 0) {
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->x, 1ll, cap, 3, (const int*)perm, alt, cap, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->f, 1ll, cap, M3_NFTRAC, (const int*)perm, alt + 3 * cap, cap, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->v, 1ll, cap, 3, (const int*)perm, alt + (3 + M3_NFTRAC) * cap, cap, 0u);
+    }
+    M3_HIP(ctx, hipGetLastError());
+    M->x = alt; M->f = alt + 3 * cap; M->v = alt + (3 + M3_NFTRAC) * cap;
+    M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[3] = ms;
+    return 0;
+}
+
+extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_tracers_upload", v, &M));
+    if (n < 0 || (n > 0 && (!tr_x || !tr_f))) return pl3_fail(ctx, "pl3_tracers_upload: bad argument");
+    const long long cap = ((std::max<long long>(n, 1) + 63) / 64) * 64;
+    double *aos, *a;
+    M3_TRY(m3_buf(ctx, v, M, "h_aos", (size_t)cap * (3 + M3_NFTRAC), &aos));
+    M3_TRY(m3_buf(ctx, v, M, "r_a", (size_t)cap * (6 + M3_NFTRAC), &a));
+    M->n = n; M->cap = cap; M->x = a; M->f = a + 3 * cap; M->v = a + (3 + M3_NFTRAC) * cap; M->have = true;
+    M3_HIP(ctx, hipMemsetAsync(a, 0, (size_t)cap * (6 + M3_NFTRAC) * sizeof(double), v.stream));
+    if (n > 0) {
+        M3_HIP(ctx, hipMemcpyAsync(aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, hipMemcpyAsync(aos + 3 * cap, tr_f, (size_t)n * M3_NFTRAC * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, (long long)n, (const double*)aos, 3ll, 1ll, 3, (const int*)nullptr, M->x, cap, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, (long long)n, (const double*)(aos + 3 * cap), (long long)M3_NFTRAC, 1ll, M3_NFTRAC,
+                           (const int*)nullptr, M->f, cap, 0u);
+        M3_HIP(ctx, hipGetLastError());
+    }
+    return m3_resort(ctx, v, M);
+}
+
+static int m3_down(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const double* src, int ncol, double* host) {
+    double* aos;
+    M3_TRY(m3_buf(ctx, v, M, "h_aos", (size_t)M->cap * (3 + M3_NFTRAC), &aos));
+    if (M->n > 0) {
+        hipLaunchKernelGGL(k_m3_to_aos, m3_blocks(M->n), dim3(256), 0, v.stream, M->n, src, M->cap, ncol, aos);
+        M3_HIP(ctx, hipGetLastError());
+        M3_HIP(ctx, hipMemcpyAsync(host, aos, (size_t)M->n * ncol * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    }
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    return 0;
+}
+extern "C" int pl3_tracers_download(pl3_ctx* ctx, int64_t n, double* tr_x, double* tr_f) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_tracers_download", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_tracers_download"));
+    if (n != M->n || (n > 0 && (!tr_x || !tr_f))) return pl3_fail(ctx, "pl3_tracers_download: n does not match pl3_tracers_count");
+    M3_TRY(m3_down(ctx, v, M, M->x, 3, tr_x));
+    return m3_down(ctx, v, M, M->f, M3_NFTRAC, tr_f);
+}
+extern "C" int pl3_tracers_count(pl3_ctx* ctx, int64_t* n) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_tracers_count", v, &M));
+    if (!n) return pl3_fail(ctx, "pl3_tracers_count: NULL argument");
+    *n = M->have ? M->n : 0;
+    return 0;
+}
+extern "C" int pl3_tracers_census(pl3_ctx* ctx, int64_t ncell, int32_t* counts) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_tracers_census", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_tracers_census"));
+    const long long m = (long long)(v.gn[0] - 1) * (v.gn[1] - 1) * (v.gn[2] - 1);
+    if (ncell != m || !counts) return pl3_fail(ctx, "pl3_tracers_census: counts must hold (nz-1)(nx-1)(ny-1) cells");
+    int* d;
+    M3_TRY(m3_buf(ctx, v, M, "r_census", (size_t)m, &d));
+    hipLaunchKernelGGL(k_m3_census, m3_blocks(m), dim3(256), 0, v.stream, (int)m, (const int*)M->bufs["r_start"], d);
+    M3_HIP(ctx, hipGetLastError());
+    M3_HIP(ctx, hipMemcpyAsync(counts, d, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    return 0;
+}
+extern "C" int pl3_get_tracer_velocity(pl3_ctx* ctx, int64_t n, double* out) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_get_tracer_velocity", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_get_tracer_velocity"));
+    if (n != M->n || (n > 0 && !out)) return pl3_fail(ctx, "pl3_get_tracer_velocity: n does not match pl3_tracers_count");
+    return m3_down(ctx, v, M, M->v, 3, out);
+}
+extern "C" int pl3_resident_times(pl3_ctx* ctx, double ms[4]) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_times", v, &M));
+    for (int k = 0; k < 4; k++) ms[k] = M->ms[k];
+    return 0;
+}
+
+extern "C" int pl3_resident_props(pl3_ctx* ctx, int tdep_rho, int tdep_eta, double tref, double etamin, double etamax) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_props", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_props"));
+    if (M->n > 0) hipLaunchKernelGGL(k_m3_props, m3_blocks(M->n), dim3(256), 0, v.stream, M->n, M->f, M->cap, tdep_rho, tdep_eta, tref, etamin, etamax);
+    M3_HIP(ctx, hipGetLastError());
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    return 0;
+}
+
+// scatter of resident columns (val: device pointers, logarithms taken here) to a node set; dout: device (nf x N)
+static int m3_resident_scatter(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, int nf, const double* const* col, const int* scheme, const double* const tc[3],
+                               const int tn[3], double* dout) {
+    const size_t N = (size_t)tn[0] * tn[1] * tn[2];
+    M3Scatter a{};
+    double* lg;
+    M3_TRY(m3_buf(ctx, v, M, "r_log", (size_t)M->cap * M3_MAXF, &lg));
+    for (int d = 0; d < 3; d++) a.x[d] = M->x + d * M->cap;
+    a.nf = nf;
+    for (int k = 0; k < nf; k++) {
+        a.scheme[k] = scheme[k]; a.out[k] = dout + k * N; a.val[k] = col[k];
+        if (m3_logmask(1, scheme + k) && M->n > 0) {
+            hipLaunchKernelGGL(k_m3_take, m3_blocks(M->n), dim3(256), 0, v.stream, M->n, col[k], 1ll, 0ll, 1, (const int*)nullptr, lg + k * M->cap, M->cap, 1u);
+            a.val[k] = lg + k * M->cap;
+        }
+    }
+    return m3_scatter_device(ctx, v, M, a, tc, tn, v.coord, v.gn, (const int*)M->bufs["r_start"]);
+}
+
+extern "C" int pl3_resident_trac2grid(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* zc, int nzc, const double* xc,
+                                      int nxc, const double* yc, int nyc, double* const* out) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_trac2grid", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_trac2grid"));
+    if (nf < 1 || nf > M3_MAXF || !columns || !avgscheme || !zc || !xc || !yc || !out) return pl3_fail(ctx, "pl3_resident_trac2grid: bad argument (1..8 fields per call)");
+    const double* tc[3] = {zc, xc, yc}; const int tn[3] = {nzc, nxc, nyc};
+    const size_t N = (size_t)nzc * nxc * nyc;
+    const double* col[M3_MAXF];
+    for (int k = 0; k < nf; k++) {
+        if (columns[k] < 0 || columns[k] >= M3_NFTRAC) return pl3_fail(ctx, "pl3_resident_trac2grid: tracer column out of range");
+        col[k] = M->f + (long long)columns[k] * M->cap;
+    }
+    double* dout;
+    M3_TRY(m3_buf(ctx, v, M, "r_out", N * (size_t)nf, &dout));
+    M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
+    M3_TRY(m3_resident_scatter(ctx, v, M, nf, col, avgscheme, tc, tn, dout));
+    M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
+    for (int k = 0; k < nf; k++) M3_HIP(ctx, hipMemcpyAsync(out[k], dout + k * N, N * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[0] = ms;
+    return 0;
+}
+
+// Temperature to the tracers (pylamp2.py:445-480): absolute != 0: T = interpolation of `field` (the first step); else T += interpolation
+// (field = T_new - T_old on the nodes) and, with subgrid != 0, the subgrid-diffusion correction with tstep.  A tracer outside the
+// grid is an error, as with stopOnError in 2-D.
+extern "C" int pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* field, int subgrid, double tstep) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_temp_to_tracers", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_temp_to_tracers"));
+    if (!field) return pl3_fail(ctx, "pl3_resident_temp_to_tracers: NULL field");
+    const long long n = M->n, cap = M->cap;
+    const size_t GN = (size_t)v.gn[0] * v.gn[1] * v.gn[2];
+    double *df, *w, *dnode; unsigned long long* cnt;
+    M3_TRY(m3_buf(ctx, v, M, "r_tfield", GN, &df));
+    M3_TRY(m3_buf(ctx, v, M, "r_twork", (size_t)cap * 3, &w));
+    M3_TRY(m3_buf(ctx, v, M, "r_tnode", GN, &dnode));
+    M3_TRY(m3_buf(ctx, v, M, "h_counter", (size_t)8, &cnt));
+    M3_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(*cnt), v.stream));
+    M3_HIP(ctx, hipMemcpyAsync(df, field, GN * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    M3Gather a{};
+    M3_TRY(m3_node_grid(ctx, v, M, a.g));
+    double* T = M->f + M3_TMP * cap;
+    const bool sub = !absolute && subgrid;
+    M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
+    if (sub) M3_HIP(ctx, hipMemcpyAsync(w, T, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, v.stream));      // T_old
+    a.n = n; a.p = M3Pos{{M->x, M->x + cap, M->x + 2 * cap}, 1}; a.nf = 1; a.os = 1; a.method = PL_INTERP_LINEAR; a.defval = NAN;
+    a.accumulate = absolute ? 0 : 1; a.nout = cnt; a.f[0] = df; a.out[0] = T;
+    if (n > 0) hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
+    if (sub && n > 0) {
+        double inv2 = 0.0;
+        for (int d = 0; d < 3; d++) { const double h = (v.coord[d][v.gn[d] - 1] - v.coord[d][0]) / (v.gn[d] - 1); inv2 += (2.0 / h) * (2.0 / h); }
+        hipLaunchKernelGGL(k_m3_subgrid, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->f, cap, (const double*)w, inv2, tstep, w + cap, w + 2 * cap);
+        const double* col[1] = {w + 2 * cap}; const int sch[1] = {PL_AVG_ARITHMETIC | PL_AVG_WEIGHTED};
+        M3_TRY(m3_resident_scatter(ctx, v, M, 1, col, sch, v.coord, v.gn, dnode));
+        a.f[0] = dnode; a.out[0] = w; a.accumulate = 0;                       // the correction back on the tracers
+        hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
+        hipLaunchKernelGGL(k_m3_sub, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)(w + cap), (const double*)w, T);
+    }
+    M3_HIP(ctx, hipGetLastError());
+    M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
+    unsigned long long nout = 0;
+    M3_HIP(ctx, hipMemcpyAsync(&nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[1] = ms;
+    if (nout > 0) return pl3_fail(ctx, "stopOnError in grid2trac");
+    return 0;
+}
+
+// RK4 on the padded centre grid (nz+1, nx+1, ny+1), fence (pylamp2.py:558-572, length = the node grid's extent), re-sort
+extern "C" int pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
+                                const double* vy, double tstep, int fence) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_rk4", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_rk4"));
+    if (!gz || !gx || !gy || !vz || !vx || !vy) return pl3_fail(ctx, "pl3_resident_rk4: bad argument");
+    const double* gc[3] = {gz, gx, gy}; const int gn[3] = {v.gn[0] + 1, v.gn[1] + 1, v.gn[2] + 1}; const double* vel[3] = {vz, vx, vy};
+    const size_t GN = (size_t)gn[0] * gn[1] * gn[2];
+    const long long n = M->n, cap = M->cap;
+    double* df;
+    M3Rk4 a{};
+    M3_TRY(m3_grid(ctx, v, M, "r_vgrid", gc, gn, a.g));
+    M3_TRY(m3_fields_up(ctx, v, M, "r_vfields", 3, vel, GN, &df));
+    a.n = n; a.p = M3Pos{{M->x, M->x + cap, M->x + 2 * cap}, 1}; a.dt = tstep; a.os = 1; a.fence = fence ? 1 : 0; a.eps = 1.0 / 1024.0;   // EPS of pylamp_const.py
+    for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = M->x + d * cap; a.vo[d] = M->v + d * cap; a.L[d] = v.coord[d][v.gn[d] - 1]; }
+    M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
+    if (n > 0) hipLaunchKernelGGL(k_m3_rk4, m3_blocks(n), dim3(256), 0, v.stream, a);       // in place: a tracer reads its position before it writes
+    M3_HIP(ctx, hipGetLastError());
+    M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[2] = ms;
+    return m3_resort(ctx, v, M);
+}

@@ -69,6 +69,10 @@ class Context3:
         self.check(self.lib.pl3_comm_stats(self.handle(), v, 1 if reset else 0))
         return int(v[0]), int(v[1])
 
+    def nranks_attached(self):
+        """True once attach_comm has made this context one block of several."""
+        return getattr(self, "layout", None) is not None and int(np.prod(self.layout)) > 1
+
     def handle(self):
         """Native handle for a library call; a closed context raises instead of handing NULL to C."""
         if self.h is None:
@@ -277,3 +281,395 @@ class VirtualCluster3:
             c.close()
         self.pool.shutdown(wait=False)
         self.lib.pl_local_group_destroy(self.group)
+
+
+# =====================================================================================================================
+# 3-D marker-in-cell: tracers, advection and a time step (one rank)
+# =====================================================================================================================
+# The reference's marker code is 2-D (pylamp_trac.py); these are its functions extended by one axis.  tr_x is (n, 3) in
+# [z, x, y] order, tr_f has the 2-D columns of pylamp_const.py, grid arrays are C-order (nz, nx, ny).
+from .pylamp_const import (NFTRAC, EPS, TR_RHO, TR_ETA, TR_TMP, TR_HCD, TR_HCP, TR_MAT, TR_IHT, TR__ID)  # noqa: E402,F401
+
+INTERP_AVG_ARITHMETIC = 1
+INTERP_AVG_GEOMETRIC = 2
+INTERP_AVG_WEIGHTED = 4
+INTERP_AVG_ARITHW = INTERP_AVG_ARITHMETIC + INTERP_AVG_WEIGHTED
+INTERP_AVG_GEOMW = INTERP_AVG_GEOMETRIC + INTERP_AVG_WEIGHTED
+INTERP_METHOD_ELEM = 4
+INTERP_METHOD_NEAREST = 8
+INTERP_METHOD_LINEAR = 16
+INTERP_METHOD_VELDIV = 32
+SECINYR = 60 * 60 * 24 * 365.25
+
+_MAXF = 8
+_carrier = None
+
+
+def _mic_ctx(ctx):
+    """The marker kernels need a context only for its device and stream: any Context3 will do, a tiny one is kept."""
+    global _carrier
+    if ctx is not None:
+        return ctx
+    if _carrier is None or _carrier.h is None:
+        _carrier = Context3([5, 5, 5], [np.linspace(0, 1, 5)] * 3)
+    return _carrier
+
+
+def _x3(tr_x):
+    x = _lib.f64(tr_x)
+    if x.ndim != 2 or x.shape[1] != DIM3:
+        raise Exception("tracer positions must be (n, 3) in [z, x, y] order")
+    return x
+
+
+def trac2grid(tr_x, tr_f, mesh, grid, gridfield, nx, distweight=None, avgscheme=None, method=INTERP_METHOD_ELEM, debug=False,
+              ctx=None):
+    """Average tracer values onto the node set `grid` = [z, x, y] coordinates, writing gridfield[k][:, :, :] in place:
+    pylamp_trac.trac2grid (method ELEM) extended by one axis.  Two calls with the same input agree bitwise."""
+    if avgscheme is None:
+        avgscheme = [INTERP_AVG_ARITHW] * len(gridfield)
+    if len(gridfield) != tr_f.shape[1] or len(avgscheme) != len(gridfield) or tr_x.shape[0] != tr_f.shape[0]:
+        raise Exception("trac2grid: tr_f, gridfield and avgscheme do not match")
+    if not (method & INTERP_METHOD_ELEM):
+        raise Exception("trac2grid: only INTERP_METHOD_ELEM is implemented on the GPU")
+    ctx = _mic_ctx(ctx)
+    txc = _x3(tr_x)
+    n = txc.shape[0]
+    g = [_lib.f64(grid[d]) for d in range(3)]
+    shp = tuple(int(v) for v in nx)
+    if tuple(c.size for c in g) != shp:
+        raise Exception("trac2grid: grid arrays do not match nx")
+    nf = len(gridfield)
+    for k0 in range(0, nf, _MAXF):
+        k1 = min(nf, k0 + _MAXF)
+        sub = _lib.f64(tr_f[:, k0:k1])
+        outs = [np.empty(shp) for _ in range(k1 - k0)]
+        op = (_lib.c_double_p * (k1 - k0))(*[_lib.dptr(a) for a in outs])
+        sch = (C.c_int * (k1 - k0))(*[int(s) for s in avgscheme[k0:k1]])
+        ctx.check(ctx.lib.pl3_trac2grid(ctx.handle(), n, _lib.dptr(txc), _lib.dptr(sub), k1 - k0, k1 - k0, sch, _lib.dptr(g[0]), shp[0],
+                                        _lib.dptr(g[1]), shp[1], _lib.dptr(g[2]), shp[2], op))
+        for k in range(k0, k1):
+            gridfield[k][...] = outs[k - k0]
+
+
+def grid2trac(tr_x, tr_f, grid, gridfield, nx, defval=np.nan, method=INTERP_METHOD_LINEAR, stopOnError=False, ctx=None):
+    """Interpolate gridfield (list of (nz, nx, ny) arrays) to the tracers, writing tr_f in place.  LINEAR is trilinear, NEAREST
+    the nearest of the eight corners, VELDIV the divergence-conserving interpolation of (vz, vx, vy).
+    Out-of-grid tracers get defval in every column."""
+    nf = len(gridfield)
+    if nf != tr_f.shape[1] or tr_x.shape[0] != tr_f.shape[0]:
+        raise Exception("grid2trac: tr_f and gridfield do not match")
+    if not method & (INTERP_METHOD_LINEAR | INTERP_METHOD_NEAREST | INTERP_METHOD_VELDIV):
+        raise Exception("grid2trac: unknown interpolation method")
+    ctx = _mic_ctx(ctx)
+    txc = _x3(tr_x)
+    n = txc.shape[0]
+    shp = tuple(int(v) for v in nx)
+    g = [_lib.f64(grid[d]) for d in range(3)]
+    out = np.empty((n, nf))
+    nout = C.c_int64(0); total = 0
+    for k0 in range(0, nf, _MAXF):
+        k1 = min(nf, k0 + _MAXF)
+        fl = [_f3(gridfield[k], shp) for k in range(k0, k1)]
+        fp = (_lib.c_double_p * (k1 - k0))(*[_lib.dptr(a) for a in fl])
+        sub = np.empty((n, k1 - k0))
+        ctx.check(ctx.lib.pl3_grid2trac(ctx.handle(), n, _lib.dptr(txc), k1 - k0, fp, shp[0], shp[1], shp[2], _lib.dptr(g[0]), _lib.dptr(g[1]),
+                                        _lib.dptr(g[2]), int(method), float(defval), 1 if stopOnError else 0, _lib.dptr(sub), k1 - k0,
+                                        C.byref(nout)))
+        out[:, k0:k1] = sub
+        total = max(total, nout.value)
+    if total > 0:
+        print("!!! Warning, grid2trac(): Using default value for extrapolation in ", total, "tracers")
+    tr_f[:, :] = out
+
+
+def RK(tr_x, grids, vels, nx, tstep, order=4, ctx=None):
+    """Runge-Kutta advection; returns (vel_final, tr_x_final), both (n, 3).  grids / vels live on the padded
+    (nz+1, nx+1, ny+1) cell-centre grid (advection_velocity); the reference's weights (1,1,1,1)/6 are kept."""
+    if order != 4:
+        raise Exception("RK: only order=4 is functional (as in 2-D)")
+    if len(nx) != 3:
+        raise Exception("RK: nx must have three entries")
+    ctx = _mic_ctx(ctx)
+    shp = tuple(int(v) + 1 for v in nx)
+    txc = _x3(tr_x)
+    n = txc.shape[0]
+    g = [_lib.f64(grids[d]) for d in range(3)]
+    if tuple(c.size for c in g) != shp:
+        raise Exception("RK: velocity grids must have shape (nz+1, nx+1, ny+1)")
+    V = [_f3(vels[d], shp) for d in range(3)]
+    v = np.empty((n, 3)); xn = np.empty((n, 3))
+    ctx.check(ctx.lib.pl3_rk4(ctx.handle(), n, _lib.dptr(txc), shp[0], shp[1], shp[2], *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V],
+                              float(tstep), _lib.dptr(v), _lib.dptr(xn)))
+    return v, xn
+
+
+def gridmp_of(grid):
+    """Midpoint coordinates with one extrapolated extra entry per axis (pylamp2.py:92-95)."""
+    out = []
+    for c in grid:
+        c = np.asarray(c, dtype=np.float64)
+        m = (c[1:] + c[:-1]) / 2
+        out.append(np.append(m, m[-1] + (m[-1] - m[-2])))
+    return out
+
+
+def advection_velocity(newvel, gridmp, nx):
+    """Cell-centred velocities on the padded (nz+1, nx+1, ny+1) grid (pylamp2.py:491-545 extended by one axis): every
+    component is averaged along its own axis; free-slip ghosts -- normal component mirrored with a sign flip, tangential
+    copied -- wall by wall in the order z0, x0, y0, zL, xL, yL.  Returns ([gz, gx, gy], [Vz, Vx, Vy])."""
+    shp = tuple(int(v) + 1 for v in nx)
+    vz, vx, vy = newvel
+    V = [np.zeros(shp) for _ in range(3)]
+    V[0][1:-1, 1:-1, 1:-1] = 0.5 * (vz[1:, :-1, :-1] + vz[:-1, :-1, :-1])
+    V[1][1:-1, 1:-1, 1:-1] = 0.5 * (vx[:-1, 1:, :-1] + vx[:-1, :-1, :-1])
+    V[2][1:-1, 1:-1, 1:-1] = 0.5 * (vy[:-1, :-1, 1:] + vy[:-1, :-1, :-1])
+    g = [np.insert(np.asarray(m, dtype=np.float64), 0, m[0] - (m[1] - m[0])) for m in gridmp]
+    for ghost, inner in ((0, 1), (-1, -2)):
+        for axis in range(3):
+            for comp in range(3):
+                dst = [slice(None)] * 3; src = [slice(None)] * 3
+                dst[axis] = ghost; src[axis] = inner
+                V[comp][tuple(dst)] = -V[comp][tuple(src)] if comp == axis else V[comp][tuple(src)]
+    return g, V
+
+
+class Options3:
+    """Options of pylamp2.py:37-77 that Simulation3 honours (the 2-D driver's names)."""
+
+    def __init__(self, **kw):
+        self.do_heatdiff = True
+        self.do_subgrid_heatdiff = True
+        self.tdep_rho = True
+        self.tdep_eta = True
+        self.etamin, self.etamax, self.Tref = 1e17, 1e23, 1623.0
+        self.tstep_adv_max = 50e9 * SECINYR; self.tstep_adv_min = 50e-9 * SECINYR
+        self.tstep_dif_max = 50e9 * SECINYR; self.tstep_dif_min = 50e-9 * SECINYR
+        self.tstep_modifier = 0.67
+        self.bcstokes = [BC_TYPE_FREESLIP] * 6
+        self.bcheat = [BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW, BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW]
+        self.bcheatvals = [273.0, 0.0, 0.0, 1623.0, 0.0, 0.0]
+        self.stokes_rtol, self.stokes_maxit = DEFAULT_RTOL, DEFAULT_MAXIT
+        self.heat_rtol, self.heat_maxit = 1e-12, 2000
+        self.grav = None
+        # parts of the 2-D step that do not exist in 3-D yet: anything but these values is rejected by name
+        self.tracdens, self.tracdens_min = 0, 0
+        self.tracs_fence_enabled = True
+        self.surface_stabilization = False
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise Exception("unknown option " + k)
+            setattr(self, k, v)
+
+
+class Simulation3:
+    """The 3-D counterpart of driver.Simulation: tracers stay on the GPU, step() follows the loop of pylamp2.py:290-581 with a
+    third axis -- properties, tracer->grid, Stokes, time step, heat, grid->tracer (+ subgrid diffusion), RK4, fence.  One rank,
+    regular grid, all walls free-slip.  Not built: injection, the fence-off deletion path, surface stabilisation, non-uniform
+    grids for the markers, several ranks -- each is rejected with an error that names it."""
+
+    def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
+        self.nx = [int(v) for v in nx]
+        self.L = [float(v) for v in L]
+        if len(self.nx) != 3 or len(self.L) != 3:
+            raise Exception("Simulation3: nx and L need three entries (z, x, y)")
+        if grid is not None:
+            for d in range(3):
+                if not np.allclose(np.asarray(grid[d], dtype=np.float64), np.linspace(0, self.L[d], self.nx[d]), rtol=0, atol=1e-9 * self.L[d]):
+                    raise Exception("Simulation3: non-uniform grids are not supported by the 3-D markers")
+        self.grid = [np.linspace(0, self.L[d], self.nx[d]) for d in range(3)]          # pylamp2.py:90
+        self.gridmp = gridmp_of(self.grid)
+        self.opt = options or Options3()
+        o = self.opt
+        if o.tracdens_min != 0:
+            raise Exception("Simulation3: tracer injection (tracdens_min > 0) is not supported in 3-D")
+        if not o.tracs_fence_enabled:
+            raise Exception("Simulation3: the fence-off deletion path (tracs_fence_enabled = False) is not supported in 3-D")
+        if o.surface_stabilization:
+            raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
+        if any(int(b) != BC_TYPE_FREESLIP for b in o.bcstokes):
+            raise Exception("Simulation3: all Stokes walls are free-slip")
+        self.ctx = Context3(self.nx, self.grid, device)
+        self.it = 0
+        self.totaltime = 0.0
+        self.last = None
+        self.ntrac = 0
+        self.fields = {}
+        self._newtemp = None
+        if tr_x is not None:
+            self.upload(tr_x, tr_f)
+
+    # -- tracer state ------------------------------------------------------------------------------------------------
+    def _lib_call(self, name, *args):
+        if self.ctx.nranks_attached():
+            raise Exception("Simulation3: several ranks are not supported by the 3-D markers")
+        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.handle(), *args))
+
+    def upload(self, tr_x, tr_f):
+        tr_x = _x3(tr_x); tr_f = _lib.f64(tr_f)
+        if tr_f.shape != (tr_x.shape[0], NFTRAC):
+            raise Exception("tracer arrays must be (n, 3) and (n, %d)" % NFTRAC)
+        self.ntrac = tr_x.shape[0]
+        self._lib_call("pl3_tracers_upload", self.ntrac, _lib.dptr(tr_x), _lib.dptr(tr_f))
+
+    def count(self):
+        n = C.c_int64()
+        self._lib_call("pl3_tracers_count", C.byref(n))
+        self.ntrac = n.value
+        return n.value
+
+    def tracers(self):
+        """(tr_x, tr_f) in the resident (cell-sorted) order; TR__ID identifies a tracer."""
+        n = self.count()
+        tr_x = np.empty((n, 3)); tr_f = np.empty((n, NFTRAC))
+        self._lib_call("pl3_tracers_download", n, _lib.dptr(tr_x), _lib.dptr(tr_f))
+        return tr_x, tr_f
+
+    def tracer_velocity(self):
+        """(n, 3) velocities of the last advection, in the order tracers() returns."""
+        n = self.count()
+        v = np.empty((n, 3))
+        self._lib_call("pl3_get_tracer_velocity", n, _lib.dptr(v))
+        return v
+
+    def census(self):
+        """Tracers per cell, (nz-1, nx-1, ny-1): a by-product of the sort."""
+        cnt = np.empty([v - 1 for v in self.nx], dtype=np.int32)
+        self._lib_call("pl3_tracers_census", cnt.size, cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+        return cnt
+
+    def field(self, name):
+        """A grid field of the last step: rho, etas, etan, cp, T, H, mat, kz, kx, ky, velz, velx, vely, pres, temp."""
+        if name not in self.fields:
+            raise Exception("Simulation3.field: no field '%s' (have: %s)" % (name, ", ".join(sorted(self.fields))))
+        return self.fields[name]
+
+    def stage_times(self):
+        ms = (C.c_double * 4)()
+        self._lib_call("pl3_resident_times", ms)
+        return dict(scatter=ms[0], gather=ms[1], rk4=ms[2], sort=ms[3])
+
+    # -- the marker stages of a step, one at a time (the same kernels as the module-level functions) ------------------
+    def update_properties(self):
+        o = self.opt
+        self._lib_call("pl3_resident_props", int(o.tdep_rho), int(o.tdep_eta), float(o.Tref), float(o.etamin), float(o.etamax))
+
+    def scatter(self, columns, avgscheme, grid=None):
+        """Tracer columns -> the node set `grid` (default: the nodes); returns the list of (nz, nx, ny) arrays."""
+        g = [_lib.f64(c) for c in (grid or self.grid)]
+        shp = tuple(c.size for c in g)
+        nf = len(columns)
+        outs = [np.empty(shp) for _ in range(nf)]
+        op = (_lib.c_double_p * nf)(*[_lib.dptr(a) for a in outs])
+        self._lib_call("pl3_resident_trac2grid", nf, (C.c_int * nf)(*[int(c) for c in columns]), (C.c_int * nf)(*[int(s) for s in avgscheme]),
+                       _lib.dptr(g[0]), shp[0], _lib.dptr(g[1]), shp[1], _lib.dptr(g[2]), shp[2], op)
+        return outs
+
+    def scatter_fields(self):
+        """Properties + the field list of a step: nodes (rho, etas, cp, T, H, mat), cell centres (etan) and the three mixed sets
+        of the conductivity (k_d at the midpoints along d and the nodes along the other two axes, cf. pylamp2.py:312-313)."""
+        self.update_properties()
+        g, mp, f = self.grid, self.gridmp, {}
+        A, G = INTERP_AVG_ARITHW, INTERP_AVG_GEOMW
+        if self.opt.do_heatdiff:
+            f["rho"], f["etas"], f["cp"], f["T"], f["H"], f["mat"] = self.scatter([TR_RHO, TR_ETA, TR_HCP, TR_TMP, TR_IHT, TR_MAT], [A, G, A, A, A, A])
+            f["etan"], = self.scatter([TR_ETA], [G], mp)
+            f["kz"], = self.scatter([TR_HCD], [A], [mp[0], g[1], g[2]])
+            f["kx"], = self.scatter([TR_HCD], [A], [g[0], mp[1], g[2]])
+            f["ky"], = self.scatter([TR_HCD], [A], [g[0], g[1], mp[2]])
+        else:
+            f["rho"], f["etas"] = self.scatter([TR_RHO, TR_ETA], [A, G])
+            f["etan"], = self.scatter([TR_ETA], [INTERP_AVG_GEOMETRIC], mp)            # unweighted, as pylamp2.py:322
+        return f
+
+    def temp_to_tracers(self, field, absolute, tstep=0.0):
+        """Nodal temperature (absolute) or its increment to the tracers; the increment with subgrid diffusion if enabled."""
+        self._lib_call("pl3_resident_temp_to_tracers", 1 if absolute else 0, _lib.dptr(_f3(field, self.nx)),
+                       0 if absolute or not self.opt.do_subgrid_heatdiff else 1, float(tstep))
+
+    def advect(self, grids, vels, tstep):
+        shp = tuple(v + 1 for v in self.nx)
+        g = [_lib.f64(c) for c in grids]; V = [_f3(a, shp) for a in vels]
+        self._lib_call("pl3_resident_rk4", *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V], float(tstep), 1)
+
+    # -- one time step -----------------------------------------------------------------------------------------------
+    def step(self):
+        o = self.opt
+        self.it += 1
+        dx = [self.L[d] / (self.nx[d] - 1) for d in range(3)]
+        f = self.scatter_fields()
+        if o.do_heatdiff:
+            if self.it > 1:                      # pylamp2.py:327-331: the walls keep the solved temperature
+                nt = self._newtemp
+                for d in range(3):
+                    for w in (0, -1):
+                        s = [slice(None)] * 3; s[d] = w
+                        f["T"][tuple(s)] = nt[tuple(s)]
+            diffusivity = f["kz"] / (f["rho"] * f["cp"])
+            tstep_temp = o.tstep_modifier * np.min(dx) ** 2 / np.max(2 * diffusivity)
+            tstep_temp = max(min(tstep_temp, o.tstep_dif_max), o.tstep_dif_min)
+        A, _ = makeStokesMatrix(self.nx, self.grid, f["etas"], f["etan"], f["rho"], grav=o.grav, ctx=self.ctx)
+        x = solve(A, rtol=o.stokes_rtol, maxit=o.stokes_maxit)
+        newvel, pres = x2vp(x, self.nx)
+        tstep_stokes = o.tstep_modifier * np.min(dx) / max(np.max(v) for v in newvel)
+        tstep_stokes = max(min(tstep_stokes, o.tstep_adv_max), o.tstep_adv_min)
+        if o.do_heatdiff:
+            limiter = "H" if tstep_temp < tstep_stokes else "S"
+            tstep = min(tstep_temp, tstep_stokes)
+        else:
+            tstep, limiter = tstep_stokes, "S"
+        rep = dict(it=self.it, tstep=tstep, limiter=limiter, stokes=A.last_stats, heat=None)
+        f.update(velz=newvel[0], velx=newvel[1], vely=newvel[2], pres=pres)
+        if o.do_heatdiff:
+            H, _ = makeDiffusionMatrix(self.nx, self.grid, self.gridmp, f["T"], [f["kz"], f["kx"], f["ky"]], f["cp"], f["rho"], f["H"],
+                                       o.bcheat, o.bcheatvals, tstep, ctx=self.ctx)
+            newtemp = x2t(solve_heat(H, rtol=o.heat_rtol, maxit=o.heat_maxit), self.nx).copy()
+            rep["heat"] = H.last_stats
+            if self.it == 1:
+                self.temp_to_tracers(newtemp, True)
+            else:
+                self.temp_to_tracers(newtemp - f["T"], False, tstep)
+            self._newtemp = newtemp
+            f["temp"] = newtemp
+        grids, vels = advection_velocity(newvel, self.gridmp, self.nx)
+        self.advect(grids, vels, tstep)
+        self.totaltime += tstep
+        rep["time"] = self.totaltime; rep["ntrac"] = self.count()
+        self.fields = f
+        self.last = rep
+        return rep
+
+    def write_snapshot(self, outdir="out"):
+        """griddata.NNNNNN.npz / tracs.NNNNNN.npz with the keys of the 2-D snapshots (pylamp2.py:637-650) plus the third axis."""
+        import os
+        f = self.fields
+        temp = f["temp"] if "temp" in f else f["velx"] * 0.0
+        tr_x, tr_f = self.tracers(); tr_v = self.tracer_velocity()
+        os.makedirs(outdir, exist_ok=True)
+        np.savez(os.path.join(outdir, "griddata.{:06d}.npz".format(self.it)), gridz=self.grid[0], gridx=self.grid[1], gridy=self.grid[2],
+                 velz=f["velz"], velx=f["velx"], vely=f["vely"], pres=f["pres"], rho=f["rho"], temp=temp, tstep=self.it, time=self.totaltime)
+        np.savez(os.path.join(outdir, "tracs.{:06d}.npz".format(self.it)), tr_x=tr_x, tr_f=tr_f, tr_v=tr_v, tstep=self.it, time=self.totaltime)
+
+    def close(self):
+        self.ctx.close()
+
+
+def falling_sphere_tracers(nx, L, rng, per_axis=2, radius=0.15, centre=(0.3, 0.5, 0.5), jitter=0.2):
+    """A dense, stiff sphere (3400 kg/m3, 1e22 Pa s) in a lighter, weaker fluid (3300 kg/m3, 1e19 Pa s): the 3-D counterpart of
+    the reference's falling-block model (pylamp2.py:172-183).  Tracers sit on a jittered regular lattice of per_axis^3 per
+    cell, so that no cell starts empty; radius and centre are fractions of L[0] and of L."""
+    ax = []
+    for d in range(3):
+        m = per_axis * (int(nx[d]) - 1)
+        ax.append((np.arange(m) + 0.5) * (float(L[d]) / m))
+    Z, X, Y = np.meshgrid(*ax, indexing="ij")
+    tr_x = np.stack([Z.ravel(), X.ravel(), Y.ravel()], axis=1)
+    n = tr_x.shape[0]
+    tr_x += rng.uniform(-jitter, jitter, (n, 3)) * np.array([float(L[d]) / (per_axis * (int(nx[d]) - 1)) for d in range(3)])
+    tr_f = np.zeros((n, NFTRAC))
+    tr_f[:, TR__ID] = np.arange(n)
+    tr_f[:, 6] = 3300; tr_f[:, TR_MAT] = 1; tr_f[:, 10] = 1e19            # TR_RH0, TR_ET0
+    r2 = sum((tr_x[:, d] - centre[d] * float(L[d])) ** 2 for d in range(3))
+    inside = r2 < (radius * float(L[0])) ** 2
+    tr_f[inside, 6] = 3400; tr_f[inside, TR_MAT] = 2; tr_f[inside, 10] = 1e22
+    return tr_x, tr_f

@@ -1,0 +1,73 @@
+"""Times the resident 3-D marker stages -- scatter of a step's field list, temperature to tracers, RK4 (+ the re-sort) -- and
+writes one JSON line.  Device-event times of the stages' kernel windows (pl3_resident_times), median over the repetitions after
+a warm-up; bytes per tracer are the algorithmic minimum, the roof is 8 TB/s.
+
+    python tools/mic3_bench.py [--n 129] [--per-axis 2] [--reps 20] [--warmup 3] [--out profiles/mic3_129.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from pylamp_amd import pylamp3d as P3                                             # noqa: E402
+
+ROOF = 8.0e12
+# positions 24 B; scatter reads the 7 columns rho, eta, cp, T, H, mat, k and writes 10 nodal fields (80 B per node, one node per cell);
+# gather reads and writes T; RK4 writes the new position and the velocity
+BYTES = dict(scatter=lambda tpc: 24 + 56 + 80.0 / tpc, gather=lambda tpc: 24 + 16, gather_subgrid=lambda tpc: 24 + 16 + 32 + 8.0 / tpc,
+             rk4=lambda tpc: 72, sort=lambda tpc: 2 * 8 * 19 + 12)      # sort: every one of the 19 columns read and written, key + index
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=129); ap.add_argument("--per-axis", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=20); ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join("profiles", "mic3_129.json"))
+    a = ap.parse_args()
+    nx = [a.n] * 3; L = [100e3] * 3
+    rng = np.random.default_rng(0)
+    tr_x, tr_f = P3.falling_sphere_tracers(nx, L, rng, per_axis=a.per_axis)
+    n = tr_x.shape[0]
+    tr_f[:, 3] = 273 + 1350 * tr_x[:, 0] / L[0]; tr_f[:, 4] = 4.0; tr_f[:, 5] = 1250; tr_f[:, 7] = 3.5e-5; tr_f[:, 9] = 120e3
+    sim = P3.Simulation3(nx, L, tr_x, tr_f)
+    del tr_x, tr_f
+    h = L[0] / (a.n - 1)
+    dT = rng.standard_normal(nx)
+    dt = 1e12
+    vel = [rng.standard_normal(nx) * (1e-3 * h / dt) for _ in range(3)]          # the tracers stay where they are: every repetition sees the same load
+    grids, V = P3.advection_velocity(vel, sim.gridmp, nx)
+    t = {k: [] for k in ("scatter", "gather", "gather_subgrid", "rk4", "sort")}
+    mp, g = sim.gridmp, sim.grid
+    sets = [([0, 1, 5, 3, 11, 8], [5, 6, 5, 5, 5, 5], g), ([1], [6], mp), ([4], [5], [mp[0], g[1], g[2]]), ([4], [5], [g[0], mp[1], g[2]]),
+            ([4], [5], [g[0], g[1], mp[2]])]
+    for rep in range(a.warmup + a.reps):
+        sim.update_properties()
+        ms = 0.0
+        for cols, sch, tg in sets:
+            sim.scatter(cols, sch, tg); ms += sim.stage_times()["scatter"]
+        sim.opt.do_subgrid_heatdiff = False
+        sim.temp_to_tracers(dT, False, dt); tg_ = sim.stage_times()["gather"]
+        sim.opt.do_subgrid_heatdiff = True
+        sim.temp_to_tracers(-dT, False, dt); ts_ = sim.stage_times()["gather"]
+        sim.advect(grids, V, dt); st = sim.stage_times()
+        if rep >= a.warmup:
+            t["scatter"].append(ms); t["gather"].append(tg_); t["gather_subgrid"].append(ts_); t["rk4"].append(st["rk4"]); t["sort"].append(st["sort"])
+    tpc = n / float((a.n - 1) ** 3)
+    out = dict(config="mic3_%d" % a.n, nodes=a.n ** 3, tracers=n, tracers_per_cell=tpc, reps=a.reps, warmup=a.warmup, stages={})
+    for k, v in t.items():
+        ms = float(np.median(v)); b = BYTES[k](tpc)
+        out["stages"][k] = dict(ms=round(ms, 4), ms_min=round(float(np.min(v)), 4), ms_max=round(float(np.max(v)), 4),
+                                ps_per_tracer=round(ms * 1e9 / n, 2), bytes_per_tracer=round(b, 1), fraction_of_8TBs_roof=round(b * n / (ms * 1e-3) / ROOF, 4))
+    sim.close()
+    line = json.dumps(out)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
