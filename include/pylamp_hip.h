@@ -413,6 +413,24 @@ int  pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* fiel
 int  pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
                       const double* vy, double tstep, int fence);
 int  pl3_get_tracer_velocity(pl3_ctx* ctx, int64_t n, double* out);
+/* Census + refill of depleted cells (the extension of pylamp2.py:588-633 by one axis), fused into the sort by cell.  The census is
+ * the sort's own count array.  A cell with fewer than tracdens_min tracers receives tracdens - count new ones, written directly
+ * behind its residents, so the resident state stays cell-sorted and pl3_tracers_census counts them.  New tracer q of cell
+ * c = (i (nx-1) + j)(ny-1) + k sits at g_d[i_d] + u_d (g_d[i_d+1] - g_d[i_d]) with u_d a counter-based uniform of
+ * (seed, c, q, 3 it + d) alone, d = 0, 1, 2 = z, x, y; every field but TR__ID is the plain mean of the cell's residents, summed
+ * in resident order (an EMPTY cell gives 0/0 = NaN as in the reference: it is counted in out[2], and the next scatter shows it);
+ * the stored velocity is 0.  IDs: the reference's rule (numbering starts AT the largest ID and the first new ID of every refilled
+ * cell repeats the last one handed out) or, with unique_ids, largest ID + 1, + 2, ... in cell order.  No floating-point atomics
+ * and a fixed order of summation: two runs agree bitwise.  tracdens_min <= 0, or no deficient cell: the state is bit for bit
+ * what the plain sort leaves.  The arrays grow inside the sort when the new total exceeds their capacity.
+ * refill: sort + refill without advection (top up a sparse initial set).  advect: pl3_resident_rk4 with the refill in its sort.
+ * out = { tracers injected, cells refilled, cells that were empty, smallest count of a cell before the refill }.
+ * Errors: tracdens < tracdens_min; tracdens_min > 0 with fence == 0 (a tracer outside the box would be counted in the nearest
+ * cell, and the deletion the reference does instead is not built in 3-D); a context with pl3_set_comm attached. */
+int  pl3_resident_refill(pl3_ctx* ctx, int tracdens, int tracdens_min, uint64_t seed, int it, int unique_ids, int64_t out[4]);
+int  pl3_resident_advect(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
+                         const double* vy, double tstep, int fence, int tracdens, int tracdens_min, uint64_t seed, int it,
+                         int unique_ids, int64_t out[4]);
 int  pl3_resident_times(pl3_ctx* ctx, double ms[4]);
 
 /* sizeof / offsetof of the structs above as compiled into the library: out = { sizeof(pl_solve_stats),

@@ -88,6 +88,9 @@ SIGNATURES = {
     "pl3_resident_temp_to_tracers": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int, C.c_double]),
     "pl3_resident_rk4": (C.c_int, [C.c_void_p] + [c_double_p] * 6 + [C.c_double, C.c_int]),
     "pl3_get_tracer_velocity": (C.c_int, [C.c_void_p, C.c_int64, c_double_p]),
+    "pl3_resident_refill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "pl3_resident_advect": (C.c_int, [C.c_void_p] + [c_double_p] * 6 + [C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
+                                      C.POINTER(C.c_int64)]),
     "pl3_resident_times": (C.c_int, [C.c_void_p, c_double_p]),
     "pl_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, c_int_p, C.POINTER(C.c_size_t)]),
     "pl_set_comm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

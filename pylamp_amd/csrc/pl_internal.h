@@ -125,6 +125,15 @@ __device__ inline double pl_rcp(double x) {
 // single precision (the FP32 multigrid levels): v_rcp_f32 is good to 1 ulp
 __device__ inline float pl_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
+// Counter-based uniform in [0,1) of the tracer injection, 2-D (pl_step.hip) and 3-D (pl_mic3.hip): a function of
+// (seed, cell, ordinal of the new tracer in its cell, 2 or 3 x step + axis) only, so the stream does not depend on the launch shape
+// or on which other cells are refilled
+__device__ inline double inj_uniform(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
+    unsigned long long h = seed ^ (0x9E3779B97F4A7C15ull * (a + 1)) ^ (0xC2B2AE3D27D4EB4Full * (b + 1)) ^ (0x165667B19E3779F9ull * (c + 1));
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+    return (double)(h >> 11) * (1.0 / 9007199254740992.0);          // [0,1)
+}
+
 // ---- two-columns-per-lane row loads (see k_stokes_apply_v2) ----
 template <typename T> struct PlVec2;
 template <> struct PlVec2<double> { typedef double2 type; static __host__ __device__ inline double2 make(double a, double b) { return make_double2(a, b); } };

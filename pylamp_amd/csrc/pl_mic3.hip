@@ -17,6 +17,7 @@
 
 #define M3_MAXF 8
 #define M3_NFTRAC 13
+#define M3_ID 12
 enum { M3_RHO = 0, M3_ETA = 1, M3_TMP = 3, M3_HCD = 4, M3_HCP = 5, M3_RH0 = 6, M3_ALP = 7, M3_ACE = 9, M3_ET0 = 10 };
 #define M3_GASR 8.31446
 
@@ -50,23 +51,162 @@ __global__ __launch_bounds__(256) void k_m3_key(long long n, M3Pos p, M3Grid s, 
     key[t] = c;
     atomicAdd(&count[c], 1);                      // integer: the counts do not depend on the order of arrival
 }
-// exclusive prefix sum of count[0..m) into start[0..m] and cursor[0..m): one workgroup, each thread a contiguous chunk
-__global__ __launch_bounds__(1024) void k_m3_scan(int m, const int* __restrict__ count, int* __restrict__ start, int* __restrict__ cursor) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x, chunk = (m + 1023) / 1024, b = tid * chunk, e = min(b + chunk, m);
-    int s = 0;
-    for (int i = b; i < e; i++) s += count[i];
-    part[tid] = s;
+// Exclusive prefix sum over the cells in three plain launches, reduce-then-scan, so that no workgroup ever waits on another one:
+// (1) k_m3_tile_sums: every workgroup sums its tile of M3_TILE cells, (2) k_m3_scan_sums: ONE workgroup scans the tile sums (a
+// thousand of them for two million cells), (3) k_m3_scan_tiles: every workgroup scans its tile again, starting from its base.
+// What is scanned is computed from the count array on the fly, so the scans of a refill share the pass (NS = 3):
+//   0: count + deficit -> start (every cell's slice with the room for its new tracers behind the residents) and cursor,
+//   1: deficit         -> ordinal of the cell's first new tracer among all new ones,
+//   2: deficient flag  -> rank of the cell among the deficient ones = its slot in the compacted list the injection works from;
+// 1 and 2 are only stored for the deficient cells, in that list.  NS = 1 scans the counts alone (no refill).  Integers
+// throughout: the result does not depend on the tiling.
+#define M3_TILE 2048
+#define M3_NOCELL 0x7fffffff                      // padding behind the last cell: counts as nothing in every sum
+struct M3Need { int dens, dmin; };               // a cell with count < dmin receives dens - count new tracers (dmin <= 0: none)
+struct M3Totals { int v[6]; double maxid; };     // sums of 0..2, empty cells, smallest count; largest TR__ID (when asked for)
+
+__device__ inline int m3_need(int c, M3Need r) { return c < r.dmin ? r.dens - c : 0; }
+__device__ inline void m3_load8(int m, const int* __restrict__ cnt, long long base, int v[8]) {
+    if (base + 8 <= (long long)m) {
+        const int4 a = *(const int4*)(cnt + base), b = *(const int4*)(cnt + base + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else
+        for (int k = 0; k < 8; k++) v[k] = base + k < (long long)m ? cnt[base + k] : M3_NOCELL;
+}
+template <int NS>
+__device__ inline void m3_thread_sums(const int v[8], M3Need r, int s[NS]) {
+    for (int a = 0; a < NS; a++) s[a] = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (v[k] == M3_NOCELL) continue;
+        const int need = NS > 1 ? m3_need(v[k], r) : 0;
+        s[0] += v[k] + need;
+        if constexpr (NS > 1) { s[1] += need; s[2] += need > 0 ? 1 : 0; }
+    }
+}
+// exclusive prefix of s[] over the 256 threads of the workgroup (in place)
+template <int NS>
+__device__ inline void m3_block_exscan(int s[NS]) {
+    __shared__ int wsum[NS][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc[NS];
+    for (int a = 0; a < NS; a++) {
+        int x = s[a];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
+        inc[a] = x;
+        if (lane == 63) wsum[a][w] = x;
+    }
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
+    for (int a = 0; a < NS; a++) {
+        int b = 0;
+        for (int q = 0; q < w; q++) b += wsum[a][q];
+        s[a] = b + inc[a] - s[a];
+    }
+}
+// bsum[a * nb + tile]: a < NS the tile sums; NS = 3: a = 3 the empty cells and a = 4 the smallest count of the tile
+template <int NS>
+__global__ __launch_bounds__(256) void k_m3_tile_sums(int m, const int* __restrict__ cnt, M3Need r, int nb, int* __restrict__ bsum) {
+    constexpr int NR = NS > 1 ? NS + 2 : NS;
+    __shared__ int sh[NR][4];
+    int v[8], s[NR];
+    m3_load8(m, cnt, (long long)blockIdx.x * M3_TILE + threadIdx.x * 8, v);
+    m3_thread_sums<NS>(v, r, s);
+    if constexpr (NS > 1) {
+        s[NS] = 0; s[NS + 1] = M3_NOCELL;
+#pragma unroll
+        for (int k = 0; k < 8; k++) { s[NS] += v[k] == 0 ? 1 : 0; s[NS + 1] = min(s[NS + 1], v[k]); }
+    }
+    for (int a = 0; a < NR; a++) {
+        int x = s[a];
+        const bool mn = NS > 1 && a == NS + 1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_down(x, o, 64); x = mn ? min(x, y) : x + y; }
+        if ((threadIdx.x & 63) == 0) sh[a][threadIdx.x >> 6] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < NR) {
+        const int a = threadIdx.x;
+        const bool mn = NS > 1 && a == NS + 1;
+        int x = sh[a][0];
+        for (int q = 1; q < 4; q++) x = mn ? min(x, sh[a][q]) : x + sh[a][q];
+        bsum[(size_t)a * nb + blockIdx.x] = x;
+    }
+}
+// one workgroup: the tile sums become the tiles' bases (exclusive, in place), the totals go to tot; with idpart the largest
+// tracer ID is finished from the partial maxima of k_m3_max
+template <int NS>
+__global__ __launch_bounds__(1024) void k_m3_scan_sums(int nb, int* __restrict__ bsum, M3Totals* __restrict__ tot, const double* __restrict__ idpart, int nid) {
+    __shared__ int part[1024];
+    __shared__ double dpart[16];
+    const int tid = threadIdx.x, chunk = (nb + 1023) / 1024, b = min(tid * chunk, nb), e = min(b + chunk, nb);
+    for (int a = 0; a < NS; a++) {
+        int* x = bsum + (size_t)a * nb;
+        int s = 0;
+        for (int i = b; i < e; i++) s += x[i];
+        part[tid] = s;
         __syncthreads();
-        part[tid] += v;
+        for (int d = 1; d < 1024; d <<= 1) {
+            const int u = tid >= d ? part[tid - d] : 0;
+            __syncthreads();
+            part[tid] += u;
+            __syncthreads();
+        }
+        int run = part[tid] - s;
+        for (int i = b; i < e; i++) { const int u = x[i]; x[i] = run; run += u; }
+        if (tid == 1023) tot->v[a] = part[1023];
         __syncthreads();
     }
-    int run = part[tid] - s;
-    for (int i = b; i < e; i++) { start[i] = run; cursor[i] = run; run += count[i]; }
-    if (tid == 1023) start[m] = part[1023];
+    if constexpr (NS > 1) {
+        for (int a = NS; a < NS + 2; a++) {
+            const bool mn = a == NS + 1;
+            const int* x = bsum + (size_t)a * nb;
+            int s = mn ? M3_NOCELL : 0;
+            for (int i = b; i < e; i++) s = mn ? min(s, x[i]) : s + x[i];
+            part[tid] = s;
+            __syncthreads();
+            for (int d = 512; d > 0; d >>= 1) {
+                if (tid < d) part[tid] = mn ? min(part[tid], part[tid + d]) : part[tid] + part[tid + d];
+                __syncthreads();
+            }
+            if (tid == 0) tot->v[a] = part[0];
+            __syncthreads();
+        }
+    }
+    if (idpart) {
+        double mx = -INFINITY;
+        for (int i = tid; i < nid; i += 1024) mx = fmax(mx, idpart[i]);
+        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o, 64));
+        if ((tid & 63) == 0) dpart[tid >> 6] = mx;
+        __syncthreads();
+        if (tid == 0) { for (int q = 1; q < 16; q++) mx = fmax(mx, dpart[q]); tot->maxid = mx; }
+    }
+}
+template <int NS>
+__global__ __launch_bounds__(256) void k_m3_scan_tiles(int m, const int* __restrict__ cnt, M3Need r, int nb, const int* __restrict__ bsum,
+                                                       const M3Totals* __restrict__ tot, int* __restrict__ start, int* __restrict__ cursor,
+                                                       int* __restrict__ list, int* __restrict__ loff) {
+    const long long base = (long long)blockIdx.x * M3_TILE + threadIdx.x * 8;
+    int v[8], s[NS], o[8];
+    m3_load8(m, cnt, base, v);
+    m3_thread_sums<NS>(v, r, s);
+    m3_block_exscan<NS>(s);
+    for (int a = 0; a < NS; a++) s[a] += bsum[(size_t)a * nb + blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        o[k] = s[0];
+        if (v[k] == M3_NOCELL) continue;
+        const int need = NS > 1 ? m3_need(v[k], r) : 0;
+        s[0] += v[k] + need;
+        if constexpr (NS > 1) if (need > 0) { list[s[2]] = (int)(base + k); loff[s[2]] = s[1]; s[1] += need; s[2]++; }
+    }
+    if (base + 8 <= (long long)m) {
+        const int4 a = make_int4(o[0], o[1], o[2], o[3]), b = make_int4(o[4], o[5], o[6], o[7]);
+        *(int4*)(start + base) = a; *(int4*)(start + base + 4) = b;
+        *(int4*)(cursor + base) = a; *(int4*)(cursor + base + 4) = b;
+    } else
+        for (int k = 0; k < 8; k++) if (base + k < (long long)m) { start[base + k] = o[k]; cursor[base + k] = o[k]; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) start[m] = tot->v[0];
 }
 __global__ __launch_bounds__(256) void k_m3_place(long long n, const int* __restrict__ key, int* __restrict__ cursor, int* __restrict__ perm) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -74,12 +214,13 @@ __global__ __launch_bounds__(256) void k_m3_place(long long n, const int* __rest
     perm[atomicAdd(&cursor[key[t]], 1)] = (int)t;
 }
 // the slots inside a cell were handed out in order of arrival: order every cell's slice by the previous index, which makes the
-// sort stable and its result independent of the scheduling
-__global__ __launch_bounds__(256) void k_m3_cell_order(int m, const int* __restrict__ start, int* __restrict__ perm) {
+// sort stable and its result independent of the scheduling.  cnt: the residents of every cell when its slice holds room for new tracers
+// behind them (NULL: the slice is the residents)
+__global__ __launch_bounds__(256) void k_m3_cell_order(int m, const int* __restrict__ start, const int* __restrict__ cnt, int* __restrict__ perm) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= m) return;
     int* a = perm + start[c];
-    const int k = start[c + 1] - start[c];
+    const int k = cnt ? cnt[c] : start[c + 1] - start[c];
     if (k <= 32) {
         for (int i = 1; i < k; i++) { const int v = a[i]; int j = i - 1; while (j >= 0 && a[j] > v) { a[j + 1] = a[j]; j--; } a[j + 1] = v; }
         return;
@@ -98,12 +239,14 @@ __global__ __launch_bounds__(256) void k_m3_cell_order(int m, const int* __restr
         a[root] = v;
     }
 }
-// dst[j * dstride + p] = g(src[perm[p] * ts + j * cs]) for ncol columns; bit j of logmask: g = log (geometric averaging)
+// dst[j * dstride + p] = g(src[perm[p] * ts + j * cs]) for ncol columns; bit j of logmask: g = log (geometric averaging);
+// perm[p] < 0: the slot of a tracer that k_m3_inject writes
 __global__ __launch_bounds__(256) void k_m3_take(long long n, const double* __restrict__ src, long long ts, long long cs, int ncol,
                                                  const int* __restrict__ perm, double* __restrict__ dst, long long dstride, unsigned logmask) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const long long t = perm ? (long long)perm[p] : p;
+    if (t < 0) return;
     for (int j = 0; j < ncol; j++) {
         const double v = src[t * ts + j * cs];
         dst[j * dstride + p] = ((logmask >> j) & 1u) ? log(v) : v;
@@ -118,6 +261,62 @@ __global__ __launch_bounds__(256) void k_m3_to_aos(long long n, const double* __
 __global__ __launch_bounds__(256) void k_m3_census(int m, const int* __restrict__ start, int* __restrict__ cnt) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < m) cnt[c] = start[c + 1] - start[c];
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// refill of depleted cells (the extension of pylamp2.py:588-633 by one axis), fused into the sort
+// ---------------------------------------------------------------------------------------------------------------------
+// block partials of the largest tracer ID (NaN ignored)
+__global__ __launch_bounds__(256) void k_m3_max(long long n, const double* __restrict__ x, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double m = -INFINITY;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) m = fmax(m, x[t]);
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+}
+// The new tracers of the deficient cells, written into the room the sort left behind the residents of each cell.  One wave per
+// deficient cell, taken from the compacted list (in a typical step a few cells in a million are deficient: a thread per cell would
+// idle 63 lanes of 64 and touch 64 cache lines with every load).  Lane j < 13 sums column j of the residents one after the other in
+// resident order -- a fixed order, no atomics, so two runs agree bitwise; then lane q writes the q-th new tracer, column by column
+// (neighbouring lanes, neighbouring addresses).  0 residents: 0/0 = NaN in every field, as in the reference.
+struct M3Inject {
+    int nref; const int* list; const int* loff; const int* start; const int* cnt; int dens;
+    M3Grid g; double* x; double* f; double* v; long long cap;
+    unsigned long long seed; unsigned it3; double id0; int unique;
+};
+__global__ __launch_bounds__(256) void k_m3_inject(M3Inject a) {
+    const int w = (int)(((long long)blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (w >= a.nref) return;                                          // the whole wave leaves
+    const int c = a.list[w], k = a.cnt[c], t0 = a.start[c], t1 = t0 + k, m = a.dens - k, off = a.loff[w];
+    const int ncx = a.g.a[1].n - 1, ncy = a.g.a[2].n - 1;
+    const int ic[3] = {c / (ncy * ncx), (c / ncy) % ncx, c % ncy};
+    double mean = 0.0;
+    if (lane < M3_NFTRAC && lane != M3_ID) {
+        const double* col = a.f + (long long)lane * a.cap;
+        double s = 0.0;
+        for (int t = t0; t < t1; t++) s += col[t];
+        mean = s / (double)k;
+    }
+    for (int j = 0; j < M3_NFTRAC; j++) {
+        const double mj = __shfl(mean, j, 64);
+        if (j == M3_ID) continue;
+        for (int q = lane; q < m; q += 64) a.f[(long long)j * a.cap + t1 + q] = mj;
+    }
+    for (int q = lane; q < m; q += 64) {
+        // pylamp2.py:621-622: numbering starts AT the largest ID and the first new ID of every cell repeats the last one handed out
+        const long long ord = a.unique ? (long long)off + q + 1 : (long long)off + q - w;
+        a.f[(long long)M3_ID * a.cap + t1 + q] = a.id0 + (double)ord;
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            const double g0 = a.g.a[d].c[ic[d]], h = a.g.a[d].c[ic[d] + 1] - g0;
+            const double u = inj_uniform(a.seed, (unsigned)c, (unsigned)q, a.it3 + d);
+            a.x[(long long)d * a.cap + t1 + q] = __dadd_rn(g0, __dmul_rn(u, h));       // the compiler makes one FMA of it: within an ulp of NumPy's two roundings
+            a.v[(long long)d * a.cap + t1 + q] = 0.0;                                  // not advected yet
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -343,6 +542,15 @@ struct Mic3 {
     long long n = 0, cap = 0; bool have = false;
     double *x = nullptr, *f = nullptr, *v = nullptr;
     double ms[4] = {0, 0, 0, 0};         // device time of the last resident scatter / temperature gather / RK4 / sort
+    // largest TR__ID of the resident tracers: reduced on the device when a refill first needs it after an upload, then kept up to
+    // date by the refill (nothing deletes tracers in 3-D; whatever does one day sets have_maxid = false)
+    bool have_maxid = false; double maxid = 0.0;
+};
+// a refill riding on a sort: what to do, and what the sort found
+struct M3Refill {
+    int dens, dmin; unsigned long long seed; int it, unique;
+    long long ninj = 0, nref = 0, nempty = 0, mincnt = 0;
+    const int *list = nullptr, *loff = nullptr, *cnt = nullptr;
 };
 #define M3_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return pl3_fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 #define M3_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
@@ -401,23 +609,66 @@ static int m3_grid(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, cons
 }
 static long long m3_ncells(const M3Grid& s) { return (long long)(s.a[0].n - 1) * (s.a[1].n - 1) * (s.a[2].n - 1); }
 
-// counting sort by cell of the node set s: perm (sorted slot -> previous index) and start (ncell + 1)
-static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long long n, const M3Pos& p, const M3Grid& s, int** perm_out, int** start_out) {
+// the three launches of the scan (see k_m3_tile_sums); rf: the scans of a refill ride along and the totals are left in *tot
+template <int NS>
+static void m3_scan_sums(Pl3HostView& v, int m, const int* cnt, M3Need r, int nb, int* bsum, M3Totals* tot, const double* idpart, int nid) {
+    hipLaunchKernelGGL(k_m3_tile_sums<NS>, dim3(nb), dim3(256), 0, v.stream, m, cnt, r, nb, bsum);
+    hipLaunchKernelGGL(k_m3_scan_sums<NS>, dim3(1), dim3(1024), 0, v.stream, nb, bsum, tot, idpart, nid);
+}
+// counting sort by cell of the node set s: perm (sorted slot -> previous index) and start (ncell + 1).  With rf the cells that hold
+// fewer than rf->dmin tracers get room for rf->dens - count more behind their residents: start describes the slices WITH the room,
+// perm has n + rf->ninj slots (-1 in those of the new tracers) and rf carries the counters and the list of the deficient cells.
+static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long long n, const M3Pos& p, const M3Grid& s, int** perm_out, int** start_out,
+                   M3Refill* rf = nullptr) {
     const long long m = m3_ncells(s);
     if (m >= (1ll << 31) - 1 || n >= (1ll << 31) - 1) return pl3_fail(ctx, "3-D marker-in-cell: more than 2^31 cells or tracers");
-    int *key, *perm, *cnt, *start, *cur;
+    int *key, *perm, *cnt, *start, *cur, *bsum; M3Totals* tot;
     const std::string t(tag);
+    const int nb = (int)((m + M3_TILE - 1) / M3_TILE);
     M3_TRY(m3_buf(ctx, v, M, (t + "_key").c_str(), (size_t)n, &key));
-    M3_TRY(m3_buf(ctx, v, M, (t + "_perm").c_str(), (size_t)n, &perm));
     M3_TRY(m3_buf(ctx, v, M, (t + "_cnt").c_str(), (size_t)m, &cnt));
     M3_TRY(m3_buf(ctx, v, M, (t + "_start").c_str(), (size_t)m + 1, &start));
     M3_TRY(m3_buf(ctx, v, M, (t + "_cur").c_str(), (size_t)m, &cur));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_bsum").c_str(), (size_t)nb * 5, &bsum));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_tot").c_str(), (size_t)1, &tot));
     M3_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(int), v.stream));
     if (n > 0) hipLaunchKernelGGL(k_m3_key, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
-    hipLaunchKernelGGL(k_m3_scan, dim3(1), dim3(1024), 0, v.stream, (int)m, (const int*)cnt, start, cur);
+    long long slots = n;
+    if (!rf) {
+        const M3Need none{0, 0};
+        M3_TRY(m3_buf(ctx, v, M, (t + "_perm").c_str(), (size_t)n, &perm));
+        m3_scan_sums<1>(v, (int)m, cnt, none, nb, bsum, tot, nullptr, 0);
+        hipLaunchKernelGGL(k_m3_scan_tiles<1>, dim3(nb), dim3(256), 0, v.stream, (int)m, (const int*)cnt, none, nb, (const int*)bsum, (const M3Totals*)tot,
+                           start, cur, (int*)nullptr, (int*)nullptr);
+    } else {
+        const M3Need need{rf->dens, rf->dmin};
+        double* idpart = nullptr; int nid = 0;
+        if (!M->have_maxid && rf->dmin > 0) {
+            nid = (int)std::min<long long>(1024, (std::max<long long>(n, 1) + 255) / 256);
+            M3_TRY(m3_buf(ctx, v, M, (t + "_idpart").c_str(), (size_t)nid, &idpart));
+            hipLaunchKernelGGL(k_m3_max, dim3(nid), dim3(256), 0, v.stream, n, (const double*)(M->f + (long long)M3_ID * M->cap), idpart);
+        }
+        m3_scan_sums<3>(v, (int)m, cnt, need, nb, bsum, tot, idpart, nid);
+        M3_HIP(ctx, hipGetLastError());
+        M3Totals h;                                   // the one read-back of a refill: how many tracers the arrays must hold
+        M3_HIP(ctx, hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, hipStreamSynchronize(v.stream));
+        rf->ninj = h.v[1]; rf->nref = h.v[2]; rf->nempty = h.v[3]; rf->mincnt = m > 0 ? h.v[4] : 0;
+        if (idpart) { M->maxid = std::isfinite(h.maxid) ? h.maxid : -1.0; M->have_maxid = true; }     // no finite ID: numbering starts at 0
+        slots = n + rf->ninj;
+        if (slots >= (1ll << 31) - 1) return pl3_fail(ctx, "3-D marker-in-cell: the refill would take the tracers beyond 2^31");
+        int *list, *loff;
+        M3_TRY(m3_buf(ctx, v, M, (t + "_perm").c_str(), (size_t)slots, &perm));
+        M3_TRY(m3_buf(ctx, v, M, (t + "_list").c_str(), (size_t)rf->nref, &list));
+        M3_TRY(m3_buf(ctx, v, M, (t + "_loff").c_str(), (size_t)rf->nref, &loff));
+        if (rf->ninj > 0) M3_HIP(ctx, hipMemsetAsync(perm, 0xff, (size_t)slots * sizeof(int), v.stream));
+        hipLaunchKernelGGL(k_m3_scan_tiles<3>, dim3(nb), dim3(256), 0, v.stream, (int)m, (const int*)cnt, need, nb, (const int*)bsum, (const M3Totals*)tot,
+                           start, cur, list, loff);
+        rf->list = list; rf->loff = loff; rf->cnt = cnt;
+    }
     if (n > 0) {
         hipLaunchKernelGGL(k_m3_place, m3_blocks(n), dim3(256), 0, v.stream, n, (const int*)key, cur, perm);
-        hipLaunchKernelGGL(k_m3_cell_order, m3_blocks(m), dim3(256), 0, v.stream, (int)m, (const int*)start, perm);
+        hipLaunchKernelGGL(k_m3_cell_order, m3_blocks(m), dim3(256), 0, v.stream, (int)m, (const int*)start, (const int*)(slots > n ? cnt : nullptr), perm);
     }
     M3_HIP(ctx, hipGetLastError());
     *perm_out = perm; *start_out = start;
@@ -586,24 +837,37 @@ static int m3_node_grid(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Grid& g) { retu
 static int m3_need_tracers(pl3_ctx* ctx, Mic3* M, const char* who) {
     return M->have ? 0 : pl3_fail(ctx, std::string(who) + ": no resident tracers (pl3_tracers_upload first)");
 }
-// (re-)sort the resident columns x | f | v by cell into the other of two buffers, which then becomes the resident one
-static int m3_resort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M) {
+// (re-)sort the resident columns x | f | v by cell into the other of two buffers, which then becomes the resident one.  rf: refill
+// the depleted cells in the same pass; when the arrays outgrow `cap`, the other buffer is simply allocated with a larger column
+// stride (k_m3_take has separate strides for source and destination), with an eighth of headroom so that a run that injects a
+// little in every step does not reallocate in every step.  Every other buffer sized by cap follows at its next use (m3_buf).
+static int m3_resort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Refill* rf = nullptr) {
     M3Grid sg;
     M3_TRY(m3_node_grid(ctx, v, M, sg));
     const long long n = M->n, cap = M->cap;
     M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
     M3Pos p{{M->x, M->x + cap, M->x + 2 * cap}, 1};
     int *perm, *start;
-    M3_TRY(m3_sort(ctx, v, M, "r", n, p, sg, &perm, &start));
+    M3_TRY(m3_sort(ctx, v, M, "r", n, p, sg, &perm, &start, rf));
+    const long long nn = n + (rf ? rf->ninj : 0);
+    const long long ncap = nn <= cap ? cap : ((nn + nn / 8 + 63) / 64) * 64;
     double* alt;
-    M3_TRY(m3_buf(ctx, v, M, M->x == (double*)M->bufs["r_a"] ? "r_b" : "r_a", (size_t)cap * (6 + M3_NFTRAC), &alt));
+    M3_TRY(m3_buf(ctx, v, M, M->x == (double*)M->bufs["r_a"] ? "r_b" : "r_a", (size_t)ncap * (6 + M3_NFTRAC), &alt));
     if (n > 0) {
-        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->x, 1ll, cap, 3, (const int*)perm, alt, cap, 0u);
-        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->f, 1ll, cap, M3_NFTRAC, (const int*)perm, alt + 3 * cap, cap, 0u);
-        hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)M->v, 1ll, cap, 3, (const int*)perm, alt + (3 + M3_NFTRAC) * cap, cap, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(nn), dim3(256), 0, v.stream, nn, (const double*)M->x, 1ll, cap, 3, (const int*)perm, alt, ncap, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(nn), dim3(256), 0, v.stream, nn, (const double*)M->f, 1ll, cap, M3_NFTRAC, (const int*)perm, alt + 3 * ncap, ncap, 0u);
+        hipLaunchKernelGGL(k_m3_take, m3_blocks(nn), dim3(256), 0, v.stream, nn, (const double*)M->v, 1ll, cap, 3, (const int*)perm, alt + (3 + M3_NFTRAC) * ncap, ncap, 0u);
+    }
+    M->x = alt; M->f = alt + 3 * ncap; M->v = alt + (3 + M3_NFTRAC) * ncap; M->n = nn; M->cap = ncap;
+    if (rf && rf->nref > 0) {
+        M3Inject a{};
+        a.nref = (int)rf->nref; a.list = rf->list; a.loff = rf->loff; a.start = start; a.cnt = rf->cnt; a.dens = rf->dens;
+        a.g = sg; a.x = M->x; a.f = M->f; a.v = M->v; a.cap = ncap;
+        a.seed = rf->seed; a.it3 = 3u * (unsigned)rf->it; a.id0 = M->maxid; a.unique = rf->unique;
+        hipLaunchKernelGGL(k_m3_inject, m3_blocks(rf->nref * 64), dim3(256), 0, v.stream, a);
+        M->maxid += (double)(rf->unique ? rf->ninj : rf->ninj - rf->nref);
     }
     M3_HIP(ctx, hipGetLastError());
-    M->x = alt; M->f = alt + 3 * cap; M->v = alt + (3 + M3_NFTRAC) * cap;
     M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[3] = ms;
@@ -618,7 +882,7 @@ extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, c
     double *aos, *a;
     M3_TRY(m3_buf(ctx, v, M, "h_aos", (size_t)cap * (3 + M3_NFTRAC), &aos));
     M3_TRY(m3_buf(ctx, v, M, "r_a", (size_t)cap * (6 + M3_NFTRAC), &a));
-    M->n = n; M->cap = cap; M->x = a; M->f = a + 3 * cap; M->v = a + (3 + M3_NFTRAC) * cap; M->have = true;
+    M->n = n; M->cap = cap; M->x = a; M->f = a + 3 * cap; M->v = a + (3 + M3_NFTRAC) * cap; M->have = true; M->have_maxid = false;
     M3_HIP(ctx, hipMemsetAsync(a, 0, (size_t)cap * (6 + M3_NFTRAC) * sizeof(double), v.stream));
     if (n > 0) {
         M3_HIP(ctx, hipMemcpyAsync(aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
@@ -784,13 +1048,23 @@ extern "C" int pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const do
     return 0;
 }
 
-// RK4 on the padded centre grid (nz+1, nx+1, ny+1), fence (pylamp2.py:558-572, length = the node grid's extent), re-sort
-extern "C" int pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
-                                const double* vy, double tstep, int fence) {
-    Pl3HostView v; Mic3* M;
-    M3_TRY(m3_open(ctx, "pl3_resident_rk4", v, &M));
-    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_rk4"));
-    if (!gz || !gx || !gy || !vz || !vx || !vy) return pl3_fail(ctx, "pl3_resident_rk4: bad argument");
+// what a refill may be asked for; out = the four counters of the header
+static int m3_refill_args(pl3_ctx* ctx, const char* who, int tracdens, int tracdens_min, int fence, const int64_t* out) {
+    const std::string w(who);
+    if (!out) return pl3_fail(ctx, w + ": NULL out");
+    if (tracdens < 0 || tracdens_min < 0) return pl3_fail(ctx, w + ": tracdens and tracdens_min must not be negative");
+    if (tracdens_min > 0 && tracdens < tracdens_min) return pl3_fail(ctx, w + ": tracdens < tracdens_min (a refilled cell would still be deficient)");
+    if (tracdens_min > 0 && !fence)
+        return pl3_fail(ctx, w + ": tracer injection needs the fence: without it a tracer outside the box would be counted in the nearest "
+                                 "cell, and the deletion that pylamp2.py:574-581 does instead is not built in 3-D");
+    return 0;
+}
+static void m3_refill_out(const M3Refill& rf, int64_t out[4]) { out[0] = rf.ninj; out[1] = rf.nref; out[2] = rf.nempty; out[3] = rf.mincnt; }
+
+// RK4 on the padded centre grid (nz+1, nx+1, ny+1), fence (pylamp2.py:558-572, length = the node grid's extent), re-sort (+ refill)
+static int m3_advect(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* who, const double* gz, const double* gx, const double* gy, const double* vz,
+                     const double* vx, const double* vy, double tstep, int fence, M3Refill* rf) {
+    if (!gz || !gx || !gy || !vz || !vx || !vy) return pl3_fail(ctx, std::string(who) + ": bad argument");
     const double* gc[3] = {gz, gx, gy}; const int gn[3] = {v.gn[0] + 1, v.gn[1] + 1, v.gn[2] + 1}; const double* vel[3] = {vz, vx, vy};
     const size_t GN = (size_t)gn[0] * gn[1] * gn[2];
     const long long n = M->n, cap = M->cap;
@@ -806,5 +1080,34 @@ extern "C" int pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx
     M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[2] = ms;
-    return m3_resort(ctx, v, M);
+    return m3_resort(ctx, v, M, rf);
+}
+extern "C" int pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
+                                const double* vy, double tstep, int fence) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_rk4", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_rk4"));
+    return m3_advect(ctx, v, M, "pl3_resident_rk4", gz, gx, gy, vz, vx, vy, tstep, fence, nullptr);
+}
+extern "C" int pl3_resident_advect(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
+                                   const double* vy, double tstep, int fence, int tracdens, int tracdens_min, uint64_t seed, int it,
+                                   int unique_ids, int64_t out[4]) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_advect", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_advect"));
+    M3_TRY(m3_refill_args(ctx, "pl3_resident_advect", tracdens, tracdens_min, fence, out));
+    M3Refill rf{tracdens, tracdens_min, seed, it, unique_ids ? 1 : 0};
+    M3_TRY(m3_advect(ctx, v, M, "pl3_resident_advect", gz, gx, gy, vz, vx, vy, tstep, fence, &rf));
+    m3_refill_out(rf, out);
+    return 0;
+}
+extern "C" int pl3_resident_refill(pl3_ctx* ctx, int tracdens, int tracdens_min, uint64_t seed, int it, int unique_ids, int64_t out[4]) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_refill", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_refill"));
+    M3_TRY(m3_refill_args(ctx, "pl3_resident_refill", tracdens, tracdens_min, 1, out));
+    M3Refill rf{tracdens, tracdens_min, seed, it, unique_ids ? 1 : 0};
+    M3_TRY(m3_resort(ctx, v, M, &rf));
+    m3_refill_out(rf, out);
+    return 0;
 }

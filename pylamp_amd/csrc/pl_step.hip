@@ -285,11 +285,6 @@ __global__ __launch_bounds__(256) void k_remap_orig(long long n, int* __restrict
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n) orig[t] = rank[orig[t]];
 }
-__device__ inline double inj_uniform(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
-    unsigned long long h = seed ^ (0x9E3779B97F4A7C15ull * (a + 1)) ^ (0xC2B2AE3D27D4EB4Full * (b + 1)) ^ (0x165667B19E3779F9ull * (c + 1));
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);          // [0,1)
-}
 // pylamp2.py:291-303
 __global__ __launch_bounds__(256) void k_property_update(long long n, const double* __restrict__ T,
                                                          const double* __restrict__ rh0, const double* __restrict__ alp,

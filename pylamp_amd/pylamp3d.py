@@ -452,8 +452,11 @@ class Options3:
         self.stokes_rtol, self.stokes_maxit = DEFAULT_RTOL, DEFAULT_MAXIT
         self.heat_rtol, self.heat_maxit = 1e-12, 2000
         self.grav = None
-        # parts of the 2-D step that do not exist in 3-D yet: anything but these values is rejected by name
+        # census + refill (pylamp2.py:588-633 with a third axis): a cell below tracdens_min tracers is refilled to tracdens; 0 = off
         self.tracdens, self.tracdens_min = 0, 0
+        self.inject_seed = 12345                # seed of the counter-based stream of the new positions
+        self.inject_unique_ids = False          # False: the reference's ID rule (pylamp2.py:621-622, repeats IDs); True: max + 1, + 2, ...
+        # parts of the 2-D step that do not exist in 3-D yet: anything but these values is rejected by name
         self.tracs_fence_enabled = True
         self.surface_stabilization = False
         for k, v in kw.items():
@@ -464,9 +467,12 @@ class Options3:
 
 class Simulation3:
     """The 3-D counterpart of driver.Simulation: tracers stay on the GPU, step() follows the loop of pylamp2.py:290-581 with a
-    third axis -- properties, tracer->grid, Stokes, time step, heat, grid->tracer (+ subgrid diffusion), RK4, fence.  One rank,
-    regular grid, all walls free-slip.  Not built: injection, the fence-off deletion path, surface stabilisation, non-uniform
-    grids for the markers, several ranks -- each is rejected with an error that names it."""
+    third axis -- properties, tracer->grid, Stokes, time step, heat, grid->tracer (+ subgrid diffusion), RK4, fence, and the census
+    + refill of depleted cells inside the end-of-step sort (Options3.tracdens / tracdens_min / inject_seed / inject_unique_ids;
+    refill() does it without a step).  step() reports ninjected, nrefilled (cells) and nempty (cells that held no tracer: their new
+    tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank,
+    regular grid, all walls free-slip.  Not built: the fence-off deletion path, surface stabilisation, non-uniform grids for the
+    markers, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
         self.nx = [int(v) for v in nx]
@@ -481,8 +487,9 @@ class Simulation3:
         self.gridmp = gridmp_of(self.grid)
         self.opt = options or Options3()
         o = self.opt
-        if o.tracdens_min != 0:
-            raise Exception("Simulation3: tracer injection (tracdens_min > 0) is not supported in 3-D")
+        if int(o.tracdens) < 0 or int(o.tracdens_min) < 0 or int(o.tracdens_min) > int(o.tracdens):
+            raise Exception("Simulation3: tracer injection needs tracdens >= tracdens_min >= 0 (got tracdens = %s, tracdens_min = %s)"
+                            % (o.tracdens, o.tracdens_min))
         if not o.tracs_fence_enabled:
             raise Exception("Simulation3: the fence-off deletion path (tracs_fence_enabled = False) is not supported in 3-D")
         if o.surface_stabilization:
@@ -587,10 +594,33 @@ class Simulation3:
         self._lib_call("pl3_resident_temp_to_tracers", 1 if absolute else 0, _lib.dptr(_f3(field, self.nx)),
                        0 if absolute or not self.opt.do_subgrid_heatdiff else 1, float(tstep))
 
-    def advect(self, grids, vels, tstep):
+    def _refill_args(self, it):
+        o = self.opt
+        out = (C.c_int64 * 4)()
+        return out, (int(o.tracdens), int(o.tracdens_min), int(o.inject_seed) & (2 ** 64 - 1), int(self.it if it is None else it),
+                     1 if o.inject_unique_ids else 0, out)
+
+    @staticmethod
+    def _counters(out):
+        return dict(ninjected=int(out[0]), nrefilled=int(out[1]), nempty=int(out[2]), mincount=int(out[3]))
+
+    def refill(self, it=None):
+        """Sort + census + refill of the cells below opt.tracdens_min to opt.tracdens, without advection (a sparse initial set is
+        topped up with it).  `it` selects the random stream (default: the step counter).  Returns ninjected, nrefilled (cells),
+        nempty (cells without any tracer before the call) and mincount (smallest count before the call)."""
+        out, args = self._refill_args(it)
+        self._lib_call("pl3_resident_refill", *args)
+        self.ntrac += int(out[0])
+        return self._counters(out)
+
+    def advect(self, grids, vels, tstep, it=None):
+        """RK4 + fence + the sort by cell with the refill in the same pass; returns the counters of refill()."""
         shp = tuple(v + 1 for v in self.nx)
         g = [_lib.f64(c) for c in grids]; V = [_f3(a, shp) for a in vels]
-        self._lib_call("pl3_resident_rk4", *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V], float(tstep), 1)
+        out, args = self._refill_args(it)
+        self._lib_call("pl3_resident_advect", *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V], float(tstep), 1, *args)
+        self.ntrac += int(out[0])
+        return self._counters(out)
 
     # -- one time step -----------------------------------------------------------------------------------------------
     def step(self):
@@ -598,6 +628,13 @@ class Simulation3:
         self.it += 1
         dx = [self.L[d] / (self.nx[d] - 1) for d in range(3)]
         f = self.scatter_fields()
+        for name in ("rho", "etas"):
+            if np.isnan(f[name]).any():
+                self.it -= 1
+                raise Exception("Simulation3.step: the scattered field '%s' holds NaN at %d nodes - a grid node without any marker in "
+                                "reach makes the interpolated fields NaN, and so do tracers injected into a cell without residents "
+                                "(their fields are 0/0 as in pylamp2.py:624-629): raise the marker density or enable injection "
+                                "(Options3.tracdens / tracdens_min) before cells run empty" % (name, int(np.isnan(f[name]).sum())))
         if o.do_heatdiff:
             if self.it > 1:                      # pylamp2.py:327-331: the walls keep the solved temperature
                 nt = self._newtemp
@@ -632,7 +669,7 @@ class Simulation3:
             self._newtemp = newtemp
             f["temp"] = newtemp
         grids, vels = advection_velocity(newvel, self.gridmp, self.nx)
-        self.advect(grids, vels, tstep)
+        rep.update(self.advect(grids, vels, tstep, self.it))
         self.totaltime += tstep
         rep["time"] = self.totaltime; rep["ntrac"] = self.count()
         self.fields = f

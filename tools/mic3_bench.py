@@ -3,6 +3,14 @@ writes one JSON line.  Device-event times of the stages' kernel windows (pl3_res
 a warm-up; bytes per tracer are the algorithmic minimum, the roof is 8 TB/s.
 
     python tools/mic3_bench.py [--n 129] [--per-axis 2] [--reps 20] [--warmup 3] [--out profiles/mic3_129.json]
+
+--sort-only times the end-of-step sort alone, in up to three states, and writes profiles/mic3_129_refill.json:
+  sort_off       RK4 + sort with injection off (the only state a tree without Simulation3.refill has),
+  sort_on_idle   the same with tracdens = 8, tracdens_min = 4 and no deficient cell (the two alternate inside one loop),
+  sort_on_1pct   sort + refill of a set in which 1 % of the cells were thinned to 2 tracers (uploaded afresh for every repetition:
+                 a refilled set has nothing left to inject), --refill-reps repetitions.
+--parent FILE [FILE ...] embeds the sort_off figures that the same script wrote for another tree (the parent commit's), run in
+separate processes alternating with this one, and reports the run-to-run spread of both next to the medians.
 """
 import argparse
 import json
@@ -21,12 +29,80 @@ BYTES = dict(scatter=lambda tpc: 24 + 56 + 80.0 / tpc, gather=lambda tpc: 24 + 1
              rk4=lambda tpc: 72, sort=lambda tpc: 2 * 8 * 19 + 12)      # sort: every one of the 19 columns read and written, key + index
 
 
+def _stat(v, n):
+    ms = float(np.median(v))
+    return dict(ms=round(ms, 4), ms_min=round(float(np.min(v)), 4), ms_max=round(float(np.max(v)), 4), ps_per_tracer=round(ms * 1e9 / n, 2), reps=len(v))
+
+
+def sort_only(a):
+    nx = [a.n] * 3; L = [100e3] * 3
+    rng = np.random.default_rng(0)
+    tr_x, tr_f = P3.falling_sphere_tracers(nx, L, rng, per_axis=a.per_axis)
+    n = tr_x.shape[0]
+    have = hasattr(P3.Simulation3, "refill")
+    sim = P3.Simulation3(nx, L, tr_x, tr_f)
+    h = L[0] / (a.n - 1); dt = 1e12
+    vel = [rng.standard_normal(nx) * (1e-3 * h / dt) for _ in range(3)]          # the tracers stay where they are
+    grids, V = P3.advection_velocity(vel, sim.gridmp, nx)
+    t = dict(sort_off=[], sort_on_idle=[])
+    for rep in range(a.warmup + a.reps):
+        for key, dens, dmin in (("sort_off", 0, 0), ("sort_on_idle", 8, 4)):
+            if key != "sort_off" and not have:
+                continue
+            sim.opt.tracdens, sim.opt.tracdens_min = dens, dmin
+            c = sim.advect(grids, V, dt)
+            assert not have or c["ninjected"] == 0, c
+            if rep >= a.warmup:
+                t[key].append(sim.stage_times()["sort"])
+    out = dict(config="mic3_%d_sort" % a.n, nodes=a.n ** 3, tracers=n, reps=a.reps, warmup=a.warmup, states={})
+    out["states"]["sort_off"] = _stat(t["sort_off"], n)
+    if have:
+        out["states"]["sort_on_idle"] = _stat(t["sort_on_idle"], n)
+        # 1 % of the cells thinned to 2 of their tracers
+        m = (a.n - 1) ** 3
+        cell = np.zeros(n, dtype=np.int64)
+        for d in range(3):
+            cell = cell * (a.n - 1) + np.clip(np.floor(tr_x[:, d] / h).astype(np.int64), 0, a.n - 2)
+        thin = np.zeros(m, dtype=bool); thin[rng.choice(m, m // 100, replace=False)] = True
+        order = np.argsort(cell, kind="stable")
+        first = np.concatenate([[0], np.cumsum(np.bincount(cell, minlength=m))[:-1]])
+        rank = np.empty(n, dtype=np.int64); rank[order] = np.arange(n) - first[cell[order]]
+        keep = ~thin[cell] | (rank < 2)
+        sx, sf = np.ascontiguousarray(tr_x[keep]), np.ascontiguousarray(tr_f[keep])
+        del tr_x, tr_f, cell, order, rank
+        sim.opt.tracdens, sim.opt.tracdens_min = 8, 4
+        ts, inj = [], 0
+        for rep in range(1 + a.refill_reps):
+            sim.upload(sx, sf)
+            c = sim.refill(it=1)
+            inj = c["ninjected"]
+            if rep >= 1:
+                ts.append(sim.stage_times()["sort"])
+        out["states"]["sort_on_1pct"] = dict(_stat(ts, sx.shape[0]), tracers_before=int(sx.shape[0]), cells_refilled=int(c["nrefilled"]), injected=int(inj))
+    if a.parent:
+        runs = [json.loads(open(f).read())["states"]["sort_off"] for f in a.parent]
+        out["parent_sort"] = dict(ms=round(float(np.median([r["ms"] for r in runs])), 4), runs=runs)
+    sim.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=129); ap.add_argument("--per-axis", type=int, default=2)
     ap.add_argument("--reps", type=int, default=20); ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join("profiles", "mic3_129.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sort-only", action="store_true"); ap.add_argument("--refill-reps", type=int, default=7)
+    ap.add_argument("--parent", nargs="*", default=[])
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "mic3_129_refill.json" if a.sort_only else "mic3_129.json")
+    if a.sort_only:
+        line = json.dumps(sort_only(a))
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        print(line)
+        return
     nx = [a.n] * 3; L = [100e3] * 3
     rng = np.random.default_rng(0)
     tr_x, tr_f = P3.falling_sphere_tracers(nx, L, rng, per_axis=a.per_axis)
