@@ -2,7 +2,9 @@
 griddata.NNNNNN.npz / tracs.NNNNNN.npz in the style of the 2-D example, with a third axis (gridy, vely, tr_x (n, 3)).
 Cells that run below tracdens_min markers are refilled to tracdens inside the end-of-step sort (0 0 switches that off).
 
-    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4]
+    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident]
+
+--resident runs the device-resident step (Options3.resident): the grid fields stay on the GPU and are downloaded for the snapshots only.
 """
 import os
 import sys
@@ -12,16 +14,18 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from pylamp_amd import pylamp3d as P3                                             # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 65
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-outdir = sys.argv[3] if len(sys.argv) > 3 else "out"
-tracdens = int(sys.argv[4]) if len(sys.argv) > 4 else 8
-tracdens_min = int(sys.argv[5]) if len(sys.argv) > 5 else 4
+resident = "--resident" in sys.argv[1:]
+argv = [a for a in sys.argv if a != "--resident"]
+n = int(argv[1]) if len(argv) > 1 else 65
+steps = int(argv[2]) if len(argv) > 2 else 20
+outdir = argv[3] if len(argv) > 3 else "out"
+tracdens = int(argv[4]) if len(argv) > 4 else 8
+tracdens_min = int(argv[5]) if len(argv) > 5 else 4
 
 nx = [n, n, n]; L = [100e3, 100e3, 100e3]
 tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1))          # 2 x 2 x 2 jittered markers per cell
 opt = P3.Options3(do_heatdiff=False, tdep_rho=False, tdep_eta=False,             # isothermal, constant properties
-                  tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True)
+                  tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident)
 sim = P3.Simulation3(nx, L, tr_x, tr_f, opt)
 sphere = None
 for it in range(1, steps + 1):

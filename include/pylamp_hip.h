@@ -433,6 +433,64 @@ int  pl3_resident_advect(pl3_ctx* ctx, const double* gz, const double* gx, const
                          int unique_ids, int64_t out[4]);
 int  pl3_resident_times(pl3_ctx* ctx, double ms[4]);
 
+/* ---- device-resident 3-D time step (one rank) ------------------------------------------------------------------------
+ * pl3_resident_step is one step of the loop of pylamp2.py:290-581 with a third axis on the resident tracers, with every grid field
+ * kept on the device: properties -> tracer->grid (nodes: rho, etas, cp, T, H, mat; cell centres: etan; the three mixed sets of the
+ * conductivity; with do_heatdiff == 0 only rho, etas and the unweighted geometric etan) -> NaN check -> heat time-step rule ->
+ * Stokes coefficients and a cold resident solve -> Stokes time-step rule, limiter and clamps -> heat coefficients and a resident
+ * solve -> temperature to the tracers (absolute when it == 1, otherwise the increment newtemp - T, with the subgrid diffusion if
+ * enabled) -> advection velocity on the padded centre grid -> RK4 + fence + sort + refill.  From it == 2 on the six walls of the
+ * scattered T take the previous solved temperature (pylamp2.py:327-331).  The kernels and solvers are those of the host-array
+ * entry points, called in the same order, and the scalars of the time-step rules (min(eta), max(2 kz / (rho cp)), max(vz), max(vx),
+ * max(vy): reduced on the device, NaN-propagating like NumPy's) are combined as Python combines them; only those scalars, the
+ * solvers' own and the report cross the bus.  `it` counts from 1 and selects the random stream of the refill.
+ * Errors: NaN in the scattered rho or etas (the message names the field and the count, report->nan_rho / nan_etas are set, the
+ * tracers' positions and temperature and the previous temperature are untouched); it > 1 with heat on and no previous resident step;
+ * a context with pl3_set_comm attached. */
+typedef struct pl3_step_config {
+    int    do_heatdiff, do_subgrid_heatdiff, tdep_rho, tdep_eta;
+    double etamin, etamax, tref;
+    double tstep_adv_max, tstep_adv_min, tstep_dif_max, tstep_dif_min, tstep_modifier;
+    int    bcheat[6];          /* z0, x0, y0, zL, xL, yL */
+    double bcheatvals[6];
+    double stokes_rtol, heat_rtol;
+    int    stokes_maxit, heat_maxit;
+    int    use_grav;           /* 0: gravity (9.81, 0, 0) */
+    int    reserved_;          /* 0 */
+    double grav[3];
+    int    tracdens, tracdens_min;
+    uint64_t inject_seed;
+    int    inject_unique_ids;
+    int    reserved2_;         /* 0 */
+} pl3_step_config;
+typedef struct pl3_step_report {
+    double tstep;
+    int    limiter;            /* 0: the Stokes (advection) rule set the step, 1: the heat rule */
+    int    reserved_;
+    double tstep_heat, tstep_stokes;
+    pl_solve_stats stokes, heat;
+    int64_t ninjected, nrefilled, nempty, mincount;     /* the four counters of pl3_resident_refill */
+    int64_t ntrac;
+    int64_t nan_rho, nan_etas; /* nodes of the scattered rho / etas that hold NaN */
+    double ms_scatter, ms_stokes, ms_heat, ms_gather, ms_rk4, ms_sort;      /* device time of the stages */
+    double ms_total;           /* host wall time of the call */
+} pl3_step_report;
+int  pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* report);
+/* A grid field of the last resident step, downloaded on demand into out (nz, nx, ny): rho, etas, etan, cp, T, H, mat, kz, kx, ky,
+ * velz, velx, vely, pres (Kcont-scaled, ghosts retained), temp.  An unknown or not-yet-computed name is an error that lists the
+ * available ones. */
+int  pl3_get_field(pl3_ctx* ctx, const char* name, double* out);
+/* The step's advection-velocity kernel on host arrays: vz, vx, vy (nz, nx, ny) -> Vz, Vx, Vy on the padded (nz+1, nx+1, ny+1)
+ * centre grid: every component averaged along its own axis, then the free-slip ghosts wall by wall in the order z0, x0, y0, zL, xL,
+ * yL (normal component mirrored with a sign flip, tangential copied); that order decides the edge and corner values. */
+int  pl3_advection_velocity(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* Vz, double* Vx, double* Vy);
+/* Host <-> device copies issued by the pl3_* entry points of this context since the last reset: out = { copies of at least one node
+ * field (8 nz nx ny bytes), their bytes, smaller copies, their bytes }; reset != 0 clears the counters after reading. */
+int  pl3_transfer_stats(pl3_ctx* ctx, int64_t out[4], int reset);
+/* out = { sizeof(pl3_step_config), sizeof(pl3_step_report), offsetof(config.bcheatvals), offsetof(config.grav),
+ * offsetof(config.inject_seed), offsetof(report.heat), offsetof(report.ntrac), offsetof(report.ms_total) } */
+int  pl3_abi_layout(size_t out[8]);
+
 /* sizeof / offsetof of the structs above as compiled into the library: out = { sizeof(pl_solve_stats),
  * sizeof(pl_step_config), sizeof(pl_step_report), offsetof(config.length), offsetof(config.inject_seed),
  * offsetof(config.tracs_fence_disabled), offsetof(report.ntrac), offsetof(report.nremoved) } -- lets a binding

@@ -45,6 +45,26 @@ class StepReport(C.Structure):
                 ("stokes_resolves", C.c_int), ("nremoved", C.c_int64)]
 
 
+class Step3Config(C.Structure):
+    _fields_ = [("do_heatdiff", C.c_int), ("do_subgrid_heatdiff", C.c_int), ("tdep_rho", C.c_int), ("tdep_eta", C.c_int),
+                ("etamin", C.c_double), ("etamax", C.c_double), ("tref", C.c_double),
+                ("tstep_adv_max", C.c_double), ("tstep_adv_min", C.c_double), ("tstep_dif_max", C.c_double),
+                ("tstep_dif_min", C.c_double), ("tstep_modifier", C.c_double), ("bcheat", C.c_int * 6),
+                ("bcheatvals", C.c_double * 6), ("stokes_rtol", C.c_double), ("heat_rtol", C.c_double),
+                ("stokes_maxit", C.c_int), ("heat_maxit", C.c_int), ("use_grav", C.c_int), ("reserved_", C.c_int),
+                ("grav", C.c_double * 3), ("tracdens", C.c_int), ("tracdens_min", C.c_int), ("inject_seed", C.c_uint64),
+                ("inject_unique_ids", C.c_int), ("reserved2_", C.c_int)]
+
+
+class Step3Report(C.Structure):
+    _fields_ = [("tstep", C.c_double), ("limiter", C.c_int), ("reserved_", C.c_int), ("tstep_heat", C.c_double),
+                ("tstep_stokes", C.c_double), ("stokes", SolveStats), ("heat", SolveStats),
+                ("ninjected", C.c_int64), ("nrefilled", C.c_int64), ("nempty", C.c_int64), ("mincount", C.c_int64),
+                ("ntrac", C.c_int64), ("nan_rho", C.c_int64), ("nan_etas", C.c_int64),
+                ("ms_scatter", C.c_double), ("ms_stokes", C.c_double), ("ms_heat", C.c_double), ("ms_gather", C.c_double),
+                ("ms_rk4", C.c_double), ("ms_sort", C.c_double), ("ms_total", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pylamp_hip.h
 SIGNATURES = {
     "pl_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, c_double_p, c_double_p]),
@@ -92,6 +112,11 @@ SIGNATURES = {
     "pl3_resident_advect": (C.c_int, [C.c_void_p] + [c_double_p] * 6 + [C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                       C.POINTER(C.c_int64)]),
     "pl3_resident_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_resident_step": (C.c_int, [C.c_void_p, C.POINTER(Step3Config), C.c_int, C.POINTER(Step3Report)]),
+    "pl3_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p]),
+    "pl3_advection_velocity": (C.c_int, [C.c_void_p] + [c_double_p] * 6),
+    "pl3_transfer_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "pl3_abi_layout": (C.c_int, [C.POINTER(C.c_size_t)]),
     "pl_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, c_int_p, C.POINTER(C.c_size_t)]),
     "pl_set_comm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pl_set_comm_2d": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

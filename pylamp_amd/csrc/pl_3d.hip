@@ -15,6 +15,7 @@
 // coarse operators with natural wall rows, arithmetic viscosity coarsening) for A_vv.  One GPU per problem.
 #include "pl_internal.h"
 #include "pl_mic3.h"
+#include "pl_step3.h"
 #include <algorithm>
 #include <cmath>
 #include <functional>
@@ -1052,11 +1053,17 @@ struct pl3_ctx {
     bool dfl_active = false; double dfl_yAw = 0.0, dfl_wvel2 = 0.0;      // of the running solve: the anchor-mode term of the error estimate
     double etol = 3e-8;                     // bound on the velocity-error estimate of a converged Stokes solve (PYLAMP_STOKES_ETOL)
     void* mic3 = nullptr;                   // pl_mic3.hip: resident tracers and the work buffers of the 3-D marker kernels
+    void* step3 = nullptr;                  // pl_step3.hip: state of the device-resident time step
+    int64_t xfer[4] = {0, 0, 0, 0};         // host <-> device copies (pl3_transfer_stats): count and bytes of those of at least one node field, of the smaller ones
 };
 static thread_local std::string p3_tls_error;
 static int p3_fail(pl3_ctx* ctx, const std::string& m) { if (ctx) ctx->err = m; p3_tls_error = m; return 1; }
 #define P3_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return p3_fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 #define P3_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+void pl3_count_copy(pl3_ctx* ctx, size_t bytes) {
+    const int c = bytes >= sizeof(double) * (size_t)ctx->gn[0] * ctx->gn[1] * ctx->gn[2] ? 0 : 2;
+    ctx->xfer[c]++; ctx->xfer[c + 1] += (int64_t)bytes;
+}
 
 // gn / c: the GLOBAL grid of the level; the block of this rank follows from ctx->P / ctx->pc: C = (gn - 1) / P cells per block, first
 // node pc C, the last block of an axis also owns the last node
@@ -1139,6 +1146,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    pl3_step_free(&ctx->step3);
     pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
     for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf}) if (q) (void)hipFree(q);
@@ -1164,6 +1172,7 @@ static int upload3(pl3_ctx* ctx, const double* host, int ncomp, double* const* d
     const G3& g = ctx->geom.d;
     const size_t bytes = (size_t)g.gn[0] * g.gn[1] * g.gn[2] * ncomp * sizeof(double);
     P3_TRY(stage3(ctx, bytes));
+    pl3_count_copy(ctx, bytes);
     P3_HIP(ctx, hipMemcpyAsync(ctx->stage, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     const dim3 gr((g.n[2] + 2 + 63) / 64, (g.n[1] + 2 + 3) / 4, g.n[0] + 2);
     for (int q = 0; q < ncomp; q++) hipLaunchKernelGGL(k3_from_host, gr, dim3(64, 4), 0, ctx->stream, g, (const double*)ctx->stage, ncomp, q, dst[q]);
@@ -1176,6 +1185,7 @@ static int download3(pl3_ctx* ctx, double* const* src, int ncomp, double* host) 
     P3_TRY(stage3(ctx, bytes));
     if (ctx->nranks > 1) P3_HIP(ctx, hipMemsetAsync(ctx->stage, 0, bytes, ctx->stream));
     for (int q = 0; q < ncomp; q++) hipLaunchKernelGGL(k3_to_host, grid3(g), dim3(64, 4), 0, ctx->stream, g, (const double*)src[q], ncomp, q, ctx->stage);
+    pl3_count_copy(ctx, bytes);
     P3_HIP(ctx, hipMemcpyAsync(host, ctx->stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->nranks > 1 && pl_allreduce_host(ctx->comm, host, (long long)count, 0)) return p3_fail(ctx, std::string("3-D download: ") + pl_last_error(ctx->comm));
@@ -1275,6 +1285,26 @@ extern "C" int pl3_comm_stats(pl3_ctx* ctx, int64_t out[2], int reset) {
 }
 
 // pylamp_stokes.py:116-122 extended dimension-wise: Kcont = DIM mineta / sum(avgd), Kbond = DIM^2 mineta / sum(avgd)^2
+// plain (nz, nx, ny) DEVICE arrays -> the ringed coefficient arrays (the second half of upload3)
+static int ring3(pl3_ctx* ctx, const double* src, double* dst) {
+    const G3& g = ctx->geom.d;
+    const dim3 gr((g.n[2] + 2 + 63) / 64, (g.n[1] + 2 + 3) / 4, g.n[0] + 2);
+    hipLaunchKernelGGL(k3_from_host, gr, dim3(64, 4), 0, ctx->stream, g, src, 1, 0, dst);
+    P3_HIP(ctx, hipGetLastError());
+    return 0;
+}
+static void stokes_op3(pl3_ctx* ctx, double mineta, const double grav[3]) {
+    const G3& g = ctx->geom.d;
+    double sum = 0.0;
+    for (int a = 0; a < 3; a++) sum += (ctx->geom.c[a].back() - ctx->geom.c[a].front()) / g.gn[a];     // avgd = L / n (sic, :119-120)
+    Op3& op = ctx->op;
+    op.g = g; op.es = ctx->es; op.en = ctx->en; op.rho = ctx->rho;
+    op.Kc = 3.0 * mineta / sum; op.Kb = 9.0 * mineta / (sum * sum); op.iKc = 1.0 / op.Kc;
+    op.slave = 1;
+    for (int a = 0; a < 3; a++) op.grav[a] = grav ? grav[a] : (a == 0 ? 9.81 : 0.0);
+    op.anchor[0] = 3; op.anchor[1] = 2; op.anchor[2] = 2;
+    ctx->op_ready = true;
+}
 extern "C" int pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3]) {
     if (!etas || !etan || !rho) return p3_fail(ctx, "pl3_stokes_set_coeffs: NULL argument");
     P3_HIP(ctx, hipSetDevice(ctx->device));
@@ -1289,15 +1319,16 @@ extern "C" int pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const dou
     for (size_t t = 0; t < N; t++) { if (etas[t] != etas[t]) nes = true; else mes = std::min(mes, etas[t]); if (etan[t] != etan[t]) nen = true; else men = std::min(men, etan[t]); }
     if (nes) mes = NAN; if (nen) men = NAN;
     const double mineta = (men < mes) ? men : mes;                  // python's min(a, b), pylamp_stokes.py:116-118
-    double sum = 0.0;
-    for (int a = 0; a < 3; a++) sum += (ctx->geom.c[a].back() - ctx->geom.c[a].front()) / g.gn[a];     // avgd = L / n (sic, :119-120)
-    Op3& op = ctx->op;
-    op.g = g; op.es = ctx->es; op.en = ctx->en; op.rho = ctx->rho;
-    op.Kc = 3.0 * mineta / sum; op.Kb = 9.0 * mineta / (sum * sum); op.iKc = 1.0 / op.Kc;
-    op.slave = 1;
-    for (int a = 0; a < 3; a++) op.grav[a] = grav ? grav[a] : (a == 0 ? 9.81 : 0.0);
-    op.anchor[0] = 3; op.anchor[1] = 2; op.anchor[2] = 2;
-    ctx->op_ready = true;
+    stokes_op3(ctx, mineta, grav);
+    return 0;
+}
+// the same from plain (nz, nx, ny) device arrays, with min(eta) reduced by the caller (pl_step3.hip): nothing crosses the bus
+int pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3], double mineta) {
+    if (ctx->nranks > 1) return p3_fail(ctx, "device-source Stokes coefficients run on one rank");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    for (double** q : {&ctx->es, &ctx->en, &ctx->rho}) if (!*q) P3_TRY(dmal(ctx, q, ctx->geom.d.vol));
+    P3_TRY(ring3(ctx, etas, ctx->es)); P3_TRY(ring3(ctx, etan, ctx->en)); P3_TRY(ring3(ctx, rho, ctx->rho));
+    stokes_op3(ctx, mineta, grav);
     return 0;
 }
 // slaved != 0 (default): the reference's wall treatment extended to 3-D -- the outermost in-domain tangential velocities are
@@ -1372,13 +1403,15 @@ static int dots3(pl3_ctx* ctx, long long n, int nd, const double* const* a, cons
         for (size_t l = 0; !g && l < ctx->levels.size(); l++) if (n % ctx->levels[l]->gh.d.vol == 0 && n / ctx->levels[l]->gh.d.vol <= 4) g = &ctx->levels[l]->gh.d;
         if (!g) return p3_fail(ctx, "dots3: vector length matches no grid level (internal error)");
         hipLaunchKernelGGL(k3_dots_own, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, *g, (int)(n / g->vol), d, ctx->part);
+        pl3_count_copy(ctx, 5 * D3_BLOCKS * sizeof(double));
         P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 5 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (int q = 0; q < nd; q++) { double sum = 0.0; for (int k = 0; k < D3_BLOCKS; k++) sum += ctx->hpart[5 * k + q]; out[q] = sum; }
         return allreduce3(ctx, out, nd, 0);
     }
     hipLaunchKernelGGL(k3_dots, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, n, d, ctx->part);
-    P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 5 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    pl3_count_copy(ctx, 5 * D3_BLOCKS * sizeof(double));
+        P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 5 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int q = 0; q < nd; q++) { double s = 0.0; for (int k = 0; k < D3_BLOCKS; k++) s += ctx->hpart[5 * k + q]; out[q] = s; }
     return 0;
@@ -1663,6 +1696,7 @@ static int bicgstab3(pl3_ctx* ctx, long long vol, int na, const Op3Fn& A, const 
                 Fuse11 fa{}; fa.t = t[0]; fa.s = s[0]; fa.rt = rt[0]; fa.vol = vol;
                 if (late) { fa.x = x[0]; fa.dx = (dx != x) ? dx[0] : nullptr; fa.yw = anchor_term ? ctx->dfl_y : nullptr; }
                 hipLaunchKernelGGL(k3_dots11, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, fa, ctx->part);
+                pl3_count_copy(ctx, 11 * D3_BLOCKS * sizeof(double));
                 P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 11 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
                 P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 for (int q = 0; q < 11; q++) { double sm = 0.0; for (int kk = 0; kk < D3_BLOCKS; kk++) sm += ctx->hpart[11 * kk + q]; f11[q] = sm; }
@@ -1925,25 +1959,27 @@ extern "C" int pl3_stokes_mg_info(pl3_ctx* ctx, int* nlevels, double* lmax, int 
 }
 
 // ---- heat ----------------------------------------------------------------------------------------------------------------------
-extern "C" int pl3_heat_set_coeffs(pl3_ctx* ctx, const double* zmp, const double* xmp, const double* ymp, const double* T, const double* kz,
-                                   const double* kx, const double* ky, const double* cp, const double* rho, const double* H, const int bc[6],
-                                   const double bcvalue[6], double tstep) {
-    if (!zmp || !xmp || !ymp || !T || !kz || !kx || !ky || !cp || !rho || !H || !bc || !bcvalue) return p3_fail(ctx, "pl3_heat_set_coeffs: NULL argument");
+// src: kz, kx, ky, T, H, rho, cp -- host arrays (upload3) or, with dev, plain device arrays (ring3)
+static int heat_set3(pl3_ctx* ctx, const double* const mp[3], const double* const src[7], bool dev, const int bc[6], const double bcvalue[6], double tstep) {
     for (int w = 0; w < 6; w++) if (bc[w] != PL_BC_FIXTEMP && bc[w] != PL_BC_FIXFLOW) return p3_fail(ctx, "heat: boundary condition must be FIXTEMP or FIXFLOW");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     const G3& g = ctx->geom.d;
     for (double** q : {&ctx->hk[0], &ctx->hk[1], &ctx->hk[2], &ctx->hT, &ctx->hH, &ctx->hcdt, &ctx->hrho, &ctx->hcp}) if (!*q) P3_TRY(dmal(ctx, q, g.vol));
-    const double* src[7] = {kz, kx, ky, T, H, rho, cp}; double* dst[7] = {ctx->hk[0], ctx->hk[1], ctx->hk[2], ctx->hT, ctx->hH, ctx->hrho, ctx->hcp};
-    for (int q = 0; q < 7; q++) { double* d1[1] = {dst[q]}; P3_TRY(upload3(ctx, src[q], 1, d1)); }
-    const double* mp[3] = {zmp, xmp, ymp};
+    double* dst[7] = {ctx->hk[0], ctx->hk[1], ctx->hk[2], ctx->hT, ctx->hH, ctx->hrho, ctx->hcp};
+    for (int q = 0; q < 7; q++) {
+        if (dev) P3_TRY(ring3(ctx, src[q], dst[q]));
+        else { double* d1[1] = {dst[q]}; P3_TRY(upload3(ctx, src[q], 1, d1)); }
+    }
     size_t len[3], tot = 0;
     for (int a = 0; a < 3; a++) { len[a] = (size_t)g.gn[a] + 2 * PL_TOFF + 2; tot += len[a]; }
     std::vector<double> t(tot, 0.0);
     size_t off = 0, offs[3];
     for (int a = 0; a < 3; a++) { offs[a] = off; for (int i = 1; i < g.gn[a]; i++) t[off + i + PL_TOFF] = 1.0 / (mp[a][i] - mp[a][i - 1]); off += len[a]; }
     if (!ctx->htab) P3_HIP(ctx, hipMalloc((void**)&ctx->htab, tot * sizeof(double)));
+    pl3_count_copy(ctx, tot * sizeof(double));
     P3_HIP(ctx, hipMemcpy(ctx->htab, t.data(), tot * sizeof(double), hipMemcpyHostToDevice));
     if (!ctx->hbcv) P3_HIP(ctx, hipMalloc((void**)&ctx->hbcv, 6 * sizeof(double)));
+    pl3_count_copy(ctx, 6 * sizeof(double));
     P3_HIP(ctx, hipMemcpy(ctx->hbcv, bcvalue, 6 * sizeof(double), hipMemcpyHostToDevice));
     Heat3& op = ctx->hop;
     op.g = g; for (int a = 0; a < 3; a++) { op.kk[a] = ctx->hk[a]; op.rdb[a] = ctx->htab + offs[a]; }
@@ -1952,6 +1988,17 @@ extern "C" int pl3_heat_set_coeffs(pl3_ctx* ctx, const double* zmp, const double
     P3_HIP(ctx, hipGetLastError());
     ctx->hop_ready = true;
     return 0;
+}
+extern "C" int pl3_heat_set_coeffs(pl3_ctx* ctx, const double* zmp, const double* xmp, const double* ymp, const double* T, const double* kz,
+                                   const double* kx, const double* ky, const double* cp, const double* rho, const double* H, const int bc[6],
+                                   const double bcvalue[6], double tstep) {
+    if (!zmp || !xmp || !ymp || !T || !kz || !kx || !ky || !cp || !rho || !H || !bc || !bcvalue) return p3_fail(ctx, "pl3_heat_set_coeffs: NULL argument");
+    const double* src[7] = {kz, kx, ky, T, H, rho, cp}; const double* mp[3] = {zmp, xmp, ymp};
+    return heat_set3(ctx, mp, src, false, bc, bcvalue, tstep);
+}
+int pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const double* const src[7], const int bc[6], const double bcvalue[6], double tstep) {
+    if (ctx->nranks > 1) return p3_fail(ctx, "device-source heat coefficients run on one rank");
+    return heat_set3(ctx, mp, src, true, bc, bcvalue, tstep);
 }
 static int need_hvecs(pl3_ctx* ctx) {
     for (int v = 0; v < 12; v++) if (!ctx->hvec[v]) P3_TRY(dmal(ctx, &ctx->hvec[v], ctx->geom.d.vol));
@@ -2019,4 +2066,24 @@ extern "C" int pl3_get_solution(pl3_ctx* ctx, int which, double* out) {
     if (!ctx->have_T) return p3_fail(ctx, "pl3_get_solution: no heat solution yet");
     double* X[1] = {ctx->hvec[11]};
     return download3(ctx, X, 1, out);
+}
+
+// ---- what the device-resident step (pl_step3.hip) needs of a context ----------------------------------------------------------
+int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    P3_TRY(need_hvecs(ctx));
+    const G3& g = ctx->geom.d;
+    v->s0 = g.s[0]; v->s1 = g.s[1]; v->pad = P3_PAD; v->stream = ctx->stream; v->slot = &ctx->step3;
+    for (int q = 0; q < 4; q++) { v->X[q] = ctx->vec[11][q]; v->scratch[q] = ctx->vec[0][q]; }
+    v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T;
+    return 0;
+}
+// counts and bytes of the host <-> device copies of this context's pl3_* calls since the last reset: out = { copies of at least one
+// node field (8 nz nx ny bytes), their bytes, smaller copies, their bytes }
+extern "C" int pl3_transfer_stats(pl3_ctx* ctx, int64_t out[4], int reset) {
+    if (!ctx) return p3_fail(nullptr, "pl3_transfer_stats: NULL context");
+    if (out) for (int q = 0; q < 4; q++) out[q] = ctx->xfer[q];
+    if (reset) for (int q = 0; q < 4; q++) ctx->xfer[q] = 0;
+    return 0;
 }

@@ -12,6 +12,7 @@
 // pylamp_trac.py:83-156 (which leaves vz extrapolated under VELDIV): it has no meaning with three components.
 #include "pl_internal.h"
 #include "pl_mic3.h"
+#include "pl_step3.h"
 #include <algorithm>
 #include <cmath>
 
@@ -545,6 +546,7 @@ struct Mic3 {
     // largest TR__ID of the resident tracers: reduced on the device when a refill first needs it after an upload, then kept up to
     // date by the refill (nothing deletes tracers in 3-D; whatever does one day sets have_maxid = false)
     bool have_maxid = false; double maxid = 0.0;
+    bool have_vgrid = false; M3Grid vgrid;           // the padded centre grid of the resident step: uploaded once per context
 };
 // a refill riding on a sort: what to do, and what the sort found
 struct M3Refill {
@@ -554,6 +556,11 @@ struct M3Refill {
 };
 #define M3_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return pl3_fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 #define M3_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+// every copy between host and device is counted (pl3_transfer_stats)
+static inline hipError_t m3_copy(pl3_ctx* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t stream) {
+    pl3_count_copy(ctx, bytes);
+    return hipMemcpyAsync(dst, src, bytes, kind, stream);
+}
 
 void pl3_mic_free(void** slot) {
     Mic3* M = (Mic3*)*slot;
@@ -599,7 +606,7 @@ static int m3_grid(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, cons
     for (int a = 0; a < 3; a++) {
         if (n[a] < 2) return pl3_fail(ctx, "3-D marker-in-cell: a node set needs at least 2 coordinates per axis");
         for (int i = 0; i + 1 < n[a]; i++) if (!(c[a][i + 1] > c[a][i])) return pl3_fail(ctx, "3-D marker-in-cell: coordinates must increase");
-        M3_HIP(ctx, hipMemcpyAsync(d + off, c[a], (size_t)n[a] * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, d + off, c[a], (size_t)n[a] * sizeof(double), hipMemcpyHostToDevice, v.stream));
         g.a[a].n = n[a]; g.a[a].c0 = c[a][0]; g.a[a].L = c[a][n[a] - 1] - c[a][0]; g.a[a].h0 = c[a][1] - c[a][0];
         g.a[a].h1 = c[a][n[a] - 1] - c[a][n[a] - 2]; g.a[a].c = d + off;
         off += n[a];
@@ -651,7 +658,7 @@ static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long 
         m3_scan_sums<3>(v, (int)m, cnt, need, nb, bsum, tot, idpart, nid);
         M3_HIP(ctx, hipGetLastError());
         M3Totals h;                                   // the one read-back of a refill: how many tracers the arrays must hold
-        M3_HIP(ctx, hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, &h, tot, sizeof(h), hipMemcpyDeviceToHost, v.stream));
         M3_HIP(ctx, hipStreamSynchronize(v.stream));
         rf->ninj = h.v[1]; rf->nref = h.v[2]; rf->nempty = h.v[3]; rf->mincnt = m > 0 ? h.v[4] : 0;
         if (idpart) { M->maxid = std::isfinite(h.maxid) ? h.maxid : -1.0; M->have_maxid = true; }     // no finite ID: numbering starts at 0
@@ -708,7 +715,7 @@ static int m3_scatter_device(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Scatter& a
         a.lo[d] = d_tab + off; a.hi[d] = d_tab + off + n;
         off += 2 * (size_t)n;
     }
-    M3_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, v.stream));
+    M3_HIP(ctx, m3_copy(ctx, d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     a.start = start;
     const long long N = (long long)tn[0] * tn[1] * tn[2];
@@ -743,8 +750,8 @@ extern "C" int pl3_trac2grid(pl3_ctx* ctx, int64_t n, const double* tr_x, const 
     M3Grid sg;
     M3_TRY(m3_grid(ctx, v, M, "h_sgrid", tc, tn, sg));
     if (n > 0) {
-        M3_HIP(ctx, hipMemcpyAsync(aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
-        M3_HIP(ctx, hipMemcpyAsync(aos + 3 * nn, tr_f, (size_t)n * ld_f * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, aos + 3 * nn, tr_f, (size_t)n * ld_f * sizeof(double), hipMemcpyHostToDevice, v.stream));
     }
     M3Pos p{{aos, aos + 1, aos + 2}, 3};
     int *perm, *start;
@@ -759,14 +766,14 @@ extern "C" int pl3_trac2grid(pl3_ctx* ctx, int64_t n, const double* tr_x, const 
     a.nf = nf;
     for (int k = 0; k < nf; k++) { a.val[k] = vals + k * nn; a.scheme[k] = avgscheme[k]; a.out[k] = dout + k * N; }
     M3_TRY(m3_scatter_device(ctx, v, M, a, tc, tn, tc, tn, start));
-    for (int k = 0; k < nf; k++) M3_HIP(ctx, hipMemcpyAsync(out[k], dout + k * N, N * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    for (int k = 0; k < nf; k++) M3_HIP(ctx, m3_copy(ctx, out[k], dout + k * N, N * sizeof(double), hipMemcpyDeviceToHost, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     return 0;
 }
 
 static int m3_fields_up(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, int nf, const double* const* fields, size_t GN, double** d) {
     M3_TRY(m3_buf(ctx, v, M, name, GN * (size_t)nf, d));
-    for (int k = 0; k < nf; k++) M3_HIP(ctx, hipMemcpyAsync(*d + k * GN, fields[k], GN * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    for (int k = 0; k < nf; k++) M3_HIP(ctx, m3_copy(ctx, *d + k * GN, fields[k], GN * sizeof(double), hipMemcpyHostToDevice, v.stream));
     return 0;
 }
 
@@ -789,17 +796,18 @@ extern "C" int pl3_grid2trac(pl3_ctx* ctx, int64_t n, const double* tr_x, int nf
     M3Gather a{};
     M3_TRY(m3_grid(ctx, v, M, "h_ggrid", gc, gn, a.g));
     M3_TRY(m3_fields_up(ctx, v, M, "h_gfields", nf, fields, GN, &df));
-    if (n > 0) M3_HIP(ctx, hipMemcpyAsync(dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    if (n > 0) M3_HIP(ctx, m3_copy(ctx, dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
     a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.nf = nf; a.os = nf; a.method = method; a.defval = defval; a.accumulate = 0; a.nout = cnt;
     for (int k = 0; k < nf; k++) { a.f[k] = df + k * GN; a.out[k] = dout + k; }
     if (n > 0) hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
     M3_HIP(ctx, hipGetLastError());
     unsigned long long nout = 0;
-    M3_HIP(ctx, hipMemcpyAsync(&nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, m3_copy(ctx, &nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     if (n_outside) *n_outside = (int64_t)nout;
     if (stop_on_error && nout > 0) return pl3_fail(ctx, "stopOnError in grid2trac");
     if (n > 0) {
+        pl3_count_copy(ctx, (size_t)n * nf * sizeof(double));
         M3_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ld_out * sizeof(double), dout, (size_t)nf * sizeof(double), (size_t)nf * sizeof(double), (size_t)n,
                                      hipMemcpyDeviceToHost, v.stream));
         M3_HIP(ctx, hipStreamSynchronize(v.stream));
@@ -819,14 +827,14 @@ extern "C" int pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int
     M3Rk4 a{};
     M3_TRY(m3_grid(ctx, v, M, "h_ggrid", gc, gn, a.g));
     M3_TRY(m3_fields_up(ctx, v, M, "h_gfields", 3, vel, GN, &df));
-    if (n > 0) M3_HIP(ctx, hipMemcpyAsync(dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    if (n > 0) M3_HIP(ctx, m3_copy(ctx, dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
     a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.dt = tstep; a.os = 3; a.fence = 0;
     for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = dx + 3 * nn + d; a.vo[d] = dx + 6 * nn + d; }
     if (n > 0) {
         hipLaunchKernelGGL(k_m3_rk4, m3_blocks(n), dim3(256), 0, v.stream, a);
         M3_HIP(ctx, hipGetLastError());
-        M3_HIP(ctx, hipMemcpyAsync(x_out, dx + 3 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-        M3_HIP(ctx, hipMemcpyAsync(v_out, dx + 6 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, x_out, dx + 3 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, v_out, dx + 6 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
     }
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     return 0;
@@ -885,8 +893,8 @@ extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, c
     M->n = n; M->cap = cap; M->x = a; M->f = a + 3 * cap; M->v = a + (3 + M3_NFTRAC) * cap; M->have = true; M->have_maxid = false;
     M3_HIP(ctx, hipMemsetAsync(a, 0, (size_t)cap * (6 + M3_NFTRAC) * sizeof(double), v.stream));
     if (n > 0) {
-        M3_HIP(ctx, hipMemcpyAsync(aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
-        M3_HIP(ctx, hipMemcpyAsync(aos + 3 * cap, tr_f, (size_t)n * M3_NFTRAC * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, aos + 3 * cap, tr_f, (size_t)n * M3_NFTRAC * sizeof(double), hipMemcpyHostToDevice, v.stream));
         hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, (long long)n, (const double*)aos, 3ll, 1ll, 3, (const int*)nullptr, M->x, cap, 0u);
         hipLaunchKernelGGL(k_m3_take, m3_blocks(n), dim3(256), 0, v.stream, (long long)n, (const double*)(aos + 3 * cap), (long long)M3_NFTRAC, 1ll, M3_NFTRAC,
                            (const int*)nullptr, M->f, cap, 0u);
@@ -901,7 +909,7 @@ static int m3_down(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const double* src, int
     if (M->n > 0) {
         hipLaunchKernelGGL(k_m3_to_aos, m3_blocks(M->n), dim3(256), 0, v.stream, M->n, src, M->cap, ncol, aos);
         M3_HIP(ctx, hipGetLastError());
-        M3_HIP(ctx, hipMemcpyAsync(host, aos, (size_t)M->n * ncol * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+        M3_HIP(ctx, m3_copy(ctx, host, aos, (size_t)M->n * ncol * sizeof(double), hipMemcpyDeviceToHost, v.stream));
     }
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     return 0;
@@ -931,7 +939,7 @@ extern "C" int pl3_tracers_census(pl3_ctx* ctx, int64_t ncell, int32_t* counts) 
     M3_TRY(m3_buf(ctx, v, M, "r_census", (size_t)m, &d));
     hipLaunchKernelGGL(k_m3_census, m3_blocks(m), dim3(256), 0, v.stream, (int)m, (const int*)M->bufs["r_start"], d);
     M3_HIP(ctx, hipGetLastError());
-    M3_HIP(ctx, hipMemcpyAsync(counts, d, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, m3_copy(ctx, counts, d, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     return 0;
 }
@@ -978,6 +986,24 @@ static int m3_resident_scatter(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, int nf, co
     return m3_scatter_device(ctx, v, M, a, tc, tn, v.coord, v.gn, (const int*)M->bufs["r_start"]);
 }
 
+// resident columns -> a node set, into the plain device array dout (nf x N); the device time goes to pl3_resident_times
+static int m3_columns_scatter(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* who, int nf, const int* columns, const int* avgscheme,
+                              const double* const tc[3], const int tn[3], double* dout) {
+    const double* col[M3_MAXF];
+    for (int k = 0; k < nf; k++) {
+        if (columns[k] < 0 || columns[k] >= M3_NFTRAC) return pl3_fail(ctx, std::string(who) + ": tracer column out of range");
+        col[k] = M->f + (long long)columns[k] * M->cap;
+    }
+    M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
+    M3_TRY(m3_resident_scatter(ctx, v, M, nf, col, avgscheme, tc, tn, dout));
+    M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
+    return 0;
+}
+static int m3_scatter_time(pl3_ctx* ctx, Pl3HostView& v, Mic3* M) {
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[0] = ms;
+    return 0;
+}
 extern "C" int pl3_resident_trac2grid(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* zc, int nzc, const double* xc,
                                       int nxc, const double* yc, int nyc, double* const* out) {
     Pl3HostView v; Mic3* M;
@@ -986,39 +1012,50 @@ extern "C" int pl3_resident_trac2grid(pl3_ctx* ctx, int nf, const int* columns, 
     if (nf < 1 || nf > M3_MAXF || !columns || !avgscheme || !zc || !xc || !yc || !out) return pl3_fail(ctx, "pl3_resident_trac2grid: bad argument (1..8 fields per call)");
     const double* tc[3] = {zc, xc, yc}; const int tn[3] = {nzc, nxc, nyc};
     const size_t N = (size_t)nzc * nxc * nyc;
-    const double* col[M3_MAXF];
-    for (int k = 0; k < nf; k++) {
-        if (columns[k] < 0 || columns[k] >= M3_NFTRAC) return pl3_fail(ctx, "pl3_resident_trac2grid: tracer column out of range");
-        col[k] = M->f + (long long)columns[k] * M->cap;
-    }
     double* dout;
     M3_TRY(m3_buf(ctx, v, M, "r_out", N * (size_t)nf, &dout));
-    M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
-    M3_TRY(m3_resident_scatter(ctx, v, M, nf, col, avgscheme, tc, tn, dout));
-    M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
-    for (int k = 0; k < nf; k++) M3_HIP(ctx, hipMemcpyAsync(out[k], dout + k * N, N * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    M3_HIP(ctx, hipStreamSynchronize(v.stream));
-    float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[0] = ms;
+    M3_TRY(m3_columns_scatter(ctx, v, M, "pl3_resident_trac2grid", nf, columns, avgscheme, tc, tn, dout));
+    for (int k = 0; k < nf; k++) M3_HIP(ctx, m3_copy(ctx, out[k], dout + k * N, N * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    return m3_scatter_time(ctx, v, M);
+}
+int pl3i_mic_scatter(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* const tc[3], const int tn[3], double* dout) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_step", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_step"));
+    M3_TRY(m3_columns_scatter(ctx, v, M, "pl3_resident_step", nf, columns, avgscheme, tc, tn, dout));
+    return m3_scatter_time(ctx, v, M);
+}
+int pl3i_mic_buf(pl3_ctx* ctx, const char* name, size_t count, double** out) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_step", v, &M));
+    return m3_buf(ctx, v, M, name, count, out);
+}
+int pl3i_mic_columns(pl3_ctx* ctx, double** f, long long* n, long long* cap) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_step", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_step"));
+    *f = M->f; *n = M->n; *cap = M->cap;
     return 0;
+}
+double* pl3i_mic_ms(pl3_ctx* ctx) {
+    Pl3HostView v; Mic3* M;
+    return m3_open(ctx, "pl3_resident_step", v, &M) ? nullptr : M->ms;
 }
 
 // Temperature to the tracers (pylamp2.py:445-480): absolute != 0: T = interpolation of `field` (the first step); else T += interpolation
 // (field = T_new - T_old on the nodes) and, with subgrid != 0, the subgrid-diffusion correction with tstep.  A tracer outside the
 // grid is an error, as with stopOnError in 2-D.
-extern "C" int pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* field, int subgrid, double tstep) {
-    Pl3HostView v; Mic3* M;
-    M3_TRY(m3_open(ctx, "pl3_resident_temp_to_tracers", v, &M));
-    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_temp_to_tracers"));
-    if (!field) return pl3_fail(ctx, "pl3_resident_temp_to_tracers: NULL field");
+// field: host array, or with dev a plain device array that is read in place
+static int m3_temp_to_tracers(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, int absolute, const double* field, bool dev, int subgrid, double tstep) {
     const long long n = M->n, cap = M->cap;
     const size_t GN = (size_t)v.gn[0] * v.gn[1] * v.gn[2];
-    double *df, *w, *dnode; unsigned long long* cnt;
-    M3_TRY(m3_buf(ctx, v, M, "r_tfield", GN, &df));
+    double *df = const_cast<double*>(field), *w, *dnode; unsigned long long* cnt;
+    if (!dev) M3_TRY(m3_buf(ctx, v, M, "r_tfield", GN, &df));
     M3_TRY(m3_buf(ctx, v, M, "r_twork", (size_t)cap * 3, &w));
     M3_TRY(m3_buf(ctx, v, M, "r_tnode", GN, &dnode));
     M3_TRY(m3_buf(ctx, v, M, "h_counter", (size_t)8, &cnt));
     M3_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(*cnt), v.stream));
-    M3_HIP(ctx, hipMemcpyAsync(df, field, GN * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    if (!dev) M3_HIP(ctx, m3_copy(ctx, df, field, GN * sizeof(double), hipMemcpyHostToDevice, v.stream));
     M3Gather a{};
     M3_TRY(m3_node_grid(ctx, v, M, a.g));
     double* T = M->f + M3_TMP * cap;
@@ -1041,11 +1078,24 @@ extern "C" int pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const do
     M3_HIP(ctx, hipGetLastError());
     M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
     unsigned long long nout = 0;
-    M3_HIP(ctx, hipMemcpyAsync(&nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, m3_copy(ctx, &nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[1] = ms;
     if (nout > 0) return pl3_fail(ctx, "stopOnError in grid2trac");
     return 0;
+}
+extern "C" int pl3_resident_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* field, int subgrid, double tstep) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_temp_to_tracers", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_temp_to_tracers"));
+    if (!field) return pl3_fail(ctx, "pl3_resident_temp_to_tracers: NULL field");
+    return m3_temp_to_tracers(ctx, v, M, absolute, field, false, subgrid, tstep);
+}
+int pl3i_mic_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* dfield, int subgrid, double tstep) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_step", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_step"));
+    return m3_temp_to_tracers(ctx, v, M, absolute, dfield, true, subgrid, tstep);
 }
 
 // what a refill may be asked for; out = the four counters of the header
@@ -1062,16 +1112,12 @@ static int m3_refill_args(pl3_ctx* ctx, const char* who, int tracdens, int tracd
 static void m3_refill_out(const M3Refill& rf, int64_t out[4]) { out[0] = rf.ninj; out[1] = rf.nref; out[2] = rf.nempty; out[3] = rf.mincnt; }
 
 // RK4 on the padded centre grid (nz+1, nx+1, ny+1), fence (pylamp2.py:558-572, length = the node grid's extent), re-sort (+ refill)
-static int m3_advect(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* who, const double* gz, const double* gx, const double* gy, const double* vz,
-                     const double* vx, const double* vy, double tstep, int fence, M3Refill* rf) {
-    if (!gz || !gx || !gy || !vz || !vx || !vy) return pl3_fail(ctx, std::string(who) + ": bad argument");
-    const double* gc[3] = {gz, gx, gy}; const int gn[3] = {v.gn[0] + 1, v.gn[1] + 1, v.gn[2] + 1}; const double* vel[3] = {vz, vx, vy};
-    const size_t GN = (size_t)gn[0] * gn[1] * gn[2];
+// g / df: the padded centre grid and the three velocity arrays on it, on the device
+static int m3_advect_dev(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const M3Grid& g, const double* df, double tstep, int fence, M3Refill* rf) {
+    const size_t GN = (size_t)(v.gn[0] + 1) * (v.gn[1] + 1) * (v.gn[2] + 1);
     const long long n = M->n, cap = M->cap;
-    double* df;
     M3Rk4 a{};
-    M3_TRY(m3_grid(ctx, v, M, "r_vgrid", gc, gn, a.g));
-    M3_TRY(m3_fields_up(ctx, v, M, "r_vfields", 3, vel, GN, &df));
+    a.g = g;
     a.n = n; a.p = M3Pos{{M->x, M->x + cap, M->x + 2 * cap}, 1}; a.dt = tstep; a.os = 1; a.fence = fence ? 1 : 0; a.eps = 1.0 / 1024.0;   // EPS of pylamp_const.py
     for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = M->x + d * cap; a.vo[d] = M->v + d * cap; a.L[d] = v.coord[d][v.gn[d] - 1]; }
     M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
@@ -1081,6 +1127,43 @@ static int m3_advect(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* who, con
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[2] = ms;
     return m3_resort(ctx, v, M, rf);
+}
+static int m3_advect(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* who, const double* gz, const double* gx, const double* gy, const double* vz,
+                     const double* vx, const double* vy, double tstep, int fence, M3Refill* rf) {
+    if (!gz || !gx || !gy || !vz || !vx || !vy) return pl3_fail(ctx, std::string(who) + ": bad argument");
+    const double* gc[3] = {gz, gx, gy}; const int gn[3] = {v.gn[0] + 1, v.gn[1] + 1, v.gn[2] + 1}; const double* vel[3] = {vz, vx, vy};
+    const size_t GN = (size_t)gn[0] * gn[1] * gn[2];
+    double* df;
+    M3Grid g;
+    M3_TRY(m3_grid(ctx, v, M, "r_vgrid", gc, gn, g));
+    M3_TRY(m3_fields_up(ctx, v, M, "r_vfields", 3, vel, GN, &df));
+    return m3_advect_dev(ctx, v, M, g, df, tstep, fence, rf);
+}
+// The step's advection: dV = the three padded velocity arrays on the device.  The padded coordinates (pylamp2.py:92-95 and :491-493:
+// midpoints, one extrapolated entry at either end) are computed and uploaded once per context.
+int pl3i_mic_advect(pl3_ctx* ctx, const double* dV, double tstep, int tracdens, int tracdens_min, uint64_t seed, int it, int unique_ids, int64_t out[4]) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_resident_step", v, &M));
+    M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_step"));
+    M3_TRY(m3_refill_args(ctx, "pl3_resident_step", tracdens, tracdens_min, 1, out));
+    const int gn[3] = {v.gn[0] + 1, v.gn[1] + 1, v.gn[2] + 1};
+    if (!M->have_vgrid) {
+        std::vector<double> c[3];
+        for (int d = 0; d < 3; d++) {
+            const int n = v.gn[d]; const double* x = v.coord[d];
+            c[d].resize((size_t)n + 1);
+            for (int i = 0; i + 1 < n; i++) c[d][i + 1] = (x[i + 1] + x[i]) / 2;
+            c[d][n] = c[d][n - 1] + (c[d][n - 1] - c[d][n - 2]);
+            c[d][0] = c[d][1] - (c[d][2] - c[d][1]);
+        }
+        const double* gc[3] = {c[0].data(), c[1].data(), c[2].data()};
+        M3_TRY(m3_grid(ctx, v, M, "s_vgrid", gc, gn, M->vgrid));
+        M->have_vgrid = true;
+    }
+    M3Refill rf{tracdens, tracdens_min, seed, it, unique_ids ? 1 : 0};
+    M3_TRY(m3_advect_dev(ctx, v, M, M->vgrid, dV, tstep, 1, &rf));
+    m3_refill_out(rf, out);
+    return 0;
 }
 extern "C" int pl3_resident_rk4(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
                                 const double* vy, double tstep, int fence) {

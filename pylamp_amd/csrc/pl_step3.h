@@ -1,0 +1,28 @@
+// What pl_step3.hip (the device-resident 3-D time step) needs of pl_3d.hip (the context and the solvers) and of pl_mic3.hip (the
+// resident tracers): device-source variants of the entry points that otherwise take host arrays.
+#pragma once
+#include "pl_internal.h"
+
+// the context's ringed device arrays: node (i, j, k) of an array sits at (i + 1) s0 + (j + 1) s1 + k + pad
+struct Pl3DevView {
+    long long s0, s1; int pad; hipStream_t stream;
+    double* X[4];                           // Stokes solution of the last solve: vz, vx, vy, P (Kcont-scaled)
+    double* T;                              // heat solution of the last solve
+    double* scratch[4];                     // work vectors that are free outside a solve
+    bool have_x, have_T;
+    void** slot;                            // opaque state owned by pl_step3.hip, released by pl3_step_free
+};
+// pl_3d.hip
+int  pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v);
+int  pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3], double mineta);
+int  pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const double* const src[7], const int bc[6], const double bcvalue[6], double tstep);
+void pl3_count_copy(pl3_ctx* ctx, size_t bytes);          // every host <-> device copy of a pl3_* entry point reports here
+// pl_mic3.hip (plain (nz, nx, ny) device arrays in and out)
+int  pl3i_mic_scatter(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* const tc[3], const int tn[3], double* dout);
+int  pl3i_mic_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* dfield, int subgrid, double tstep);
+int  pl3i_mic_advect(pl3_ctx* ctx, const double* dV, double tstep, int tracdens, int tracdens_min, uint64_t seed, int it, int unique_ids, int64_t out[4]);
+int  pl3i_mic_buf(pl3_ctx* ctx, const char* name, size_t count, double** out);      // a device buffer that lives as long as the tracers' state
+int  pl3i_mic_columns(pl3_ctx* ctx, double** f, long long* n, long long* cap);    // the resident tracer fields: column j at f + j cap
+double* pl3i_mic_ms(pl3_ctx* ctx);                        // the four stage times of pl3_resident_times
+// pl_step3.hip
+void pl3_step_free(void** slot);

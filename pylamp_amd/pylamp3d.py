@@ -459,6 +459,8 @@ class Options3:
         # parts of the 2-D step that do not exist in 3-D yet: anything but these values is rejected by name
         self.tracs_fence_enabled = True
         self.surface_stabilization = False
+        # True: step() is one pl3_resident_step call -- every grid field stays on the device, field() downloads on demand
+        self.resident = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
@@ -471,7 +473,8 @@ class Simulation3:
     + refill of depleted cells inside the end-of-step sort (Options3.tracdens / tracdens_min / inject_seed / inject_unique_ids;
     refill() does it without a step).  step() reports ninjected, nrefilled (cells) and nempty (cells that held no tracer: their new
     tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank,
-    regular grid, all walls free-slip.  Not built: the fence-off deletion path, surface stabilisation, non-uniform grids for the
+    regular grid, all walls free-slip.  Options3.resident = True runs the same sequence inside the library with every grid field
+    kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Not built: the fence-off deletion path, surface stabilisation, non-uniform grids for the
     markers, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
@@ -503,6 +506,7 @@ class Simulation3:
         self.ntrac = 0
         self.fields = {}
         self._newtemp = None
+        self._stepped = False                    # resident: the library holds the fields of a step
         if tr_x is not None:
             self.upload(tr_x, tr_f)
 
@@ -547,9 +551,20 @@ class Simulation3:
 
     def field(self, name):
         """A grid field of the last step: rho, etas, etan, cp, T, H, mat, kz, kx, ky, velz, velx, vely, pres, temp."""
+        if self.opt.resident and name not in self.fields:
+            out = np.empty(self.nx)
+            self._lib_call("pl3_get_field", name.encode(), _lib.dptr(out))
+            self.fields[name] = out                  # cached until the next step
         if name not in self.fields:
             raise Exception("Simulation3.field: no field '%s' (have: %s)" % (name, ", ".join(sorted(self.fields))))
         return self.fields[name]
+
+    def transfer_stats(self, reset=False):
+        """Host <-> device copies of this simulation's library calls since the last reset: counts and bytes of those of at least one
+        node field (8 nz nx ny bytes) and of the smaller ones."""
+        v = (C.c_int64 * 4)()
+        self.ctx.check(self.ctx.lib.pl3_transfer_stats(self.ctx.handle(), v, 1 if reset else 0))
+        return dict(large=int(v[0]), large_bytes=int(v[1]), small=int(v[2]), small_bytes=int(v[3]))
 
     def stage_times(self):
         ms = (C.c_double * 4)()
@@ -623,18 +638,60 @@ class Simulation3:
         return self._counters(out)
 
     # -- one time step -----------------------------------------------------------------------------------------------
+    _NAN_MESSAGE = ("Simulation3.step: the scattered field '%s' holds NaN at %d nodes - a grid node without any marker in "
+                    "reach makes the interpolated fields NaN, and so do tracers injected into a cell without residents "
+                    "(their fields are 0/0 as in pylamp2.py:624-629): raise the marker density or enable injection "
+                    "(Options3.tracdens / tracdens_min) before cells run empty")
+
+    def _step_resident(self):
+        """step() as one library call: the fields stay on the device."""
+        o = self.opt
+        cfg = _lib.Step3Config()
+        for k in ("do_heatdiff", "do_subgrid_heatdiff", "tdep_rho", "tdep_eta", "stokes_maxit", "heat_maxit", "tracdens", "tracdens_min"):
+            setattr(cfg, k, int(getattr(o, k)))
+        for k in ("etamin", "etamax", "tstep_adv_max", "tstep_adv_min", "tstep_dif_max", "tstep_dif_min", "tstep_modifier", "stokes_rtol",
+                  "heat_rtol"):
+            setattr(cfg, k, float(getattr(o, k)))
+        cfg.tref = float(o.Tref)
+        for w in range(6):
+            cfg.bcheat[w] = int(o.bcheat[w]); cfg.bcheatvals[w] = float(o.bcheatvals[w])
+        cfg.use_grav = 0 if o.grav is None else 1
+        for d in range(3):
+            cfg.grav[d] = 0.0 if o.grav is None else float(o.grav[d])
+        cfg.inject_seed = int(o.inject_seed) & (2 ** 64 - 1)
+        cfg.inject_unique_ids = 1 if o.inject_unique_ids else 0
+        r = _lib.Step3Report()
+        if self.ctx.nranks_attached():
+            raise Exception("Simulation3: several ranks are not supported by the 3-D markers")
+        rc = self.ctx.lib.pl3_resident_step(self.ctx.handle(), C.byref(cfg), self.it + 1, C.byref(r))
+        if rc != 0:
+            self.fields = {}
+            for name, n in (("rho", r.nan_rho), ("etas", r.nan_etas)):
+                if n > 0:
+                    raise Exception(self._NAN_MESSAGE % (name, int(n)))
+            self.ctx.check(rc)
+        self.it += 1
+        self.ntrac = int(r.ntrac)
+        self.totaltime += r.tstep
+        rep = dict(it=self.it, tstep=r.tstep, limiter="H" if r.limiter else "S", stokes=r.stokes.as_dict(),
+                   heat=r.heat.as_dict() if o.do_heatdiff else None, ninjected=int(r.ninjected), nrefilled=int(r.nrefilled),
+                   nempty=int(r.nempty), mincount=int(r.mincount), time=self.totaltime, ntrac=self.ntrac)
+        self.fields = {}
+        self._stepped = True
+        self.last = rep
+        return rep
+
     def step(self):
         o = self.opt
+        if o.resident:
+            return self._step_resident()
         self.it += 1
         dx = [self.L[d] / (self.nx[d] - 1) for d in range(3)]
         f = self.scatter_fields()
         for name in ("rho", "etas"):
             if np.isnan(f[name]).any():
                 self.it -= 1
-                raise Exception("Simulation3.step: the scattered field '%s' holds NaN at %d nodes - a grid node without any marker in "
-                                "reach makes the interpolated fields NaN, and so do tracers injected into a cell without residents "
-                                "(their fields are 0/0 as in pylamp2.py:624-629): raise the marker density or enable injection "
-                                "(Options3.tracdens / tracdens_min) before cells run empty" % (name, int(np.isnan(f[name]).sum())))
+                raise Exception(self._NAN_MESSAGE % (name, int(np.isnan(f[name]).sum())))
         if o.do_heatdiff:
             if self.it > 1:                      # pylamp2.py:327-331: the walls keep the solved temperature
                 nt = self._newtemp
@@ -679,7 +736,12 @@ class Simulation3:
     def write_snapshot(self, outdir="out"):
         """griddata.NNNNNN.npz / tracs.NNNNNN.npz with the keys of the 2-D snapshots (pylamp2.py:637-650) plus the third axis."""
         import os
-        f = self.fields
+        if self.opt.resident and self._stepped:
+            f = {k: self.field(k) for k in ("velz", "velx", "vely", "pres", "rho")}
+            if self.opt.do_heatdiff:
+                f["temp"] = self.field("temp")
+        else:
+            f = self.fields
         temp = f["temp"] if "temp" in f else f["velx"] * 0.0
         tr_x, tr_f = self.tracers(); tr_v = self.tracer_velocity()
         os.makedirs(outdir, exist_ok=True)

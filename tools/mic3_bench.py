@@ -11,6 +11,13 @@ a warm-up; bytes per tracer are the algorithmic minimum, the roof is 8 TB/s.
                  a refilled set has nothing left to inject), --refill-reps repetitions.
 --parent FILE [FILE ...] embeds the sort_off figures that the same script wrote for another tree (the parent commit's), run in
 separate processes alternating with this one, and reports the run-to-run spread of both next to the medians.
+
+--step [--resident] times whole steps of Simulation3 -- the falling sphere with heat on, --n nodes per axis, 8 tracers per cell:
+host wall time per step (device synchronisation, then perf_counter, on either side of step()), median and min-max over --reps
+steps after --warmup, and the medians of the stage times (device events); writes profiles/mic3_step_129.json unless --out says
+otherwise.  --resident selects Options3.resident (one pl3_resident_step call per step, the grid fields stay on the device).
+--tree DIR imports pylamp_amd from another checkout: the host-staged yardstick is run on the parent commit's library, in
+separate processes alternating with the resident runs of this one.
 """
 import argparse
 import json
@@ -19,7 +26,8 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+_TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv[1:-1] else os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.abspath(_TREE))
 from pylamp_amd import pylamp3d as P3                                             # noqa: E402
 
 ROOF = 8.0e12
@@ -86,6 +94,42 @@ def sort_only(a):
     return out
 
 
+def step_bench(a):
+    import time
+    import torch
+    nx = [a.n] * 3; L = [100e3] * 3
+    tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(0), per_axis=a.per_axis)
+    n = tr_x.shape[0]
+    tr_f[:, 3] = 273 + 1350 * tr_x[:, 0] / L[0]; tr_f[:, 4] = 4.0; tr_f[:, 5] = 1250; tr_f[:, 7] = 3.5e-5; tr_f[:, 11] = 1e-9
+    kw = dict(resident=True) if a.resident else {}
+    sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**kw))
+    del tr_x, tr_f
+    wall, stages, its = [], {}, []
+    for rep in range(a.warmup + a.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = sim.step()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        assert r["stokes"]["converged"] == 1 and r["heat"]["converged"] == 1, r
+        if rep >= a.warmup:
+            wall.append(ms); its.append(r["stokes"]["iterations"])
+            st = dict(sim.stage_times(), stokes=r["stokes"]["solve_ms"], heat=r["heat"]["solve_ms"])
+            for k, v in st.items():
+                stages.setdefault(k, []).append(v)
+    out = dict(config="mic3_%d_step" % a.n, mode="resident" if a.resident else "staged", tree=a.tree or ".", nodes=a.n ** 3, tracers=n,
+               reps=a.reps, warmup=a.warmup, step_ms=round(float(np.median(wall)), 2), step_ms_min=round(float(np.min(wall)), 2),
+               step_ms_max=round(float(np.max(wall)), 2), stokes_iterations=its,
+               stage_ms={k: round(float(np.median(v)), 3) for k, v in stages.items()})
+    # what the stage times do not cover: host work and copies (staged: "scatter" is the LAST of the step's five scatters alone)
+    out["other_ms"] = round(out["step_ms"] - sum(out["stage_ms"].values()), 2)
+    if hasattr(sim, "transfer_stats"):
+        sim.transfer_stats(reset=True); sim.step()
+        out["transfers_per_step"] = sim.transfer_stats()
+    sim.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=129); ap.add_argument("--per-axis", type=int, default=2)
@@ -93,11 +137,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sort-only", action="store_true"); ap.add_argument("--refill-reps", type=int, default=7)
     ap.add_argument("--parent", nargs="*", default=[])
+    ap.add_argument("--step", action="store_true"); ap.add_argument("--resident", action="store_true"); ap.add_argument("--tree", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join("profiles", "mic3_129_refill.json" if a.sort_only else "mic3_129.json")
-    if a.sort_only:
-        line = json.dumps(sort_only(a))
+        a.out = os.path.join("profiles", "mic3_step_129.json" if a.step else ("mic3_129_refill.json" if a.sort_only else "mic3_129.json"))
+    if a.sort_only or a.step:
+        line = json.dumps(step_bench(a) if a.step else sort_only(a))
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(line + "\n")
