@@ -1,11 +1,11 @@
-"""3-D staggered Stokes + heat on HIP kernels (BASELINE config 5) -- PARITY UNPINNED.
+"""3-D staggered Stokes + heat on HIP kernels (BASELINE config 5) -- pinned to the NumPy model tests/stokes3_model.py.
 
 The reference implements DIM = 2 only (pylamp_const.py:6; pylamp_stokes.gidx prints "NOT IMPLEMENTED" for dim != 2,
 pylamp_stokes.py:30-35).  What it fixes is the intent: axis order z, x, y (pylamp_const.py:9-13), arrays (nz, nx, ny),
 IP = DIM = 3 and the DOF order of the comment at pylamp_stokes.py:24.  The functions below mirror the 2-D module API
 (makeStokesMatrix / x2vp / solve, makeDiffusionMatrix / x2t / solve) with those conventions; the operators extend the
 2-D rows dimension by dimension (pylamp_amd/csrc/pl_3d.hip) so that a y-invariant extrusion reproduces the 2-D
-operator and solution on every y-slice.
+operator and solution on every y-slice.  The row rules are written out in DESIGN.md section 6c.
 """
 import ctypes as C
 import weakref

@@ -1,7 +1,9 @@
-"""3-D staggered Stokes + heat (BASELINE config 5).  The reference has no 3-D implementation, so there is no oracle to
-pin (parity UNPINNED).  Validation follows the survey's recipe: (i) a y-invariant extrusion of a 2-D
-problem must reproduce the 2-D oracle on every y-slice -- operator to 1e-12, solution to 1e-6; (ii) a manufactured
-solution with genuinely 3-D structure converges at second order; (iii) true residuals."""
+"""3-D staggered Stokes + heat (BASELINE config 5).  The reference has no 3-D implementation, so there is no
+reference output to pin; what pins the 3-D operators, right-hand sides and solutions is the independent NumPy model
+tests/stokes3_model.py (tied to the 2-D oracle by tests/test_stokes3_model.py, compared with the kernels by
+tests/test_hip_3d_model.py).  This module keeps the survey's recipe: (i) a y-invariant extrusion of a 2-D problem must
+reproduce the 2-D oracle on every y-slice -- operator to 1e-12, solution to 1e-6; (ii) a manufactured solution with
+genuinely 3-D structure converges at second order; (iii) true residuals; (iv) blocks against one rank."""
 import numpy as np
 import pytest
 
