@@ -188,6 +188,14 @@ int  pl_stream_triad_bench(pl_ctx* ctx, int64_t n, int reps, double* avg_ms);
  * wall/slave/ghost velocity rows of r are ignored - they are identically zero in the solver), and
  * the hierarchy's level count / per-level Chebyshev lambda_max. */
 int  pl_stokes_precond_apply(pl_ctx* ctx, const double* r, double* z);
+/* One launch of the operator with a reduction epilogue, as the Krylov solver uses it (PYLAMP_KRYLOV_FUSED), for the UNSCALED
+ * operator of pl_stokes_apply on host vectors.  mode 1: out = A x, sums[0] = aux1 . out.  mode 2: out = A x, sums[0..7] = out.aux1,
+ * out.out, aux2.aux1, aux2.out, aux1.aux1, then out.aux1, out.out, aux1.aux1 over the continuity rows.  mode 3: out = aux1 - A x,
+ * out2 (may be NULL) = A x, sums[0..4] = |out|^2, its continuity part, |aux1|^2, the sum of (x + aux2)^2 over the velocities
+ * (aux2 may be NULL), the deflation's weighted sum of the continuity rows of out.  rows: row-block height of the launch
+ * (4 or 16; 0: the default of the grid size).  sums holds 8 doubles. */
+int  pl_stokes_apply_reduce(pl_ctx* ctx, int mode, int rows, const double* x, const double* aux1, const double* aux2,
+                            double* out, double* out2, double* sums);
 int  pl_stokes_mg_info(pl_ctx* ctx, int* nlevels, double* lmax, int max_levels);
 /* Average duration (HIP events) of one Chebyshev smoothing sweep on the finest multigrid level -- the kernel
  * with the largest share of a time step (80 B/node algorithmic).  Call after at least one solve. */

@@ -234,8 +234,36 @@ int pl_vec3_upload(pl_ctx* ctx, const PlGeom& g, const double* host, double* dve
 int pl_vec3_download(pl_ctx* ctx, const PlGeom& g, const double* dvec, double* host);
 
 // ---- kernels launched from several units -------------------------------------------------
-void pl_launch_stokes_apply(pl_ctx* ctx, const PlStokesOp& op, const double* x, double* y, const double* add = nullptr,
-                            const double* coef = nullptr);
+// Epilogue of the Stokes operator kernel (pl_stokes.hip): the Krylov solver's reductions over the vector the kernel has just
+// computed, summed while it is still in registers.  Every mode leaves PL_EPI_NSUM (DOT1: 2) partial sums per workgroup in `part`,
+// workgroup b = blockIdx.y * gridDim.x + blockIdx.x, pl_apply_blocks() of them; the second stage is the solver's (pl_solver.hip).
+enum PlApplyMode : int {
+    PL_EPI_NONE = 0,        // y = A x (+ coef[0] * add)
+    PL_EPI_DOT1 = 1,        // ... and part[2b] = sum a1 . y  (a1: r~), part[2b + 1] = 0  -- k_dot2's layout
+    PL_EPI_DOT5 = 2,        // ... and part[8b ..] = t.s, t.t, r~.s, r~.t, s.s, then t.s, t.t, s.s over the continuity plane (cont != 0),
+                            //     t = y, a1 = s, a2 = r~  -- k_dot5's layout
+    PL_EPI_RESID = 3,       // y = a1 - (A x (+ coef[0] * add)), a1 = b; y2 (optional) = A x; part[8b ..] = PlResidSum
+};
+enum PlResidSum : int {
+    PL_RS_RR = 0,           // |y|^2
+    PL_RS_RR_C = 1,         // ... over the continuity plane
+    PL_RS_BB = 2,           // |b|^2
+    PL_RS_XX = 3,           // want_xx: sum over the two velocity planes of (x + a2)^2 (a2 may be NULL)
+    PL_RS_YR = 4,           // want_ysum: the k_defl_ysum-weighted sum of the continuity plane of y
+    PL_EPI_NSUM = 8,
+};
+struct PlApplyArgs {
+    const double* add = nullptr; const double* coef = nullptr;   // add != NULL: + coef[0] * add (coef on the device; add: 3 planes like y)
+    int mode = PL_EPI_NONE;
+    const double* a1 = nullptr; const double* a2 = nullptr;
+    double* y2 = nullptr;
+    double* part = nullptr;
+    int cont = 0, want_xx = 0, want_ysum = 0;
+    int rows = 0;                                                // row-block height of this launch (0: the default of the grid size)
+};
+int pl_apply_rows(const PlGeom& g, int mode, int rows = 0);      // the row-block height a launch uses
+inline int pl_apply_blocks(const PlGeom& g, int rows) { return ((g.lnx + 127) / 128) * ((g.lnz + rows - 1) / rows); }
+void pl_launch_stokes_apply(pl_ctx* ctx, const PlStokesOp& op, const double* x, double* y, const PlApplyArgs& a = PlApplyArgs());
 void pl_launch_stokes_rhs(pl_ctx* ctx, const PlStokesOp& op, double* rhs);
 void pl_launch_heat_apply(pl_ctx* ctx, const PlHeatOp& op, const double* x, double* y, bool scaled = false);
 

@@ -1025,21 +1025,45 @@ __device__ inline void bicg_derive(double* __restrict__ out) {
     out[SC_YR] = (1.0 - om) * out[SC_YSR];
     out[SC_YP] = out[SC_YR] + out[SC_BETA] * (1.0 - om) * out[SC_YP];
 }
-__global__ __launch_bounds__(256) void k_sum_partials5(int nb, const double* __restrict__ part, double* __restrict__ out, int derive) {
-    __shared__ double sh[8][4];
+// One workgroup of 256 threads for the <= DOT_BLOCKS partials of k_dot5, of 1024 for the partials the operator's epilogue leaves
+// (one set per workgroup of ITS grid, 8 721 at 2049^2): sum8_partials is the shared first part, q-th sum of the workgroup in sh[q][0]
+static inline int sum_block(int nb) { return nb > DOT_BLOCKS ? 1024 : 256; }
+__device__ inline void sum8_partials(int nb, const double* __restrict__ part, double (&sh)[8][16]) {
     double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = threadIdx.x; k < nb; k += 256)
+    const int nt = blockDim.x, nw = nt >> 6;
+#pragma unroll 2
+    for (int k = threadIdx.x; k < nb; k += nt)
 #pragma unroll
-        for (int q = 0; q < 8; q++) a[q] += part[8 * k + q];
+        for (int q = 0; q < 8; q++) a[q] += part[8 * (long long)k + q];
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         for (int o = 32; o > 0; o >>= 1) a[q] += __shfl_down(a[q], o, 64);
         if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = a[q];
     }
     __syncthreads();
+    if (threadIdx.x < 8) {
+        double t = sh[threadIdx.x][0];
+        for (int w = 1; w < nw; w++) t += sh[threadIdx.x][w];
+        sh[threadIdx.x][0] = t;
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(1024) void k_sum_partials5(int nb, const double* __restrict__ part, double* __restrict__ out, int derive) {
+    __shared__ double sh[8][16];
+    sum8_partials(nb, part, sh);
     if (threadIdx.x == 0) {
-        for (int q = 0; q < SC_DOT5_N; q++) out[SC_DOT5 + q] = sh[q][0] + sh[q][1] + sh[q][2] + sh[q][3];
+        for (int q = 0; q < SC_DOT5_N; q++) out[SC_DOT5 + q] = sh[q][0];
         if (derive) bicg_derive(out);
+    }
+}
+// the sums of a residual launch of the operator (PL_EPI_RESID) -> sums[PlResidSum]; sc != NULL: its y.r starts the lazy
+// deflation's recurrences (what ysum_dev into SC_YR and k_defl_init do at a (re)start)
+__global__ __launch_bounds__(1024) void k_sum_resid(int nb, const double* __restrict__ part, double* __restrict__ sums, double* __restrict__ sc) {
+    __shared__ double sh[8][16];
+    sum8_partials(nb, part, sh);
+    if (threadIdx.x == 0) {
+        for (int q = 0; q < PL_EPI_NSUM; q++) sums[q] = sh[q][0];
+        if (sc) { sc[SC_YR] = sh[PL_RS_YR][0]; sc[SC_YP] = sh[PL_RS_YR][0]; sc[SC_YSR] = sh[PL_RS_YR][0]; }
     }
 }
 __global__ void k_bicg_derive(double* __restrict__ out) { bicg_derive(out); }
@@ -1528,6 +1552,8 @@ struct PlSolver {
            *bu = nullptr;      // bu: the unscaled right-hand side, kept where the LU solves up front (compensated residual)
     double* scal = nullptr;     // device scalars (PlScal) + block partials (SC_PART, SC_PART2)
     double* hpart = nullptr;    // pinned host copy of the dot partials
+    double* epi = nullptr;      // reductions in the operator's epilogue (PlEpiArea): the sums of a residual launch, then the workgroup partials
+    long long epi_blocks = 0;   // workgroups the partial area holds
     int nu_pre = 2, nu_post = 2, coarse_sweeps = 12;
     int nu0_pre = -1, nu0_post = -1;                    // finest level only (PYLAMP_MG_NU0), -1: as the other levels
     bool aniso_auto = true, ratio_knob = false;        // PYLAMP_MG_ANISO=0 / an explicit PYLAMP_MG_RATIO disable the anisotropy rule
@@ -1635,6 +1661,7 @@ void pl_solver_free(pl_ctx* ctx) {
     if (S->hc_part) (void)hipFree(S->hc_part);
     if (S->hc3) (void)hipFree(S->hc3);
     if (S->hpart) (void)hipHostFree(S->hpart);
+    if (S->epi) (void)hipFree(S->epi);
     delete S;
     ctx->krylov = nullptr;
 }
@@ -1666,21 +1693,24 @@ __global__ void k_s_update_dev(long long n, double* __restrict__ y, const double
 // x += alpha y + omega z ; r = s - omega t
 // x += alpha y + omega z ; r = s - omega t ; and the NEXT iteration's direction p = r + beta (p - omega v) in the same
 // pass (beta from the fused reduction, SC_BETA): r is not read back, 10 instead of 13 vector passes
+// FIRST: the first update after a fused set-up -- x starts from 0 without having been cleared, and the direction that p would
+// hold is still the initial residual p0 (no copy of it was made)
+template <bool FIRST>
 __global__ void k_xrp_update_dev(long long n, double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
                                  double* __restrict__ r, const double* __restrict__ s, const double* __restrict__ t,
                                  double* __restrict__ p, const double* __restrict__ v, const double* __restrict__ sc,
-                                 const double* __restrict__ wd, const double* __restrict__ awd) {
+                                 const double* __restrict__ wd, const double* __restrict__ awd, const double* __restrict__ p0) {
     const double alpha = sc[SC_ALPHA], omega = sc[SC_OMEGA], beta = sc[SC_BETA];
     const double cw = wd ? alpha * sc[SC_CY] + omega * sc[SC_CZ] : 0.0;    // lazy deflation: y and z stand for y + c_y w and z + c_z w
     const double cz = awd ? sc[SC_CZ] : 0.0;                               // ... and (several ranks) t for t + c_z A w
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; k < n; k += (long long)gridDim.x * blockDim.x) {
-        double xn = x[k] + alpha * y[k] + omega * z[k];
+        double xn = FIRST ? alpha * y[k] + omega * z[k] : x[k] + alpha * y[k] + omega * z[k];
         if (wd) xn += cw * wd[k];
         x[k] = xn;
         const double rn = s[k] - omega * (awd ? t[k] + cz * awd[k] : t[k]);
         r[k] = rn;
-        p[k] = rn + beta * (p[k] - omega * v[k]);
+        p[k] = rn + beta * ((FIRST ? p0[k] : p[k]) - omega * v[k]);
     }
 }
 __global__ void k_xr_update_dev(long long n, double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
@@ -1693,17 +1723,21 @@ __global__ void k_xr_update_dev(long long n, double* __restrict__ x, const doubl
 
 // sum the block partials on the device (one workgroup): out[0], out[1] -- always BOTH, so a one-value reduction into slot k also
 // writes its shadow k + 1 (see PlScal).  mode 1 (single rank, out = the scalar block): also alpha = rho_new / out[0] and rho_new
-__global__ __launch_bounds__(256) void k_sum_partials(int nb, const double* __restrict__ part, double* __restrict__ out,
-                                                      int mode = 0, double rho_new = 0.0) {
+// (256 threads, or 1024 for the partials of the operator's epilogue: sum_block)
+__global__ __launch_bounds__(1024) void k_sum_partials(int nb, const double* __restrict__ part, double* __restrict__ out,
+                                                       int mode = 0, double rho_new = 0.0) {
     double s0 = 0.0, s1 = 0.0;
-    for (int k = threadIdx.x; k < nb; k += 256) { s0 += part[2 * k]; s1 += part[2 * k + 1]; }
-    __shared__ double sh[2][4];
+    const int nt = blockDim.x, nw = nt >> 6;
+#pragma unroll 2
+    for (int k = threadIdx.x; k < nb; k += nt) { s0 += part[2 * k]; s1 += part[2 * k + 1]; }
+    __shared__ double sh[2][16];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_down(s0, o, 64); s1 += __shfl_down(s1, o, 64); }
     if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s0; sh[1][threadIdx.x >> 6] = s1; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double a0 = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3], a1 = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+        double a0 = sh[0][0], a1 = sh[1][0];
+        for (int w = 1; w < nw; w++) { a0 += sh[0][w]; a1 += sh[1][w]; }
         out[0] = a0; out[1] = a1;
         if (mode == 1) { out[SC_ALPHA] = rho_new / a0; out[SC_RHO] = rho_new; }
     }
@@ -1800,6 +1834,56 @@ static int dots_dev(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const dou
         if (ride) hipLaunchKernelGGL(k_defl_alpha_ride, dim3(1), dim3(1), 0, ctx->stream, S->scal, rho_new);
         else hipLaunchKernelGGL(k_scalar_alpha, dim3(1), dim3(1), 0, ctx->stream, S->scal, rho_new);
     }
+    return 0;
+}
+
+// ---- reductions in the epilogue of the Stokes operator (PYLAMP_KRYLOV_FUSED, one rank, device scalars) ---------------------------
+// The operator kernel leaves one set of partial sums per workgroup of its own grid -- far more than DOT_BLOCKS -- so they live in
+// an area of their own on the solver: the named sums of a residual launch (PlResidSum) in front, the partials behind them.
+// One workgroup takes 14-18 us to read the 8 721 sets of eight that a launch at 2049^2 leaves (558 KB through one CU): beyond
+// EPI_FOLD_MIN sets, EPI_FOLD_BLOCKS workgroups first fold a contiguous share each -- fixed shares, fixed order: deterministic.
+enum PlEpiArea : int { EPI_FOLD_MIN = 256, EPI_FOLD_BLOCKS = 64, EPI_SUMS = 0, EPI_FOLD = PL_EPI_NSUM, EPI_PART = EPI_FOLD + PL_EPI_NSUM * EPI_FOLD_BLOCKS };
+__global__ __launch_bounds__(256) void k_fold_partials8(int nb, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double sh[8][16];
+    const int chunk = (nb + gridDim.x - 1) / gridDim.x, k0 = blockIdx.x * chunk, k1 = min(nb, k0 + chunk);
+    sum8_partials(k1 - k0, part + 8 * (long long)k0, sh);              // (an empty share sums to 0 without reading)
+    if (threadIdx.x < 8) out[8 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+}
+static int epi_alloc(pl_ctx* ctx, PlSolver* S, const PlGeom& g) {
+    const long long nb = pl_apply_blocks(g, 4);                 // the lower row-block height: the larger grid
+    if (S->epi && S->epi_blocks >= nb) return 0;
+    if (S->epi) { PL_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(S->epi); S->epi = nullptr; }
+    PL_TRY(dmalloc0(ctx, &S->epi, (size_t)(EPI_PART + PL_EPI_NSUM * nb) * sizeof(double)));
+    S->epi_blocks = nb;
+    return 0;
+}
+// the sets of eight of the last epilogue launch for the second stage, folded where there are many
+static const double* epi_partials8(pl_ctx* ctx, PlSolver* S, int* nb) {
+    if (*nb <= EPI_FOLD_MIN) return S->epi + EPI_PART;
+    hipLaunchKernelGGL(k_fold_partials8, dim3(EPI_FOLD_BLOCKS), dim3(256), 0, ctx->stream, *nb, (const double*)(S->epi + EPI_PART), S->epi + EPI_FOLD);
+    *nb = EPI_FOLD_BLOCKS;
+    return S->epi + EPI_FOLD;
+}
+// PYLAMP_KRYLOV_FUSED=0: the separate reduction passes; 1 (default): every epilogue but r~.v of the first reduction point
+// (PL_EPI_DOT1, see bicgstab); 2: that one too (read per solve: tests compare them)
+static int krylov_fused_level() { const char* e = getenv("PYLAMP_KRYLOV_FUSED"); return e ? atoi(e) : 1; }
+static bool krylov_fused_knob() { return krylov_fused_level() != 0; }
+// the operator with an epilogue: out = A in (+ lazy deflation term) and the sums of e.mode
+typedef std::function<int(const double*, double*, PlApplyArgs)> EpiOp;
+// out = e.a1 - A in in ONE launch, its sums (PlResidSum) summed on the device and read back: one host synchronisation.
+// init_defl: y.out also starts the lazy deflation's recurrences (k_sum_resid)
+static int apply_resid(pl_ctx* ctx, PlSolver* S, const EpiOp& AE, const PlGeom& g, const double* in, double* out, PlApplyArgs e,
+                       bool init_defl, double (&sums)[PL_EPI_NSUM]) {
+    PL_TRY(epi_alloc(ctx, S, g));
+    e.mode = PL_EPI_RESID; e.part = S->epi + EPI_PART;
+    PL_TRY(AE(in, out, e));
+    int nb = pl_apply_blocks(g, pl_apply_rows(g, e.mode, e.rows));
+    const double* part = epi_partials8(ctx, S, &nb);
+    hipLaunchKernelGGL(k_sum_resid, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part, S->epi + EPI_SUMS, init_defl ? S->scal : (double*)nullptr);
+    double* hs = S->hpart + PL_HSCAL;
+    PL_HIP(ctx, hipMemcpyAsync(hs, S->epi + EPI_SUMS, PL_EPI_NSUM * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < PL_EPI_NSUM; q++) sums[q] = hs[q];
     return 0;
 }
 
@@ -3282,11 +3366,32 @@ struct BicgVecs { double *r, *rt, *p, *v, *s, *t, *y, *z; double* xbest; double 
 // evaluated from the true residual, and if that fails the same iteration continues -- no restart.
 static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const VecOp& A, const VecOp* M,
                     const double* b, double* x, bool use_x0, double rtol, int maxit, BicgVecs w,
-                    pl_solve_stats* st, double ref_norm = 0.0, double etol = 0.0, int np_vel = 0) {
+                    pl_solve_stats* st, double ref_norm = 0.0, double etol = 0.0, int np_vel = 0, const EpiOp* AE = nullptr) {
     const long long n = (long long)np * g.plane;
     const size_t bytes = (size_t)n * sizeof(double);
     double d2[2];
-    PL_TRY(dots(ctx, S, g, np, b, b, nullptr, nullptr, d2));
+    const bool on_device = !getenv("PYLAMP_HOST_SCALARS");
+    static const int shadow_mode = getenv("PYLAMP_SHADOW") ? atoi(getenv("PYLAMP_SHADOW")) : 1;      // (see the shadow residual below)
+    // The reductions of the iteration, the set-up and the confirmation come out of the operator's epilogue (AE): the Stokes solve on
+    // one rank with the scalars on the device.  fused_setup: a warm start whose shadow residual is r0 -- ONE launch gives
+    // r0 = b - A x0, |b|^2, |r0|^2 = r~.r0, |x0_vel|^2 and y.r0; r~ IS r0, and r and p are r0 until the first update writes them
+    // (`first`): no copy, no zero fill, one host synchronisation.
+    const bool fused = AE && M && np == 3 && on_device && ctx->nranks == 1 && !pl_geom_is_dist(g) && krylov_fused_knob() &&
+                       (!(etol > 0.0 && np_vel > 0) || np_vel == 2);
+    const bool fused_setup = fused && use_x0 && shadow_mode == 1;
+    // r~.v in the epilogue of v = A y is 13 us per iteration faster than the k_dot2 pass at 2049^2, but ships switched off: with
+    // its summation order the cold 257^2 block case of the suite stops two iterations earlier, at an iterate whose true error is
+    // 23 x the estimate, beyond the factor 16 the suite asserts; PYLAMP_KRYLOV_FUSED=2 switches it on
+    const bool epi_dot1 = fused && krylov_fused_level() >= 2;
+    if (fused) PL_TRY(epi_alloc(ctx, S, g));
+    const bool lazy_defl = S->defl_lazy && S->defl_active && np == 3 && M;
+    double rsum[PL_EPI_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (fused_setup) {
+        PlApplyArgs e; e.a1 = b; e.want_xx = (etol > 0.0 && np_vel > 0 && np > np_vel) ? 1 : 0; e.want_ysum = lazy_defl ? 1 : 0;
+        PL_TRY(apply_resid(ctx, S, *AE, g, x, w.r0, e, lazy_defl, rsum));
+        d2[0] = rsum[PL_RS_BB];
+    } else
+        PL_TRY(dots(ctx, S, g, np, b, b, nullptr, nullptr, d2));
     double bnorm = std::sqrt(d2[0]);
     if (ref_norm > 0.0 && bnorm > 0.0) bnorm = ref_norm;
     st->iterations = 0; st->converged = 0; st->rel_residual = 0.0;
@@ -3296,6 +3401,13 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
         return 0;
     }
     double* dx = x; const double* r0 = b;       // no initial guess: the correction IS the solution
+    const double* rt = w.rt;                    // the shadow residual
+    bool first = false;                         // fused set-up, before the first update: r0 stands for r and p, dx has not been written
+    double xx_guess = 0.0;                        // ||x0_vel||^2 of a warm start (0: unknown / cold start from a state without velocities)
+    if (fused_setup) {
+        dx = w.dx; r0 = w.r0; first = true;
+        if (etol > 0.0 && np_vel > 0 && np > np_vel && std::isfinite(rsum[PL_RS_XX]) && rsum[PL_RS_XX] > 0.0) xx_guess = rsum[PL_RS_XX];
+    } else {
     if (use_x0) {
         dx = w.dx;
         PL_TRY(A(x, w.v));
@@ -3304,28 +3416,27 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
     }
     PL_HIP(ctx, hipMemsetAsync(dx, 0, bytes, ctx->stream));
     PL_HIP(ctx, hipMemcpyAsync(w.r, r0, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    double xx_guess = 0.0;                        // ||x0_vel||^2 of a warm start (0: unknown / cold start from a state without velocities)
     if (use_x0 && etol > 0.0 && np_vel > 0 && np > np_vel) {
         double dxx[2];
         PL_TRY(dots(ctx, S, g, np_vel, x, x, nullptr, nullptr, dxx));
         if (std::isfinite(dxx[0]) && dxx[0] > 0.0) xx_guess = dxx[0];
     }
+    }
     // Shadow residual: the textbook choice r0 when a preconditioned solve starts from a guess (r0 = b - A x0 has components in all
     // rows), the seeded random vector otherwise -- with r0 = b the method breaks down (b lives on the vz rows only).  Against the
     // random vector in the time-step loop at 2049^2 the first iterations no longer stall on an arbitrary alpha (10.7 -> 9.7
     // iterations per solve, 8..11 instead of 8..14); the unpreconditioned heat solve gains nothing from it.  PYLAMP_SHADOW=0: random always.
-    static const int shadow_mode = getenv("PYLAMP_SHADOW") ? atoi(getenv("PYLAMP_SHADOW")) : 1;
-    if (shadow_mode == 1 && use_x0 && M) PL_HIP(ctx, hipMemcpyAsync(w.rt, r0, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (fused_setup) rt = w.r0;                          // r~ aliases r0: no copy
+    else if (shadow_mode == 1 && use_x0 && M) PL_HIP(ctx, hipMemcpyAsync(w.rt, r0, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     else {
         PL_HIP(ctx, hipMemsetAsync(w.rt, 0, bytes, ctx->stream));
         hipLaunchKernelGGL(k_random_interior, grid2d(g), dim3(64, 4), 0, ctx->stream, g, np, w.rt, 1234u);
     }
-    const bool on_device = !getenv("PYLAMP_HOST_SCALARS");
     // lazy deflation on several ranks: its coefficients ride in the two reductions of an iteration (k_defl_alpha_ride ...)
     const bool ride = S->defl_lazy && S->defl_active && np == 3 && M && on_device && ctx->nranks > 1 && pl_geom_is_dist(g);
     if (ride) {                                          // r~.Aw, Aw.Aw and its continuity part: constant during this solve
         double c1[2], c2[2];
-        PL_TRY(dots(ctx, S, g, 3, w.rt, S->Awdefl, S->Awdefl, S->Awdefl, c1));
+        PL_TRY(dots(ctx, S, g, 3, rt, S->Awdefl, S->Awdefl, S->Awdefl, c1));
         PL_TRY(dots(ctx, S, g, 1, S->Awdefl + 2 * g.plane, S->Awdefl + 2 * g.plane, nullptr, nullptr, c2));
         hipLaunchKernelGGL(k_set3, dim3(1), dim3(1), 0, ctx->stream, S->scal + SC_RT_AW, c1[0], S->scal + SC_AW_AW, c1[1], S->scal + SC_AW_AW_C, c2[0]);
     }
@@ -3392,18 +3503,26 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
     auto set_kappa = [&](double rn) { S->kappa = (std::isfinite(rn) && rn > 0.0) ? sqrt_n / rn : 1.0; };
     st->error_estimate = 0.0;
     for (;;) {
-        if (!resume) {
+        if (!resume && first) {
+            // ---- start from r0 (fused set-up): r~.r0 = |r0|^2 and y.r0 came with it, p and v are not read before they are written
+            rho = alpha = omega = 1.0;
+            p_fused = false;
+            rho_new = rsum[PL_RS_RR]; rnorm = std::sqrt(rsum[PL_RS_RR]);
+            best = rnorm;
+            set_kappa(rnorm);
+            broke = false;
+        } else if (!resume) {
             // ---- (re)start from the residual in w.r
             PL_HIP(ctx, hipMemsetAsync(w.p, 0, bytes, ctx->stream));
             PL_HIP(ctx, hipMemsetAsync(w.v, 0, bytes, ctx->stream));
             rho = alpha = omega = 1.0;
             p_fused = false;
-            PL_TRY(dots(ctx, S, g, np, w.rt, w.r, w.r, w.r, d2));
+            PL_TRY(dots(ctx, S, g, np, rt, w.r, w.r, w.r, d2));
             rho_new = d2[0]; rnorm = std::sqrt(d2[1]);
             if (restarts == 0) best = rnorm;
             set_kappa(rnorm);
             broke = false;
-            if (S->defl_lazy && S->defl_active && np == 3 && M) {       // y.r of the (re)start residual; p = r
+            if (lazy_defl) {       // y.r of the (re)start residual; p = r
                 ysum_dev(w.r + 2 * g.plane, SC_YR);                     // (clears SC_YP, which k_defl_init then sets)
                 if (ride) PL_TRY(pl_comm_allreduce_dev(ctx, S->scal + SC_YR, 1));
                 hipLaunchKernelGGL(k_defl_init, dim3(1), dim3(1), 0, ctx->stream, S->scal);
@@ -3414,40 +3533,70 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
             it++;
             if (!(std::fabs(rho_new) > 0.0) || !std::isfinite(rho_new)) { broke = true; break; }
             const double beta = (rho_new / rho) * (alpha / omega);
-            if (!p_fused) hipLaunchKernelGGL(k_p_update, grid1d(n), dim3(256), 0, ctx->stream, n, w.p, w.r, w.v, beta, omega);
-            const double* yv = w.p;
-            if (M) { PL_TRY((*M)(w.p, w.y)); yv = w.y; }
+            if (!p_fused && !first) hipLaunchKernelGGL(k_p_update, grid1d(n), dim3(256), 0, ctx->stream, n, w.p, w.r, w.v, beta, omega);
+            const double* pv = first ? r0 : w.p;                 // (first: p = r = r0)
+            const double* rv = first ? r0 : w.r;
+            const double* yv = pv;
+            if (M) { PL_TRY((*M)(pv, w.y)); yv = w.y; }
+            const int epi_nb = fused ? pl_apply_blocks(g, pl_apply_rows(g, PL_EPI_DOT1)) : 0;
+            if (epi_dot1) {
+                // v = A y with r~.v summed in its epilogue; alpha = rho / r~.v on the device (k_sum_partials mode 1)
+                PlApplyArgs e; e.mode = PL_EPI_DOT1; e.a1 = rt; e.part = S->epi + EPI_PART;
+                PL_TRY((*AE)(yv, w.v, e));
+                hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(sum_block(epi_nb)), 0, ctx->stream, epi_nb, (const double*)(S->epi + EPI_PART),
+                                   S->scal + SC_SUM_A, 1, rho_new);
+            } else
             PL_TRY(A(yv, w.v));
             const double* zv = w.s;
             if (on_device) {
                 // alpha, omega stay on the device; a breakdown (rt.v = 0) shows up as a non-finite alpha / ||r|| below
-                PL_TRY(dots_dev(ctx, S, g, np, w.rt, w.v, rho_new, ride));
+                if (!epi_dot1) PL_TRY(dots_dev(ctx, S, g, np, rt, w.v, rho_new, ride));
                 if (ride) hipLaunchKernelGGL(k_s_update_defl, grid1d(n), dim3(256), 0, ctx->stream, n, w.s, (const double*)w.r, w.v, (const double*)S->Awdefl, (const double*)S->scal);
-                else hipLaunchKernelGGL(k_s_update_dev, grid1d(n), dim3(256), 0, ctx->stream, n, w.s, w.r, w.v, S->scal);
+                else hipLaunchKernelGGL(k_s_update_dev, grid1d(n), dim3(256), 0, ctx->stream, n, w.s, rv, (const double*)w.v, (const double*)S->scal);
                 if (M) { PL_TRY((*M)(w.s, w.z)); zv = w.z; }
+                if (fused) {
+                    // t = A z with the eight sums of the second reduction point in its epilogue
+                    PlApplyArgs e; e.mode = PL_EPI_DOT5; e.a1 = w.s; e.a2 = rt; e.cont = use_est ? 1 : 0; e.part = S->epi + EPI_PART;
+                    PL_TRY((*AE)(zv, w.t, e));
+                } else
                 PL_TRY(A(zv, w.t));
                 // near the end: ||x_vel||^2 for the error estimate (-> SC_XX; of the iterate BEFORE this update, so that
                 // it can ride along in the fused reduction -- the estimate needs it to ~10 %)
                 const bool want_xx = use_est && rnorm <= 1e3 * tol * bnorm;
                 // (warm start: ||x0_vel|| stands for ||x_vel|| in the per-iteration estimate -- they differ by the relative size of the
                 //  correction, and the estimate needs the norm to ~10 %; the check on the true residual below uses the exact one)
-                if (want_xx && !(xx_guess > 0.0)) PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, dx, dx != x ? (const double*)x : (const double*)nullptr, false));
+                if (want_xx && !(xx_guess > 0.0)) {
+                    if (first) PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, x, nullptr, false));            // (dx = 0, not yet written)
+                    else PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, dx, dx != x ? (const double*)x : (const double*)nullptr, false));
+                }
                 // (the amplification moves slowly: measured in the first two late iterations, then in every third)
                 const bool amom_now = want_xx && M && (amom_count < 2 || amom_count % 3 == 0);
                 if (want_xx && M) amom_count++;
                 if (amom_now) PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, zv, nullptr, false, SC_ZZ));      // ||z_vel||^2 of z = M^-1 s
-                const bool y_recur = S->defl_lazy && S->defl_active && np == 3 && M;       // y.r of the updated residual comes out of bicg_derive (SC_YR)
+                const bool y_recur = lazy_defl;       // y.r of the updated residual comes out of bicg_derive (SC_YR)
                 if (want_xx && anchor_term && !y_recur) {            // y.r of the updated residual = y.s - omega y.t: both ride in the reduction as well
                     // (in this order, after SC_XX: each reduction clears the slot behind its own; SC_YS is the shadow of SC_XX, SC_YT of SC_YS)
                     ysum_dev(w.s + (long long)np_vel * g.plane, SC_YS);
                     ysum_dev(w.t + (long long)np_vel * g.plane, SC_YT);
                 }
-                PL_TRY(dots5_dev(ctx, S, g, np, use_est ? np_vel : np, w.t, w.s, w.rt, ride ? (const double*)S->Awdefl : (const double*)nullptr));       // omega, rho' and |r|^2 from ONE reduction
+                if (fused) {
+                    int nb5 = epi_nb;
+                    const double* part = epi_partials8(ctx, S, &nb5);
+                    hipLaunchKernelGGL(k_sum_partials5, dim3(1), dim3(sum_block(nb5)), 0, ctx->stream, nb5, part, S->scal, 1);
+                }
+                else
+                PL_TRY(dots5_dev(ctx, S, g, np, use_est ? np_vel : np, w.t, w.s, rt, ride ? (const double*)S->Awdefl : (const double*)nullptr));       // omega, rho' and |r|^2 from ONE reduction
                 // ... and the next direction in the same pass (the host's beta above is then only the breakdown test)
-                if (yv != w.p) {
-                    hipLaunchKernelGGL(k_xrp_update_dev, grid1d(n), dim3(256), 0, ctx->stream, n, dx, yv, zv, w.r, w.s, w.t, w.p, w.v, S->scal,
-                                       (S->defl_lazy && S->defl_active && np == 3) ? (const double*)S->wdefl : (const double*)nullptr,
-                                       ride ? (const double*)S->Awdefl : (const double*)nullptr);
+                if (yv != pv) {
+                    const double* wd = (S->defl_lazy && S->defl_active && np == 3) ? (const double*)S->wdefl : (const double*)nullptr;
+                    const double* awd = ride ? (const double*)S->Awdefl : (const double*)nullptr;
+                    if (first)
+                        hipLaunchKernelGGL(k_xrp_update_dev<true>, grid1d(n), dim3(256), 0, ctx->stream, n, dx, yv, zv, w.r, (const double*)w.s, (const double*)w.t,
+                                           w.p, (const double*)w.v, (const double*)S->scal, wd, awd, r0);
+                    else
+                        hipLaunchKernelGGL(k_xrp_update_dev<false>, grid1d(n), dim3(256), 0, ctx->stream, n, dx, yv, zv, w.r, (const double*)w.s, (const double*)w.t,
+                                           w.p, (const double*)w.v, (const double*)S->scal, wd, awd, (const double*)nullptr);
+                    first = false;
                     p_fused = true;
                 } else            // no preconditioner: y IS p
                     hipLaunchKernelGGL(k_xr_update_dev, grid1d(n), dim3(256), 0, ctx->stream, n, dx, yv, zv, w.r, w.s, w.t, S->scal);
@@ -3516,9 +3665,19 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
             restored = true;
         }
         // ---- true residual of the current dx
+        double csum[PL_EPI_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (first) PL_HIP(ctx, hipMemsetAsync(dx, 0, bytes, ctx->stream));        // no update has run: the correction is still 0
+        if (fused) {
+            // one launch: s = r0 - A dx, |s|^2, its continuity part, ||(x0 + dx)_vel||^2 and y.s; one host read
+            PlApplyArgs e; e.a1 = r0; e.a2 = dx != x ? (const double*)x : (const double*)nullptr;
+            e.want_xx = use_est ? 1 : 0; e.want_ysum = anchor_term ? 1 : 0;
+            PL_TRY(apply_resid(ctx, S, *AE, g, dx, w.s, e, false, csum));
+            d2[0] = csum[PL_RS_RR];
+        } else {
         PL_TRY(A(dx, w.t));
         hipLaunchKernelGGL(k_axpy_out, grid1d(n), dim3(256), 0, ctx->stream, n, w.s, r0, w.t, -1.0);
         PL_TRY(dots(ctx, S, g, np, w.s, w.s, nullptr, nullptr, d2));
+        }
         last_true = true_norm; true_norm = std::sqrt(d2[0]);
         if (trace) fprintf(stderr, "[pylamp bicgstab] it %3d  TRUE |r|/|b| %.3e (recurrence %.3e) restarts %d\n", it, true_norm / bnorm, rnorm / bnorm, restarts);
         if (true_norm <= tol * bnorm && !broke && it < maxit && use_est && M && est_checks < 6) {
@@ -3527,25 +3686,28 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
             // (the block preconditioner's answer to the continuity residual is part of it too, but far too small: its Schur
             // complement is only an approximation; measured 37 x below the true error on the 33 x 41 fixture)
             double dc[2], dz[2];
-            PL_TRY(dots(ctx, S, g, np - np_vel, w.s + (long long)np_vel * g.plane, w.s + (long long)np_vel * g.plane, nullptr, nullptr, dc));
+            if (fused) dc[0] = csum[PL_RS_RR_C];
+            else PL_TRY(dots(ctx, S, g, np - np_vel, w.s + (long long)np_vel * g.plane, w.s + (long long)np_vel * g.plane, nullptr, nullptr, dc));
             const bool exact = est_exact || !a_mom_measured;
             if (exact) {
                 PL_TRY((*M)(w.s, w.z));
                 PL_TRY(dots(ctx, S, g, np_vel, w.z, w.z, nullptr, nullptr, dz));
             }
-            PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, dx, dx != x ? (const double*)x : (const double*)nullptr, true));
-            PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_HSCAL, S->scal + SC_XX, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (!fused) {
+                PL_TRY(norm2_sum_dev(ctx, S, g, np_vel, dx, dx != x ? (const double*)x : (const double*)nullptr, true));
+                PL_HIP(ctx, hipMemcpyAsync(S->hpart + PL_HSCAL, S->scal + SC_XX, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            }
             est_checks++;
-            const double xx = S->hpart[PL_HSCAL];
+            const double xx = fused ? csum[PL_RS_XX] : S->hpart[PL_HSCAL];
             if (xx_guess > 0.0 && xx > 0.0) xx_guess = xx;               // (the exact norm of this iterate from here on)
             const double rc = dc[0] > 0.0 ? dc[0] : 0.0, rm = true_norm * true_norm - rc;
             if (!exact) dz[0] = a_mom * a_mom * (rm > 0.0 ? rm : 0.0);            // the response the last iteration measured, scaled to this residual
             double est = xx > 0.0 ? (n_amp * std::sqrt(rc) + std::sqrt(dz[0] > 0.0 ? dz[0] : 0.0)) / std::sqrt(xx) : 0.0;
             double anchor_part = 0.0;
             if (anchor_term && xx > 0.0) {
-                double yr = 0.0;
-                PL_TRY(ysum_host(w.s + (long long)np_vel * g.plane, yr));
+                double yr = csum[PL_RS_YR];
+                if (!fused) PL_TRY(ysum_host(w.s + (long long)np_vel * g.plane, yr));
                 anchor_part = std::fabs(yr / S->defl_yAw) * std::sqrt(S->defl_wvel2 / xx);
                 est += anchor_part;
             }
@@ -3559,7 +3721,7 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
                 if (!restored) { resume = true; continue; }            // same Krylov iteration, smaller target
                 // the iterate is the restored best one: w.r / w.p / rho belong to another dx -- restart from its true residual
                 // (in w.s) instead of resuming
-                restarts++;
+                restarts++; first = false;
                 PL_HIP(ctx, hipMemcpyAsync(w.r, w.s, bytes, hipMemcpyDeviceToDevice, ctx->stream));
                 best = true_norm; best_it = it; have_best = false;
                 continue;
@@ -3568,7 +3730,7 @@ static int bicgstab(pl_ctx* ctx, PlSolver* S, const PlGeom& g, int np, const Vec
         if (true_norm <= tol * bnorm || broke || it >= maxit || restarts >= PL_MAX_RESTARTS) break;
         if (last_true >= 0.0 && !(true_norm < 0.5 * last_true)) break;      // a restart no longer pays: attainable accuracy
         // ---- residual replacement: continue from the TRUE residual
-        restarts++;
+        restarts++; first = false;
         PL_HIP(ctx, hipMemcpyAsync(w.r, w.s, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         best = true_norm; best_it = it; have_best = false;
     }
@@ -3720,12 +3882,23 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
     VecOp A = [&](const double* in, double* out) -> int {
         PL_TRY(pl_halo(ctx, g, (double*)in, 3, g.plane));
         // y = D_r A x in one pass; for a vector the preconditioner has just produced: + c A w (its lazy deflation correction)
-        if (S->defl_lazy && S->defl_active && ctx->nranks == 1 && (in == S->y || in == S->z))
-            pl_launch_stokes_apply(ctx, sop_scaled, in, out, S->Awdefl, S->scal + (in == S->y ? SC_CY : SC_CZ));
-        else pl_launch_stokes_apply(ctx, sop_scaled, in, out);
+        PlApplyArgs a;
+        if (S->defl_lazy && S->defl_active && ctx->nranks == 1 && (in == S->y || in == S->z)) { a.add = S->Awdefl; a.coef = S->scal + (in == S->y ? SC_CY : SC_CZ); }
+        pl_launch_stokes_apply(ctx, sop_scaled, in, out, a);
         S->napply++;
         return 0;
     };
+    // the same with one of the reductions in its epilogue (PlApplyArgs::mode)
+    EpiOp AE = [&](const double* in, double* out, PlApplyArgs a) -> int {
+        PL_TRY(pl_halo(ctx, g, (double*)in, 3, g.plane));
+        if (S->defl_lazy && S->defl_active && ctx->nranks == 1 && (in == S->y || in == S->z)) { a.add = S->Awdefl; a.coef = S->scal + (in == S->y ? SC_CY : SC_CZ); }
+        pl_launch_stokes_apply(ctx, sop_scaled, in, out, a);
+        S->napply++;
+        return 0;
+    };
+    // residuals and their norms in one launch (apply_resid): one rank, scalars on the device
+    const bool kfused = krylov_fused_knob() && ctx->nranks == 1 && !pl_geom_is_dist(g) && !getenv("PYLAMP_HOST_SCALARS");
+    double rs[PL_EPI_NSUM];
     const long long n3v = 3 * g.plane;
     VecOp M = [&](const double* in, double* out) -> int {
         PL_TRY(stokes_precond(ctx, S, in, out));
@@ -3764,9 +3937,15 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
         double q = 1.0;
         if (S->defl_valid) {
             double dq[2];
+            if (kfused) {                                   // A w is kept, u - A w only summed
+                PlApplyArgs e; e.a1 = S->udefl; e.y2 = S->Awdefl;
+                PL_TRY(apply_resid(ctx, S, AE, g, S->wdefl, S->s, e, false, rs));
+                dq[0] = rs[PL_RS_RR]; dq[1] = rs[PL_RS_BB];
+            } else {
             PL_TRY(A(S->wdefl, S->Awdefl));                 // kept: A w under this solve's operator (lazy correction)
             hipLaunchKernelGGL(k_axpy_out, grid1d(n3v), dim3(256), 0, ctx->stream, n3v, S->s, (const double*)S->udefl, (const double*)S->Awdefl, -1.0);
             PL_TRY(dots(ctx, S, g, 3, S->s, S->s, S->udefl, S->udefl, dq));
+            }
             q = (dq[1] > 0.0 && std::isfinite(dq[0])) ? std::sqrt(dq[0] / dq[1]) : 1.0;
         }
         static const bool trace_d = getenv("PYLAMP_SOLVER_TRACE") != nullptr;
@@ -3781,7 +3960,7 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
         if (!reuse || q > q_refresh) {
             if (!reuse) PL_HIP(ctx, hipMemsetAsync(S->wdefl, 0, (size_t)n3v * sizeof(double), ctx->stream));
             pl_solve_stats st2{};
-            PL_TRY(bicgstab(ctx, S, g, 3, A, &M, S->udefl, S->wdefl, reuse, 1e-3, 80, w, &st2));
+            PL_TRY(bicgstab(ctx, S, g, 3, A, &M, S->udefl, S->wdefl, reuse, 1e-3, 80, w, &st2, 0.0, 0.0, 0, &AE));
             S->defl_valid = st2.rel_residual < 0.05 && std::isfinite(st2.rel_residual);
             if (S->defl_valid) {
                 hipLaunchKernelGGL(k_defl_coef, dim3(1), dim3(1), 0, ctx->stream, sop, (const double*)S->wdefl, S->scal, 1);
@@ -3882,9 +4061,15 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
         PL_HIP(ctx, hipMemcpyAsync(prefix, pre.data(), (size_t)g.lnx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_hydrostatic_apply_shift, grid2d(g), dim3(64, 4), 0, ctx->stream, sop, S->y, prefix, pa);
         PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (kfused) {
+            PlApplyArgs e; e.a1 = S->b;
+            PL_TRY(apply_resid(ctx, S, AE, g, S->y, S->s, e, false, rs));
+            d2[0] = rs[PL_RS_RR]; d2[1] = rs[PL_RS_BB];
+        } else {
         PL_TRY(A(S->y, S->t));
         hipLaunchKernelGGL(k_axpy_out, grid1d(n3), dim3(256), 0, ctx->stream, n3, S->s, S->b, S->t, -1.0);
         PL_TRY(dots(ctx, S, g, 3, S->s, S->s, S->b, S->b, d2));
+        }
         ref = std::sqrt(d2[0]);
         // no dynamic load (density contrasts below 1e-9 of the hydrostatic load are marker-averaging round-off):
         // fall back to ||b||, against which the hydrostatic state already is the solution
@@ -3902,7 +4087,7 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
     hipLaunchKernelGGL(k_close_constraints, grid2d(g), dim3(64, 4), 0, ctx->stream, sop, S->levels[0]->op, S->b, S->x);
     if (trace_t) tph[3] = now();
     if (force_direct) { st->iterations = 0; st->converged = 0; st->reserved_ = 0; st->rel_residual = 1.0; st->error_estimate = 0.0; }
-    else PL_TRY(bicgstab(ctx, S, g, 3, A, &M, S->b, S->x, use_x0, rtol, maxit, w, st, ref, S->etol, 2));
+    else PL_TRY(bicgstab(ctx, S, g, 3, A, &M, S->b, S->x, use_x0, rtol, maxit, w, st, ref, S->etol, 2, &AE));
     // Beyond the gate the solve is judged by the UNSCALED residual ||b - A x|| / ||b|| of the iterate it returns: measured on the stock
     // model, velocity error / unscaled residual = 140 (LU path: 4.4e-7 / 3.2e-9) and 290 (iterative path: 4.1e-3 / 1.4e-5), i.e. the
     // domain's n = max(nz, nx) = 201 within a factor 1.5 -- the same amplification the continuity term of the estimate uses.  Hence
@@ -4042,6 +4227,57 @@ extern "C" int pl_stokes_solve(pl_ctx* ctx, const double* rhs, double* x, int us
     PL_TRY(pl_stokes_solve_device(ctx, S->b, use_x0 != 0, rtol, maxit, &st));
     PL_TRY(pl_vec3_download(ctx, g, S->x, x));
     if (stats) *stats = st;
+    return 0;
+}
+
+// One launch of the operator with an epilogue, as the solver uses it, on host vectors in the reference's DOF order (component tests).
+// The operator is the UNSCALED one of pl_stokes_apply.  mode 1: out = A x, sums[0] = aux1 . out.  mode 2: out = A x,
+// sums[0..7] = out.aux1, out.out, aux2.aux1, aux2.out, aux1.aux1 and out.aux1, out.out, aux1.aux1 over the continuity rows.
+// mode 3: out = aux1 - A x, out2 (may be NULL) = A x, sums[0..4] = |out|^2, its continuity part, |aux1|^2, the sum of (x + aux2)^2
+// over the velocities (aux2 may be NULL) and the deflation's y . out.  rows: row-block height of the launch (4 or 16; 0: the
+// default of the grid size).  sums: 8 doubles.
+extern "C" int pl_stokes_apply_reduce(pl_ctx* ctx, int mode, int rows, const double* x, const double* aux1, const double* aux2,
+                                      double* out, double* out2, double* sums) {
+    if (!ctx->sop_ready) return pl_fail(ctx, "stokes operator not set");
+    if (mode < PL_EPI_DOT1 || mode > PL_EPI_RESID || !x || !aux1 || !out || !sums || (mode == PL_EPI_DOT5 && !aux2))
+        return pl_fail(ctx, "pl_stokes_apply_reduce: bad argument");
+    if (rows != 0 && rows != 4 && rows != 16) return pl_fail(ctx, "pl_stokes_apply_reduce: rows must be 0, 4 or 16");
+    if (ctx->nranks > 1) return pl_fail(ctx, "pl_stokes_apply_reduce: one rank only");
+    PL_HIP(ctx, hipSetDevice(ctx->device));
+    PlSolver* S = solver_of(ctx);
+    PL_TRY(scal_alloc(ctx, S));
+    const PlGeom& g = ctx->geom.d;
+    PL_TRY(epi_alloc(ctx, S, g));
+    const size_t vb = (size_t)3 * g.plane * sizeof(double);
+    double *dx, *dy, *d1, *d2 = nullptr, *dy2 = nullptr;
+    PL_TRY(pl_buf(ctx, "api_x", vb, &dx)); PL_TRY(pl_buf(ctx, "api_y", vb, &dy)); PL_TRY(pl_buf(ctx, "api_a1", vb, &d1));
+    PL_TRY(pl_vec3_upload(ctx, g, x, dx));
+    PL_TRY(pl_halo(ctx, g, dx, 3, g.plane));
+    PL_TRY(pl_vec3_upload(ctx, g, aux1, d1));
+    if (aux2) { PL_TRY(pl_buf(ctx, "api_a2", vb, &d2)); PL_TRY(pl_vec3_upload(ctx, g, aux2, d2)); }
+    if (out2 && mode == PL_EPI_RESID) PL_TRY(pl_buf(ctx, "api_y2", vb, &dy2));
+    PlApplyArgs e; e.mode = mode; e.rows = rows; e.a1 = d1; e.a2 = d2; e.y2 = dy2; e.part = S->epi + EPI_PART;
+    e.cont = 1; e.want_xx = 1; e.want_ysum = 1;
+    pl_launch_stokes_apply(ctx, ctx->sop, dx, dy, e);
+    int nb = pl_apply_blocks(g, pl_apply_rows(g, mode, rows));
+    const double* part8 = mode == PL_EPI_DOT1 ? nullptr : epi_partials8(ctx, S, &nb);
+    double* dsum = S->epi + EPI_SUMS;               // mode 1: the pair k_sum_partials writes; mode 2: SC_DOT5 of a scratch scalar block
+    if (mode == PL_EPI_DOT1)
+        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, (const double*)(S->epi + EPI_PART), dsum, 0, 0.0);
+    else if (mode == PL_EPI_DOT5) {
+        double* sc;
+        PL_TRY(pl_buf(ctx, "api_scal", PL_SCAL_N * sizeof(double), &sc));
+        hipLaunchKernelGGL(k_sum_partials5, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part8, sc, 0);
+        dsum = sc + SC_DOT5;
+    } else
+        hipLaunchKernelGGL(k_sum_resid, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part8, dsum, (double*)nullptr);
+    PL_HIP(ctx, hipGetLastError());
+    double* hs = S->hpart + PL_HSCAL;
+    PL_HIP(ctx, hipMemcpyAsync(hs, dsum, PL_EPI_NSUM * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < PL_EPI_NSUM; q++) sums[q] = (mode == PL_EPI_DOT1 && q > 0) ? 0.0 : hs[q];
+    PL_TRY(pl_vec3_download(ctx, g, dy, out));
+    if (dy2) PL_TRY(pl_vec3_download(ctx, g, dy2, out2));
     return 0;
 }
 

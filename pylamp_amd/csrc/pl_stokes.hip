@@ -130,11 +130,14 @@ __device__ inline void stokes_interior_vals(const StokesRowK& k, const StokesVal
 
 // Both columns of one lane from the twelve loaded rows, then the (double2) stores.
 struct StokesRows { Row2 vz_s, vz_i, vz_n, vx_s, vx_i, vx_n, p_s, p_i, en_s, en_i, es_i, es_n, t_rdx, t_rDx; };
-template <bool SCALED>
+// MODE (PlApplyMode) != 0: the lane's contributions to the epilogue sums are ADDED to acc[] (see PlApplyArgs)
+template <bool SCALED, int MODE>
 __device__ inline void stokes_compute_store(const PlStokesOp& op, const StokesRows& R, int i, int jw, int lj0, int c,
-                                            const double* __restrict__ x, double* __restrict__ y,
-                                            const double* __restrict__ add, const double* __restrict__ coef) {
+                                            const double* __restrict__ x, double* __restrict__ y, const PlApplyArgs& a,
+                                            double (&acc)[PL_EPI_NSUM]) {
     const PlGeom& g = op.g;
+    const double* __restrict__ add = a.add;
+    const double* __restrict__ coef = a.coef;
     const Row2 &vz_s = R.vz_s, &vz_i = R.vz_i, &vz_n = R.vz_n, &vx_s = R.vx_s, &vx_i = R.vx_i, &vx_n = R.vx_n;
     const Row2 &p_s = R.p_s, &p_i = R.p_i, &en_s = R.en_s, &en_i = R.en_i, &es_i = R.es_i, &es_n = R.es_n;
     const double rdx_a = R.t_rdx.v.x, rdx_b = R.t_rdx.v.y, rdx_m = R.t_rdx.w;
@@ -179,6 +182,59 @@ __device__ inline void stokes_compute_store(const PlStokesOp& op, const StokesRo
             oz[0] += cf * az.x; oz[1] += cf * az.y; ox[0] += cf * ax.x; ox[1] += cf * ax.y; opv[0] += cf * ap.x; opv[1] += cf * ap.y;
         } else { oz[0] += cf * add[c]; ox[0] += cf * add[c + P]; opv[0] += cf * add[c + 2 * P]; }
     }
+    if (!colB) { oz[1] = 0.0; ox[1] = 0.0; opv[1] = 0.0; }     // (the epilogue sums run over both columns)
+    // a lane's two values of one plane of a vector (the second one 0 beyond the row)
+    auto ld2 = [&](const double* __restrict__ v, int q) {
+        const double* __restrict__ ptr = v + c + q * g.plane;
+        return colB ? *reinterpret_cast<const double2*>(ptr) : make_double2(ptr[0], 0.0);
+    };
+    if (MODE == PL_EPI_DOT1) {
+        const double2 rz = ld2(a.a1, 0), rx = ld2(a.a1, 1), rp = ld2(a.a1, 2);
+        acc[0] += rz.x * oz[0] + rz.y * oz[1] + rx.x * ox[0] + rx.y * ox[1] + rp.x * opv[0] + rp.y * opv[1];
+    }
+    if (MODE == PL_EPI_DOT5) {
+        const double2 sz = ld2(a.a1, 0), sx = ld2(a.a1, 1), sp = ld2(a.a1, 2);
+        const double2 rz = ld2(a.a2, 0), rx = ld2(a.a2, 1), rp = ld2(a.a2, 2);
+        const double ts_c = opv[0] * sp.x + opv[1] * sp.y, tt_c = opv[0] * opv[0] + opv[1] * opv[1], ss_c = sp.x * sp.x + sp.y * sp.y;
+        acc[0] += oz[0] * sz.x + oz[1] * sz.y + ox[0] * sx.x + ox[1] * sx.y + ts_c;
+        acc[1] += oz[0] * oz[0] + oz[1] * oz[1] + ox[0] * ox[0] + ox[1] * ox[1] + tt_c;
+        acc[2] += rz.x * sz.x + rz.y * sz.y + rx.x * sx.x + rx.y * sx.y + rp.x * sp.x + rp.y * sp.y;
+        acc[3] += rz.x * oz[0] + rz.y * oz[1] + rx.x * ox[0] + rx.y * ox[1] + rp.x * opv[0] + rp.y * opv[1];
+        acc[4] += sz.x * sz.x + sz.y * sz.y + sx.x * sx.x + sx.y * sx.y + ss_c;
+        if (a.cont) { acc[5] += ts_c; acc[6] += tt_c; acc[7] += ss_c; }
+    }
+    if (MODE == PL_EPI_RESID) {
+        const double2 bz = ld2(a.a1, 0), bx = ld2(a.a1, 1), bp = ld2(a.a1, 2);
+        if (a.y2) {                                         // A x itself is kept too
+            double* __restrict__ y2 = a.y2;
+            if (colB) {
+                *reinterpret_cast<double2*>(y2 + c) = make_double2(oz[0], oz[1]);
+                *reinterpret_cast<double2*>(y2 + c + g.plane) = make_double2(ox[0], ox[1]);
+                *reinterpret_cast<double2*>(y2 + c + 2 * g.plane) = make_double2(opv[0], opv[1]);
+            } else { y2[c] = oz[0]; y2[c + g.plane] = ox[0]; y2[c + 2 * g.plane] = opv[0]; }
+        }
+        oz[0] = bz.x - oz[0]; oz[1] = bz.y - oz[1]; ox[0] = bx.x - ox[0]; ox[1] = bx.y - ox[1]; opv[0] = bp.x - opv[0]; opv[1] = bp.y - opv[1];
+        const double rr_c = opv[0] * opv[0] + opv[1] * opv[1];
+        acc[PL_RS_RR] += oz[0] * oz[0] + oz[1] * oz[1] + ox[0] * ox[0] + ox[1] * ox[1] + rr_c;
+        acc[PL_RS_RR_C] += rr_c;
+        acc[PL_RS_BB] += bz.x * bz.x + bz.y * bz.y + bx.x * bx.x + bx.y * bx.y + bp.x * bp.x + bp.y * bp.y;
+        if (a.want_xx) {
+            double2 uz = make_double2(vz_i.v.x, colB ? vz_i.v.y : 0.0), ux = make_double2(vx_i.v.x, colB ? vx_i.v.y : 0.0);
+            if (a.a2) { const double2 wz = ld2(a.a2, 0), wx = ld2(a.a2, 1); uz.x += wz.x; uz.y += wz.y; ux.x += wx.x; ux.y += wx.y; }
+            acc[PL_RS_XX] += uz.x * uz.x + uz.y * uz.y + ux.x * ux.x + ux.y * ux.y;
+        }
+        if (a.want_ysum) {                                  // y . r over the continuity rows (k_defl_ysum, pl_solver.hip)
+            const int nz = g.nz, nx = g.nx;
+            const double hz = (i < nz - 1) ? 1.0 / TB(g.rdz, i) : 0.0;
+            const bool zwall = (i == 0 || i == nz - 2);
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int j = j0 + k;
+                const bool is_cont = !(i >= nz - 1 || j >= nx - 1 || (i == op.anchor_i && j == op.anchor_j)) && !(zwall && (j == 0 || j == nx - 2));
+                if (is_cont && (k == 0 || colB)) acc[PL_RS_YR] += (hz + 1.0 / (k ? rdx_b : rdx_a)) * opv[k];
+            }
+        }
+    }
     if (colB) {
         *reinterpret_cast<double2*>(y + c) = make_double2(oz[0], oz[1]);
         *reinterpret_cast<double2*>(y + c + g.plane) = make_double2(ox[0], ox[1]);
@@ -188,15 +244,35 @@ __device__ inline void stokes_compute_store(const PlStokesOp& op, const StokesRo
     }
 }
 
-template <int ROWS, bool SCALED>
-__global__ __launch_bounds__(64 * ROWS) void k_stokes_apply_v2(PlStokesOp op, const double* __restrict__ x,
-                                                               double* __restrict__ y, const double* __restrict__ add,
-                                                               const double* __restrict__ coef) {
+// Sum of acc[q] over the wave for all eight q in 10 exchanges instead of 48: every step halves both the lanes a value is spread
+// over and the values a lane carries (lane bits 5, 4, 3 select the half that is kept), three plain steps finish.  On return
+// lane L holds the wave's sum of value L >> 3.  The order of the additions is fixed by the lane numbers: deterministic.
+__device__ inline double wave_sum8(const double (&a)[PL_EPI_NSUM], int lane) {
+    double b[4], d[2];
+    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8;
+#pragma unroll
+    for (int q = 0; q < 4; q++) { const double keep = h5 ? a[q + 4] : a[q], send = h5 ? a[q] : a[q + 4]; b[q] = keep + __shfl_xor(send, 32, 64); }
+#pragma unroll
+    for (int q = 0; q < 2; q++) { const double keep = h4 ? b[q + 2] : b[q], send = h4 ? b[q] : b[q + 2]; d[q] = keep + __shfl_xor(send, 16, 64); }
+    double e = (h3 ? d[1] : d[0]) + __shfl_xor(h3 ? d[0] : d[1], 8, 64);
+    e += __shfl_xor(e, 4, 64); e += __shfl_xor(e, 2, 64); e += __shfl_xor(e, 1, 64);
+    return e;
+}
+
+// MODE 0 returns early for the rows beyond the block and the lanes beyond the row; with an epilogue these fall through with zero
+// contributions, because the whole workgroup meets in the reduction: wave exchange, ROWS x 8 doubles of LDS, one store of the
+// workgroup's partial sums (no atomics: the second stage adds them in a fixed order).  The epilogue kernels are held to 4 waves per
+// SIMD (128 VGPRs; the compiler takes 140 by itself, and DOT5 then runs in 131 instead of 118 us at 2049^2); MODE 0 is left alone.
+template <int ROWS, bool SCALED, int MODE>
+__global__ __launch_bounds__(64 * ROWS, MODE != 0 ? 4 : 1) void k_stokes_apply_v2(PlStokesOp op, const double* __restrict__ x,
+                                                               double* __restrict__ y, PlApplyArgs a) {
     const PlGeom& g = op.g;
     const int lane = threadIdx.x;
     const int lj0 = (blockIdx.x * 64 + lane) * 2;          // this lane's two columns: lj0, lj0+1
     const int li = blockIdx.y * ROWS + threadIdx.y;
-    if (li >= g.lnz) return;                                // wave-uniform
+    double acc[PL_EPI_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (MODE == PL_EPI_NONE && li >= g.lnz) return;         // wave-uniform
+    if (li < g.lnz) {
     const bool active = lj0 < g.lnx;                        // lanes beyond the row take part in shuffles only
     const bool has_right = (lj0 + 2) < g.lnx;               // the lane to the right holds real columns
     const int p = g.pitch;
@@ -216,10 +292,38 @@ __global__ __launch_bounds__(64 * ROWS) void k_stokes_apply_v2(PlStokesOp op, co
     // x tables: pair at (j, j+1) plus the two outer neighbours (tables are padded by PL_TOFF entries)
     const Row2 t_rdx = load_row2(g.rdx + PL_TOFF + g.gj0, lj0, active, true, false, lane, has_right);
     const Row2 t_rDx = load_row2(g.rDx + PL_TOFF + g.gj0, lj0, active, false, true, lane, has_right);
-    if (!active) return;
-    const int i = g.gi0 + li;
-    StokesRows R{vz_s, vz_i, vz_n, vx_s, vx_i, vx_n, p_s, p_i, en_s, en_i, es_i, es_n, t_rdx, t_rDx};
-    stokes_compute_store<SCALED>(op, R, i, g.gj0 + blockIdx.x * 128, lj0, c, x, y, add, coef);
+    if (MODE == PL_EPI_NONE && !active) return;
+    if (active) {
+        const int i = g.gi0 + li;
+        StokesRows R{vz_s, vz_i, vz_n, vx_s, vx_i, vx_n, p_s, p_i, en_s, en_i, es_i, es_n, t_rdx, t_rDx};
+        stokes_compute_store<SCALED, MODE>(op, R, i, g.gj0 + blockIdx.x * 128, lj0, c, x, y, a, acc);
+    }
+    }
+    if (MODE != PL_EPI_NONE) {
+        __shared__ double sh[ROWS][PL_EPI_NSUM];
+        const int blk = blockIdx.y * gridDim.x + blockIdx.x;
+        if (MODE == PL_EPI_DOT1) {
+            double s = acc[0];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (lane == 0) sh[threadIdx.y][0] = s;
+            __syncthreads();
+            if (threadIdx.y == 0 && lane < 2) {
+                double t = 0.0;
+                for (int w = 0; w < ROWS; w++) t += sh[w][0];
+                a.part[2 * (long long)blk + lane] = lane == 0 ? t : 0.0;
+            }
+        } else {
+            const double s = wave_sum8(acc, lane);
+            if ((lane & 7) == 0) sh[threadIdx.y][lane >> 3] = s;
+            __syncthreads();
+            if (threadIdx.y == 0 && lane < PL_EPI_NSUM) {
+                double t = 0.0;
+                for (int w = 0; w < ROWS; w++) t += sh[w][lane];
+                a.part[PL_EPI_NSUM * (long long)blk + lane] = t;
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void k_stokes_rhs(PlStokesOp op, double* __restrict__ rhs) {
@@ -237,8 +341,17 @@ __global__ __launch_bounds__(256) void k_stokes_rhs(PlStokesOp op, double* __res
 
 static dim3 grid2d(const PlGeom& g) { return dim3((g.lnx + 63) / 64, (g.lnz + 3) / 4); }
 
-// add != NULL: y = A x + coef[0] * add  (coef on the device; add: 3 planes like y)
-void pl_launch_stokes_apply(pl_ctx* ctx, const PlStokesOp& op, const double* x, double* y, const double* add, const double* coef) {
+// The row-block height of a launch: 16 on large grids, 4 otherwise (PYLAMP_APPLY_ROWS: 2, 4, 8 or 16 for every plain launch;
+// the epilogue modes exist for the two heights in use, 4 and 16)
+int pl_apply_rows(const PlGeom& g, int mode, int rows) {
+    static const int rows_knob = [] { const char* e = getenv("PYLAMP_APPLY_ROWS"); return e ? atoi(e) : 0; }();
+    if (!rows) rows = rows_knob ? rows_knob : ((long long)g.lnz * g.lnx >= 8000000LL ? 16 : 4);
+    if (mode != PL_EPI_NONE) return rows >= 16 ? 16 : 4;
+    return (rows == 16 || rows == 8 || rows == 2) ? rows : 4;
+}
+
+// a.add != NULL: y = A x + a.coef[0] * a.add; a.mode: the reductions of PlApplyArgs
+void pl_launch_stokes_apply(pl_ctx* ctx, const PlStokesOp& op, const double* x, double* y, const PlApplyArgs& a) {
     // Variants measured on MI355X at 2049^2: 8-byte loads 84 us; double2 81 us; + register row
     // marching (R = 8/16) 99/104 us; XCD-aware block remap, plane-stride padding: no effect; a memory-only twin
     // (same loads and stores, no arithmetic) 58 us -> the arithmetic was exposed: no divisions in the plain
@@ -249,21 +362,26 @@ void pl_launch_stokes_apply(pl_ctx* ctx, const PlStokesOp& op, const double* x, 
     // (The scalar one-column-per-lane kernel of round 1 is gone: the vectorised one is pinned directly against the reference's
     // explicit matrices on five grids, tests/test_hip_parity.py.)  double2 accesses need even plane strides and an even first
     // column: the pitch is a multiple of 16 and block columns start at even multiples (pl_set_comm_2d enforces even block widths).
-    {
-        const int gx = (op.g.lnx + 127) / 128;
-#define PL_APPLY_LAUNCH(KERNEL, ROWS)                                                                                   \
-        do {                                                                                                            \
-            if (op.scaled) hipLaunchKernelGGL((KERNEL<ROWS, true>), dim3(gx, (op.g.lnz + ROWS - 1) / ROWS), dim3(64, ROWS), 0, ctx->stream, op, x, y, add, coef);  \
-            else hipLaunchKernelGGL((KERNEL<ROWS, false>), dim3(gx, (op.g.lnz + ROWS - 1) / ROWS), dim3(64, ROWS), 0, ctx->stream, op, x, y, add, coef);           \
-        } while (0)
-        static const int rows_knob = [] { const char* e = getenv("PYLAMP_APPLY_ROWS"); return e ? atoi(e) : 0; }();
-        const int rows = rows_knob ? rows_knob : ((long long)op.g.lnz * op.g.lnx >= 8000000LL ? 16 : 4);
-        if (rows == 16) PL_APPLY_LAUNCH(k_stokes_apply_v2, 16);
-        else if (rows == 8) PL_APPLY_LAUNCH(k_stokes_apply_v2, 8);
-        else if (rows == 2) PL_APPLY_LAUNCH(k_stokes_apply_v2, 2);
-        else PL_APPLY_LAUNCH(k_stokes_apply_v2, 4);
-#undef PL_APPLY_LAUNCH
+    const int gx = (op.g.lnx + 127) / 128;
+    const int rows = pl_apply_rows(op.g, a.mode, a.rows);
+#define PL_APPLY_LAUNCH(ROWS, MODE)                                                                                     \
+    do {                                                                                                                \
+        if (op.scaled) hipLaunchKernelGGL((k_stokes_apply_v2<ROWS, true, MODE>), dim3(gx, (op.g.lnz + ROWS - 1) / ROWS), dim3(64, ROWS), 0, ctx->stream, op, x, y, a);  \
+        else hipLaunchKernelGGL((k_stokes_apply_v2<ROWS, false, MODE>), dim3(gx, (op.g.lnz + ROWS - 1) / ROWS), dim3(64, ROWS), 0, ctx->stream, op, x, y, a);           \
+    } while (0)
+#define PL_APPLY_MODE(MODE) do { if (rows == 16) PL_APPLY_LAUNCH(16, MODE); else PL_APPLY_LAUNCH(4, MODE); } while (0)
+    switch (a.mode) {
+    case PL_EPI_DOT1: PL_APPLY_MODE(PL_EPI_DOT1); break;
+    case PL_EPI_DOT5: PL_APPLY_MODE(PL_EPI_DOT5); break;
+    case PL_EPI_RESID: PL_APPLY_MODE(PL_EPI_RESID); break;
+    default:
+        if (rows == 16) PL_APPLY_LAUNCH(16, PL_EPI_NONE);
+        else if (rows == 8) PL_APPLY_LAUNCH(8, PL_EPI_NONE);
+        else if (rows == 2) PL_APPLY_LAUNCH(2, PL_EPI_NONE);
+        else PL_APPLY_LAUNCH(4, PL_EPI_NONE);
     }
+#undef PL_APPLY_MODE
+#undef PL_APPLY_LAUNCH
 }
 
 void pl_launch_stokes_rhs(pl_ctx* ctx, const PlStokesOp& op, double* rhs) {
