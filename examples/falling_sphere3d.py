@@ -2,9 +2,12 @@
 griddata.NNNNNN.npz / tracs.NNNNNN.npz in the style of the 2-D example, with a third axis (gridy, vely, tr_x (n, 3)).
 Cells that run below tracdens_min markers are refilled to tracdens inside the end-of-step sort (0 0 switches that off).
 
-    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident]
+    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R]
 
 --resident runs the device-resident step (Options3.resident): the grid fields stay on the GPU and are downloaded for the snapshots only.
+--refine=R (e.g. 3) makes the cells R times finer around the sphere's path than far from it (pylamp3d.refined_grid) and switches
+the markers' per-axis cell search on (Options3.marker_search), which a grid that is not regular needs; the markers start denser
+so that the fine cells are populated.
 """
 import os
 import sys
@@ -15,7 +18,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from pylamp_amd import pylamp3d as P3                                             # noqa: E402
 
 resident = "--resident" in sys.argv[1:]
-argv = [a for a in sys.argv if a != "--resident"]
+refine = [float(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--refine=")]
+refine = refine[0] if refine else 0.0
+argv = [a for a in sys.argv if not a.startswith("--")]
 n = int(argv[1]) if len(argv) > 1 else 65
 steps = int(argv[2]) if len(argv) > 2 else 20
 outdir = argv[3] if len(argv) > 3 else "out"
@@ -23,10 +28,15 @@ tracdens = int(argv[4]) if len(argv) > 4 else 8
 tracdens_min = int(argv[5]) if len(argv) > 5 else 4
 
 nx = [n, n, n]; L = [100e3, 100e3, 100e3]
-tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1))          # 2 x 2 x 2 jittered markers per cell
+grid = None
+per_axis = 2                                                                     # 2 x 2 x 2 jittered markers per (mean) cell
+if refine > 1.0:                                                                 # the sphere starts at z = 0.3 L and sinks along +z
+    grid = [P3.refined_grid(n, L[0], 0.45, refine, 0.35), P3.refined_grid(n, L[1], 0.5, refine, 0.2), P3.refined_grid(n, L[2], 0.5, refine, 0.2)]
+    per_axis = int(np.ceil(2 * refine / 1.5))
+tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1), per_axis=per_axis)
 opt = P3.Options3(do_heatdiff=False, tdep_rho=False, tdep_eta=False,             # isothermal, constant properties
-                  tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident)
-sim = P3.Simulation3(nx, L, tr_x, tr_f, opt)
+                  tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident, marker_search=grid is not None)
+sim = P3.Simulation3(nx, L, tr_x, tr_f, opt, grid=grid)
 sphere = None
 for it in range(1, steps + 1):
     rep = sim.step()

@@ -403,6 +403,23 @@ int  pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int gnx, int 
 /* Resident tracers of a context: (n, 3) positions and (n, 13) fields, kept on the device sorted by cell of the context's node grid
  * (tracers outside it count to the nearest cell).  Download returns them in the resident order: TR__ID identifies a tracer.
  * Census: tracers per cell, (nz-1, nx-1, ny-1) int32, a by-product of the sort. */
+/* Rectilinear grids: an opt-in per-axis cell search (default off = the regular-grid formula above, bit for bit).  With the switch
+ * on, every marker call of the context (pl3_trac2grid, pl3_grid2trac, pl3_rk4, pl3_tracers_*, every pl3_resident_* marker call and
+ * pl3_resident_step) finds cells from the stored coordinates -- the 3-D extension of the 2-D rule of pl_mic_set_search.  Per axis,
+ * with strictly increasing c[0..n-1], h0 = c[1] - c[0], h1 = c[n-1] - c[n-2], the cell of a position p is
+ *   c[0] <= p < c[n-1]:  the i with c[i] <= p < c[i+1], decided by exact comparisons with c[] (searchsorted(c, p, 'right') - 1);
+ *   p < c[0]:            floor((p - c[0]) / h0) < 0 (the auto-extended node set);
+ *   p >= c[n-1]:         n - 1 + floor((p - c[n-1]) / h1).
+ * Sort and census clamp the cell into 0..n-2 (NaN: cell 0).  Grid -> tracer and RK4: a tracer is outside (defval / velocity 0) when
+ * p < c[0], p >= c[n-1] or p is NaN on any axis; weights d0 / (d0 + d1); VELDIV uses the spacings of the found cell.  Tracer -> grid:
+ * node i receives t = (p - c(i-1)) / (c(i) - c(i-1)) from a tracer in [c(i-1), c(i)) and 1 - t, t = (p - c(i)) / (c(i+1) - c(i)), from
+ * one in [c(i), c(i+1)), with c(-1) = c[0] - h0 and c(n) = c[n-1] + h1; contributions to nodes outside the set are dropped.  A
+ * bucket table per axis only shortens the search: results rest on comparisons with c[] alone.  On a regular grid the rule agrees
+ * with the formula except within rounding of a cell face.  Not changed by the switch: the time-step rules and the subgrid time
+ * scale use the mean spacing L / (n - 1), the padded centre grid's ghost coordinate is m[0] - (m[1] - m[0]), the fence is EPS.
+ * Changing the switch while tracers are resident re-sorts them by the new rule. */
+int  pl3_mic_set_search(pl3_ctx* ctx, int on);
+int  pl3_mic_get_search(pl3_ctx* ctx, int* on);
 int  pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f);
 int  pl3_tracers_download(pl3_ctx* ctx, int64_t n, double* tr_x, double* tr_f);
 int  pl3_tracers_count(pl3_ctx* ctx, int64_t* n);

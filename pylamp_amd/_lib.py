@@ -98,6 +98,8 @@ SIGNATURES = {
                                 C.POINTER(C.c_int64)]),
     "pl3_rk4": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, C.c_int, C.c_int, C.c_int] + [c_double_p] * 6 +
                 [C.c_double, c_double_p, c_double_p]),
+    "pl3_mic_set_search": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl3_mic_get_search": (C.c_int, [C.c_void_p, c_int_p]),
     "pl3_tracers_upload": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
     "pl3_tracers_download": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
     "pl3_tracers_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

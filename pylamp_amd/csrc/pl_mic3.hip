@@ -22,8 +22,10 @@
 enum { M3_RHO = 0, M3_ETA = 1, M3_TMP = 3, M3_HCD = 4, M3_HCP = 5, M3_RH0 = 6, M3_ALP = 7, M3_ACE = 9, M3_ET0 = 10 };
 #define M3_GASR 8.31446
 
-// one axis of a regular node set: n coordinates c[], cell = floor((n-1)(x - c0)/L) (pylamp_trac.py:42-47,222-227)
-struct M3Axis { int n; double c0, L, h0, h1; const double* c; };
+// one axis of a node set: n coordinates c[].  Regular grids: cell = floor((n-1)(x - c0)/L) (pylamp_trac.py:42-47,222-227).  With
+// the per-axis search (pl3_mic_set_search) the cell comes from comparisons with c[]: cl = c[n-1], and bin[] holds, for nbin equal
+// buckets over [c0, cl], a cell that is not above the cell of any point of the bucket (binv = nbin / (cl - c0)); nbin = 0 without it.
+struct M3Axis { int n; double c0, L, h0, h1; const double* c; double cl, binv; int nbin; const int* bin; };
 struct M3Grid { M3Axis a[3]; };
 
 __device__ inline double m3_cellf(const M3Axis& a, double p) { return floor((double)(a.n - 1) * (p - a.c0) / a.L); }
@@ -38,16 +40,43 @@ __device__ inline int m3_sort_cell(const M3Axis& a, double p) {
     return f >= (double)(a.n - 2) ? a.n - 2 : (f > 0.0 ? (int)f : 0);       // clamped into the node set (NaN -> 0)
 }
 
+// Search mode, c0 <= p < cl: the i with c[i] <= p < c[i+1].  The bucket is clamped as a double before the conversion (NaN, inf and
+// huge values never index the table); from the bucket's entry the walk goes up while p >= c[i+1] and then down while p < c[i], so the
+// answer rests on the comparisons alone and the table can only shorten the walk.  Both loops are bounded by n.  lo, hi = c[i], c[i+1]
+// of the answer.  The three coordinates from the entry on are loaded together, so that the usual cases -- no step, or the one step
+// up of a point whose bucket starts on a cell face -- cost two dependent loads (table, coordinates) and no more.
+__device__ inline int m3_search_cell(const M3Axis& a, double p, double& lo, double& hi) {
+    const double b = (p - a.c0) * a.binv;
+    int i = a.bin[b >= (double)(a.nbin - 1) ? a.nbin - 1 : (b > 0.0 ? (int)b : 0)];
+    lo = a.c[i]; hi = a.c[i + 1];
+    const double h2 = a.c[min(i + 2, a.n - 1)];
+    if (i < a.n - 2 && p >= hi) { i++; lo = hi; hi = h2; }
+    for (int s = 0; s < a.n && i < a.n - 2 && p >= hi; s++) { i++; lo = hi; hi = a.c[i + 1]; }
+    for (int s = 0; s < a.n && i > 0 && p < lo; s++) { i--; hi = lo; lo = a.c[i]; }
+    return i;
+}
+template <bool SEARCH>
+__device__ inline int m3_sort_cell_of(const M3Axis& a, double p) {
+    if constexpr (!SEARCH) return m3_sort_cell(a, p);
+    else {
+        if (!(p >= a.c0)) return 0;                                         // below the set, or NaN
+        double lo, hi;
+        return p >= a.cl ? a.n - 2 : m3_search_cell(a, p, lo, hi);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // sort by cell
 // ---------------------------------------------------------------------------------------------------------------------
 // position of tracer t along axis a is x[a][t * xs]: xs = 1 for the resident SoA columns, 3 for a host (n,3) array
 struct M3Pos { const double* x[3]; long long xs; };
 
+template <bool SEARCH>
 __global__ __launch_bounds__(256) void k_m3_key(long long n, M3Pos p, M3Grid s, int* __restrict__ key, int* __restrict__ count) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
-    const int ci = m3_sort_cell(s.a[0], p.x[0][t * p.xs]), cj = m3_sort_cell(s.a[1], p.x[1][t * p.xs]), ck = m3_sort_cell(s.a[2], p.x[2][t * p.xs]);
+    const int ci = m3_sort_cell_of<SEARCH>(s.a[0], p.x[0][t * p.xs]), cj = m3_sort_cell_of<SEARCH>(s.a[1], p.x[1][t * p.xs]),
+              ck = m3_sort_cell_of<SEARCH>(s.a[2], p.x[2][t * p.xs]);
     const int c = (ci * (s.a[1].n - 1) + cj) * (s.a[2].n - 1) + ck;
     key[t] = c;
     atomicAdd(&count[c], 1);                      // integer: the counts do not depend on the order of arrival
@@ -335,7 +364,10 @@ struct M3Scatter {
 
 // One thread per target node; lanes run along y, so neighbouring lanes read neighbouring cells' slices of the sorted arrays.
 // NF > 0: field count known at compile time (accumulators stay in registers); 0: generic.
-template <int NF>
+// SEARCH: the thread keeps c(i-1), c(i), c(i+1) of its own node per axis (extended by the end spacing at the ends); a tracer in
+// [c(i-1), c(i)) gives the node t = (p - c(i-1)) / (c(i) - c(i-1)), one in [c(i), c(i+1)) gives 1 - t with t = (p - c(i)) / (c(i+1) - c(i)):
+// two interval tests per axis, no search, no floor, and one division only for the tracers that contribute.
+template <int NF, bool SEARCH>
 __global__ __launch_bounds__(256) void k_m3_scatter(M3Scatter a) {
     const int nz = a.t.a[0].n, nx = a.t.a[1].n, ny = a.t.a[2].n;
     const long long node = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -345,6 +377,11 @@ __global__ __launch_bounds__(256) void k_m3_scatter(M3Scatter a) {
     const int idx[3] = {i, j, k};
     double wsum = 0.0, cnt = 0.0, acc[NF > 0 ? NF : M3_MAXF];
     for (int q = 0; q < nf; q++) acc[q] = 0.0;
+    double cm[3], cc[3], cp[3];
+    if constexpr (SEARCH) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) { cm[d] = m3_coord(a.t.a[d], idx[d] - 1); cc[d] = a.t.a[d].c[idx[d]]; cp[d] = m3_coord(a.t.a[d], idx[d] + 1); }
+    }
     const int lo2 = a.lo[2][k], hi2 = a.hi[2][k];
     for (int cz = a.lo[0][i]; cz <= a.hi[0][i]; cz++)
         for (int cx = a.lo[1][j]; cx <= a.hi[1][j]; cx++) {
@@ -352,6 +389,15 @@ __global__ __launch_bounds__(256) void k_m3_scatter(M3Scatter a) {
             const int t0 = a.start[row + lo2], t1 = a.start[row + hi2 + 1];        // the cells of a y-row are contiguous
             for (int t = t0; t < t1; t++) {
                 double w = 1.0; bool mine = true;
+                if constexpr (SEARCH) {
+#pragma unroll
+                    for (int d = 0; d < 3; d++) {
+                        const double p = a.x[d][t];
+                        if (p >= cm[d] && p < cc[d]) w *= (p - cm[d]) / (cc[d] - cm[d]);
+                        else if (p >= cc[d] && p < cp[d]) w *= 1.0 - (p - cc[d]) / (cp[d] - cc[d]);
+                        else { mine = false; break; }
+                    }
+                } else
 #pragma unroll
                 for (int d = 0; d < 3; d++) {
                     const M3Axis& ax = a.t.a[d];
@@ -382,15 +428,22 @@ __global__ __launch_bounds__(256) void k_m3_scatter(M3Scatter a) {
 // ---------------------------------------------------------------------------------------------------------------------
 struct M3Loc { int ie[3]; double t[3], h[3], d0[3], d1[3]; bool bad; long long o; };
 
+template <bool SEARCH>
 __device__ inline M3Loc m3_locate(const M3Grid& g, const double p[3]) {
     M3Loc c; c.bad = false;
     double f[3];
 #pragma unroll
-    for (int d = 0; d < 3; d++) { f[d] = m3_cellf(g.a[d], p[d]); c.bad = c.bad || !(f[d] >= 0.0 && f[d] <= (double)(g.a[d].n - 2)); }
+    for (int d = 0; d < 3; d++) {
+        if constexpr (SEARCH) c.bad = c.bad || !(p[d] >= g.a[d].c0 && p[d] < g.a[d].cl);       // outside on any axis, or NaN
+        else { f[d] = m3_cellf(g.a[d], p[d]); c.bad = c.bad || !(f[d] >= 0.0 && f[d] <= (double)(g.a[d].n - 2)); }
+    }
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-        const int ie = c.bad ? 0 : (int)f[d];
-        const double lo = g.a[d].c[ie], hi = g.a[d].c[ie + 1];
+        int ie; double lo, hi;
+        if constexpr (SEARCH) {
+            if (c.bad) { ie = 0; lo = g.a[d].c[0]; hi = g.a[d].c[1]; }
+            else ie = m3_search_cell(g.a[d], p[d], lo, hi);
+        } else { ie = c.bad ? 0 : (int)f[d]; lo = g.a[d].c[ie]; hi = g.a[d].c[ie + 1]; }
         c.ie[d] = ie; c.d0[d] = p[d] - lo; c.d1[d] = hi - p[d]; c.h[d] = hi - lo;
         c.t[d] = c.d0[d] / (c.d0[d] + c.d1[d]);                          // pylamp_trac.py:89-90
     }
@@ -417,9 +470,10 @@ __device__ inline double m3_mixed(const double v[8], double s) {
 }
 // Divergence-conserving interpolation in 3-D: trilinear plus t_d (1 - t_d) (h_d / 2) [M_de / h_e + M_df / h_f],
 // the symmetric extension of pylamp_trac.py:98-154.  Out of grid: all three components = defval.
+template <bool SEARCH>
 __device__ inline void m3_veldiv(const M3Grid& g, const double* __restrict__ Vz, const double* __restrict__ Vx, const double* __restrict__ Vy,
                                  const double p[3], double defval, double u[3], bool& bad) {
-    const M3Loc c = m3_locate(g, p);
+    const M3Loc c = m3_locate<SEARCH>(g, p);
     double vz[8], vx[8], vy[8];
     m3_corners(Vz, g, c, vz); m3_corners(Vx, g, c, vx); m3_corners(Vy, g, c, vy);
     const double* t = c.t; const double* h = c.h;
@@ -440,13 +494,14 @@ struct M3Gather {
     int method; double defval; int accumulate;                               // LINEAR only: out += value
     unsigned long long* nout;
 };
+template <bool SEARCH>
 __global__ __launch_bounds__(256) void k_m3_gather(M3Gather a) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n) return;
     const double p[3] = {a.p.x[0][t * a.p.xs], a.p.x[1][t * a.p.xs], a.p.x[2][t * a.p.xs]};
     bool bad;
     if (a.method & PL_INTERP_NEAREST) {
-        const M3Loc c = m3_locate(a.g, p);
+        const M3Loc c = m3_locate<SEARCH>(a.g, p);
         int m = 0; double dm = 0.0;
 #pragma unroll
         for (int q = 0; q < 8; q++) {       // exactly rounded products and sums in a fixed order: ties break as np.argmin does
@@ -458,7 +513,7 @@ __global__ __launch_bounds__(256) void k_m3_gather(M3Gather a) {
         for (int k = 0; k < a.nf; k++) a.out[k][t * a.os] = c.bad ? a.defval : a.f[k][o];
         bad = c.bad;
     } else if (a.method & PL_INTERP_LINEAR) {
-        const M3Loc c = m3_locate(a.g, p);
+        const M3Loc c = m3_locate<SEARCH>(a.g, p);
         for (int k = 0; k < a.nf; k++) {
             double v[8];
             m3_corners(a.f[k], a.g, c, v);
@@ -468,7 +523,7 @@ __global__ __launch_bounds__(256) void k_m3_gather(M3Gather a) {
         bad = c.bad;
     } else {
         double u[3];
-        m3_veldiv(a.g, a.f[0], a.f[1], a.f[2], p, a.defval, u, bad);
+        m3_veldiv<SEARCH>(a.g, a.f[0], a.f[1], a.f[2], p, a.defval, u, bad);
         for (int k = 0; k < 3; k++) a.out[k][t * a.os] = u[k];
     }
     if (bad) atomicAdd(a.nout, 1ull);
@@ -481,19 +536,20 @@ struct M3Rk4 {
     double* xo[3]; double* vo[3]; long long os;
     int fence; double eps, L[3];                   // pylamp2.py:558-572 per axis
 };
+template <bool SEARCH>
 __global__ __launch_bounds__(256) void k_m3_rk4(M3Rk4 a) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n) return;
     const double x[3] = {a.p.x[0][t * a.p.xs], a.p.x[1][t * a.p.xs], a.p.x[2][t * a.p.xs]};
     const double dt = a.dt;
     double k1[3], k2[3], k3[3], k4[3], q[3]; bool bad;
-    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], x, 0.0, k1, bad);
+    m3_veldiv<SEARCH>(a.g, a.V[0], a.V[1], a.V[2], x, 0.0, k1, bad);
     for (int d = 0; d < 3; d++) q[d] = x[d] + 0.5 * dt * k1[d];
-    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k2, bad);
+    m3_veldiv<SEARCH>(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k2, bad);
     for (int d = 0; d < 3; d++) q[d] = x[d] + 0.5 * dt * k2[d];
-    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k3, bad);
+    m3_veldiv<SEARCH>(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k3, bad);
     for (int d = 0; d < 3; d++) q[d] = x[d] + dt * k3[d];
-    m3_veldiv(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k4, bad);
+    m3_veldiv<SEARCH>(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k4, bad);
     for (int d = 0; d < 3; d++) {
         const double xn = x[d] + (1.0 / 6.0) * dt * (k1[d] + k2[d] + k3[d] + k4[d]);
         a.vo[d][t * a.os] = (xn - x[d]) / dt;
@@ -547,6 +603,7 @@ struct Mic3 {
     // date by the refill (nothing deletes tracers in 3-D; whatever does one day sets have_maxid = false)
     bool have_maxid = false; double maxid = 0.0;
     bool have_vgrid = false; M3Grid vgrid;           // the padded centre grid of the resident step: uploaded once per context
+    bool search = false;                             // pl3_mic_set_search: cells by per-axis search in every marker kernel of this context
 };
 // a refill riding on a sort: what to do, and what the sort found
 struct M3Refill {
@@ -598,14 +655,49 @@ static int m3_buf(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, size_
 }
 static inline dim3 m3_blocks(long long n) { return dim3((unsigned)((std::max<long long>(n, 1) + 255) / 256)); }
 
-// a node set given by three host coordinate arrays -> device axes (coordinates in the buffer `name`)
+// The bucket table of one axis for the search: at most M3_MAXBIN equal buckets over [c[0], c[n-1]], two per smallest spacing when
+// that fits (the walk from a bucket's entry is then at most one step; beyond the cap it simply gets longer).  A bucket's entry is
+// the cell of a point just below everything the device can map to the bucket, so it is never above the cell of a point in it.
+#define M3_MAXBIN 4096
+static void m3_bins(const double* c, int n, std::vector<int>& tab, double& binv) {
+    const double L = c[n - 1] - c[0];
+    double hmin = L;
+    for (int i = 0; i + 1 < n; i++) hmin = std::min(hmin, c[i + 1] - c[i]);
+    const double want = std::ceil(2.0 * L / hmin);
+    const int nbin = (int)std::min<double>(M3_MAXBIN, std::max<double>(want, 1.0));
+    binv = (double)nbin / L;
+    tab.resize((size_t)nbin);
+    for (int b = 0; b < nbin; b++) {
+        const double e = c[0] + ((double)b / binv) * (1.0 - 1e-15);
+        const double lo = std::nextafter(std::nextafter(e, -INFINITY), -INFINITY);
+        const int i = (int)(std::upper_bound(c, c + n, lo) - c) - 1;
+        tab[(size_t)b] = std::min(std::max(i, 0), n - 2);
+    }
+}
+// a node set given by three host coordinate arrays -> device axes (coordinates in the buffer `name`; with the search switched on
+// the bucket tables go beside them, into `name`_bin)
 static int m3_grid(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* name, const double* const c[3], const int n[3], M3Grid& g) {
     double* d;
     M3_TRY(m3_buf(ctx, v, M, name, (size_t)n[0] + n[1] + n[2], &d));
-    size_t off = 0;
     for (int a = 0; a < 3; a++) {
         if (n[a] < 2) return pl3_fail(ctx, "3-D marker-in-cell: a node set needs at least 2 coordinates per axis");
         for (int i = 0; i + 1 < n[a]; i++) if (!(c[a][i + 1] > c[a][i])) return pl3_fail(ctx, "3-D marker-in-cell: coordinates must increase");
+        g.a[a].nbin = 0; g.a[a].bin = nullptr; g.a[a].binv = 0.0; g.a[a].cl = c[a][n[a] - 1];
+    }
+    std::vector<int> tab[3];
+    if (M->search) {
+        for (int a = 0; a < 3; a++) m3_bins(c[a], n[a], tab[a], g.a[a].binv);
+        int* db;
+        M3_TRY(m3_buf(ctx, v, M, (std::string(name) + "_bin").c_str(), tab[0].size() + tab[1].size() + tab[2].size(), &db));
+        size_t boff = 0;
+        for (int a = 0; a < 3; a++) {
+            M3_HIP(ctx, m3_copy(ctx, db + boff, tab[a].data(), tab[a].size() * sizeof(int), hipMemcpyHostToDevice, v.stream));
+            g.a[a].nbin = (int)tab[a].size(); g.a[a].bin = db + boff;
+            boff += tab[a].size();
+        }
+    }
+    size_t off = 0;
+    for (int a = 0; a < 3; a++) {
         M3_HIP(ctx, m3_copy(ctx, d + off, c[a], (size_t)n[a] * sizeof(double), hipMemcpyHostToDevice, v.stream));
         g.a[a].n = n[a]; g.a[a].c0 = c[a][0]; g.a[a].L = c[a][n[a] - 1] - c[a][0]; g.a[a].h0 = c[a][1] - c[a][0];
         g.a[a].h1 = c[a][n[a] - 1] - c[a][n[a] - 2]; g.a[a].c = d + off;
@@ -639,7 +731,8 @@ static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long 
     M3_TRY(m3_buf(ctx, v, M, (t + "_bsum").c_str(), (size_t)nb * 5, &bsum));
     M3_TRY(m3_buf(ctx, v, M, (t + "_tot").c_str(), (size_t)1, &tot));
     M3_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(int), v.stream));
-    if (n > 0) hipLaunchKernelGGL(k_m3_key, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
+    if (n > 0 && M->search) hipLaunchKernelGGL(k_m3_key<true>, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
+    else if (n > 0) hipLaunchKernelGGL(k_m3_key<false>, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
     long long slots = n;
     if (!rf) {
         const M3Need none{0, 0};
@@ -703,7 +796,16 @@ static int m3_scatter_device(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Scatter& a
         for (int i = 0; i < n; i++) {
             int lo, hi;
             if (same) { lo = i - 1; hi = i; }                      // the tracer's cell and the sort cell come from the same expression
-            else {
+            else if (M->search) {
+                // the sort cells of the ends of the node's support [c(i-1), c(i+1)), found as the kernels find them; one more cell on
+                // either side where an end coincides with a sort coordinate
+                const double pl = i > 0 ? tc[d][i - 1] : tc[d][0] - (tc[d][1] - tc[d][0]);
+                const double ph = i < n - 1 ? tc[d][i + 1] : tc[d][n - 1] + (tc[d][n - 1] - tc[d][n - 2]);
+                const double* ul = std::upper_bound(sc[d], sc[d] + ns, pl); const double* uh = std::upper_bound(sc[d], sc[d] + ns, ph);
+                lo = (int)(ul - sc[d]) - 1; hi = (int)(uh - sc[d]) - 1;
+                if (ul != sc[d] && ul[-1] == pl) lo--;
+                if (uh != sc[d] && uh[-1] == ph) hi++;
+            } else {
                 const double pl = i > 0 ? tc[d][i - 1] : tc[d][0] - (tc[d][1] - tc[d][0]);
                 const double ph = i < n - 1 ? tc[d][i + 1] : tc[d][n - 1] + (tc[d][n - 1] - tc[d][n - 2]);
                 lo = (int)std::floor(std::min(std::max((ns - 1) * (pl - s0) / Ls - 1e-6, -1.0), (double)ns));
@@ -719,12 +821,27 @@ static int m3_scatter_device(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Scatter& a
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     a.start = start;
     const long long N = (long long)tn[0] * tn[1] * tn[2];
-    if (a.nf == 1) hipLaunchKernelGGL(k_m3_scatter<1>, m3_blocks(N), dim3(256), 0, v.stream, a);
-    else if (a.nf == 2) hipLaunchKernelGGL(k_m3_scatter<2>, m3_blocks(N), dim3(256), 0, v.stream, a);
-    else if (a.nf == 6) hipLaunchKernelGGL(k_m3_scatter<6>, m3_blocks(N), dim3(256), 0, v.stream, a);
-    else hipLaunchKernelGGL(k_m3_scatter<0>, m3_blocks(N), dim3(256), 0, v.stream, a);
+    if (M->search) {
+        if (a.nf == 1) hipLaunchKernelGGL((k_m3_scatter<1, true>), m3_blocks(N), dim3(256), 0, v.stream, a);
+        else if (a.nf == 2) hipLaunchKernelGGL((k_m3_scatter<2, true>), m3_blocks(N), dim3(256), 0, v.stream, a);
+        else if (a.nf == 6) hipLaunchKernelGGL((k_m3_scatter<6, true>), m3_blocks(N), dim3(256), 0, v.stream, a);
+        else hipLaunchKernelGGL((k_m3_scatter<0, true>), m3_blocks(N), dim3(256), 0, v.stream, a);
+    } else if (a.nf == 1) hipLaunchKernelGGL((k_m3_scatter<1, false>), m3_blocks(N), dim3(256), 0, v.stream, a);
+    else if (a.nf == 2) hipLaunchKernelGGL((k_m3_scatter<2, false>), m3_blocks(N), dim3(256), 0, v.stream, a);
+    else if (a.nf == 6) hipLaunchKernelGGL((k_m3_scatter<6, false>), m3_blocks(N), dim3(256), 0, v.stream, a);
+    else hipLaunchKernelGGL((k_m3_scatter<0, false>), m3_blocks(N), dim3(256), 0, v.stream, a);
     M3_HIP(ctx, hipGetLastError());
     return 0;
+}
+
+// the host picks the instantiation: with the switch off the kernels are the regular-grid code
+static void m3_launch_gather(Pl3HostView& v, Mic3* M, const M3Gather& a) {
+    if (M->search) hipLaunchKernelGGL(k_m3_gather<true>, m3_blocks(a.n), dim3(256), 0, v.stream, a);
+    else hipLaunchKernelGGL(k_m3_gather<false>, m3_blocks(a.n), dim3(256), 0, v.stream, a);
+}
+static void m3_launch_rk4(Pl3HostView& v, Mic3* M, const M3Rk4& a) {
+    if (M->search) hipLaunchKernelGGL(k_m3_rk4<true>, m3_blocks(a.n), dim3(256), 0, v.stream, a);
+    else hipLaunchKernelGGL(k_m3_rk4<false>, m3_blocks(a.n), dim3(256), 0, v.stream, a);
 }
 
 static unsigned m3_logmask(int nf, const int* scheme) {
@@ -799,7 +916,7 @@ extern "C" int pl3_grid2trac(pl3_ctx* ctx, int64_t n, const double* tr_x, int nf
     if (n > 0) M3_HIP(ctx, m3_copy(ctx, dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
     a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.nf = nf; a.os = nf; a.method = method; a.defval = defval; a.accumulate = 0; a.nout = cnt;
     for (int k = 0; k < nf; k++) { a.f[k] = df + k * GN; a.out[k] = dout + k; }
-    if (n > 0) hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
+    if (n > 0) m3_launch_gather(v, M, a);
     M3_HIP(ctx, hipGetLastError());
     unsigned long long nout = 0;
     M3_HIP(ctx, m3_copy(ctx, &nout, cnt, sizeof(nout), hipMemcpyDeviceToHost, v.stream));
@@ -831,7 +948,7 @@ extern "C" int pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int
     a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.dt = tstep; a.os = 3; a.fence = 0;
     for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = dx + 3 * nn + d; a.vo[d] = dx + 6 * nn + d; }
     if (n > 0) {
-        hipLaunchKernelGGL(k_m3_rk4, m3_blocks(n), dim3(256), 0, v.stream, a);
+        m3_launch_rk4(v, M, a);
         M3_HIP(ctx, hipGetLastError());
         M3_HIP(ctx, m3_copy(ctx, x_out, dx + 3 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
         M3_HIP(ctx, m3_copy(ctx, v_out, dx + 6 * nn, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, v.stream));
@@ -879,6 +996,24 @@ static int m3_resort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Refill* rf = nullp
     M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[3] = ms;
+    return 0;
+}
+
+// The switch is context state: it selects the kernel instantiations of every marker call of this context.  The resident tracers are
+// "sorted by cell", so a change re-sorts them by the new rule; the cached padded velocity grid is rebuilt with (or without) its tables.
+extern "C" int pl3_mic_set_search(pl3_ctx* ctx, int on) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_set_search", v, &M));
+    const bool s = on != 0;
+    if (s == M->search) return 0;
+    M->search = s; M->have_vgrid = false;
+    return M->have ? m3_resort(ctx, v, M) : 0;
+}
+extern "C" int pl3_mic_get_search(pl3_ctx* ctx, int* on) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_get_search", v, &M));
+    if (!on) return pl3_fail(ctx, "pl3_mic_get_search: NULL argument");
+    *on = M->search ? 1 : 0;
     return 0;
 }
 
@@ -1064,7 +1199,7 @@ static int m3_temp_to_tracers(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, int absolut
     if (sub) M3_HIP(ctx, hipMemcpyAsync(w, T, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, v.stream));      // T_old
     a.n = n; a.p = M3Pos{{M->x, M->x + cap, M->x + 2 * cap}, 1}; a.nf = 1; a.os = 1; a.method = PL_INTERP_LINEAR; a.defval = NAN;
     a.accumulate = absolute ? 0 : 1; a.nout = cnt; a.f[0] = df; a.out[0] = T;
-    if (n > 0) hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
+    if (n > 0) m3_launch_gather(v, M, a);
     if (sub && n > 0) {
         double inv2 = 0.0;
         for (int d = 0; d < 3; d++) { const double h = (v.coord[d][v.gn[d] - 1] - v.coord[d][0]) / (v.gn[d] - 1); inv2 += (2.0 / h) * (2.0 / h); }
@@ -1072,7 +1207,7 @@ static int m3_temp_to_tracers(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, int absolut
         const double* col[1] = {w + 2 * cap}; const int sch[1] = {PL_AVG_ARITHMETIC | PL_AVG_WEIGHTED};
         M3_TRY(m3_resident_scatter(ctx, v, M, 1, col, sch, v.coord, v.gn, dnode));
         a.f[0] = dnode; a.out[0] = w; a.accumulate = 0;                       // the correction back on the tracers
-        hipLaunchKernelGGL(k_m3_gather, m3_blocks(n), dim3(256), 0, v.stream, a);
+        m3_launch_gather(v, M, a);
         hipLaunchKernelGGL(k_m3_sub, m3_blocks(n), dim3(256), 0, v.stream, n, (const double*)(w + cap), (const double*)w, T);
     }
     M3_HIP(ctx, hipGetLastError());
@@ -1121,7 +1256,7 @@ static int m3_advect_dev(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const M3Grid& g,
     a.n = n; a.p = M3Pos{{M->x, M->x + cap, M->x + 2 * cap}, 1}; a.dt = tstep; a.os = 1; a.fence = fence ? 1 : 0; a.eps = 1.0 / 1024.0;   // EPS of pylamp_const.py
     for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = M->x + d * cap; a.vo[d] = M->v + d * cap; a.L[d] = v.coord[d][v.gn[d] - 1]; }
     M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
-    if (n > 0) hipLaunchKernelGGL(k_m3_rk4, m3_blocks(n), dim3(256), 0, v.stream, a);       // in place: a tracer reads its position before it writes
+    if (n > 0) m3_launch_rk4(v, M, a);       // in place: a tracer reads its position before it writes
     M3_HIP(ctx, hipGetLastError());
     M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));

@@ -86,6 +86,16 @@ class Context3:
             msg = self.lib.pl3_last_error(self.h)
             raise Exception(msg.decode() if msg else "libpylamp_hip error %d" % rc)
 
+    def set_marker_search(self, on):
+        """Per-axis cell search for the 3-D marker kernels of this context (rectilinear grids; default off = the regular-grid
+        formula).  Resident tracers are re-sorted by the new rule."""
+        self.check(self.lib.pl3_mic_set_search(self.handle(), 1 if on else 0))
+
+    def marker_search(self):
+        on = C.c_int()
+        self.check(self.lib.pl3_mic_get_search(self.handle(), C.byref(on)))
+        return bool(on.value)
+
     def close(self):
         if self.h is not None:
             self._fin()
@@ -315,6 +325,23 @@ def _mic_ctx(ctx):
     return _carrier
 
 
+class _searching:
+    """The context's marker search set to `on` for one call and restored afterwards (the shared carrier must not keep it)."""
+
+    def __init__(self, ctx, on):
+        self.ctx, self.on = ctx, bool(on)
+
+    def __enter__(self):
+        self.was = self.ctx.marker_search()
+        if self.was != self.on:
+            self.ctx.set_marker_search(self.on)
+
+    def __exit__(self, *exc):
+        if self.was != self.on and self.ctx.h is not None:
+            self.ctx.set_marker_search(self.was)
+        return False
+
+
 def _x3(tr_x):
     x = _lib.f64(tr_x)
     if x.ndim != 2 or x.shape[1] != DIM3:
@@ -323,9 +350,10 @@ def _x3(tr_x):
 
 
 def trac2grid(tr_x, tr_f, mesh, grid, gridfield, nx, distweight=None, avgscheme=None, method=INTERP_METHOD_ELEM, debug=False,
-              ctx=None):
+              ctx=None, search=False):
     """Average tracer values onto the node set `grid` = [z, x, y] coordinates, writing gridfield[k][:, :, :] in place:
-    pylamp_trac.trac2grid (method ELEM) extended by one axis.  Two calls with the same input agree bitwise."""
+    pylamp_trac.trac2grid (method ELEM) extended by one axis.  Two calls with the same input agree bitwise.
+    search=True: cells by per-axis search in the coordinates (rectilinear grids) instead of the regular-grid formula."""
     if avgscheme is None:
         avgscheme = [INTERP_AVG_ARITHW] * len(gridfield)
     if len(gridfield) != tr_f.shape[1] or len(avgscheme) != len(gridfield) or tr_x.shape[0] != tr_f.shape[0]:
@@ -340,22 +368,23 @@ def trac2grid(tr_x, tr_f, mesh, grid, gridfield, nx, distweight=None, avgscheme=
     if tuple(c.size for c in g) != shp:
         raise Exception("trac2grid: grid arrays do not match nx")
     nf = len(gridfield)
-    for k0 in range(0, nf, _MAXF):
-        k1 = min(nf, k0 + _MAXF)
-        sub = _lib.f64(tr_f[:, k0:k1])
-        outs = [np.empty(shp) for _ in range(k1 - k0)]
-        op = (_lib.c_double_p * (k1 - k0))(*[_lib.dptr(a) for a in outs])
-        sch = (C.c_int * (k1 - k0))(*[int(s) for s in avgscheme[k0:k1]])
-        ctx.check(ctx.lib.pl3_trac2grid(ctx.handle(), n, _lib.dptr(txc), _lib.dptr(sub), k1 - k0, k1 - k0, sch, _lib.dptr(g[0]), shp[0],
-                                        _lib.dptr(g[1]), shp[1], _lib.dptr(g[2]), shp[2], op))
-        for k in range(k0, k1):
-            gridfield[k][...] = outs[k - k0]
+    with _searching(ctx, search):
+        for k0 in range(0, nf, _MAXF):
+            k1 = min(nf, k0 + _MAXF)
+            sub = _lib.f64(tr_f[:, k0:k1])
+            outs = [np.empty(shp) for _ in range(k1 - k0)]
+            op = (_lib.c_double_p * (k1 - k0))(*[_lib.dptr(a) for a in outs])
+            sch = (C.c_int * (k1 - k0))(*[int(s) for s in avgscheme[k0:k1]])
+            ctx.check(ctx.lib.pl3_trac2grid(ctx.handle(), n, _lib.dptr(txc), _lib.dptr(sub), k1 - k0, k1 - k0, sch, _lib.dptr(g[0]), shp[0],
+                                            _lib.dptr(g[1]), shp[1], _lib.dptr(g[2]), shp[2], op))
+            for k in range(k0, k1):
+                gridfield[k][...] = outs[k - k0]
 
 
-def grid2trac(tr_x, tr_f, grid, gridfield, nx, defval=np.nan, method=INTERP_METHOD_LINEAR, stopOnError=False, ctx=None):
+def grid2trac(tr_x, tr_f, grid, gridfield, nx, defval=np.nan, method=INTERP_METHOD_LINEAR, stopOnError=False, ctx=None, search=False):
     """Interpolate gridfield (list of (nz, nx, ny) arrays) to the tracers, writing tr_f in place.  LINEAR is trilinear, NEAREST
     the nearest of the eight corners, VELDIV the divergence-conserving interpolation of (vz, vx, vy).
-    Out-of-grid tracers get defval in every column."""
+    Out-of-grid tracers get defval in every column.  search=True: cells by per-axis search (rectilinear grids)."""
     nf = len(gridfield)
     if nf != tr_f.shape[1] or tr_x.shape[0] != tr_f.shape[0]:
         raise Exception("grid2trac: tr_f and gridfield do not match")
@@ -368,24 +397,26 @@ def grid2trac(tr_x, tr_f, grid, gridfield, nx, defval=np.nan, method=INTERP_METH
     g = [_lib.f64(grid[d]) for d in range(3)]
     out = np.empty((n, nf))
     nout = C.c_int64(0); total = 0
-    for k0 in range(0, nf, _MAXF):
-        k1 = min(nf, k0 + _MAXF)
-        fl = [_f3(gridfield[k], shp) for k in range(k0, k1)]
-        fp = (_lib.c_double_p * (k1 - k0))(*[_lib.dptr(a) for a in fl])
-        sub = np.empty((n, k1 - k0))
-        ctx.check(ctx.lib.pl3_grid2trac(ctx.handle(), n, _lib.dptr(txc), k1 - k0, fp, shp[0], shp[1], shp[2], _lib.dptr(g[0]), _lib.dptr(g[1]),
-                                        _lib.dptr(g[2]), int(method), float(defval), 1 if stopOnError else 0, _lib.dptr(sub), k1 - k0,
-                                        C.byref(nout)))
-        out[:, k0:k1] = sub
-        total = max(total, nout.value)
+    with _searching(ctx, search):
+        for k0 in range(0, nf, _MAXF):
+            k1 = min(nf, k0 + _MAXF)
+            fl = [_f3(gridfield[k], shp) for k in range(k0, k1)]
+            fp = (_lib.c_double_p * (k1 - k0))(*[_lib.dptr(a) for a in fl])
+            sub = np.empty((n, k1 - k0))
+            ctx.check(ctx.lib.pl3_grid2trac(ctx.handle(), n, _lib.dptr(txc), k1 - k0, fp, shp[0], shp[1], shp[2], _lib.dptr(g[0]),
+                                            _lib.dptr(g[1]), _lib.dptr(g[2]), int(method), float(defval), 1 if stopOnError else 0,
+                                            _lib.dptr(sub), k1 - k0, C.byref(nout)))
+            out[:, k0:k1] = sub
+            total = max(total, nout.value)
     if total > 0:
         print("!!! Warning, grid2trac(): Using default value for extrapolation in ", total, "tracers")
     tr_f[:, :] = out
 
 
-def RK(tr_x, grids, vels, nx, tstep, order=4, ctx=None):
+def RK(tr_x, grids, vels, nx, tstep, order=4, ctx=None, search=False):
     """Runge-Kutta advection; returns (vel_final, tr_x_final), both (n, 3).  grids / vels live on the padded
-    (nz+1, nx+1, ny+1) cell-centre grid (advection_velocity); the reference's weights (1,1,1,1)/6 are kept."""
+    (nz+1, nx+1, ny+1) cell-centre grid (advection_velocity); the reference's weights (1,1,1,1)/6 are kept.
+    search=True: cells by per-axis search (rectilinear grids)."""
     if order != 4:
         raise Exception("RK: only order=4 is functional (as in 2-D)")
     if len(nx) != 3:
@@ -399,8 +430,9 @@ def RK(tr_x, grids, vels, nx, tstep, order=4, ctx=None):
         raise Exception("RK: velocity grids must have shape (nz+1, nx+1, ny+1)")
     V = [_f3(vels[d], shp) for d in range(3)]
     v = np.empty((n, 3)); xn = np.empty((n, 3))
-    ctx.check(ctx.lib.pl3_rk4(ctx.handle(), n, _lib.dptr(txc), shp[0], shp[1], shp[2], *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V],
-                              float(tstep), _lib.dptr(v), _lib.dptr(xn)))
+    with _searching(ctx, search):
+        ctx.check(ctx.lib.pl3_rk4(ctx.handle(), n, _lib.dptr(txc), shp[0], shp[1], shp[2], *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V],
+                                  float(tstep), _lib.dptr(v), _lib.dptr(xn)))
     return v, xn
 
 
@@ -412,6 +444,25 @@ def gridmp_of(grid):
         m = (c[1:] + c[:-1]) / 2
         out.append(np.append(m, m[-1] + (m[-1] - m[-2])))
     return out
+
+
+def graded_grid(n, L, ratio):
+    """n coordinates from 0 to L whose spacings grow smoothly (geometrically) by `ratio` from the first cell to the last: a
+    rectilinear grid for Simulation3(..., grid=, options=Options3(marker_search=True))."""
+    h = float(ratio) ** np.linspace(0.0, 1.0, int(n) - 1)
+    c = np.concatenate([[0.0], np.cumsum(h)]) * (float(L) / h.sum())
+    c[-1] = float(L)
+    return c
+
+
+def refined_grid(n, L, centre=0.5, ratio=3.0, width=0.2):
+    """n coordinates from 0 to L with cells `ratio` times finer around cell number centre * (n - 1) than far from it; the
+    spacing follows a Gaussian of width * (n - 1) cells, so neighbouring cells differ little."""
+    s = (np.arange(int(n) - 1) + 0.5) / (int(n) - 1)
+    h = 1.0 / (1.0 + (float(ratio) - 1.0) * np.exp(-((s - centre) / width) ** 2))
+    c = np.concatenate([[0.0], np.cumsum(h)]) * (float(L) / h.sum())
+    c[-1] = float(L)
+    return c
 
 
 def advection_velocity(newvel, gridmp, nx):
@@ -461,6 +512,8 @@ class Options3:
         self.surface_stabilization = False
         # True: step() is one pl3_resident_step call -- every grid field stays on the device, field() downloads on demand
         self.resident = False
+        # beyond the reference: cells of the markers by per-axis search, which lets Simulation3 take a rectilinear grid=
+        self.marker_search = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
@@ -473,23 +526,35 @@ class Simulation3:
     + refill of depleted cells inside the end-of-step sort (Options3.tracdens / tracdens_min / inject_seed / inject_unique_ids;
     refill() does it without a step).  step() reports ninjected, nrefilled (cells) and nempty (cells that held no tracer: their new
     tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank,
-    regular grid, all walls free-slip.  Options3.resident = True runs the same sequence inside the library with every grid field
-    kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Not built: the fence-off deletion path, surface stabilisation, non-uniform grids for the
-    markers, several ranks -- each is rejected with an error that names it."""
+    all walls free-slip; a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
+    axis strictly increasing from 0 to L[d]): the marker kernels then find cells by search in the coordinates (the rule is in
+    include/pylamp_hip.h at pl3_mic_set_search), while the time-step rules and the subgrid time scale keep the mean spacing.  Options3.resident = True runs the same sequence inside the library with every grid field
+    kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Not built: the fence-off deletion path, surface stabilisation, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
         self.nx = [int(v) for v in nx]
         self.L = [float(v) for v in L]
         if len(self.nx) != 3 or len(self.L) != 3:
             raise Exception("Simulation3: nx and L need three entries (z, x, y)")
-        if grid is not None:
-            for d in range(3):
-                if not np.allclose(np.asarray(grid[d], dtype=np.float64), np.linspace(0, self.L[d], self.nx[d]), rtol=0, atol=1e-9 * self.L[d]):
-                    raise Exception("Simulation3: non-uniform grids are not supported by the 3-D markers")
-        self.grid = [np.linspace(0, self.L[d], self.nx[d]) for d in range(3)]          # pylamp2.py:90
-        self.gridmp = gridmp_of(self.grid)
         self.opt = options or Options3()
         o = self.opt
+        self.grid = [np.linspace(0, self.L[d], self.nx[d]) for d in range(3)]          # pylamp2.py:90
+        if grid is not None and o.marker_search:
+            given = [np.array(grid[d], dtype=np.float64).reshape(-1) for d in range(3)]
+            for d in range(3):
+                c = given[d]
+                if c.size != self.nx[d]:
+                    raise Exception("Simulation3: grid[%d] has %d coordinates, nx[%d] = %d" % (d, c.size, d, self.nx[d]))
+                if not np.all(np.diff(c) > 0):
+                    raise Exception("Simulation3: grid[%d] is not strictly increasing" % d)
+                if c[0] != 0.0 or abs(c[-1] - self.L[d]) > 1e-12 * self.L[d]:
+                    raise Exception("Simulation3: grid[%d] does not span 0..L[%d] (it runs from %r to %r, L = %r)" % (d, d, c[0], c[-1], self.L[d]))
+            self.grid = given
+        elif grid is not None:
+            for d in range(3):
+                if not np.allclose(np.asarray(grid[d], dtype=np.float64), np.linspace(0, self.L[d], self.nx[d]), rtol=0, atol=1e-9 * self.L[d]):
+                    raise Exception("Simulation3: non-uniform grids are not supported by the 3-D markers unless Options3.marker_search = True")
+        self.gridmp = gridmp_of(self.grid)
         if int(o.tracdens) < 0 or int(o.tracdens_min) < 0 or int(o.tracdens_min) > int(o.tracdens):
             raise Exception("Simulation3: tracer injection needs tracdens >= tracdens_min >= 0 (got tracdens = %s, tracdens_min = %s)"
                             % (o.tracdens, o.tracdens_min))
@@ -500,6 +565,8 @@ class Simulation3:
         if any(int(b) != BC_TYPE_FREESLIP for b in o.bcstokes):
             raise Exception("Simulation3: all Stokes walls are free-slip")
         self.ctx = Context3(self.nx, self.grid, device)
+        if o.marker_search:
+            self.ctx.set_marker_search(True)
         self.it = 0
         self.totaltime = 0.0
         self.last = None

@@ -2,7 +2,11 @@
 writes one JSON line.  Device-event times of the stages' kernel windows (pl3_resident_times), median over the repetitions after
 a warm-up; bytes per tracer are the algorithmic minimum, the roof is 8 TB/s.
 
-    python tools/mic3_bench.py [--n 129] [--per-axis 2] [--reps 20] [--warmup 3] [--out profiles/mic3_129.json]
+    python tools/mic3_bench.py [--n 129] [--per-axis 2] [--reps 20] [--warmup 3] [--out profiles/mic3_129.json] [--search | --graded R]
+
+--search runs the stages with the per-axis cell search (Options3.marker_search) on the same regular grid; --graded R on a grid
+whose spacings grow smoothly by the factor R along every axis (search on; every cell keeps its per-axis^3 tracers).  The JSON line
+then carries "search" and "graded".
 
 --sort-only times the end-of-step sort alone, in up to three states, and writes profiles/mic3_129_refill.json:
   sort_off       RK4 + sort with injection off (the only state a tree without Simulation3.refill has),
@@ -138,6 +142,7 @@ def main():
     ap.add_argument("--sort-only", action="store_true"); ap.add_argument("--refill-reps", type=int, default=7)
     ap.add_argument("--parent", nargs="*", default=[])
     ap.add_argument("--step", action="store_true"); ap.add_argument("--resident", action="store_true"); ap.add_argument("--tree", default=None)
+    ap.add_argument("--search", action="store_true"); ap.add_argument("--graded", type=float, default=0.0)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join("profiles", "mic3_step_129.json" if a.step else ("mic3_129_refill.json" if a.sort_only else "mic3_129.json"))
@@ -153,7 +158,19 @@ def main():
     tr_x, tr_f = P3.falling_sphere_tracers(nx, L, rng, per_axis=a.per_axis)
     n = tr_x.shape[0]
     tr_f[:, 3] = 273 + 1350 * tr_x[:, 0] / L[0]; tr_f[:, 4] = 4.0; tr_f[:, 5] = 1250; tr_f[:, 7] = 3.5e-5; tr_f[:, 9] = 120e3
-    sim = P3.Simulation3(nx, L, tr_x, tr_f)
+    if a.graded > 0.0:
+        # the lattice mapped cell by cell onto the graded grid: the same tracers per cell as on the regular one
+        grid = [P3.graded_grid(a.n, L[d], a.graded) for d in range(3)]
+        for d in range(3):
+            u = tr_x[:, d] / (L[d] / (a.n - 1))
+            i = np.clip(np.floor(u).astype(np.int64), 0, a.n - 2)
+            tr_x[:, d] = grid[d][i] + (u - i) * (grid[d][i + 1] - grid[d][i])
+        tr_x = np.clip(tr_x, 1e-6 * L[0], (1 - 1e-6) * L[0])
+        sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(marker_search=True), grid=grid)
+    elif a.search:
+        sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(marker_search=True))
+    else:
+        sim = P3.Simulation3(nx, L, tr_x, tr_f)
     del tr_x, tr_f
     h = L[0] / (a.n - 1)
     dT = rng.standard_normal(nx)
@@ -178,6 +195,10 @@ def main():
             t["scatter"].append(ms); t["gather"].append(tg_); t["gather_subgrid"].append(ts_); t["rk4"].append(st["rk4"]); t["sort"].append(st["sort"])
     tpc = n / float((a.n - 1) ** 3)
     out = dict(config="mic3_%d" % a.n, nodes=a.n ** 3, tracers=n, tracers_per_cell=tpc, reps=a.reps, warmup=a.warmup, stages={})
+    if a.search or a.graded > 0.0:
+        out["search"] = True; out["graded"] = a.graded
+    if a.tree:
+        out["tree"] = a.tree
     for k, v in t.items():
         ms = float(np.median(v)); b = BYTES[k](tpc)
         out["stages"][k] = dict(ms=round(ms, 4), ms_min=round(float(np.min(v)), 4), ms_max=round(float(np.max(v)), 4),
