@@ -1,13 +1,15 @@
-"""A dense, stiff sphere sinking in a free-slip box: the 3-D marker-in-cell time step (pylamp3d.Simulation3).  Writes
+"""A dense, stiff sphere sinking in a box with free-slip or sticking walls: the 3-D marker-in-cell time step (pylamp3d.Simulation3).  Writes
 griddata.NNNNNN.npz / tracs.NNNNNN.npz in the style of the 2-D example, with a third axis (gridy, vely, tr_x (n, 3)).
 Cells that run below tracdens_min markers are refilled to tracdens inside the end-of-step sort (0 0 switches that off).
 
-    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R]
+    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R] [--noslip=z]
 
 --resident runs the device-resident step (Options3.resident): the grid fields stay on the GPU and are downloaded for the snapshots only.
 --refine=R (e.g. 3) makes the cells R times finer around the sphere's path than far from it (pylamp3d.refined_grid) and switches
 the markers' per-axis cell search on (Options3.marker_search), which a grid that is not regular needs; the markers start denser
 so that the fine cells are populated.
+--noslip=z makes the two z-walls (lid and base) no-slip, --noslip=zx the z- and x-walls, --noslip=zxy all six (Options3.bcstokes); the
+other walls stay free-slip.
 """
 import os
 import sys
@@ -20,6 +22,11 @@ from pylamp_amd import pylamp3d as P3                                           
 resident = "--resident" in sys.argv[1:]
 refine = [float(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--refine=")]
 refine = refine[0] if refine else 0.0
+noslip = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--noslip=")]
+noslip = noslip[0] if noslip else ""
+if noslip not in ("", "z", "zx", "zxy"):
+    sys.exit("--noslip takes z, zx or zxy")
+bcstokes = [P3.BC_TYPE_NOSLIP if "zxy"[w % 3] in noslip else P3.BC_TYPE_FREESLIP for w in range(6)]      # [z0, x0, y0, zL, xL, yL]
 argv = [a for a in sys.argv if not a.startswith("--")]
 n = int(argv[1]) if len(argv) > 1 else 65
 steps = int(argv[2]) if len(argv) > 2 else 20
@@ -35,7 +42,8 @@ if refine > 1.0:                                                                
     per_axis = int(np.ceil(2 * refine / 1.5))
 tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1), per_axis=per_axis)
 opt = P3.Options3(do_heatdiff=False, tdep_rho=False, tdep_eta=False,             # isothermal, constant properties
-                  tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident, marker_search=grid is not None)
+                  tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident, marker_search=grid is not None,
+                  bcstokes=bcstokes)
 sim = P3.Simulation3(nx, L, tr_x, tr_f, opt, grid=grid)
 sphere = None
 for it in range(1, steps + 1):

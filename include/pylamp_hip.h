@@ -339,8 +339,9 @@ int  pl_get_tracer_velocity(pl_ctx* ctx, int64_t n, double* out);
  * IP = DIM, DOF order iz*nx*ny*4 + ix*ny*4 + iy*4 + ieq (pylamp_stokes.py:24) -- and these entry points extend the 2-D
  * rows (pylamp_stokes.py:376-518, pylamp_diff.py:99-179) dimension by dimension: a y-invariant extrusion reproduces the
  * 2-D operator and solution on every y-slice.  Host arrays are C-order (nz, nx, ny) doubles; Stokes vectors are
- * (nz, nx, ny, 4) with components (vz, vx, vy, P).  All walls free-slip; heat walls FIXTEMP / FIXFLOW in the order
- * [z0, x0, y0, zL, xL, yL].  The shear viscosity is given at the NODES and averaged onto the edges. */
+ * (nz, nx, ny, 4) with components (vz, vx, vy, P).  Walls are numbered [z0, x0, y0, zL, xL, yL]: Stokes walls FREESLIP (the
+ * default) or NOSLIP per wall (pl3_stokes_set_walls), heat walls FIXTEMP / FIXFLOW.  The shear viscosity is given at the NODES
+ * and averaged onto the edges. */
 typedef struct pl3_ctx pl3_ctx;
 int  pl3_create(pl3_ctx** out, int device, int nz, int nx, int ny, const double* zc, const double* xc, const double* yc);
 void pl3_destroy(pl3_ctx* ctx);
@@ -362,6 +363,20 @@ int  pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const double* etan,
 /* slaved != 0 (default): the reference's wall rows extended to 3-D (outermost in-domain tangential velocities slaved to their
  * inner neighbours, pylamp_stokes.py:170-175 ...: first-order accurate at the walls); 0: natural mirror rows (second order) */
 int  pl3_stokes_set_wall_rows(pl3_ctx* ctx, int slaved);
+/* bc[6] = [z0, x0, y0, zL, xL, yL], each PL_BC_FREESLIP or PL_BC_NOSLIP; any other kind is an error that names the wall and the
+ * value.  The setting belongs to the context (all free-slip at creation), survives pl3_stokes_set_coeffs and is read by the solves,
+ * pl3_resident_step and pl3_advection_velocity.  The rows, with (D, E, F) a cyclic permutation of (z, x, y), v_D tangential to the
+ * walls of E and F, and per axis rd[i] = 1/(c[i+1] - c[i]), rD[i] = 1/(c[i+1] - c[i-1]):
+ *  - identity rows (wall-normal velocities, ghosts, anchor), pressure rows and the right-hand side do not depend on the kind;
+ *  - slaved rows (pl3_stokes_set_wall_rows(1), finest level): a v_D on the outermost in-domain layer couples to its inward neighbour
+ *    v_nb along the first boundary axis a, E before F, and the kind of THAT wall sets the coefficients: FREESLIP Kcont (v - v_nb);
+ *    NOSLIP the reference's extrapolation row (pylamp_stokes.py:165-166, 204-205), low side
+ *    Kcont [-(rD_a[1] + rd_a[0]) v + rD_a[1] v_nb], high side Kcont [(rD_a[n-2] + rd_a[n-2]) v - rD_a[n-2] v_nb]: v_D extrapolated
+ *    linearly to the wall is zero (uniform grid: v = v_nb / 3).  Row scale 1 / (Kcont x the coefficient of v);
+ *  - natural rows (pl3_stokes_set_wall_rows(0), every coarse multigrid level): on an edge of a NOSLIP wall the shear stress keeps both
+ *    halves, dv_D/dx_E one-sided against v_D = 0 on the wall -- low side v_D[0] / ((c_E[1] - c_E[0]) / 2), high side
+ *    -v_D[n-2] / ((c_E[n-1] - c_E[n-2]) / 2) -- and dv_E/dx_D as on a FREESLIP wall, which drops the first half. */
+int  pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]);
 int  pl3_stokes_get_scaling(pl3_ctx* ctx, double* kcont, double* kbond);
 int  pl3_stokes_apply(pl3_ctx* ctx, const double* x, double* y);
 int  pl3_stokes_rhs(pl3_ctx* ctx, double* rhs);
@@ -506,8 +521,10 @@ int  pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_ste
  * available ones. */
 int  pl3_get_field(pl3_ctx* ctx, const char* name, double* out);
 /* The step's advection-velocity kernel on host arrays: vz, vx, vy (nz, nx, ny) -> Vz, Vx, Vy on the padded (nz+1, nx+1, ny+1)
- * centre grid: every component averaged along its own axis, then the free-slip ghosts wall by wall in the order z0, x0, y0, zL, xL,
- * yL (normal component mirrored with a sign flip, tangential copied); that order decides the edge and corner values. */
+ * centre grid: every component averaged along its own axis, then the ghosts wall by wall in the order z0, x0, y0, zL, xL, yL: a
+ * FREESLIP wall mirrors the normal component with a sign flip and copies the tangential ones, the pass of a NOSLIP wall
+ * (pl3_stokes_set_walls) is skipped and its ghosts keep what they hold (pylamp2.py:491-545); the order decides the edge and corner
+ * values. */
 int  pl3_advection_velocity(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* Vz, double* Vx, double* Vy);
 /* Host <-> device copies issued by the pl3_* entry points of this context since the last reset: out = { copies of at least one node
  * field (8 nz nx ny bytes), their bytes, smaller copies, their bytes }; reset != 0 clears the counters after reading. */

@@ -80,6 +80,7 @@ SIGNATURES = {
     "pl3_last_error": (C.c_char_p, [C.c_void_p]),
     "pl3_stokes_set_coeffs": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "pl3_stokes_set_wall_rows": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl3_stokes_set_walls": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pl3_stokes_get_scaling": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_rhs": (C.c_int, [C.c_void_p, c_double_p]),

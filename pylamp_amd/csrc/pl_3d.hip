@@ -45,6 +45,7 @@ struct Op3 {
     const double* es; const double* en; const double* rho;
     double Kc, Kb, iKc;
     int slave;                       // 1: the reference's slaved outermost in-domain tangential rows (finest level); 0: natural rows
+    int noslip;                      // bit w of [z0, x0, y0, zL, xL, yL]: that wall is no-slip (0: every wall free-slip)
     double grav[3];
     int anchor[3];
 };
@@ -63,6 +64,62 @@ template <int D> __device__ inline int cls3(const Op3& op, const int* idx, long 
         if (moff != 0) return C3_SLAVE;
     }
     return C3_INT;
+}
+
+// ---- no-slip walls (include/pylamp_hip.h).  Every row they change lies on the layers 0 and n - 2 of a tangential axis:
+// the per-node kernels and k3_rim evaluate them, the marching kernels never do.  The mask is a kernel argument and the table entries a
+// wall reads have fixed indices (0, 1, n - 2): scalar.  In the K3_PROLOGUE kernels the layer tests along z and x are wave-uniform as
+// well; in k3_rim a thread's node comes from its own index, so there the layer tests are per lane (the rim is ~4 % of the nodes).
+template <int A> __device__ inline bool nos3(const Op3& op, int hi) { return (op.noslip >> (A + 3 * hi)) & 1; }
+// a row slaved along axis A at its low / high wall is Kc (sd v + sn v_nb): free-slip 1, -1; no-slip the reference's extrapolation row
+// (pylamp_stokes.py:165-166,204-205): v extrapolated linearly to the wall is zero
+template <int A> __device__ inline void slave_coef3(const Op3& op, int hi, double& sd, double& sn) {
+    const int m = hi ? op.g.gn[A] - 2 : 1;
+    const double rD = TB(op.g.rD[A], m), rd = TB(op.g.rd[A], hi ? m : 0);
+    sd = hi ? rD + rd : -(rD + rd); sn = hi ? -rD : rD;
+}
+// v / v_nb of that row
+template <int A> __device__ inline double gam3(const Op3& op, int hi) {
+    if (!nos3<A>(op, hi)) return 1.0;
+    double sd, sn;
+    slave_coef3<A>(op, hi, sd, sn);
+    return -sn / sd;
+}
+// v_slave / v_master along the chain of a C3_SLAVE row (E, then F): the closure of the smoother, the transfers and k3_close
+template <int D> __device__ inline double fac3(const Op3& op, const int* idx) {
+    constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
+    if (!op.noslip) return 1.0;
+    double f = 1.0;
+    if (idx[E] == 0) f = gam3<E>(op, 0); else if (idx[E] == op.g.gn[E] - 2) f = gam3<E>(op, 1);
+    if (idx[F] == 0) f *= gam3<F>(op, 0); else if (idx[F] == op.g.gn[F] - 2) f *= gam3<F>(op, 1);
+    return f;
+}
+// the slaved row itself at the low / high wall of A (unb: the inward neighbour); scaled: divided by Kc sd
+template <int A> __device__ inline double slave_row3(const Op3& op, int hi, double u0, double unb, bool scaled) {
+    if (!nos3<A>(op, hi)) { const double y = u0 - unb; return scaled ? y : op.Kc * y; }
+    double sd, sn;
+    slave_coef3<A>(op, hi, sd, sn);
+    return scaled ? u0 + (sn / sd) * unb : op.Kc * (sd * u0 + sn * unb);
+}
+// 1 / (Kc sd) of component D's C3_SLAVE row: its row scale
+template <int D> __device__ inline double slave_scale3(const Op3& op, const int* idx) {
+    constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
+    if (!op.noslip) return op.iKc;
+    double sd = 1.0, sn;
+    if (idx[E] == 0) { if (nos3<E>(op, 0)) slave_coef3<E>(op, 0, sd, sn); }
+    else if (idx[E] == op.g.gn[E] - 2) { if (nos3<E>(op, 1)) slave_coef3<E>(op, 1, sd, sn); }
+    else if (idx[F] == 0) { if (nos3<F>(op, 0)) slave_coef3<F>(op, 0, sd, sn); }
+    else if (nos3<F>(op, 1)) slave_coef3<F>(op, 1, sd, sn);
+    return op.iKc / sd;
+}
+// natural rows: the coefficient of -v_D that a no-slip wall of axis A adds to the row at layer ia (0 elsewhere and on free-slip walls):
+// the dv_D/dx_A half of the shear stress on the wall edge, one-sided against v_D = 0 on the wall, eta (2 rd v) rd; em / ep: the
+// viscosities of the row's lower / upper edge along A
+template <int A> __device__ inline double wall_coef3(const Op3& op, int ia, double em, double ep) {
+    if (!op.noslip) return 0.0;
+    if (ia == 0 && nos3<A>(op, 0)) { const double rd = TB(op.g.rd[A], 0); return 2.0 * em * rd * rd; }
+    if (ia == op.g.gn[A] - 2 && nos3<A>(op, 1)) { const double rd = TB(op.g.rd[A], ia); return 2.0 * ep * rd * rd; }
+    return 0.0;
 }
 
 // (A_vv v)_D without the pressure term and the sum `dg` of the four..six own-component coefficients at element c.
@@ -87,6 +144,8 @@ template <int D> __device__ inline void row3(const Op3& op, const double* const*
         a += cE * (u[c + se] - u0) - cW * (u0 - u[c - se]) + (2.0 * ep * rD_d * rd_e) * (w[c + se] - w[c + se - sd]) -
              (2.0 * em * rD_d * rd_e) * (w[c] - w[c - sd]);
         d += cE + cW;
+        const double cw = wall_coef3<E>(op, idx[E], em, ep);
+        if (cw != 0.0) { a -= cw * u0; d += cw; }
     }
     {   // tangential axis F: averaged along E
         const double rd_f = TB(g.rd[F], idx[F]), rD_f = TB(g.rD[F], idx[F]), rD_fp = TB(g.rD[F], idx[F] + 1);
@@ -96,6 +155,8 @@ template <int D> __device__ inline void row3(const Op3& op, const double* const*
         a += cE * (u[c + sf] - u0) - cW * (u0 - u[c - sf]) + (2.0 * ep * rD_d * rd_f) * (w[c + sf] - w[c + sf - sd]) -
              (2.0 * em * rD_d * rd_f) * (w[c] - w[c - sd]);
         d += cE + cW;
+        const double cw = wall_coef3<F>(op, idx[F], em, ep);
+        if (cw != 0.0) { a -= cw * u0; d += cw; }
     }
     Av = a; dg = d;
 }
@@ -110,6 +171,10 @@ template <int D> __device__ inline double diag3(const Op3& op, long long c, cons
     const double rd_e = TB(g.rd[E], idx[E]), rd_f = TB(g.rd[F], idx[F]);
     d += (es[c + se] + es[c + se + sf]) * TB(g.rD[E], idx[E] + 1) * rd_e + (es[c] + es[c + sf]) * TB(g.rD[E], idx[E]) * rd_e;
     d += (es[c + sf] + es[c + sf + se]) * TB(g.rD[F], idx[F] + 1) * rd_f + (es[c] + es[c + se]) * TB(g.rD[F], idx[F]) * rd_f;
+    if (op.noslip) {
+        d += wall_coef3<E>(op, idx[E], 0.5 * (es[c] + es[c + sf]), 0.5 * (es[c + se] + es[c + se + sf]));
+        d += wall_coef3<F>(op, idx[F], 0.5 * (es[c] + es[c + se]), 0.5 * (es[c + sf] + es[c + sf + se]));
+    }
     return d;
 }
 
@@ -157,11 +222,10 @@ template <int D> __device__ inline double apply_vel3(const Op3& op, const double
         // the matrix row couples to the neighbour along the FIRST boundary axis (E before F), pylamp_stokes.py:170-175
         constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
         const int* n = op.g.gn;
-        long long nb;
-        if (idx[E] == 0) nb = op.g.s[E]; else if (idx[E] == n[E] - 2) nb = -op.g.s[E];
-        else nb = (idx[F] == 0) ? op.g.s[F] : -op.g.s[F];
-        const double y = u0 - v[D][c + nb];
-        return scaled ? y : op.Kc * y;
+        if (idx[E] == 0) return slave_row3<E>(op, 0, u0, v[D][c + op.g.s[E]], scaled);
+        if (idx[E] == n[E] - 2) return slave_row3<E>(op, 1, u0, v[D][c - op.g.s[E]], scaled);
+        if (idx[F] == 0) return slave_row3<F>(op, 0, u0, v[D][c + op.g.s[F]], scaled);
+        return slave_row3<F>(op, 1, u0, v[D][c - op.g.s[F]], scaled);
     }
     double Av, dg;
     row3<D>(op, v, c, idx, Av, dg);
@@ -214,12 +278,17 @@ __global__ __launch_bounds__(256) void k3_rhs(Op3 op, W4 b, int scaled) {
     b.p[3][c] = 0.0;
 }
 // b *= D_r (a user-supplied right-hand side)
+template <int D> __device__ inline double scale_vel3(const Op3& op, long long c, const int* idx) {
+    long long moff;
+    const int cl = cls3<D>(op, idx, moff);
+    return cl == C3_INT ? 1.0 / diag3<D>(op, c, idx) : (cl == C3_SLAVE ? slave_scale3<D>(op, idx) : op.iKc);
+}
 __global__ __launch_bounds__(256) void k3_scale_rows(Op3 op, W4 b) {
     K3_PROLOGUE(op.g)
     long long moff;
-    b.p[0][c] *= (cls3<0>(op, idx, moff) == C3_INT) ? 1.0 / diag3<0>(op, c, idx) : op.iKc;
-    b.p[1][c] *= (cls3<1>(op, idx, moff) == C3_INT) ? 1.0 / diag3<1>(op, c, idx) : op.iKc;
-    b.p[2][c] *= (cls3<2>(op, idx, moff) == C3_INT) ? 1.0 / diag3<2>(op, c, idx) : op.iKc;
+    b.p[0][c] *= scale_vel3<0>(op, c, idx);
+    b.p[1][c] *= scale_vel3<1>(op, c, idx);
+    b.p[2][c] *= scale_vel3<2>(op, c, idx);
     const int cl = cls3_p(op, idx, moff);
     const G3& g = op.g;
     b.p[3][c] *= cl == 0 ? op.iKc : (cl == 2 ? 1.0 / op.Kb : op.iKc / (TB(g.rd[0], i) + TB(g.rd[1], j) + TB(g.rd[2], k)));
@@ -281,12 +350,15 @@ template <int D> __device__ inline double cheb3(const Op3& op, const double* con
         if (idx[E] == 0) im[E] = 1; else if (idx[E] == op.g.gn[E] - 2) im[E] = op.g.gn[E] - 3;
         if (idx[F] == 0) im[F] = 1; else if (idx[F] == op.g.gn[F] - 2) im[F] = op.g.gn[F] - 3;
     }
-    if (zero) return (-c2 * f[cm]) * pl_rcp(diag3<D>(op, cm, im));
+    // (a slave of a no-slip wall is its master's update times v_slave / v_master)
+    const bool chain = cl == C3_SLAVE && op.noslip != 0;
+    if (zero) { const double r = (-c2 * f[cm]) * pl_rcp(diag3<D>(op, cm, im)); return chain ? fac3<D>(op, idx) * r : r; }
     double Av, dg;
     row3<D>(op, v, cm, im, Av, dg);
     const double v0 = v[D][cm];
     const double mom = (c1 != 0.0) ? c1 * (v0 - (vprev ? vprev[cm] : 0.0)) : 0.0;
-    return v0 + mom + (c2 * (Av - f[cm])) * pl_rcp(dg);                                  // D = -dg
+    const double r = v0 + mom + (c2 * (Av - f[cm])) * pl_rcp(dg);                        // D = -dg
+    return chain ? fac3<D>(op, idx) * r : r;
 }
 // rim_only != 0: only the nodes with a wall or slaved row (all three rows of such a node); the interior rows are k3_sweep_m's
 __device__ inline bool k3_all_interior(const Op3& op, const int* idx) {
@@ -310,16 +382,19 @@ __global__ __launch_bounds__(256) void k3_dinv(Op3 op, W3 dinv) {
     dinv.p[1][c] = cls3<1>(op, idx, moff) == C3_INT ? pl_rcp(diag3<1>(op, c, idx)) : 0.0;
     dinv.p[2][c] = cls3<2>(op, idx, moff) == C3_INT ? pl_rcp(diag3<2>(op, c, idx)) : 0.0;
 }
+template <int D> __device__ inline double cheb0_3(const Op3& op, int cl, const int* idx, double r) {
+    return (cl == C3_SLAVE && op.noslip != 0) ? fac3<D>(op, idx) * r : r;
+}
 // v1 = -c2 f / diag at the row's master (a slave evaluates its master's update: the same numbers as k3_cheb with zero != 0)
 __global__ __launch_bounds__(256) void k3_cheb0(Op3 op, V3 f, V3 dinv, W3 vnext, double c2) {
     K3_PROLOGUE(op.g)
     long long moff;
     int cl = cls3<0>(op, idx, moff);
-    vnext.p[0][c] = cl == C3_ZERO ? 0.0 : (-c2 * f.p[0][c + moff]) * dinv.p[0][c + moff];
+    vnext.p[0][c] = cl == C3_ZERO ? 0.0 : cheb0_3<0>(op, cl, idx, (-c2 * f.p[0][c + moff]) * dinv.p[0][c + moff]);
     cl = cls3<1>(op, idx, moff);
-    vnext.p[1][c] = cl == C3_ZERO ? 0.0 : (-c2 * f.p[1][c + moff]) * dinv.p[1][c + moff];
+    vnext.p[1][c] = cl == C3_ZERO ? 0.0 : cheb0_3<1>(op, cl, idx, (-c2 * f.p[1][c + moff]) * dinv.p[1][c + moff]);
     cl = cls3<2>(op, idx, moff);
-    vnext.p[2][c] = cl == C3_ZERO ? 0.0 : (-c2 * f.p[2][c + moff]) * dinv.p[2][c + moff];
+    vnext.p[2][c] = cl == C3_ZERO ? 0.0 : cheb0_3<2>(op, cl, idx, (-c2 * f.p[2][c + moff]) * dinv.p[2][c + moff]);
 }
 // mode 0: r = f - A v on interior rows (0 elsewhere); mode 1: y = D^-1 A v with closure (power iteration)
 template <int D> __device__ inline double resid3(const Op3& op, const double* const* v, const double* __restrict__ f, long long c,
@@ -336,7 +411,9 @@ template <int D> __device__ inline double resid3(const Op3& op, const double* co
     }
     double Av, dg;
     row3<D>(op, v, cm, im, Av, dg);
-    return mode == 0 ? f[c] - Av : Av * pl_rcp(dg);
+    if (mode == 0) return f[c] - Av;
+    const double r = Av * pl_rcp(dg);
+    return (cl == C3_SLAVE && op.noslip != 0) ? fac3<D>(op, idx) * r : r;
 }
 __global__ __launch_bounds__(256) void k3_resid(Op3 op, V3 vv, V3 f, W3 r, int mode, int rim_only) {
     K3_PROLOGUE(op.g)
@@ -787,7 +864,8 @@ template <int D> __device__ inline double prolong3(const Op3& opf, const G3& gc,
         if (idx[E] == 0) im[E] = 1; else if (idx[E] == opf.g.gn[E] - 2) im[E] = opf.g.gn[E] - 3;
         if (idx[F] == 0) im[F] = 1; else if (idx[F] == opf.g.gn[F] - 2) im[F] = opf.g.gn[F] - 3;
     }
-    return vin[c + moff] + prolong3_at<D>(gc, e, im);
+    const double r = vin[c + moff] + prolong3_at<D>(gc, e, im);
+    return (cl == C3_SLAVE && opf.noslip != 0) ? fac3<D>(opf, idx) * r : r;
 }
 __global__ __launch_bounds__(256) void k3_prolong_add(Op3 opf, G3 gc, V3 ec, V3 vin, W3 vout) {
     K3_PROLOGUE(opf.g)
@@ -813,12 +891,12 @@ __global__ __launch_bounds__(256) void k3_coarsen(G3 gf, const double* __restric
     for (int a = 0; a < 2; a++) for (int q = 0; q < 2; q++) for (int p = 0; p < 2; p++) s += enf[b + a * gf.s[0] + q * gf.s[1] + p * gf.s[2]];
     enc[c] = 0.125 * s;
 }
-// make x satisfy the constraint rows of A x = b exactly (bs = scaled b): walls / ghosts x = bs, slaves x = x_master + bs
+// make x satisfy the constraint rows of A x = b exactly (bs = scaled b): walls / ghosts x = bs, slaves x = (v_slave / v_master) x_master + bs
 template <int D> __device__ inline void close3(const Op3& op, double* __restrict__ x, const double* __restrict__ bs, long long c, const int* idx) {
     long long moff;
     const int cl = cls3<D>(op, idx, moff);
     if (cl == C3_ZERO) x[c] = bs[c];
-    else if (cl == C3_SLAVE) x[c] = x[c + moff] + bs[c];
+    else if (cl == C3_SLAVE) x[c] = (op.noslip ? fac3<D>(op, idx) * x[c + moff] : x[c + moff]) + bs[c];
 }
 __global__ __launch_bounds__(256) void k3_close(Op3 op, W3 x, V3 bs) {
     K3_PROLOGUE(op.g)
@@ -1040,6 +1118,7 @@ struct pl3_ctx {
     std::string err;
     G3Host geom;
     double *es = nullptr, *en = nullptr, *rho = nullptr; Op3 op{}; bool op_ready = false;
+    int noslip = 0;                 // pl3_stokes_set_walls: bit w of [z0, x0, y0, zL, xL, yL] set = no-slip; kept across pl3_stokes_set_coeffs
     std::vector<Lev3*> levels;
     double* vec[14][4] = {{nullptr}};           // BiCGStab work vectors (4 arrays each)
     double* part = nullptr; double* hpart = nullptr;
@@ -1300,7 +1379,7 @@ static void stokes_op3(pl3_ctx* ctx, double mineta, const double grav[3]) {
     Op3& op = ctx->op;
     op.g = g; op.es = ctx->es; op.en = ctx->en; op.rho = ctx->rho;
     op.Kc = 3.0 * mineta / sum; op.Kb = 9.0 * mineta / (sum * sum); op.iKc = 1.0 / op.Kc;
-    op.slave = 1;
+    op.slave = 1; op.noslip = ctx->noslip;
     for (int a = 0; a < 3; a++) op.grav[a] = grav ? grav[a] : (a == 0 ? 9.81 : 0.0);
     op.anchor[0] = 3; op.anchor[1] = 2; op.anchor[2] = 2;
     ctx->op_ready = true;
@@ -1337,6 +1416,23 @@ int pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* e
 extern "C" int pl3_stokes_set_wall_rows(pl3_ctx* ctx, int slaved) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     ctx->op.slave = slaved ? 1 : 0;
+    return 0;
+}
+// bc = [z0, x0, y0, zL, xL, yL], each PL_BC_FREESLIP or PL_BC_NOSLIP.  Kept on the context (which starts all free-slip) across
+// pl3_stokes_set_coeffs; read by the solves, pl3_resident_step and pl3_advection_velocity.
+extern "C" int pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_walls: NULL context");
+    if (!bc) return p3_fail(ctx, "pl3_stokes_set_walls: NULL argument");
+    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
+    int m = 0;
+    for (int w = 0; w < 6; w++) {
+        if (bc[w] == PL_BC_NOSLIP) m |= 1 << w;
+        else if (bc[w] != PL_BC_FREESLIP)
+            return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + names[w] + " has kind " + std::to_string(bc[w]) +
+                                    ": a 3-D Stokes wall is FREESLIP (1) or NOSLIP (0)");
+    }
+    ctx->noslip = m;
+    if (ctx->op_ready) ctx->op.noslip = m;
     return 0;
 }
 extern "C" int pl3_stokes_get_scaling(pl3_ctx* ctx, double* kc, double* kb) {
@@ -2076,7 +2172,7 @@ int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     const G3& g = ctx->geom.d;
     v->s0 = g.s[0]; v->s1 = g.s[1]; v->pad = P3_PAD; v->stream = ctx->stream; v->slot = &ctx->step3;
     for (int q = 0; q < 4; q++) { v->X[q] = ctx->vec[11][q]; v->scratch[q] = ctx->vec[0][q]; }
-    v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T;
+    v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T; v->noslip = ctx->noslip;
     return 0;
 }
 // counts and bytes of the host <-> device copies of this context's pl3_* calls since the last reset: out = { copies of at least one

@@ -10,6 +10,7 @@ struct Pl3DevView {
     double* T;                              // heat solution of the last solve
     double* scratch[4];                     // work vectors that are free outside a solve
     bool have_x, have_T;
+    int noslip;                             // Stokes walls (pl3_stokes_set_walls): bit w of [z0, x0, y0, zL, xL, yL] set = no-slip
     void** slot;                            // opaque state owned by pl_step3.hip, released by pl3_step_free
 };
 // pl_3d.hip

@@ -98,9 +98,10 @@ __global__ __launch_bounds__(256) void k_s3_velmax(S3Dims d, S3Vel x, S3Ops ops,
 // y0, zL, xL, yL, each a copy of the neighbouring plane AS IT IS AT THAT MOMENT (normal component negated): a point of an edge or a
 // corner takes the value of the LAST wall that holds it, whose source may itself have been written by an earlier wall.  A thread
 // walks that chain backwards from its own point until it stands on an inner point; a source that no earlier wall had written yet
-// would still hold the initial zero (it cannot occur with this order, the case is kept for exactness).
+// would still hold the initial zero (it cannot occur with this order, the case is kept for exactness).  The pass of a no-slip wall
+// (bit w of `noslip`) is skipped, as in the reference: its ghost plane keeps the initial zero but where a later pass writes its edges.
 struct S3Adv { double* V[3]; };
-__global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o) {
+__global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, int noslip) {
     const int pn[3] = {d.n[0] + 1, d.n[1] + 1, d.n[2] + 1};
     const long long GN = (long long)pn[0] * pn[1] * pn[2];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o) {
         double sign = 1.0;
         for (int w = 5; w >= 0; w--) {                       // walls 0..5 = z0, x0, y0, zL, xL, yL
             const int a = w % 3, ghost = w < 3 ? 0 : pn[a] - 1;
-            if (p[a] != ghost) continue;
+            if (p[a] != ghost || ((noslip >> w) & 1)) continue;        // (the pass of a no-slip wall is skipped)
             p[a] = w < 3 ? 1 : pn[a] - 2;
             if (a == q) sign = -sign;
         }
@@ -199,7 +200,7 @@ static int s3_finish(pl3_ctx* ctx, S3Open& o, int nb, const S3Ops& ops, const do
 static void s3_advvel(S3Open& o, double* const X[3], double* adv) {
     const size_t GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
     S3Vel x{{X[0], X[1], X[2]}}; S3Adv a{{adv, adv + GNp, adv + 2 * GNp}};
-    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a);
+    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip);
 }
 
 extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* rep) {

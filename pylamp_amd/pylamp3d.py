@@ -16,7 +16,9 @@ from . import _lib
 
 DIM3 = 3
 IZ, IX, IY, IP3 = 0, 1, 2, 3
+BC_TYPE_NOSLIP = 0
 BC_TYPE_FREESLIP = 1
+WALL_NAMES = ("z0", "x0", "y0", "zL", "xL", "yL")
 BC_TYPE_FIXTEMP = 0
 BC_TYPE_FIXFLOW = 1
 DEFAULT_RTOL = 1e-7        # residual bound; the solve also has to meet the velocity-error estimate 3e-8 (as pylamp_stokes.solve)
@@ -38,6 +40,20 @@ def x2vp(x, nx):
 
 def x2t(x, nx):
     return np.asarray(x).reshape(int(nx[0]), int(nx[1]), int(nx[2]))
+
+
+def stokes_walls(bc, who="3-D Stokes"):
+    """bc = [z0, x0, y0, zL, xL, yL] (None: all free-slip) as six ints; a kind other than FREESLIP / NOSLIP is rejected with
+    the wall's name and the value (CYCLIC and FLOWTHRU walls do not exist in 3-D)."""
+    if bc is None:
+        return [BC_TYPE_FREESLIP] * 6
+    bc = list(bc)
+    if len(bc) != 6:
+        raise Exception("%s: the wall kinds need six entries [z0, x0, y0, zL, xL, yL] (got %d)" % (who, len(bc)))
+    for w, b in enumerate(bc):
+        if b not in (BC_TYPE_FREESLIP, BC_TYPE_NOSLIP) or int(b) != b:
+            raise Exception("%s: wall %s has kind %r: a wall is BC_TYPE_FREESLIP (1) or BC_TYPE_NOSLIP (0)" % (who, WALL_NAMES[w], b))
+    return [int(b) for b in bc]
 
 
 class Context3:
@@ -96,6 +112,10 @@ class Context3:
         self.check(self.lib.pl3_mic_get_search(self.handle(), C.byref(on)))
         return bool(on.value)
 
+    def set_stokes_walls(self, bc):
+        """The kinds of the six Stokes walls [z0, x0, y0, zL, xL, yL] of this context (None: all free-slip); kept until set again."""
+        self.check(self.lib.pl3_stokes_set_walls(self.handle(), (C.c_int * 6)(*stokes_walls(bc))))
+
     def close(self):
         if self.h is not None:
             self._fin()
@@ -151,13 +171,18 @@ class StokesOperator3:
 
 def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True):
     """3-D counterpart of pylamp_stokes.makeStokesMatrix: f_etas at the NODES (averaged onto the edges by the kernels),
-    f_etan at the cell centres, f_rho at the nodes; all walls free-slip (bc, if given, must say so).
+    f_etan at the cell centres, f_rho at the nodes; bc = [z0, x0, y0, zL, xL, yL], each BC_TYPE_FREESLIP or BC_TYPE_NOSLIP.
+    bc=None leaves the walls of the context as they are: all free-slip on a new context, or what Context3.set_stokes_walls /
+    an earlier call with bc= has set on the ctx= that is passed in.
     strict_reference=True keeps the reference's wall rows (outermost in-domain tangential velocities slaved to their
-    inner neighbours: free slip imposed half a cell inside the wall, first-order accurate); False uses natural mirror
-    rows (second-order accurate)."""
-    if bc is not None and any(int(b) != BC_TYPE_FREESLIP for b in bc):
-        raise Exception("3-D Stokes: all walls are free-slip")
+    inner neighbours -- free slip imposed half a cell inside the wall, first-order accurate -- or, on a no-slip wall, the
+    reference's extrapolation row); False uses natural rows (mirror rows on a free-slip wall, the one-sided shear stress
+    against v = 0 on a no-slip wall; second-order accurate).  The rows are written out in include/pylamp_hip.h at
+    pl3_stokes_set_walls."""
+    walls = None if bc is None else stokes_walls(bc)
     ctx = ctx or Context3(nx, grid, device)
+    if walls is not None:
+        ctx.set_stokes_walls(walls)
     shp = ctx.nx
     es, en, rho = _f3(f_etas, shp), _f3(f_etan, shp), _f3(f_rho, shp)
     g = None if grav is None else (C.c_double * 3)(*[float(v) for v in grav])
@@ -465,10 +490,13 @@ def refined_grid(n, L, centre=0.5, ratio=3.0, width=0.2):
     return c
 
 
-def advection_velocity(newvel, gridmp, nx):
+def advection_velocity(newvel, gridmp, nx, bc=None):
     """Cell-centred velocities on the padded (nz+1, nx+1, ny+1) grid (pylamp2.py:491-545 extended by one axis): every
-    component is averaged along its own axis; free-slip ghosts -- normal component mirrored with a sign flip, tangential
-    copied -- wall by wall in the order z0, x0, y0, zL, xL, yL.  Returns ([gz, gx, gy], [Vz, Vx, Vy])."""
+    component is averaged along its own axis; ghosts wall by wall in the order z0, x0, y0, zL, xL, yL -- a free-slip wall
+    mirrors the normal component with a sign flip and copies the tangential ones, the pass of a no-slip wall
+    (bc[w] == BC_TYPE_NOSLIP; bc None: all free-slip) is skipped as in the reference, so its ghosts keep what they hold.
+    Returns ([gz, gx, gy], [Vz, Vx, Vy])."""
+    walls = stokes_walls(bc, "advection_velocity")
     shp = tuple(int(v) + 1 for v in nx)
     vz, vx, vy = newvel
     V = [np.zeros(shp) for _ in range(3)]
@@ -478,6 +506,8 @@ def advection_velocity(newvel, gridmp, nx):
     g = [np.insert(np.asarray(m, dtype=np.float64), 0, m[0] - (m[1] - m[0])) for m in gridmp]
     for ghost, inner in ((0, 1), (-1, -2)):
         for axis in range(3):
+            if walls[axis + (0 if ghost == 0 else 3)] == BC_TYPE_NOSLIP:
+                continue
             for comp in range(3):
                 dst = [slice(None)] * 3; src = [slice(None)] * 3
                 dst[axis] = ghost; src[axis] = inner
@@ -526,7 +556,7 @@ class Simulation3:
     + refill of depleted cells inside the end-of-step sort (Options3.tracdens / tracdens_min / inject_seed / inject_unique_ids;
     refill() does it without a step).  step() reports ninjected, nrefilled (cells) and nempty (cells that held no tracer: their new
     tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank,
-    all walls free-slip; a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
+    Stokes walls free-slip or no-slip per wall (Options3.bcstokes = [z0, x0, y0, zL, xL, yL]); a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
     axis strictly increasing from 0 to L[d]): the marker kernels then find cells by search in the coordinates (the rule is in
     include/pylamp_hip.h at pl3_mic_set_search), while the time-step rules and the subgrid time scale keep the mean spacing.  Options3.resident = True runs the same sequence inside the library with every grid field
     kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Not built: the fence-off deletion path, surface stabilisation, several ranks -- each is rejected with an error that names it."""
@@ -562,9 +592,9 @@ class Simulation3:
             raise Exception("Simulation3: the fence-off deletion path (tracs_fence_enabled = False) is not supported in 3-D")
         if o.surface_stabilization:
             raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
-        if any(int(b) != BC_TYPE_FREESLIP for b in o.bcstokes):
-            raise Exception("Simulation3: all Stokes walls are free-slip")
+        self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
         self.ctx = Context3(self.nx, self.grid, device)
+        self.ctx.set_stokes_walls(self.bcstokes)        # the resident step and the device advection velocity read them from the context
         if o.marker_search:
             self.ctx.set_marker_search(True)
         self.it = 0
@@ -769,7 +799,7 @@ class Simulation3:
             diffusivity = f["kz"] / (f["rho"] * f["cp"])
             tstep_temp = o.tstep_modifier * np.min(dx) ** 2 / np.max(2 * diffusivity)
             tstep_temp = max(min(tstep_temp, o.tstep_dif_max), o.tstep_dif_min)
-        A, _ = makeStokesMatrix(self.nx, self.grid, f["etas"], f["etan"], f["rho"], grav=o.grav, ctx=self.ctx)
+        A, _ = makeStokesMatrix(self.nx, self.grid, f["etas"], f["etan"], f["rho"], bc=self.bcstokes, grav=o.grav, ctx=self.ctx)
         x = solve(A, rtol=o.stokes_rtol, maxit=o.stokes_maxit)
         newvel, pres = x2vp(x, self.nx)
         tstep_stokes = o.tstep_modifier * np.min(dx) / max(np.max(v) for v in newvel)
@@ -792,7 +822,7 @@ class Simulation3:
                 self.temp_to_tracers(newtemp - f["T"], False, tstep)
             self._newtemp = newtemp
             f["temp"] = newtemp
-        grids, vels = advection_velocity(newvel, self.gridmp, self.nx)
+        grids, vels = advection_velocity(newvel, self.gridmp, self.nx, self.bcstokes)
         rep.update(self.advect(grids, vels, tstep, self.it))
         self.totaltime += tstep
         rep["time"] = self.totaltime; rep["ntrac"] = self.count()
