@@ -196,6 +196,15 @@ int  pl_stokes_precond_apply(pl_ctx* ctx, const double* r, double* z);
  * (4 or 16; 0: the default of the grid size).  sums holds 8 doubles. */
 int  pl_stokes_apply_reduce(pl_ctx* ctx, int mode, int rows, const double* x, const double* aux1, const double* aux2,
                             double* out, double* out2, double* sums);
+/* One launch of the Stokes stencil exactly as pl_stokes_solve issues it, on host vectors in the reference's DOF order.
+ * scaled: 0 the operator of pl_stokes_apply, 1 the row-scaled one the solver iterates on.
+ * mode 0..3 (0: out = op(x) alone; 1..3 as above); rows: 0 | 2 | 4 | 8 | 16 for mode 0, 0 | 4 | 16 otherwise.
+ * add (may be NULL): out = op(x) + coef * add, added after the row scaling as in the solver (the lazy deflation correction).
+ * aux1 / aux2 / out2 / sums (8 doubles) as above; for mode 0 they may be NULL.  One rank only. */
+int  pl_stokes_apply_probe(pl_ctx* ctx, int scaled, int mode, int rows, const double* x, const double* aux1,
+                           const double* aux2, const double* add, double coef, double* out, double* out2, double* sums);
+/* out = D_r v by the solver's own kernel: the scaling the right-hand side gets before the Krylov iteration.  One rank only. */
+int  pl_stokes_scale_rows(pl_ctx* ctx, const double* v, double* out);
 int  pl_stokes_mg_info(pl_ctx* ctx, int* nlevels, double* lmax, int max_levels);
 /* Average duration (HIP events) of one Chebyshev smoothing sweep on the finest multigrid level -- the kernel
  * with the largest share of a time step (80 B/node algorithmic).  Call after at least one solve. */

@@ -153,6 +153,8 @@ SIGNATURES = {
     "pl_stream_triad_bench": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, c_double_p]),
     "pl_stokes_precond_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl_stokes_apply_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 6),
+    "pl_stokes_apply_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [c_double_p] * 4 + [C.c_double] + [c_double_p] * 3),
+    "pl_stokes_scale_rows": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl_stokes_mg_info": (C.c_int, [C.c_void_p, c_int_p, c_double_p, C.c_int]),
     "pl_stokes_mg_precision": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "pl_stokes_set_mg_precision": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),

@@ -4230,12 +4230,66 @@ extern "C" int pl_stokes_solve(pl_ctx* ctx, const double* rhs, double* x, int us
     return 0;
 }
 
-// One launch of the operator with an epilogue, as the solver uses it, on host vectors in the reference's DOF order (component tests).
-// The operator is the UNSCALED one of pl_stokes_apply.  mode 1: out = A x, sums[0] = aux1 . out.  mode 2: out = A x,
-// sums[0..7] = out.aux1, out.out, aux2.aux1, aux2.out, aux1.aux1 and out.aux1, out.out, aux1.aux1 over the continuity rows.
-// mode 3: out = aux1 - A x, out2 (may be NULL) = A x, sums[0..4] = |out|^2, its continuity part, |aux1|^2, the sum of (x + aux2)^2
-// over the velocities (aux2 may be NULL) and the deflation's y . out.  rows: row-block height of the launch (4 or 16; 0: the
-// default of the grid size).  sums: 8 doubles.
+// One launch of the Stokes stencil exactly as the solver issues it, on host vectors in the reference's DOF order (component tests).
+// scaled: 0 the operator of pl_stokes_apply, 1 the row-scaled one (sop_scaled of pl_stokes_solve_device).  mode 0: out = op(x).
+// mode 1: out = op(x), sums[0] = aux1 . out.  mode 2: out = op(x), sums[0..7] = out.aux1, out.out, aux2.aux1, aux2.out, aux1.aux1
+// and out.aux1, out.out, aux1.aux1 over the continuity rows.  mode 3: out = aux1 - op(x), out2 (may be NULL) = op(x), sums[0..4] =
+// |out|^2, its continuity part, |aux1|^2, the sum of (x + aux2)^2 over the velocities (aux2 may be NULL) and the deflation's
+// y . out.  add != NULL: op(x) + coef * add everywhere above (the lazy deflation correction; coef reaches the kernel through device
+// memory, as the solver's SC_CY / SC_CZ do).  rows: row-block height of the launch (0: the default of the grid size).  sums: 8 doubles.
+static int stokes_apply_probe(pl_ctx* ctx, int scaled, int mode, int rows, const double* x, const double* aux1,
+                              const double* aux2, const double* add, double coef, double* out, double* out2, double* sums) {
+    if (!ctx->sop_ready) return pl_fail(ctx, "stokes operator not set");
+    PL_HIP(ctx, hipSetDevice(ctx->device));
+    PlSolver* S = solver_of(ctx);
+    PL_TRY(scal_alloc(ctx, S));
+    const PlGeom& g = ctx->geom.d;
+    if (mode != PL_EPI_NONE) PL_TRY(epi_alloc(ctx, S, g));
+    const size_t vb = (size_t)3 * g.plane * sizeof(double);
+    double *dx, *dy, *d1 = nullptr, *d2 = nullptr, *dy2 = nullptr, *dadd = nullptr, *dcoef = nullptr;
+    PL_TRY(pl_buf(ctx, "api_x", vb, &dx)); PL_TRY(pl_buf(ctx, "api_y", vb, &dy));
+    PL_TRY(pl_vec3_upload(ctx, g, x, dx));
+    PL_TRY(pl_halo(ctx, g, dx, 3, g.plane));
+    if (aux1) { PL_TRY(pl_buf(ctx, "api_a1", vb, &d1)); PL_TRY(pl_vec3_upload(ctx, g, aux1, d1)); }
+    if (aux2) { PL_TRY(pl_buf(ctx, "api_a2", vb, &d2)); PL_TRY(pl_vec3_upload(ctx, g, aux2, d2)); }
+    if (out2 && mode == PL_EPI_RESID) PL_TRY(pl_buf(ctx, "api_y2", vb, &dy2));
+    if (add) {
+        PL_TRY(pl_buf(ctx, "api_add", vb, &dadd)); PL_TRY(pl_vec3_upload(ctx, g, add, dadd));
+        PL_TRY(pl_buf(ctx, "api_coef", 2 * sizeof(double), &dcoef));
+        PL_HIP(ctx, hipMemcpyAsync(dcoef, &coef, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));          // coef lives on this frame
+    }
+    PlStokesOp op = ctx->sop; op.scaled = scaled ? 1 : 0;
+    PlApplyArgs e; e.mode = mode; e.rows = rows; e.a1 = d1; e.a2 = d2; e.y2 = dy2; e.add = dadd; e.coef = dcoef;
+    if (mode != PL_EPI_NONE) { e.part = S->epi + EPI_PART; e.cont = 1; e.want_xx = 1; e.want_ysum = 1; }
+    pl_launch_stokes_apply(ctx, op, dx, dy, e);
+    PL_HIP(ctx, hipGetLastError());
+    if (mode != PL_EPI_NONE) {
+        int nb = pl_apply_blocks(g, pl_apply_rows(g, mode, rows));
+        const double* part8 = mode == PL_EPI_DOT1 ? nullptr : epi_partials8(ctx, S, &nb);
+        double* dsum = S->epi + EPI_SUMS;           // mode 1: the pair k_sum_partials writes; mode 2: SC_DOT5 of a scratch scalar block
+        if (mode == PL_EPI_DOT1)
+            hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, (const double*)(S->epi + EPI_PART), dsum, 0, 0.0);
+        else if (mode == PL_EPI_DOT5) {
+            double* sc;
+            PL_TRY(pl_buf(ctx, "api_scal", PL_SCAL_N * sizeof(double), &sc));
+            hipLaunchKernelGGL(k_sum_partials5, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part8, sc, 0);
+            dsum = sc + SC_DOT5;
+        } else
+            hipLaunchKernelGGL(k_sum_resid, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part8, dsum, (double*)nullptr);
+        PL_HIP(ctx, hipGetLastError());
+        double* hs = S->hpart + PL_HSCAL;
+        PL_HIP(ctx, hipMemcpyAsync(hs, dsum, PL_EPI_NSUM * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int q = 0; q < PL_EPI_NSUM; q++) sums[q] = (mode == PL_EPI_DOT1 && q > 0) ? 0.0 : hs[q];
+    } else if (sums)
+        for (int q = 0; q < PL_EPI_NSUM; q++) sums[q] = 0.0;
+    PL_TRY(pl_vec3_download(ctx, g, dy, out));
+    if (dy2) PL_TRY(pl_vec3_download(ctx, g, dy2, out2));
+    return 0;
+}
+
+// The UNSCALED operator of pl_stokes_apply with one of the epilogues (modes 1..3, row-block heights 4 and 16).
 extern "C" int pl_stokes_apply_reduce(pl_ctx* ctx, int mode, int rows, const double* x, const double* aux1, const double* aux2,
                                       double* out, double* out2, double* sums) {
     if (!ctx->sop_ready) return pl_fail(ctx, "stokes operator not set");
@@ -4243,41 +4297,41 @@ extern "C" int pl_stokes_apply_reduce(pl_ctx* ctx, int mode, int rows, const dou
         return pl_fail(ctx, "pl_stokes_apply_reduce: bad argument");
     if (rows != 0 && rows != 4 && rows != 16) return pl_fail(ctx, "pl_stokes_apply_reduce: rows must be 0, 4 or 16");
     if (ctx->nranks > 1) return pl_fail(ctx, "pl_stokes_apply_reduce: one rank only");
+    return stokes_apply_probe(ctx, 0, mode, rows, x, aux1, aux2, nullptr, 0.0, out, out2, sums);
+}
+
+extern "C" int pl_stokes_apply_probe(pl_ctx* ctx, int scaled, int mode, int rows, const double* x, const double* aux1,
+                                     const double* aux2, const double* add, double coef, double* out, double* out2, double* sums) {
+    if (!ctx->sop_ready) return pl_fail(ctx, "stokes operator not set");
+    if (scaled != 0 && scaled != 1) return pl_fail(ctx, "pl_stokes_apply_probe: scaled must be 0 or 1");
+    if (mode < PL_EPI_NONE || mode > PL_EPI_RESID) return pl_fail(ctx, "pl_stokes_apply_probe: mode must be 0, 1, 2 or 3");
+    if (!x) return pl_fail(ctx, "pl_stokes_apply_probe: x is NULL");
+    if (!out) return pl_fail(ctx, "pl_stokes_apply_probe: out is NULL");
+    if (mode != PL_EPI_NONE && !aux1) return pl_fail(ctx, "pl_stokes_apply_probe: aux1 is NULL (modes 1, 2 and 3 read it)");
+    if (mode == PL_EPI_DOT5 && !aux2) return pl_fail(ctx, "pl_stokes_apply_probe: aux2 is NULL (mode 2 reads it)");
+    if (mode != PL_EPI_NONE && !sums) return pl_fail(ctx, "pl_stokes_apply_probe: sums is NULL");
+    if (mode == PL_EPI_NONE ? (rows != 0 && rows != 2 && rows != 4 && rows != 8 && rows != 16) : (rows != 0 && rows != 4 && rows != 16))
+        return pl_fail(ctx, mode == PL_EPI_NONE ? "pl_stokes_apply_probe: rows must be 0, 2, 4, 8 or 16 in mode 0"
+                                                : "pl_stokes_apply_probe: rows must be 0, 4 or 16 in modes 1, 2 and 3");
+    if (!(coef == coef) && add) return pl_fail(ctx, "pl_stokes_apply_probe: coef is NaN");
+    if (ctx->nranks > 1) return pl_fail(ctx, "pl_stokes_apply_probe: one rank only");
+    return stokes_apply_probe(ctx, scaled, mode, rows, x, aux1, aux2, add, coef, out, out2, sums);
+}
+
+// out = D_r v by the kernel that scales the solver's right-hand side
+extern "C" int pl_stokes_scale_rows(pl_ctx* ctx, const double* v, double* out) {
+    if (!ctx->sop_ready) return pl_fail(ctx, "stokes operator not set");
+    if (!v) return pl_fail(ctx, "pl_stokes_scale_rows: v is NULL");
+    if (!out) return pl_fail(ctx, "pl_stokes_scale_rows: out is NULL");
+    if (ctx->nranks > 1) return pl_fail(ctx, "pl_stokes_scale_rows: one rank only");
     PL_HIP(ctx, hipSetDevice(ctx->device));
-    PlSolver* S = solver_of(ctx);
-    PL_TRY(scal_alloc(ctx, S));
     const PlGeom& g = ctx->geom.d;
-    PL_TRY(epi_alloc(ctx, S, g));
-    const size_t vb = (size_t)3 * g.plane * sizeof(double);
-    double *dx, *dy, *d1, *d2 = nullptr, *dy2 = nullptr;
-    PL_TRY(pl_buf(ctx, "api_x", vb, &dx)); PL_TRY(pl_buf(ctx, "api_y", vb, &dy)); PL_TRY(pl_buf(ctx, "api_a1", vb, &d1));
-    PL_TRY(pl_vec3_upload(ctx, g, x, dx));
-    PL_TRY(pl_halo(ctx, g, dx, 3, g.plane));
-    PL_TRY(pl_vec3_upload(ctx, g, aux1, d1));
-    if (aux2) { PL_TRY(pl_buf(ctx, "api_a2", vb, &d2)); PL_TRY(pl_vec3_upload(ctx, g, aux2, d2)); }
-    if (out2 && mode == PL_EPI_RESID) PL_TRY(pl_buf(ctx, "api_y2", vb, &dy2));
-    PlApplyArgs e; e.mode = mode; e.rows = rows; e.a1 = d1; e.a2 = d2; e.y2 = dy2; e.part = S->epi + EPI_PART;
-    e.cont = 1; e.want_xx = 1; e.want_ysum = 1;
-    pl_launch_stokes_apply(ctx, ctx->sop, dx, dy, e);
-    int nb = pl_apply_blocks(g, pl_apply_rows(g, mode, rows));
-    const double* part8 = mode == PL_EPI_DOT1 ? nullptr : epi_partials8(ctx, S, &nb);
-    double* dsum = S->epi + EPI_SUMS;               // mode 1: the pair k_sum_partials writes; mode 2: SC_DOT5 of a scratch scalar block
-    if (mode == PL_EPI_DOT1)
-        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, (const double*)(S->epi + EPI_PART), dsum, 0, 0.0);
-    else if (mode == PL_EPI_DOT5) {
-        double* sc;
-        PL_TRY(pl_buf(ctx, "api_scal", PL_SCAL_N * sizeof(double), &sc));
-        hipLaunchKernelGGL(k_sum_partials5, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part8, sc, 0);
-        dsum = sc + SC_DOT5;
-    } else
-        hipLaunchKernelGGL(k_sum_resid, dim3(1), dim3(sum_block(nb)), 0, ctx->stream, nb, part8, dsum, (double*)nullptr);
+    double* dv;
+    PL_TRY(pl_buf(ctx, "api_x", (size_t)3 * g.plane * sizeof(double), &dv));
+    PL_TRY(pl_vec3_upload(ctx, g, v, dv));
+    hipLaunchKernelGGL(k_stokes_scale_rows, grid2d(g), dim3(64, 4), 0, ctx->stream, ctx->sop, dv);
     PL_HIP(ctx, hipGetLastError());
-    double* hs = S->hpart + PL_HSCAL;
-    PL_HIP(ctx, hipMemcpyAsync(hs, dsum, PL_EPI_NSUM * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int q = 0; q < PL_EPI_NSUM; q++) sums[q] = (mode == PL_EPI_DOT1 && q > 0) ? 0.0 : hs[q];
-    PL_TRY(pl_vec3_download(ctx, g, dy, out));
-    if (dy2) PL_TRY(pl_vec3_download(ctx, g, dy2, out2));
+    PL_TRY(pl_vec3_download(ctx, g, dv, out));
     return 0;
 }
 

@@ -35,7 +35,7 @@ struct StokesVals {
 
 // The memory-only twin of this kernel runs in 58 us against 80 us (2049^2): the arithmetic is NOT free.  The
 // row scales of the scaled operator are therefore a template switch (the plain operator performs no division
-// at all) and use v_rcp_f64 + two Newton steps instead of the ~15-instruction IEEE division sequence.
+// at all) and use v_rcp_f64 + one Newton step (pl_rcp, 2.2e-15) instead of the ~15-instruction IEEE division sequence.
 template <bool SCALED>
 __device__ inline void stokes_node_vals(const PlStokesOp& op, int i, int j, int c, const StokesVals& q,
                                         const double* __restrict__ x, double& oz, double& ox, double& op_) {

@@ -128,6 +128,36 @@ def test_heat_apply_and_rhs(mods, tag):
         assert (np.abs(Dm.data).max() if Dm.nnz else 0.0) <= 1e-13 * np.abs(R).max()
 
 
+@pytest.mark.parametrize("nx,bc", [([23, 130], [1, 0, 0, 1]), ([9, 258], [0, 1, 1, 0])], ids=["23x130", "9x258"])
+def test_heat_apply_and_rhs_wide_rectilinear(mods, oracle, nx, bc):
+    """Beyond the 41 columns of the golden operators: more than one 64-column block, rectilinear in both axes, mixed Dirichlet and
+    Neumann walls as in golden b."""
+    D = mods[1]
+    rng = np.random.default_rng(310 + nx[1])
+
+    def nonuni(n, Ld):
+        w = rng.uniform(0.7, 1.3, n - 1); g = np.concatenate([[0.0], np.cumsum(w)]); return g * (Ld / g[-1])
+    grid = [nonuni(nx[d], 5e3 * (nx[d] - 1)) for d in range(2)]
+    gridmp = oracle.gridmp_of(grid)
+    kz = rng.uniform(2, 5, nx); kx = rng.uniform(2, 5, nx)
+    Cp = rng.uniform(1000, 1250, nx); rho = rng.uniform(2900, 3400, nx)
+    H = rng.uniform(0, 1e-9, nx) * 3300
+    T = rng.uniform(273, 1623, nx)
+    hmin = min(np.min(np.diff(grid[0])), np.min(np.diff(grid[1])))
+    tstep = 5.0 * 0.67 * hmin ** 2 / np.max(2 * kz / (rho * Cp))
+    bcv = [273.0, 0.0, 1623.0, 0.0]
+    for w in range(4):
+        if bc[w] == 1 and w in (0, 2):
+            bcv[w] = 0.03 if w == 0 else -0.02
+        if bc[w] == 0 and w in (1, 3):
+            bcv[w] = 800.0 + 100 * w
+    A, rhs = D.makeDiffusionMatrix(nx, grid, gridmp, T, [kz, kx], Cp, rho, H, bc, bcv, tstep)
+    assert relerr(rhs, oracle.heat_rhs(nx, T, Cp, rho, H, bc, bcv, tstep)) < 1e-13
+    for _ in range(2):
+        x = rng.standard_normal(nx[0] * nx[1])
+        assert relerr(A @ x, oracle.heat_apply(nx, grid, gridmp, [kz, kx], Cp, rho, bc, tstep, x)) < 1e-13
+
+
 def _targets(oracle, nx, L):
     grid = [np.linspace(0, L[i], nx[i]) for i in range(2)]
     gmp = oracle.gridmp_of(grid)
