@@ -386,9 +386,29 @@ int  pl3_stokes_set_wall_rows(pl3_ctx* ctx, int slaved);
  *    halves, dv_D/dx_E one-sided against v_D = 0 on the wall -- low side v_D[0] / ((c_E[1] - c_E[0]) / 2), high side
  *    -v_D[n-2] / ((c_E[n-1] - c_E[n-2]) / 2) -- and dv_E/dx_D as on a FREESLIP wall, which drops the first half. */
 int  pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]);
+/* Moving walls.  vel[18]: vel[3 w + q] is component q of U_w = (Uz, Ux, Uy) of wall w of [z0, x0, y0, zL, xL, yL]; every wall is at
+ * rest at creation.  Only the two components tangential to the wall may be non-zero, and only on a NOSLIP wall.  Errors, each naming
+ * the wall and the value: a non-finite entry; a non-zero normal component (flow through a wall needs the marker deletion path, which
+ * is not built in 3-D); a non-zero velocity on a FREESLIP wall; and pl3_stokes_set_walls turning a moving wall FREESLIP.  The state
+ * belongs to the context, survives pl3_stokes_set_coeffs like the kinds, and is read by pl3_stokes_rhs, the solves of the operator's
+ * own right-hand side, pl3_resident_step and pl3_advection_velocity.  With all velocities zero everything is bit for bit what it is
+ * without this call.  The terms are affine -- the operator, its row scaling, the multigrid hierarchy and a right-hand side given to
+ * pl3_stokes_solve are untouched -- and enter the right-hand side alone:
+ *  - slaved rows: a v_D slaved along axis a at a NOSLIP wall keeps its row and gains a right-hand side, so that the row states "v_D
+ *    extrapolated linearly to the wall is U_D": low side Kcont [-(rD_a[1] + rd_a[0]) v + rD_a[1] v_nb] = -Kcont rd_a[0] U_D, high side
+ *    Kcont [(rD_a[n-2] + rd_a[n-2]) v - rD_a[n-2] v_nb] = +Kcont rd_a[n-2] U_D; scaled, v - gamma v_nb = (1 - gamma) U_D.  A row on
+ *    a cube edge is slaved along its first boundary axis only (E before F), and the wall it is slaved to supplies U;
+ *  - natural rows: the one-sided dv_D/dx_E on the edge of a NOSLIP wall is taken against v_D = U_D on the wall; the constant part of
+ *    2 eta_edge rd_E^2 (v_D - U_D) goes to the right-hand side, -2 eta_edge rd_E^2 U_D; on a cube edge both walls contribute;
+ *  - identity rows, pressure rows and all coarse levels are unchanged: corrections are homogeneous. */
+int  pl3_stokes_set_wall_velocity(pl3_ctx* ctx, const double vel[18]);
+int  pl3_stokes_get_wall_velocity(pl3_ctx* ctx, double vel[18]);
 int  pl3_stokes_get_scaling(pl3_ctx* ctx, double* kcont, double* kbond);
 int  pl3_stokes_apply(pl3_ctx* ctx, const double* x, double* y);
 int  pl3_stokes_rhs(pl3_ctx* ctx, double* rhs);
+/* the same right-hand side row-scaled, as pl3_stokes_solve(rhs = NULL) iterates on it: every row divided by its coefficient of the
+ * row's own unknown (interior momentum rows: by minus that coefficient, the sum of their own-component couplings) */
+int  pl3_stokes_rhs_scaled(pl3_ctx* ctx, double* rhs);
 /* x == NULL: device-resident solve -- nothing crosses PCIe, the solution stays in the context (pl3_get_solution), and use_x0 != 0
  * starts from the solution of the context's previous solve. */
 int  pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int use_x0, double rtol, int maxit, pl_solve_stats* stats);
@@ -533,7 +553,10 @@ int  pl3_get_field(pl3_ctx* ctx, const char* name, double* out);
  * centre grid: every component averaged along its own axis, then the ghosts wall by wall in the order z0, x0, y0, zL, xL, yL: a
  * FREESLIP wall mirrors the normal component with a sign flip and copies the tangential ones, the pass of a NOSLIP wall
  * (pl3_stokes_set_walls) is skipped and its ghosts keep what they hold (pylamp2.py:491-545); the order decides the edge and corner
- * values. */
+ * values.  The pass of a NOSLIP wall with a non-zero velocity (pl3_stokes_set_wall_velocity) runs in its slot and writes, from the
+ * neighbouring plane as it is at that moment, -V for the normal component and 2 U_c - V for each tangential component c: the velocity
+ * interpolated onto the wall is U.  This is deliberately discontinuous at U = 0, where the pass is skipped: walls at rest keep the
+ * reference's behaviour. */
 int  pl3_advection_velocity(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* Vz, double* Vx, double* Vy);
 /* Host <-> device copies issued by the pl3_* entry points of this context since the last reset: out = { copies of at least one node
  * field (8 nz nx ny bytes), their bytes, smaller copies, their bytes }; reset != 0 clears the counters after reading. */

@@ -81,9 +81,12 @@ SIGNATURES = {
     "pl3_stokes_set_coeffs": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "pl3_stokes_set_wall_rows": (C.c_int, [C.c_void_p, C.c_int]),
     "pl3_stokes_set_walls": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "pl3_stokes_set_wall_velocity": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_stokes_get_wall_velocity": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_stokes_get_scaling": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_rhs": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_stokes_rhs_scaled": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_stokes_solve": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.POINTER(SolveStats)]),
     "pl3_stokes_apply_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),
     "pl3_stokes_mg_info": (C.c_int, [C.c_void_p, c_int_p, c_double_p, C.c_int]),

@@ -261,20 +261,59 @@ template <bool SCALED> __global__ __launch_bounds__(256) void k3_apply(Op3 op, V
 }
 
 // rhs (pylamp_stokes.py:429,490 extended: density averaged onto the face), optionally row-scaled like k3_apply<true>
-template <int D> __device__ inline double rhs_vel3(const Op3& op, long long c, const int* idx, bool scaled) {
+// ---- moving no-slip walls (pl3_stokes_set_wall_velocity; include/pylamp_hip.h).  The terms are affine: they touch the
+// right-hand side only, so the velocities travel as an argument of k3_rhs alone and Op3 stays as it is.  Wall and component of an entry
+// are template constants, the side follows from a layer test on a global index (wave-uniform along z and x): scalar reads of the kernel
+// arguments.  moving == 0 skips all of it.
+template <int A, int D> __device__ inline double wall_vel3(const Pl3WallVel& mv, int hi) { return hi ? mv.u[3 * (A + 3) + D] : mv.u[3 * A + D]; }
+// right-hand side of the row of v_D slaved along A at its low / high wall: unscaled -+Kc rd U_D ("v_D extrapolated linearly to the wall is
+// U_D"); scaled (divided by Kc sd) (1 - gamma) U_D
+template <int A, int D> __device__ inline double slave_rhs3(const Op3& op, const Pl3WallVel& mv, int hi, bool scaled) {
+    if (!((mv.moving >> (A + 3 * hi)) & 1)) return 0.0;
+    const double U = wall_vel3<A, D>(mv, hi);
+    const double rd = TB(op.g.rd[A], hi ? op.g.gn[A] - 2 : 0);
+    if (!scaled) return hi ? op.Kc * rd * U : -(op.Kc * rd * U);
+    double sd, sn;
+    slave_coef3<A>(op, hi, sd, sn);
+    return (hi ? rd : -rd) / sd * U;
+}
+// natural rows: the constant part of the wall-edge shear 2 eta rd^2 (v_D - U_D) of a moving wall of axis A, on the left-hand side
+template <int A, int D> __device__ inline double wall_rhs3(const Op3& op, const Pl3WallVel& mv, int ia, double em, double ep) {
+    const int hi = ia == 0 ? 0 : 1;
+    if ((ia != 0 && ia != op.g.gn[A] - 2) || !((mv.moving >> (A + 3 * hi)) & 1)) return 0.0;
+    return wall_coef3<A>(op, ia, em, ep) * wall_vel3<A, D>(mv, hi);
+}
+template <int D> __device__ inline double rhs_vel3(const Op3& op, const Pl3WallVel& mv, long long c, const int* idx, bool scaled) {
     constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
     long long moff;
-    if (cls3<D>(op, idx, moff) != C3_INT || op.grav[D] == 0.0) return 0.0;
-    const double* r = op.rho;
+    const int cl = cls3<D>(op, idx, moff);
+    if (mv.moving != 0 && cl == C3_SLAVE) {                  // the wall of the first boundary axis (E before F) supplies U
+        const int* n = op.g.gn;
+        if (idx[E] == 0) return slave_rhs3<E, D>(op, mv, 0, scaled);
+        if (idx[E] == n[E] - 2) return slave_rhs3<E, D>(op, mv, 1, scaled);
+        if (idx[F] == 0) return slave_rhs3<F, D>(op, mv, 0, scaled);
+        return slave_rhs3<F, D>(op, mv, 1, scaled);
+    }
+    const bool walls = mv.moving != 0 && !op.slave;          // (with slaved rows no interior row lies on a wall layer)
+    if (cl != C3_INT || (op.grav[D] == 0.0 && !walls)) return 0.0;
     const long long se = op.g.s[E], sf = op.g.s[F];
-    const double b = -0.25 * ((r[c] + r[c + se]) + (r[c + sf] + r[c + se + sf])) * op.grav[D];
+    double b = 0.0;
+    if (op.grav[D] != 0.0) {
+        const double* r = op.rho;
+        b = -0.25 * ((r[c] + r[c + se]) + (r[c + sf] + r[c + se + sf])) * op.grav[D];
+    }
+    if (walls) {                                             // on a cube edge both walls contribute
+        const double* __restrict__ es = op.es;
+        b -= wall_rhs3<E, D>(op, mv, idx[E], 0.5 * (es[c] + es[c + sf]), 0.5 * (es[c + se] + es[c + se + sf]));
+        b -= wall_rhs3<F, D>(op, mv, idx[F], 0.5 * (es[c] + es[c + se]), 0.5 * (es[c + sf] + es[c + sf + se]));
+    }
     return scaled ? b / diag3<D>(op, c, idx) : b;
 }
-__global__ __launch_bounds__(256) void k3_rhs(Op3 op, W4 b, int scaled) {
+__global__ __launch_bounds__(256) void k3_rhs(Op3 op, W4 b, int scaled, Pl3WallVel mv) {
     K3_PROLOGUE(op.g)
-    b.p[0][c] = rhs_vel3<0>(op, c, idx, scaled);
-    b.p[1][c] = rhs_vel3<1>(op, c, idx, scaled);
-    b.p[2][c] = rhs_vel3<2>(op, c, idx, scaled);
+    b.p[0][c] = rhs_vel3<0>(op, mv, c, idx, scaled);
+    b.p[1][c] = rhs_vel3<1>(op, mv, c, idx, scaled);
+    b.p[2][c] = rhs_vel3<2>(op, mv, c, idx, scaled);
     b.p[3][c] = 0.0;
 }
 // b *= D_r (a user-supplied right-hand side)
@@ -896,7 +935,20 @@ template <int D> __device__ inline void close3(const Op3& op, double* __restrict
     long long moff;
     const int cl = cls3<D>(op, idx, moff);
     if (cl == C3_ZERO) x[c] = bs[c];
-    else if (cl == C3_SLAVE) x[c] = (op.noslip ? fac3<D>(op, idx) * x[c + moff] : x[c + moff]) + bs[c];
+    else if (cl == C3_SLAVE) {
+        if (!op.noslip) { x[c] = x[c + moff] + bs[c]; return; }
+        // On a cube edge the row couples along E to a node that is itself slaved along F: that node's right-hand side comes along the
+        // chain, x = gamma_E (gamma_F x_master + bs_nb) + bs.  It is non-zero next to a moving wall (or in a given right-hand side).
+        constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
+        const int* n = op.g.gn;
+        double b = bs[c];
+        if ((idx[E] == 0 || idx[E] == n[E] - 2) && (idx[F] == 0 || idx[F] == n[F] - 2)) {
+            const int hi = idx[E] != 0;
+            const double bn = bs[hi ? c - op.g.s[E] : c + op.g.s[E]];
+            if (bn != 0.0) b += gam3<E>(op, hi) * bn;
+        }
+        x[c] = fac3<D>(op, idx) * x[c + moff] + b;
+    }
 }
 __global__ __launch_bounds__(256) void k3_close(Op3 op, W3 x, V3 bs) {
     K3_PROLOGUE(op.g)
@@ -1119,6 +1171,7 @@ struct pl3_ctx {
     G3Host geom;
     double *es = nullptr, *en = nullptr, *rho = nullptr; Op3 op{}; bool op_ready = false;
     int noslip = 0;                 // pl3_stokes_set_walls: bit w of [z0, x0, y0, zL, xL, yL] set = no-slip; kept across pl3_stokes_set_coeffs
+    Pl3WallVel wallvel{};           // pl3_stokes_set_wall_velocity: U_w = (Uz, Ux, Uy) per wall and the mask of the moving ones; kept likewise
     std::vector<Lev3*> levels;
     double* vec[14][4] = {{nullptr}};           // BiCGStab work vectors (4 arrays each)
     double* part = nullptr; double* hpart = nullptr;
@@ -1420,6 +1473,12 @@ extern "C" int pl3_stokes_set_wall_rows(pl3_ctx* ctx, int slaved) {
 }
 // bc = [z0, x0, y0, zL, xL, yL], each PL_BC_FREESLIP or PL_BC_NOSLIP.  Kept on the context (which starts all free-slip) across
 // pl3_stokes_set_coeffs; read by the solves, pl3_resident_step and pl3_advection_velocity.
+static std::string num_str3(double v) {          // the shortest decimal that reads back as v
+    char b[40];
+    for (int p = 15; p <= 17; p++) { snprintf(b, sizeof b, "%.*g", p, v); if (strtod(b, nullptr) == v) break; }
+    return b;
+}
+static std::string wallvel_str3(const double* u) { return "(" + num_str3(u[0]) + ", " + num_str3(u[1]) + ", " + num_str3(u[2]) + ")"; }
 extern "C" int pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]) {
     if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_walls: NULL context");
     if (!bc) return p3_fail(ctx, "pl3_stokes_set_walls: NULL argument");
@@ -1431,8 +1490,46 @@ extern "C" int pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]) {
             return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + names[w] + " has kind " + std::to_string(bc[w]) +
                                     ": a 3-D Stokes wall is FREESLIP (1) or NOSLIP (0)");
     }
+    for (int w = 0; w < 6; w++)
+        if (((ctx->wallvel.moving >> w) & 1) && !((m >> w) & 1)) {
+            const double* u = ctx->wallvel.u + 3 * w;
+            return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + names[w] + " moves with velocity " + wallvel_str3(u) +
+                                    " and cannot become FREESLIP: only a NOSLIP wall carries a velocity (set it to zero first)");
+        }
     ctx->noslip = m;
     if (ctx->op_ready) ctx->op.noslip = m;
+    return 0;
+}
+// vel[3 w + q]: component q of (Uz, Ux, Uy) of wall w of [z0, x0, y0, zL, xL, yL].  Only the two tangential components of a NOSLIP
+// wall may be non-zero.  Kept on the context (which starts at rest) across pl3_stokes_set_coeffs; read by pl3_stokes_rhs, the solves of
+// the operator's own right-hand side, pl3_resident_step and pl3_advection_velocity.
+extern "C" int pl3_stokes_set_wall_velocity(pl3_ctx* ctx, const double vel[18]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_wall_velocity: NULL context");
+    if (!vel) return p3_fail(ctx, "pl3_stokes_set_wall_velocity: NULL argument");
+    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
+    static const char* const comp[3] = {"Uz", "Ux", "Uy"};
+    Pl3WallVel mv{};
+    for (int w = 0; w < 6; w++) {
+        const double* u = vel + 3 * w;
+        const std::string who = std::string("pl3_stokes_set_wall_velocity: wall ") + names[w];
+        for (int q = 0; q < 3; q++)
+            if (!std::isfinite(u[q])) return p3_fail(ctx, who + " has a non-finite velocity component " + comp[q] + " = " + num_str3(u[q]));
+        if (u[w % 3] != 0.0)
+            return p3_fail(ctx, who + " has the normal velocity component " + comp[w % 3] + " = " + num_str3(u[w % 3]) +
+                                    ": only the tangential components may be non-zero -- flow through a wall needs the marker deletion path, which is not built in 3-D");
+        const bool moves = u[0] != 0.0 || u[1] != 0.0 || u[2] != 0.0;
+        if (moves && !((ctx->noslip >> w) & 1))
+            return p3_fail(ctx, who + " is FREESLIP and cannot move with velocity " + wallvel_str3(u) + ": only a NOSLIP wall carries a velocity (pl3_stokes_set_walls)");
+        for (int q = 0; q < 3; q++) mv.u[3 * w + q] = u[q];
+        if (moves) mv.moving |= 1 << w;
+    }
+    ctx->wallvel = mv;
+    return 0;
+}
+extern "C" int pl3_stokes_get_wall_velocity(pl3_ctx* ctx, double vel[18]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_get_wall_velocity: NULL context");
+    if (!vel) return p3_fail(ctx, "pl3_stokes_get_wall_velocity: NULL argument");
+    for (int e = 0; e < 18; e++) vel[e] = ctx->wallvel.u[e];
     return 0;
 }
 extern "C" int pl3_stokes_get_scaling(pl3_ctx* ctx, double* kc, double* kb) {
@@ -1460,14 +1557,17 @@ extern "C" int pl3_stokes_apply(pl3_ctx* ctx, const double* x, double* y) {
     P3_HIP(ctx, hipGetLastError());
     return download3(ctx, ctx->vec[1], 4, y);
 }
-extern "C" int pl3_stokes_rhs(pl3_ctx* ctx, double* rhs) {
+static int stokes_rhs3(pl3_ctx* ctx, double* rhs, int scaled) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 2));
-    hipLaunchKernelGGL(k3_rhs, grid3(ctx->op.g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(ctx->vec[1]), 0);
+    hipLaunchKernelGGL(k3_rhs, grid3(ctx->op.g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(ctx->vec[1]), scaled, ctx->wallvel);
     P3_HIP(ctx, hipGetLastError());
     return download3(ctx, ctx->vec[1], 4, rhs);
 }
+extern "C" int pl3_stokes_rhs(pl3_ctx* ctx, double* rhs) { return stokes_rhs3(ctx, rhs, 0); }
+// the row-scaled right-hand side D_r b that pl3_stokes_solve(rhs = NULL) iterates on
+extern "C" int pl3_stokes_rhs_scaled(pl3_ctx* ctx, double* rhs) { return stokes_rhs3(ctx, rhs, 1); }
 extern "C" int pl3_stokes_apply_bench(pl3_ctx* ctx, int scaled, int reps, double* avg_ms) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
@@ -1918,7 +2018,7 @@ extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int 
     P3_TRY(build_levels3(ctx));
     double* const* B = ctx->vec[10]; double* const* X = ctx->vec[11]; double* const* XH = ctx->vec[12];
     if (rhs) { P3_TRY(upload3(ctx, rhs, 4, B)); hipLaunchKernelGGL(k3_scale_rows, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(B)); }
-    else hipLaunchKernelGGL(k3_rhs, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(B), 1);
+    else hipLaunchKernelGGL(k3_rhs, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(B), 1, ctx->wallvel);
     int napply = 0, nprec = 0;
     bool defl_active = false; double yAw = 1.0;
     double* const* W = ctx->vec[13];
@@ -2172,7 +2272,7 @@ int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     const G3& g = ctx->geom.d;
     v->s0 = g.s[0]; v->s1 = g.s[1]; v->pad = P3_PAD; v->stream = ctx->stream; v->slot = &ctx->step3;
     for (int q = 0; q < 4; q++) { v->X[q] = ctx->vec[11][q]; v->scratch[q] = ctx->vec[0][q]; }
-    v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T; v->noslip = ctx->noslip;
+    v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T; v->noslip = ctx->noslip; v->wallvel = ctx->wallvel;
     return 0;
 }
 // counts and bytes of the host <-> device copies of this context's pl3_* calls since the last reset: out = { copies of at least one

@@ -100,22 +100,30 @@ __global__ __launch_bounds__(256) void k_s3_velmax(S3Dims d, S3Vel x, S3Ops ops,
 // walks that chain backwards from its own point until it stands on an inner point; a source that no earlier wall had written yet
 // would still hold the initial zero (it cannot occur with this order, the case is kept for exactness).  The pass of a no-slip wall
 // (bit w of `noslip`) is skipped, as in the reference: its ghost plane keeps the initial zero but where a later pass writes its edges.
+// The pass of a no-slip wall that MOVES (bit w of mv.moving; pl3_stokes_set_wall_velocity) runs in its slot: from the neighbouring plane
+// as it is at that moment it writes -V for the normal component and 2 U_c - V for a tangential component c, so that the velocity
+// interpolated onto the wall is U.  These steps round, so a chain that holds one is replayed forwards, first wall first, as the passes
+// ran; without a moving wall in the chain the walk is the one above.
 struct S3Adv { double* V[3]; };
-__global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, int noslip) {
+__global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, int noslip, Pl3WallVel mv) {
     const int pn[3] = {d.n[0] + 1, d.n[1] + 1, d.n[2] + 1};
     const long long GN = (long long)pn[0] * pn[1] * pn[2];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= GN) return;
     const int p0[3] = {(int)(t / ((long long)pn[2] * pn[1])), (int)((t / pn[2]) % pn[1]), (int)(t % pn[2])};
+    const int skip = noslip & ~mv.moving;                    // the walls whose pass does not run
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         int p[3] = {p0[0], p0[1], p0[2]};
         double sign = 1.0;
+        int chain = 0, moved = 0;                            // the walls of the walk, 3 bits each (w + 1), the earliest pass in the lowest bits
         for (int w = 5; w >= 0; w--) {                       // walls 0..5 = z0, x0, y0, zL, xL, yL
             const int a = w % 3, ghost = w < 3 ? 0 : pn[a] - 1;
-            if (p[a] != ghost || ((noslip >> w) & 1)) continue;        // (the pass of a no-slip wall is skipped)
+            if (p[a] != ghost || ((skip >> w) & 1)) continue;          // (the pass of a no-slip wall at rest is skipped)
             p[a] = w < 3 ? 1 : pn[a] - 2;
             if (a == q) sign = -sign;
+            chain = (chain << 3) | (w + 1);
+            moved |= (mv.moving >> w) & 1;
         }
         const bool inner = p[0] >= 1 && p[0] <= pn[0] - 2 && p[1] >= 1 && p[1] <= pn[1] - 2 && p[2] >= 1 && p[2] <= pn[2] - 2;
         double r = 0.0;
@@ -123,7 +131,15 @@ __global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, i
             // V_q[I, J, K] = 0.5 (v_q[.. own index I ..] + v_q[.. I - 1 ..]) at the nodes (I-1, J-1, K-1) of the other axes
             int hi[3] = {p[0] - 1, p[1] - 1, p[2] - 1}, lo[3] = {p[0] - 1, p[1] - 1, p[2] - 1};
             hi[q] = p[q];
-            r = sign * (0.5 * (x.v[q][s3_ring(d, hi[0], hi[1], hi[2])] + x.v[q][s3_ring(d, lo[0], lo[1], lo[2])]));
+            r = 0.5 * (x.v[q][s3_ring(d, hi[0], hi[1], hi[2])] + x.v[q][s3_ring(d, lo[0], lo[1], lo[2])]);
+            if (!moved) r = sign * r;
+        }
+        if (moved) {
+            for (; chain; chain >>= 3) {
+                const int w = (chain & 7) - 1;
+                if (w % 3 == q) r = -r;
+                else if ((mv.moving >> w) & 1) r = 2.0 * mv.u[3 * w + q] - r;
+            }
         }
         o.V[q][t] = r;
     }
@@ -200,7 +216,7 @@ static int s3_finish(pl3_ctx* ctx, S3Open& o, int nb, const S3Ops& ops, const do
 static void s3_advvel(S3Open& o, double* const X[3], double* adv) {
     const size_t GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
     S3Vel x{{X[0], X[1], X[2]}}; S3Adv a{{adv, adv + GNp, adv + 2 * GNp}};
-    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip);
+    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip, o.d.wallvel);
 }
 
 extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* rep) {

@@ -56,6 +56,36 @@ def stokes_walls(bc, who="3-D Stokes"):
     return [int(b) for b in bc]
 
 
+VEL_NAMES = ("Uz", "Ux", "Uy")
+
+
+def wall_velocities(wallvel, bc=None, who="3-D Stokes"):
+    """wallvel: the velocities U_w = (Uz, Ux, Uy) of the six walls [z0, x0, y0, zL, xL, yL] as a (6, 3) array (None: all at rest).
+    The checks and messages of pl3_stokes_set_wall_velocity: every entry finite, the component normal to the wall zero
+    (through-flow needs the marker deletion path, which is not built in 3-D) and -- where the kinds bc are given -- a non-zero
+    velocity on a NOSLIP wall only."""
+    if wallvel is None:
+        return np.zeros((6, 3))
+    try:
+        v = np.array(wallvel, dtype=np.float64)
+    except (TypeError, ValueError):
+        v = None
+    if v is None or v.shape != (6, 3):
+        raise Exception("%s: the wall velocities need the shape (6, 3): (Uz, Ux, Uy) for each of [z0, x0, y0, zL, xL, yL]" % who)
+    for w in range(6):
+        for q in range(3):
+            if not np.isfinite(v[w, q]):
+                raise Exception("%s: wall %s has a non-finite velocity component %s = %r" % (who, WALL_NAMES[w], VEL_NAMES[q], float(v[w, q])))
+        if v[w, w % 3] != 0.0:
+            raise Exception("%s: wall %s has the normal velocity component %s = %r: only the tangential components may be non-zero -- "
+                            "flow through a wall needs the marker deletion path, which is not built in 3-D"
+                            % (who, WALL_NAMES[w], VEL_NAMES[w % 3], float(v[w, w % 3])))
+        if bc is not None and v[w].any() and int(bc[w]) != BC_TYPE_NOSLIP:
+            raise Exception("%s: wall %s is FREESLIP and cannot move with velocity %s: only a NOSLIP wall carries a velocity"
+                            % (who, WALL_NAMES[w], tuple(float(u) for u in v[w])))
+    return v
+
+
 class Context3:
     def __init__(self, nx, grid, device=0):
         lib = _lib.load()
@@ -116,6 +146,18 @@ class Context3:
         """The kinds of the six Stokes walls [z0, x0, y0, zL, xL, yL] of this context (None: all free-slip); kept until set again."""
         self.check(self.lib.pl3_stokes_set_walls(self.handle(), (C.c_int * 6)(*stokes_walls(bc))))
 
+    def set_wall_velocity(self, wallvel):
+        """The velocities (Uz, Ux, Uy) of the six Stokes walls of this context, a (6, 3) array-like (None: all at rest); kept until
+        set again.  Only the tangential components of a NOSLIP wall may be non-zero (include/pylamp_hip.h at
+        pl3_stokes_set_wall_velocity)."""
+        v = np.ascontiguousarray(wall_velocities(wallvel))
+        self.check(self.lib.pl3_stokes_set_wall_velocity(self.handle(), _lib.dptr(v)))
+
+    def wall_velocity(self):
+        v = np.zeros((6, 3))
+        self.check(self.lib.pl3_stokes_get_wall_velocity(self.handle(), _lib.dptr(v)))
+        return v
+
     def close(self):
         if self.h is not None:
             self._fin()
@@ -153,9 +195,11 @@ class StokesOperator3:
     def __matmul__(self, x):
         return self.matvec(x)
 
-    def rhs(self):
+    def rhs(self, scaled=False):
+        """The operator's own right-hand side (gravity and the moving walls); scaled=True: row-scaled, as solve(A) iterates on it."""
         r = np.empty(self.shape[0])
-        self._ctx.check(self._ctx.lib.pl3_stokes_rhs(self._ctx.handle(), _lib.dptr(r)))
+        fn = self._ctx.lib.pl3_stokes_rhs_scaled if scaled else self._ctx.lib.pl3_stokes_rhs
+        self._ctx.check(fn(self._ctx.handle(), _lib.dptr(r)))
         return r
 
     def apply_bench(self, reps=20, scaled=True):
@@ -169,7 +213,7 @@ class StokesOperator3:
         return n.value, [lm[k] for k in range(n.value)]
 
 
-def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True):
+def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True, wallvel=None):
     """3-D counterpart of pylamp_stokes.makeStokesMatrix: f_etas at the NODES (averaged onto the edges by the kernels),
     f_etan at the cell centres, f_rho at the nodes; bc = [z0, x0, y0, zL, xL, yL], each BC_TYPE_FREESLIP or BC_TYPE_NOSLIP.
     bc=None leaves the walls of the context as they are: all free-slip on a new context, or what Context3.set_stokes_walls /
@@ -178,11 +222,19 @@ def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device
     inner neighbours -- free slip imposed half a cell inside the wall, first-order accurate -- or, on a no-slip wall, the
     reference's extrapolation row); False uses natural rows (mirror rows on a free-slip wall, the one-sided shear stress
     against v = 0 on a no-slip wall; second-order accurate).  The rows are written out in include/pylamp_hip.h at
-    pl3_stokes_set_walls."""
+    pl3_stokes_set_walls.
+    wallvel: the velocities (Uz, Ux, Uy) of the six walls, (6, 3); only the tangential components of a NOSLIP wall may be
+    non-zero.  They enter the returned right-hand side (and solve(A) without rhs=) and nothing else; None leaves the velocities
+    of the context as they are (at rest on a new context).  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_velocity."""
     walls = None if bc is None else stokes_walls(bc)
+    vel = None if wallvel is None else wall_velocities(wallvel, walls)
     ctx = ctx or Context3(nx, grid, device)
+    if vel is not None and walls is not None:
+        ctx.set_wall_velocity(None)                 # (the new kinds are checked against the new velocities, not the old ones)
     if walls is not None:
         ctx.set_stokes_walls(walls)
+    if vel is not None:
+        ctx.set_wall_velocity(vel)
     shp = ctx.nx
     es, en, rho = _f3(f_etas, shp), _f3(f_etan, shp), _f3(f_rho, shp)
     g = None if grav is None else (C.c_double * 3)(*[float(v) for v in grav])
@@ -490,13 +542,17 @@ def refined_grid(n, L, centre=0.5, ratio=3.0, width=0.2):
     return c
 
 
-def advection_velocity(newvel, gridmp, nx, bc=None):
+def advection_velocity(newvel, gridmp, nx, bc=None, wallvel=None):
     """Cell-centred velocities on the padded (nz+1, nx+1, ny+1) grid (pylamp2.py:491-545 extended by one axis): every
     component is averaged along its own axis; ghosts wall by wall in the order z0, x0, y0, zL, xL, yL -- a free-slip wall
     mirrors the normal component with a sign flip and copies the tangential ones, the pass of a no-slip wall
     (bc[w] == BC_TYPE_NOSLIP; bc None: all free-slip) is skipped as in the reference, so its ghosts keep what they hold.
+    The pass of a no-slip wall with a non-zero velocity wallvel[w] = (Uz, Ux, Uy) runs in its slot: -V for the normal component
+    and 2 U_c - V for a tangential component c, so that the velocity interpolated onto the wall is U (deliberately
+    discontinuous at U = 0, where walls at rest keep the reference's behaviour).
     Returns ([gz, gx, gy], [Vz, Vx, Vy])."""
     walls = stokes_walls(bc, "advection_velocity")
+    U = wall_velocities(wallvel, walls, "advection_velocity")
     shp = tuple(int(v) + 1 for v in nx)
     vz, vx, vy = newvel
     V = [np.zeros(shp) for _ in range(3)]
@@ -506,12 +562,19 @@ def advection_velocity(newvel, gridmp, nx, bc=None):
     g = [np.insert(np.asarray(m, dtype=np.float64), 0, m[0] - (m[1] - m[0])) for m in gridmp]
     for ghost, inner in ((0, 1), (-1, -2)):
         for axis in range(3):
-            if walls[axis + (0 if ghost == 0 else 3)] == BC_TYPE_NOSLIP:
+            w = axis + (0 if ghost == 0 else 3)
+            moving = walls[w] == BC_TYPE_NOSLIP and U[w].any()
+            if walls[w] == BC_TYPE_NOSLIP and not moving:
                 continue
             for comp in range(3):
                 dst = [slice(None)] * 3; src = [slice(None)] * 3
                 dst[axis] = ghost; src[axis] = inner
-                V[comp][tuple(dst)] = -V[comp][tuple(src)] if comp == axis else V[comp][tuple(src)]
+                if comp == axis:
+                    V[comp][tuple(dst)] = -V[comp][tuple(src)]
+                elif moving:
+                    V[comp][tuple(dst)] = 2 * U[w, comp] - V[comp][tuple(src)]
+                else:
+                    V[comp][tuple(dst)] = V[comp][tuple(src)]
     return g, V
 
 
@@ -528,6 +591,8 @@ class Options3:
         self.tstep_dif_max = 50e9 * SECINYR; self.tstep_dif_min = 50e-9 * SECINYR
         self.tstep_modifier = 0.67
         self.bcstokes = [BC_TYPE_FREESLIP] * 6
+        # beyond the reference: velocities (Uz, Ux, Uy) of the six walls, (6, 3); tangential components of NOSLIP walls only (None: at rest)
+        self.bcstokesvel = None
         self.bcheat = [BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW, BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW]
         self.bcheatvals = [273.0, 0.0, 0.0, 1623.0, 0.0, 0.0]
         self.stokes_rtol, self.stokes_maxit = DEFAULT_RTOL, DEFAULT_MAXIT
@@ -556,7 +621,7 @@ class Simulation3:
     + refill of depleted cells inside the end-of-step sort (Options3.tracdens / tracdens_min / inject_seed / inject_unique_ids;
     refill() does it without a step).  step() reports ninjected, nrefilled (cells) and nempty (cells that held no tracer: their new
     tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank,
-    Stokes walls free-slip or no-slip per wall (Options3.bcstokes = [z0, x0, y0, zL, xL, yL]); a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
+    Stokes walls free-slip or no-slip per wall (Options3.bcstokes = [z0, x0, y0, zL, xL, yL]), a no-slip wall may move in its own plane (Options3.bcstokesvel, set_wall_velocity); a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
     axis strictly increasing from 0 to L[d]): the marker kernels then find cells by search in the coordinates (the rule is in
     include/pylamp_hip.h at pl3_mic_set_search), while the time-step rules and the subgrid time scale keep the mean spacing.  Options3.resident = True runs the same sequence inside the library with every grid field
     kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Not built: the fence-off deletion path, surface stabilisation, several ranks -- each is rejected with an error that names it."""
@@ -594,7 +659,9 @@ class Simulation3:
             raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
         self.ctx = Context3(self.nx, self.grid, device)
+        self.bcstokesvel = wall_velocities(o.bcstokesvel, self.bcstokes, "Simulation3: Options3.bcstokesvel")
         self.ctx.set_stokes_walls(self.bcstokes)        # the resident step and the device advection velocity read them from the context
+        self.ctx.set_wall_velocity(self.bcstokesvel)
         if o.marker_search:
             self.ctx.set_marker_search(True)
         self.it = 0
@@ -606,6 +673,13 @@ class Simulation3:
         self._stepped = False                    # resident: the library holds the fields of a step
         if tr_x is not None:
             self.upload(tr_x, tr_f)
+
+    def set_wall_velocity(self, wallvel):
+        """New velocities (Uz, Ux, Uy) of the six walls, (6, 3) (None: all at rest), from the next step on; the kinds stay those of
+        Options3.bcstokes, so only the tangential components of its NOSLIP walls may be non-zero."""
+        v = wall_velocities(wallvel, self.bcstokes, "Simulation3.set_wall_velocity")
+        self.ctx.set_wall_velocity(v)
+        self.bcstokesvel = v
 
     # -- tracer state ------------------------------------------------------------------------------------------------
     def _lib_call(self, name, *args):
@@ -799,10 +873,12 @@ class Simulation3:
             diffusivity = f["kz"] / (f["rho"] * f["cp"])
             tstep_temp = o.tstep_modifier * np.min(dx) ** 2 / np.max(2 * diffusivity)
             tstep_temp = max(min(tstep_temp, o.tstep_dif_max), o.tstep_dif_min)
-        A, _ = makeStokesMatrix(self.nx, self.grid, f["etas"], f["etan"], f["rho"], bc=self.bcstokes, grav=o.grav, ctx=self.ctx)
+        A, _ = makeStokesMatrix(self.nx, self.grid, f["etas"], f["etan"], f["rho"], bc=self.bcstokes, grav=o.grav, ctx=self.ctx,
+                                wallvel=self.bcstokesvel)
         x = solve(A, rtol=o.stokes_rtol, maxit=o.stokes_maxit)
         newvel, pres = x2vp(x, self.nx)
-        tstep_stokes = o.tstep_modifier * np.min(dx) / max(np.max(v) for v in newvel)
+        with np.errstate(divide="ignore"):       # (a fluid at rest: the clamp below takes tstep_adv_max)
+            tstep_stokes = o.tstep_modifier * np.min(dx) / max(np.max(v) for v in newvel)
         tstep_stokes = max(min(tstep_stokes, o.tstep_adv_max), o.tstep_adv_min)
         if o.do_heatdiff:
             limiter = "H" if tstep_temp < tstep_stokes else "S"
@@ -822,7 +898,7 @@ class Simulation3:
                 self.temp_to_tracers(newtemp - f["T"], False, tstep)
             self._newtemp = newtemp
             f["temp"] = newtemp
-        grids, vels = advection_velocity(newvel, self.gridmp, self.nx, self.bcstokes)
+        grids, vels = advection_velocity(newvel, self.gridmp, self.nx, self.bcstokes, self.bcstokesvel)
         rep.update(self.advect(grids, vels, tstep, self.it))
         self.totaltime += tstep
         rep["time"] = self.totaltime; rep["ntrac"] = self.count()
