@@ -206,6 +206,10 @@ int  pl_stokes_apply_probe(pl_ctx* ctx, int scaled, int mode, int rows, const do
 /* out = D_r v by the solver's own kernel: the scaling the right-hand side gets before the Krylov iteration.  One rank only. */
 int  pl_stokes_scale_rows(pl_ctx* ctx, const double* v, double* out);
 int  pl_stokes_mg_info(pl_ctx* ctx, int* nlevels, double* lmax, int max_levels);
+/* What the last hierarchy build and preconditioner application chose (read-only; any pointer may be NULL): smoother[l] of each of the
+ * first max_levels levels (-1 point Jacobi, 0 z-lines, 1 x-lines), nu[4] = sweeps (pre, post, pre of level 0, post of level 0), the
+ * Chebyshev ratio of the smoothing window, and whether stage 1 applies the wall stencils of the pressure block. */
+int  pl_stokes_mg_plan(pl_ctx* ctx, int* smoother, int max_levels, int* nu, double* ratio, int* wall_ps);
 /* Average duration (HIP events) of one Chebyshev smoothing sweep on the finest multigrid level -- the kernel
  * with the largest share of a time step (80 B/node algorithmic).  Call after at least one solve. */
 int  pl_stokes_sweep_bench(pl_ctx* ctx, int reps, double* avg_ms);

@@ -159,6 +159,7 @@ SIGNATURES = {
     "pl_stokes_apply_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [c_double_p] * 4 + [C.c_double] + [c_double_p] * 3),
     "pl_stokes_scale_rows": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl_stokes_mg_info": (C.c_int, [C.c_void_p, c_int_p, c_double_p, C.c_int]),
+    "pl_stokes_mg_plan": (C.c_int, [C.c_void_p, c_int_p, C.c_int, c_int_p, c_double_p, c_int_p]),
     "pl_stokes_mg_precision": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "pl_stokes_set_mg_precision": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),
     "pl_stokes_sweep_bench": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),

@@ -3846,6 +3846,22 @@ __global__ void k_axpy_dev_scalar(long long n, double* __restrict__ z, const dou
 void pl_stokes_deflation(pl_ctx* ctx, bool persistent) { solver_of(ctx)->defl_persistent = persistent; }
 
 // Solve A x = b for device vectors (3 planes, UNSCALED b).  x is S->x on return.
+// Whether stage 1 of the preconditioner uses the wall stencils of the pressure block (prec_p_value): one rank, some cell at a wall at
+// least 2 x longer along the wall than across (PYLAMP_SCHUR_WALL=0: never, =1: wherever the local aspect ratio reaches 2, whatever
+// the walls look like).  A function of the grid and the knob alone; every entry point that applies the preconditioner decides it here.
+static void stokes_wall_ps(pl_ctx* ctx) {
+    const std::vector<double>& zc = ctx->geom.zc; const std::vector<double>& xc = ctx->geom.xc;
+    const int nz = ctx->nz, nx = ctx->nx;
+    double dzmin = 1e300, dxmin = 1e300;
+    for (int i = 0; i + 1 < nz; i++) dzmin = std::min(dzmin, zc[i + 1] - zc[i]);
+    for (int j = 0; j + 1 < nx; j++) dxmin = std::min(dxmin, xc[j + 1] - xc[j]);
+    const double wx = std::max(xc[1] - xc[0], xc[nx - 1] - xc[nx - 2]) / dzmin;        // widest aspect of a cell in the x-wall columns
+    const double wz = std::max(zc[1] - zc[0], zc[nz - 1] - zc[nz - 2]) / dxmin;        // ... of a cell in the z-wall rows
+    const char* e = getenv("PYLAMP_SCHUR_WALL");
+    const int knob = e ? atoi(e) : -1;
+    ctx->sop.wall_ps = (ctx->nranks == 1 && nz >= 9 && nx >= 9 && knob != 0 && (knob == 1 || wx >= 2.0 || wz >= 2.0)) ? 1 : 0;
+}
+
 int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double rtol, int maxit,
                            pl_solve_stats* st) {
     PlSolver* S = solver_of(ctx);
@@ -3858,20 +3874,7 @@ int pl_stokes_solve_device(pl_ctx* ctx, const double* b_dev, bool use_x0, double
     PL_TRY(build_hierarchy(ctx, S));
     if (trace_t) tph[1] = now();
     const PlGeom& g = ctx->geom.d;
-    {   // wall stencils of the pressure block (prec_p_value): one rank, some cell at a wall at least 2 x longer along the wall than
-        // across (PYLAMP_SCHUR_WALL=0: never, =1: wherever the local aspect ratio reaches 2, whatever the walls look like)
-        const std::vector<double>& zc = ctx->geom.zc; const std::vector<double>& xc = ctx->geom.xc;
-        const int nz = ctx->nz, nx = ctx->nx;
-        double dzmin = 1e300, dzmax = 0.0, dxmin = 1e300, dxmax = 0.0;
-        for (int i = 0; i + 1 < nz; i++) { dzmin = std::min(dzmin, zc[i + 1] - zc[i]); dzmax = std::max(dzmax, zc[i + 1] - zc[i]); }
-        for (int j = 0; j + 1 < nx; j++) { dxmin = std::min(dxmin, xc[j + 1] - xc[j]); dxmax = std::max(dxmax, xc[j + 1] - xc[j]); }
-        const double wx = std::max(xc[1] - xc[0], xc[nx - 1] - xc[nx - 2]) / dzmin;        // widest aspect of a cell in the x-wall columns
-        const double wz = std::max(zc[1] - zc[0], zc[nz - 1] - zc[nz - 2]) / dxmin;        // ... of a cell in the z-wall rows
-        const char* e = getenv("PYLAMP_SCHUR_WALL");
-        const int knob = e ? atoi(e) : -1;
-        ctx->sop.wall_ps = (ctx->nranks == 1 && nz >= 9 && nx >= 9 && knob != 0 && (knob == 1 || wx >= 2.0 || wz >= 2.0)) ? 1 : 0;
-        (void)dzmax; (void)dxmax;
-    }
+    stokes_wall_ps(ctx);
     PlStokesOp sop = ctx->sop;
     PlStokesOp sop_scaled = sop; sop_scaled.scaled = 1;
     S->napply = 0; S->nprec = 0;
@@ -4342,6 +4345,7 @@ extern "C" int pl_stokes_precond_apply(pl_ctx* ctx, const double* r, double* z) 
     PlSolver* S = solver_of(ctx);
     PL_TRY(stokes_alloc(ctx, S));
     PL_TRY(build_hierarchy(ctx, S));
+    stokes_wall_ps(ctx);
     const PlGeom& g = ctx->geom.d;
     PL_TRY(pl_vec3_upload(ctx, g, r, S->s));
     hipLaunchKernelGGL(k_stokes_scale_rows, grid2d(g), dim3(64, 4), 0, ctx->stream, ctx->sop, S->s);
@@ -4368,6 +4372,18 @@ extern "C" int pl_stokes_mg_info(pl_ctx* ctx, int* nlevels, double* lmax, int ma
     PlSolver* S = solver_of(ctx);
     if (nlevels) *nlevels = (int)S->levels.size();
     for (int l = 0; lmax && l < max_levels && l < (int)S->levels.size(); l++) lmax[l] = S->levels[l]->lmax;
+    return 0;
+}
+
+// What the last hierarchy build and preconditioner application chose (read-only): the smoother of every level (-1 point Jacobi,
+// 0 z-lines, 1 x-lines), the sweeps nu[4] = (pre, post, pre of level 0, post of level 0), the Chebyshev ratio of the smoothing
+// window, and whether stage 1 uses the wall stencils of the pressure block.  Any pointer may be NULL.
+extern "C" int pl_stokes_mg_plan(pl_ctx* ctx, int* smoother, int max_levels, int* nu, double* ratio, int* wall_ps) {
+    PlSolver* S = solver_of(ctx);
+    for (int l = 0; smoother && l < max_levels && l < (int)S->levels.size(); l++) smoother[l] = S->levels[l]->line_z ? S->levels[l]->line_ax : -1;
+    if (nu) { nu[0] = S->nu_pre; nu[1] = S->nu_post; level_nu(S, 0, nu[2], nu[3]); }
+    if (ratio) *ratio = S->cheb_ratio;
+    if (wall_ps) *wall_ps = ctx->sop.wall_ps;
     return 0;
 }
 

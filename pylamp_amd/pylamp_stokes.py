@@ -138,6 +138,14 @@ class StokesOperator:
         self._ctx.check(self._ctx.lib.pl_stokes_mg_info(self._ctx.handle(), C.byref(n), lm, 32))
         return n.value, [lm[k] for k in range(n.value)]
 
+    def mg_plan(self):
+        """What the last preconditioner build chose: dict(smoother=[-1 point | 0 z-lines | 1 x-lines per level], nu=(pre, post),
+        nu0=(pre, post) of level 0, ratio=Chebyshev ratio, wall=wall stencils of the pressure block on)."""
+        n = self.mg_info()[0]
+        sm = (C.c_int * 32)(); nu = (C.c_int * 4)(); ratio = C.c_double(); wall = C.c_int()
+        self._ctx.check(self._ctx.lib.pl_stokes_mg_plan(self._ctx.handle(), sm, 32, nu, C.byref(ratio), C.byref(wall)))
+        return dict(smoother=[sm[k] for k in range(n)], nu=(nu[0], nu[1]), nu0=(nu[2], nu[3]), ratio=ratio.value, wall=bool(wall.value))
+
     def mg_precision(self):
         """(levels, levels in FP32) of the multigrid hierarchy of the last solve."""
         n = C.c_int(); nf = C.c_int()
