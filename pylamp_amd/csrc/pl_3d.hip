@@ -18,7 +18,6 @@
 #include "pl_step3.h"
 #include <algorithm>
 #include <cmath>
-#include <functional>
 
 #define P3_PAD 16                    // left padding of a y-line: node k = 0 is 128-B aligned
 // Coefficient tables are read through the constant address space: with a wave-uniform index (the z and x axes: blockIdx.z and the
@@ -971,20 +970,25 @@ __global__ void k3_xr_update(long long n, double* __restrict__ x, const double* 
     }
 }
 #define D3_BLOCKS 1024
+// the end of every reduction kernel (256 threads): part[NQ b + q] = the sum of acc[q] over workgroup b -- a shuffle tree per wave, then
+// the four wave sums in order
+template <int NQ> __device__ inline void block_sums3(const double (&acc)[NQ], double* __restrict__ part) {
+    __shared__ double sh[NQ][4];
+    for (int q = 0; q < NQ; q++) {
+        double a = acc[q];
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
+        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < NQ) part[NQ * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+}
 // up to five dot products in one pass: part[5 b + q] = sum a_q[t] b_q[t]
 struct Dot5 { const double* a[5]; const double* b[5]; int n; };
 __global__ __launch_bounds__(256) void k3_dots(long long n, Dot5 d, double* __restrict__ part) {
     double acc[5] = {0, 0, 0, 0, 0};
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256)
         for (int q = 0; q < d.n; q++) acc[q] += d.a[q][t] * d.b[q][t];
-    __shared__ double sh[5][4];
-    for (int q = 0; q < 5; q++) {
-        double a = acc[q];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) part[5 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+    block_sums3<5>(acc, part);
 }
 // The second reduction point of BiCGStab with everything the velocity-error estimate needs, in ONE pass (one rank; vectors of 4 consecutive
 // arrays of `vol` elements, the pressure array last): part[11 b + ..] = t.s, t.t, r~.s, r~.t, s.s | the same three of the pressure array
@@ -1002,14 +1006,7 @@ __global__ __launch_bounds__(256) void k3_dots11(Fuse11 a, double* __restrict__ 
             if (a.yw) { const double Y = a.yw[e - np]; acc[9] += Y * S; acc[10] += Y * T; }
         } else if (a.x) { const double X = a.x[e] + (a.dx ? a.dx[e] : 0.0); acc[8] += X * X; }
     }
-    __shared__ double sh[11][4];
-    for (int q = 0; q < 11; q++) {
-        double v = acc[q];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 11) part[11 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+    block_sums3<11>(acc, part);
 }
 // x += alpha y + omega z, r = s - omega t, and the NEXT direction p = r + beta (p - omega v) in the same pass
 __global__ void k3_xrp_update(long long n, double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z, double* __restrict__ r,
@@ -1133,19 +1130,22 @@ __global__ __launch_bounds__(256) void k3_dots_own(G3 g, int na, Dot5 d, double*
         for (int kk = threadIdx.x; kk < g.n[2]; kk += 256)
             for (int u = 0; u < d.n; u++) acc[u] += d.a[u][base + kk] * d.b[u][base + kk];
     }
-    __shared__ double sh[5][4];
-    for (int u = 0; u < 5; u++) {
-        double a = acc[u];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if ((threadIdx.x & 63) == 0) sh[u][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) part[5 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+    block_sums3<5>(acc, part);
 }
 
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
+// A Krylov vector: na (1, 3 or 4) consecutive arrays of g->vol elements each -- one allocation (need_vecs, need_hvecs).  Array q is
+// v[q]; a 4-array Stokes vector is its velocity part vel() followed by its pressure part prs().
+struct Vec3 {
+    double* p; int na; const G3* g;
+    long long n() const { return na * g->vol; }
+    double* operator[](int q) const { return p + q * g->vol; }
+    Vec3 part(int q, int nq) const { return Vec3{p + q * g->vol, nq, g}; }
+    Vec3 vel() const { return part(0, 3); }
+    Vec3 prs() const { return part(3, 1); }
+};
 struct G3Host { G3 d; std::vector<double> c[3]; double* tables = nullptr; };
 struct Lev3 {
     G3Host gh; Op3 op{};
@@ -1166,14 +1166,16 @@ struct pl3_ctx {
     int gn[3] = {0, 0, 0}; std::vector<double> gcoord[3];     // the global grid
     double* hbuf = nullptr; size_t hbuf_n = 0;                // halo exchange: send lo | send hi | recv lo | recv hi
     long long halo_calls = 0, reduce_calls = 0;
-    bool halo_failed = false;       // an exchange inside the V-cycle failed (its callers are void): the preconditioner reports it
+    // State of the RUNNING solve, not of the context: operator and preconditioner applications, counted by stokes_A3 / stokes_M3 / heat_A3
+    // (plain functions of the context, so the counters live here).  pl3_stokes_solve and pl3_heat_solve reset them at their start.
+    int napply = 0, nprec = 0;
     std::string err;
     G3Host geom;
     double *es = nullptr, *en = nullptr, *rho = nullptr; Op3 op{}; bool op_ready = false;
     int noslip = 0;                 // pl3_stokes_set_walls: bit w of [z0, x0, y0, zL, xL, yL] set = no-slip; kept across pl3_stokes_set_coeffs
     Pl3WallVel wallvel{};           // pl3_stokes_set_wall_velocity: U_w = (Uz, Ux, Uy) per wall and the mask of the moving ones; kept likewise
     std::vector<Lev3*> levels;
-    double* vec[14][4] = {{nullptr}};           // BiCGStab work vectors (4 arrays each)
+    double* vec[14] = {nullptr};                // BiCGStab work vectors: 4 consecutive arrays each (svec)
     double* part = nullptr; double* hpart = nullptr;
     double* stage = nullptr; size_t stage_bytes = 0;
     // heat
@@ -1195,6 +1197,20 @@ static int p3_fail(pl3_ctx* ctx, const std::string& m) { if (ctx) ctx->err = m; 
 void pl3_count_copy(pl3_ctx* ctx, size_t bytes) {
     const int c = bytes >= sizeof(double) * (size_t)ctx->gn[0] * ctx->gn[1] * ctx->gn[2] ? 0 : 2;
     ctx->xfer[c]++; ctx->xfer[c + 1] += (int64_t)bytes;
+}
+static Vec3 svec(pl3_ctx* ctx, int v) { return Vec3{ctx->vec[v], 4, &ctx->geom.d}; }          // Stokes work vector v
+static Vec3 hvec(pl3_ctx* ctx, int v) { return Vec3{ctx->hvec[v], 1, &ctx->geom.d}; }         // heat work vector v
+static Vec3 arr3(pl3_ctx* ctx, double* a) { return Vec3{a, 1, &ctx->geom.d}; }                // one array of the finest grid
+// the arrays of a vector as the kernels and upload3 / download3 / halo3 take them
+static W4 wv4(const Vec3& v) { W4 w{}; for (int q = 0; q < v.na; q++) w.p[q] = v[q]; return w; }
+static V4 cv4(const Vec3& v) { V4 w{}; for (int q = 0; q < v.na; q++) w.p[q] = v[q]; return w; }
+static W3 wv3(const Vec3& v) { W3 w; for (int q = 0; q < 3; q++) w.p[q] = v[q]; return w; }
+static V3 cv3(const Vec3& v) { V3 w; for (int q = 0; q < 3; q++) w.p[q] = v[q]; return w; }
+static V3 cv3(double* const* p) { V3 v; for (int q = 0; q < 3; q++) v.p[q] = p[q]; return v; }  // (a multigrid level's three arrays)
+static W3 wv3(double* const* p) { W3 v; for (int q = 0; q < 3; q++) v.p[q] = p[q]; return v; }
+// a per-node kernel over the block of g
+template <typename K, typename... Args> static void launch3(pl3_ctx* ctx, const G3& g, K kernel, Args... args) {
+    hipLaunchKernelGGL(kernel, grid3(g), dim3(64, 4), 0, ctx->stream, args...);
 }
 
 // gn / c: the GLOBAL grid of the level; the block of this rank follows from ctx->P / ctx->pc: C = (gn - 1) / P cells per block, first
@@ -1282,7 +1298,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
     for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf}) if (q) (void)hipFree(q);
-    for (auto& v : ctx->vec) if (v[0]) (void)hipFree(v[0]);
+    for (double* q : ctx->vec) if (q) (void)hipFree(q);
     for (double* q : ctx->hk) if (q) (void)hipFree(q);
     for (double* q : ctx->hvec) if (q) (void)hipFree(q);
     if (ctx->hpart) (void)hipHostFree(ctx->hpart);
@@ -1316,7 +1332,7 @@ static int download3(pl3_ctx* ctx, double* const* src, int ncomp, double* host) 
     const size_t count = (size_t)g.gn[0] * g.gn[1] * g.gn[2] * ncomp, bytes = count * sizeof(double);
     P3_TRY(stage3(ctx, bytes));
     if (ctx->nranks > 1) P3_HIP(ctx, hipMemsetAsync(ctx->stage, 0, bytes, ctx->stream));
-    for (int q = 0; q < ncomp; q++) hipLaunchKernelGGL(k3_to_host, grid3(g), dim3(64, 4), 0, ctx->stream, g, (const double*)src[q], ncomp, q, ctx->stage);
+    for (int q = 0; q < ncomp; q++) launch3(ctx, g, k3_to_host, g, src[q], ncomp, q, ctx->stage);
     pl3_count_copy(ctx, bytes);
     P3_HIP(ctx, hipMemcpyAsync(host, ctx->stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1328,13 +1344,7 @@ static int download3(pl3_ctx* ctx, double* const* src, int ncomp, double* host) 
 // One ring of nodes around the block is all the stencils reach (faces, the edge neighbours (i-1, j+1) ... of the momentum rows, and the
 // corner nodes of the full-weighting restriction): exchanged axis by axis -- z planes, then x planes including the z ring just
 // received, then y planes including both -- so that 6 messages carry all 26 neighbours' nodes.
-static int halo3_impl(pl3_ctx* ctx, const G3& g, double* const* arr, int na);
 static int halo3(pl3_ctx* ctx, const G3& g, double* const* arr, int na) {
-    const int rc = halo3_impl(ctx, g, arr, na);
-    if (rc) ctx->halo_failed = true;
-    return rc;
-}
-static int halo3_impl(pl3_ctx* ctx, const G3& g, double* const* arr, int na) {
     if (ctx->nranks <= 1) return 0;
     ctx->halo_calls++;
     for (int a = 0; a < 3; a++) {
@@ -1362,7 +1372,7 @@ static int halo3_impl(pl3_ctx* ctx, const G3& g, double* const* arr, int na) {
     P3_HIP(ctx, hipGetLastError());
     return 0;
 }
-static int halo3_1(pl3_ctx* ctx, const G3& g, double* arr) { double* a[1] = {arr}; return halo3(ctx, g, a, 1); }
+static int halo3(pl3_ctx* ctx, const Vec3& v) { return halo3(ctx, *v.g, wv4(v).p, v.na); }
 static int allreduce3(pl3_ctx* ctx, double* v, int n, int op) {
     if (ctx->nranks <= 1) return 0;
     ctx->reduce_calls++;
@@ -1371,13 +1381,9 @@ static int allreduce3(pl3_ctx* ctx, double* v, int n, int op) {
 }
 static int need_vecs(pl3_ctx* ctx, int nvec) {
     const long long vol = ctx->geom.d.vol;
-    // the four arrays of a work vector are ONE allocation (vec[v][q] = vec[v][0] + q vol): the flat vector kernels and the reductions
-    // of BiCGStab then take a whole vector per launch (and per host synchronisation) instead of one array
-    for (int v = 0; v < nvec; v++)
-        if (!ctx->vec[v][0]) {
-            P3_TRY(dmal(ctx, &ctx->vec[v][0], 4 * vol));
-            for (int q = 1; q < 4; q++) ctx->vec[v][q] = ctx->vec[v][0] + (long long)q * vol;
-        }
+    // the four arrays of a work vector are ONE allocation (array q at vec[v] + q vol): the flat vector kernels and the reductions
+    // of BiCGStab take a whole vector per launch (and per host synchronisation)
+    for (int v = 0; v < nvec; v++) if (!ctx->vec[v]) P3_TRY(dmal(ctx, &ctx->vec[v], 4 * vol));
     if (!ctx->part) {
         P3_TRY(dmal(ctx, &ctx->part, 11 * D3_BLOCKS));
         P3_HIP(ctx, hipHostMalloc((void**)&ctx->hpart, 11 * D3_BLOCKS * sizeof(double)));
@@ -1442,10 +1448,7 @@ extern "C" int pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const dou
     P3_HIP(ctx, hipSetDevice(ctx->device));
     const G3& g = ctx->geom.d;
     for (double** q : {&ctx->es, &ctx->en, &ctx->rho}) if (!*q) P3_TRY(dmal(ctx, q, g.vol));
-    double* d1[1];
-    d1[0] = ctx->es; P3_TRY(upload3(ctx, etas, 1, d1));
-    d1[0] = ctx->en; P3_TRY(upload3(ctx, etan, 1, d1));
-    d1[0] = ctx->rho; P3_TRY(upload3(ctx, rho, 1, d1));
+    P3_TRY(upload3(ctx, etas, 1, &ctx->es)); P3_TRY(upload3(ctx, etan, 1, &ctx->en)); P3_TRY(upload3(ctx, rho, 1, &ctx->rho));
     const size_t N = (size_t)g.gn[0] * g.gn[1] * g.gn[2];
     double mes = INFINITY, men = INFINITY; bool nes = false, nen = false;
     for (size_t t = 0; t < N; t++) { if (etas[t] != etas[t]) nes = true; else mes = std::min(mes, etas[t]); if (etan[t] != etan[t]) nen = true; else men = std::min(men, etan[t]); }
@@ -1537,33 +1540,29 @@ extern "C" int pl3_stokes_get_scaling(pl3_ctx* ctx, double* kc, double* kb) {
     if (kc) *kc = ctx->op.Kc; if (kb) *kb = ctx->op.Kb;
     return 0;
 }
-static V4 cv4(double* const* p) { V4 v; for (int q = 0; q < 4; q++) v.p[q] = p[q]; return v; }
-static W4 wv4(double* const* p) { W4 v; for (int q = 0; q < 4; q++) v.p[q] = p[q]; return v; }
-static V3 cv3(double* const* p) { V3 v; for (int q = 0; q < 3; q++) v.p[q] = p[q]; return v; }
-static W3 wv3(double* const* p) { W3 v; for (int q = 0; q < 3; q++) v.p[q] = p[q]; return v; }
 
 // y = A x (scaled: D_r A x): the marching LDS kernel for the interior rows + the per-node kernel on the rim, or the per-node kernel alone
-template <bool SCALED> static void launch_apply3(pl3_ctx* ctx, const Op3& op, double* const* in, double* const* out) {
+template <bool SCALED> static void launch_apply3(pl3_ctx* ctx, const Op3& op, const Vec3& in, const Vec3& out) {
     if (k3_use_lds(op.g)) {
         hipLaunchKernelGGL(k3_apply_m<SCALED>, grid3m(op.g), dim3(64, 4), 0, ctx->stream, op, cv4(in), wv4(out), k3_band(), k3m_zc(op.g));
-    } else hipLaunchKernelGGL(k3_apply<SCALED>, grid3(op.g), dim3(64, 4), 0, ctx->stream, op, cv4(in), wv4(out), 0);
+    } else launch3(ctx, op.g, k3_apply<SCALED>, op, cv4(in), wv4(out), 0);
 }
 extern "C" int pl3_stokes_apply(pl3_ctx* ctx, const double* x, double* y) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 2));
-    P3_TRY(upload3(ctx, x, 4, ctx->vec[0]));                 // (the upload fills the ring of nodes around the block as well)
-    launch_apply3<false>(ctx, ctx->op, ctx->vec[0], ctx->vec[1]);
+    P3_TRY(upload3(ctx, x, 4, wv4(svec(ctx, 0)).p));         // (the upload fills the ring of nodes around the block as well)
+    launch_apply3<false>(ctx, ctx->op, svec(ctx, 0), svec(ctx, 1));
     P3_HIP(ctx, hipGetLastError());
-    return download3(ctx, ctx->vec[1], 4, y);
+    return download3(ctx, wv4(svec(ctx, 1)).p, 4, y);
 }
 static int stokes_rhs3(pl3_ctx* ctx, double* rhs, int scaled) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 2));
-    hipLaunchKernelGGL(k3_rhs, grid3(ctx->op.g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(ctx->vec[1]), scaled, ctx->wallvel);
+    launch3(ctx, ctx->op.g, k3_rhs, ctx->op, wv4(svec(ctx, 1)), scaled, ctx->wallvel);
     P3_HIP(ctx, hipGetLastError());
-    return download3(ctx, ctx->vec[1], 4, rhs);
+    return download3(ctx, wv4(svec(ctx, 1)).p, 4, rhs);
 }
 extern "C" int pl3_stokes_rhs(pl3_ctx* ctx, double* rhs) { return stokes_rhs3(ctx, rhs, 0); }
 // the row-scaled right-hand side D_r b that pl3_stokes_solve(rhs = NULL) iterates on
@@ -1572,10 +1571,11 @@ extern "C" int pl3_stokes_apply_bench(pl3_ctx* ctx, int scaled, int reps, double
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 2));
-    for (int q = 0; q < 4; q++) hipLaunchKernelGGL(k3_random, grid3(ctx->op.g), dim3(64, 4), 0, ctx->stream, ctx->op.g, ctx->vec[0][q], 99u + q);
+    const Vec3 in = svec(ctx, 0), out = svec(ctx, 1);
+    for (int q = 0; q < 4; q++) launch3(ctx, ctx->op.g, k3_random, ctx->op.g, in[q], 99u + q);
     auto launch = [&]() {
-        if (scaled) launch_apply3<true>(ctx, ctx->op, ctx->vec[0], ctx->vec[1]);
-        else launch_apply3<false>(ctx, ctx->op, ctx->vec[0], ctx->vec[1]);
+        if (scaled) launch_apply3<true>(ctx, ctx->op, in, out);
+        else launch_apply3<false>(ctx, ctx->op, in, out);
     };
     launch();
     P3_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -1588,53 +1588,26 @@ extern "C" int pl3_stokes_apply_bench(pl3_ctx* ctx, int scaled, int reps, double
 }
 
 // ---- reductions -----------------------------------------------------------------------------------------------------------
-static int dots3(pl3_ctx* ctx, long long n, int nd, const double* const* a, const double* const* b, double* out) {
-    Dot5 d{}; d.n = nd;
-    for (int q = 0; q < nd; q++) { d.a[q] = a[q]; d.b[q] = b[q]; }
-    if (ctx->nranks > 1) {
-        // several ranks: only the OWNED nodes count (the rings hold copies of the neighbours' values); n = m x (elements of one array
-        // of the finest grid or of a multigrid level), m <= 4 consecutive arrays per vector
-        const G3* g = nullptr;
-        if (n % ctx->geom.d.vol == 0 && n / ctx->geom.d.vol <= 4) g = &ctx->geom.d;
-        for (size_t l = 0; !g && l < ctx->levels.size(); l++) if (n % ctx->levels[l]->gh.d.vol == 0 && n / ctx->levels[l]->gh.d.vol <= 4) g = &ctx->levels[l]->gh.d;
-        if (!g) return p3_fail(ctx, "dots3: vector length matches no grid level (internal error)");
-        hipLaunchKernelGGL(k3_dots_own, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, *g, (int)(n / g->vol), d, ctx->part);
-        pl3_count_copy(ctx, 5 * D3_BLOCKS * sizeof(double));
-        P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 5 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int q = 0; q < nd; q++) { double sum = 0.0; for (int k = 0; k < D3_BLOCKS; k++) sum += ctx->hpart[5 * k + q]; out[q] = sum; }
-        return allreduce3(ctx, out, nd, 0);
-    }
-    hipLaunchKernelGGL(k3_dots, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, n, d, ctx->part);
-    pl3_count_copy(ctx, 5 * D3_BLOCKS * sizeof(double));
-        P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 5 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+// the end of every reduction on the host: the stride x D3_BLOCKS block partials of the kernel come over in one copy and one synchronisation
+// and are summed per quantity, block 0 upward
+static int sum_partials3(pl3_ctx* ctx, int stride, int nq, double* out) {
+    pl3_count_copy(ctx, stride * D3_BLOCKS * sizeof(double));
+    P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, stride * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int q = 0; q < nd; q++) { double s = 0.0; for (int k = 0; k < D3_BLOCKS; k++) s += ctx->hpart[5 * k + q]; out[q] = s; }
+    for (int q = 0; q < nq; q++) { double s = 0.0; for (int k = 0; k < D3_BLOCKS; k++) s += ctx->hpart[stride * k + q]; out[q] = s; }
     return 0;
 }
-// the na arrays of a vector follow each other in memory (need_vecs)
-static bool contig3(double* const* a, int na, long long vol) {
-    for (int c = 1; c < na; c++) if (a[c] != a[0] + (long long)c * vol) return false;
-    return true;
+// nd <= 5 dot products a[q] . b[q] of vectors of one shape in one pass.  Several ranks: only the OWNED nodes count (the rings hold copies
+// of the neighbours' values), and the sums go over the ranks.
+static int dots3(pl3_ctx* ctx, int nd, const Vec3* a, const Vec3* b, double* out) {
+    Dot5 d{}; d.n = nd;
+    for (int q = 0; q < nd; q++) { d.a[q] = a[q].p; d.b[q] = b[q].p; }
+    if (ctx->nranks > 1) hipLaunchKernelGGL(k3_dots_own, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, *a[0].g, a[0].na, d, ctx->part);
+    else hipLaunchKernelGGL(k3_dots, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, a[0].n(), d, ctx->part);
+    P3_TRY(sum_partials3(ctx, 5, nd, out));
+    return allreduce3(ctx, out, nd, 0);
 }
-// dot products of multi-array vectors (na arrays each)
-static int vdots(pl3_ctx* ctx, long long vol, int na, int nd, double* const* const* a, double* const* const* b, double* out) {
-    bool flat = na > 1;
-    for (int q = 0; q < nd && flat; q++) flat = contig3(a[q], na, vol) && contig3(b[q], na, vol);
-    if (flat) {                                    // one pass, one copy, one synchronisation for the whole vector
-        const double* aa[5]; const double* bb[5];
-        for (int q = 0; q < nd; q++) { aa[q] = a[q][0]; bb[q] = b[q][0]; }
-        return dots3(ctx, (long long)na * vol, nd, aa, bb, out);
-    }
-    for (int q = 0; q < nd; q++) out[q] = 0.0;
-    for (int c = 0; c < na; c++) {
-        const double* aa[5]; const double* bb[5]; double o[5];
-        for (int q = 0; q < nd; q++) { aa[q] = a[q][c]; bb[q] = b[q][c]; }
-        P3_TRY(dots3(ctx, vol, nd, aa, bb, o));
-        for (int q = 0; q < nd; q++) out[q] += o[q];
-    }
-    return 0;
-}
+static int dot3(pl3_ctx* ctx, const Vec3& a, const Vec3& b, double* out) { return dots3(ctx, 1, &a, &b, out); }
 
 // ---- multigrid -----------------------------------------------------------------------------------------------------------
 static int build_levels3(pl3_ctx* ctx) {
@@ -1668,34 +1641,40 @@ static int build_levels3(pl3_ctx* ctx) {
         Lev3* L = ctx->levels[l];
         if (l > 0) {
             Lev3* F = ctx->levels[l - 1];
-            hipLaunchKernelGGL(k3_coarsen, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, F->gh.d, (const double*)F->es, (const double*)F->en, L->gh.d, L->es, L->en);
-            P3_TRY(halo3_1(ctx, L->gh.d, L->es)); P3_TRY(halo3_1(ctx, L->gh.d, L->en));      // the rows of this level and the next coarsening read the ring
+            launch3(ctx, L->gh.d, k3_coarsen, F->gh.d, F->es, F->en, L->gh.d, L->es, L->en);
+            P3_TRY(halo3(ctx, L->gh.d, &L->es, 1)); P3_TRY(halo3(ctx, L->gh.d, &L->en, 1));  // the rows of this level and the next coarsening read the ring
         }
         L->op = ctx->op; L->op.g = L->gh.d; L->op.es = L->es; L->op.en = L->en; L->op.slave = (l == 0) ? ctx->op.slave : 0;
-        hipLaunchKernelGGL(k3_dinv, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, wv3(L->dinv));
-        P3_TRY(halo3(ctx, L->gh.d, L->dinv, 3));            // (a slaved row reads its master's entry, possibly in the neighbour block)
+        const G3& g = L->gh.d;
+        launch3(ctx, g, k3_dinv, L->op, wv3(L->dinv));
+        P3_TRY(halo3(ctx, g, L->dinv, 3));                  // (a slaved row reads its master's entry, possibly in the neighbour block)
         // lambda_max of D^-1 A_vv by power iteration
-        const long long vol = L->gh.d.vol;
+        const long long vol = g.vol;
         // Warm restart as in the 2-D solver (pl_solver.hip): consecutive solves on one context (a time loop, or the same operator
         // again) start from the eigenvector of the last one and stop as soon as an iteration confirms the last estimate to 1 % --
         // 12 cold iterations per level were 5 % of a 257^3 solve.
         const bool warm = L->eig_valid && L->eig[0];
         if (warm) for (int q = 0; q < 3; q++) P3_HIP(ctx, hipMemcpyAsync(L->v[0][q], L->eig[q], (size_t)vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        else for (int q = 0; q < 3; q++) hipLaunchKernelGGL(k3_random, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->gh.d, L->v[0][q], 777u + q);
+        else for (int q = 0; q < 3; q++) launch3(ctx, g, k3_random, g, L->v[0][q], 777u + q);
         {   // the start vector must satisfy the constraints of THIS operator: close it
             for (int q = 0; q < 3; q++) P3_HIP(ctx, hipMemsetAsync(L->r[q], 0, (size_t)vol * sizeof(double), ctx->stream));
-            P3_TRY(halo3(ctx, L->gh.d, L->v[0], 3));
-            hipLaunchKernelGGL(k3_close, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, wv3(L->v[0]), cv3(L->r));
+            P3_TRY(halo3(ctx, g, L->v[0], 3));
+            launch3(ctx, g, k3_close, L->op, wv3(L->v[0]), cv3(L->r));
         }
         double lam = warm ? L->lmax / 1.1 : 2.5, lam_prev = 0.0;
         for (int it = 0; it < 12; it++) {
             if (warm && it >= 1 && std::fabs(lam - lam_prev) < 0.01 * lam) break;
             lam_prev = lam;
-            P3_TRY(halo3(ctx, L->gh.d, L->v[0], 3));
-            hipLaunchKernelGGL(k3_resid, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[0]), cv3(L->f), wv3(L->v[1]), 1, 0);
-            double* const* aa[2] = {L->v[1], L->v[0]}; double* const* bb[2] = {L->v[1], L->v[0]};
-            double nn[2];
-            P3_TRY(vdots(ctx, vol, 3, 2, aa, bb, nn));
+            P3_TRY(halo3(ctx, g, L->v[0], 3));
+            launch3(ctx, g, k3_resid, L->op, cv3(L->v[0]), cv3(L->f), wv3(L->v[1]), 1, 0);
+            // |A v|^2 and |v|^2.  The three arrays of a level vector are separate allocations: the one per-array reduction left, one pass
+            // per array and the three results added here (contiguous level storage would change the order of these sums, and lmax)
+            double nn[2] = {0.0, 0.0};
+            for (int q = 0; q < 3; q++) {
+                const Vec3 a[2] = {Vec3{L->v[1][q], 1, &g}, Vec3{L->v[0][q], 1, &g}}; double o[2];
+                P3_TRY(dots3(ctx, 2, a, a, o));
+                nn[0] += o[0]; nn[1] += o[1];
+            }
             if (!(nn[0] > 0.0) || !(nn[1] > 0.0)) break;
             lam = std::sqrt(nn[0] / nn[1]);
             for (int q = 0; q < 3; q++) hipLaunchKernelGGL(k3_axpby, g1(vol), dim3(256), 0, ctx->stream, vol, L->v[0][q], 1.0 / std::sqrt(nn[0]), (const double*)L->v[1][q], 0.0, (const double*)L->v[1][q]);
@@ -1709,7 +1688,8 @@ static int build_levels3(pl3_ctx* ctx) {
     return 0;
 }
 // nsweep sweeps; cur = index of the buffer holding the iterate on entry (ignored if zero_guess) and on exit
-static void smooth3(pl3_ctx* ctx, Lev3* L, double* const* f, int nsweep, double ratio, bool zero_guess, int& cur, const W3* final_out = nullptr) {
+static int smooth3(pl3_ctx* ctx, Lev3* L, double* const* f, int nsweep, double ratio, bool zero_guess, int& cur, const W3* final_out = nullptr) {
+    const G3& g = L->gh.d;
     const double lmax = L->lmax, lmin = lmax / ratio, theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
     double rho_old = 1.0 / sigma;
     int prev = (cur + 1) % 3;
@@ -1724,26 +1704,27 @@ static void smooth3(pl3_ctx* ctx, Lev3* L, double* const* f, int nsweep, double 
         const W3 dst = (final_out && k == nsweep - 1) ? *final_out : wv3(L->v[nxt]);
         // several ranks: the sweep reads the iterate one node into the ring (the first sweep from the zero guess: only the right-hand
         // side, at a slave's master)
-        if (k == 0 && zero_guess) (void)halo3(ctx, L->gh.d, (double* const*)f, 3); else (void)halo3(ctx, L->gh.d, L->v[cur], 3);
-        if (!(k == 0 && zero_guess) && k3_use_lds(L->gh.d)) {        // interior rows: the marching LDS kernel; the rim: the per-node kernel
-            hipLaunchKernelGGL(k3_sweep_m<0>, grid3m(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[cur]), vp, cv3(f), dst, c1, c2, k3_band(), k3m_zc(L->gh.d));
-        } else if (k == 0 && zero_guess)
-            hipLaunchKernelGGL(k3_cheb0, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, cv3(f), cv3(L->dinv), dst, c2);
-        else
-        hipLaunchKernelGGL(k3_cheb, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[cur]), vp, cv3(f), dst, c1, c2, 0, 0);
+        const bool first = k == 0 && zero_guess;
+        P3_TRY(halo3(ctx, g, first ? f : L->v[cur], 3));
+        if (first) launch3(ctx, g, k3_cheb0, L->op, cv3(f), cv3(L->dinv), dst, c2);
+        else if (k3_use_lds(g))                 // interior rows: the marching LDS kernel; the rim: the per-node kernel
+            hipLaunchKernelGGL(k3_sweep_m<0>, grid3m(g), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[cur]), vp, cv3(f), dst, c1, c2, k3_band(), k3m_zc(g));
+        else launch3(ctx, g, k3_cheb, L->op, cv3(L->v[cur]), vp, cv3(f), dst, c1, c2, 0, 0);
         prev = cur; cur = nxt;
     }
+    return 0;
 }
-static void vcycle3(pl3_ctx* ctx, size_t l, double* const* f, int& out_buf, const W3* final_out = nullptr) {
+// one V-cycle of level l for the right-hand side f; the result is in buffer out_buf of the level (or in final_out)
+static int vcycle3(pl3_ctx* ctx, size_t l, double* const* f, int& out_buf, const W3* final_out = nullptr) {
     Lev3* L = ctx->levels[l];
+    const G3& g = L->gh.d;
     int cur = 0;
     if (l + 1 == ctx->levels.size()) {
-        const G3& g = L->gh.d;
         double ratio = 0.4 * std::pow((double)g.gn[0] * g.gn[1] * g.gn[2], 2.0 / 3.0); if (ratio < 30.0) ratio = 30.0;
         int n = std::max((int)std::sqrt(ratio), ctx->coarse_sweeps); if (n > 150) n = 150;
-        smooth3(ctx, L, f, n, ratio, true, cur);
+        P3_TRY(smooth3(ctx, L, f, n, ratio, true, cur));
         out_buf = cur;
-        return;
+        return 0;
     }
     // From 10^6 nodes up: V(1,1) on the finest level, V(3,3) below (the 2-D solver's choice, pl_solver.hip) -- 257^3: 494 ms per solve
     // pair with 24 iterations against 539 ms with 23 for V(2,2) throughout (1/4: 492, 2/3: 499, 1/2: 504; tools/run_nu3.sh).
@@ -1752,27 +1733,26 @@ static void vcycle3(pl3_ctx* ctx, size_t l, double* const* f, int& out_buf, cons
     const int nu_fine = ctx->nu_fine > 0 ? ctx->nu_fine : (big && !ctx->nu_set ? 1 : ctx->nu);
     const int nu_rest = (big && !ctx->nu_set) ? 3 : ctx->nu;
     const int nu = l == 0 ? nu_fine : nu_rest;
-    smooth3(ctx, L, f, nu, ctx->cheb_ratio, true, cur);
-    (void)halo3(ctx, L->gh.d, L->v[cur], 3);
-    if (k3_use_lds(L->gh.d)) {
+    P3_TRY(smooth3(ctx, L, f, nu, ctx->cheb_ratio, true, cur));
+    P3_TRY(halo3(ctx, g, L->v[cur], 3));
+    if (k3_use_lds(g)) {
         V3 none{};
-        hipLaunchKernelGGL(k3_sweep_m<1>, grid3m(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[cur]), none, cv3(f), wv3(L->r), 0.0, 0.0, k3_band(), k3m_zc(L->gh.d));
-    } else hipLaunchKernelGGL(k3_resid, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[cur]), cv3(f), wv3(L->r), 0, 0);
+        hipLaunchKernelGGL(k3_sweep_m<1>, grid3m(g), dim3(64, 4), 0, ctx->stream, L->op, cv3(L->v[cur]), none, cv3(f), wv3(L->r), 0.0, 0.0, k3_band(), k3m_zc(g));
+    } else launch3(ctx, g, k3_resid, L->op, cv3(L->v[cur]), cv3(f), wv3(L->r), 0, 0);
     Lev3* C = ctx->levels[l + 1];
-    (void)halo3(ctx, L->gh.d, L->r, 3);
-    hipLaunchKernelGGL(k3_restrict, grid3(C->gh.d), dim3(64, 4), 0, ctx->stream, L->gh.d, C->op, cv3(L->r), wv3(C->f));
+    P3_TRY(halo3(ctx, g, L->r, 3));
+    launch3(ctx, C->gh.d, k3_restrict, g, C->op, cv3(L->r), wv3(C->f));
     int cb = 0;
-    vcycle3(ctx, l + 1, C->f, cb);
+    P3_TRY(vcycle3(ctx, l + 1, C->f, cb));
     const int nxt = (cur + 1) % 3;
-    (void)halo3(ctx, C->gh.d, C->v[cb], 3);              // (the ring of L->v[cur] is still the one exchanged for the residual)
-    hipLaunchKernelGGL(k3_prolong_add, grid3(L->gh.d), dim3(64, 4), 0, ctx->stream, L->op, C->gh.d, cv3(C->v[cb]), cv3(L->v[cur]), wv3(L->v[nxt]));
+    P3_TRY(halo3(ctx, C->gh.d, C->v[cb], 3));            // (the ring of L->v[cur] is still the one exchanged for the residual)
+    launch3(ctx, g, k3_prolong_add, L->op, C->gh.d, cv3(C->v[cb]), cv3(L->v[cur]), wv3(L->v[nxt]));
     cur = nxt;
-    smooth3(ctx, L, f, nu, ctx->cheb_ratio, false, cur, final_out);
+    P3_TRY(smooth3(ctx, L, f, nu, ctx->cheb_ratio, false, cur, final_out));
     out_buf = cur;
+    return 0;
 }
 
-// ---- generic right-preconditioned BiCGStab on multi-array vectors (correction form, true-residual stopping) --------------------
-typedef std::function<int(double* const*, double* const*)> Op3Fn;
 // ---- deflation of the pressure-anchor mode and the velocity-error estimate: the 3-D counterparts of pl_solver.hip --------------
 // u: the continuity residual that the block preconditioner turns into a constant pressure; yw: cell volume x (rdz + rdx + rdy) on the
 // continuity rows, so that yw . (scaled continuity row of v) = sum of volume x div(v)
@@ -1799,176 +1779,172 @@ __global__ __launch_bounds__(256) void k3_cont_rows(Op3 op, V3 v, double* __rest
     out[c] = o;
 }
 
-struct Stats3 { int iterations, converged; double rel_residual; int napply, nprec; double error_estimate; };
-static int bicgstab3(pl3_ctx* ctx, long long vol, int na, const Op3Fn& A, const Op3Fn* M, double* const* b, double* const* x, bool use_x0,
-                     double rtol, int maxit, double* const* const* w /* r rt p v s t y z dx r0 */, G3 g, Stats3* st, double ref_norm,
-                     double etol = 0.0) {
-    double* const* r = w[0]; double* const* rt = w[1]; double* const* p = w[2]; double* const* v = w[3]; double* const* s = w[4];
-    double* const* t = w[5]; double* const* y = w[6]; double* const* z = w[7]; double* const* dxb = w[8]; double* const* r0b = w[9];
-    auto flat3 = [&](double* const* a0, double* const* a1 = nullptr, double* const* a2 = nullptr) {
-        return na > 1 && contig3(a0, na, vol) && (!a1 || contig3(a1, na, vol)) && (!a2 || contig3(a2, na, vol));
-    };
-    auto axpby = [&](double* const* yy, double a, double* const* xx, double bb, double* const* zz) {
-        if (flat3(yy, xx, zz)) { hipLaunchKernelGGL(k3_axpby, g1(na * vol), dim3(256), 0, ctx->stream, na * vol, yy[0], a, (const double*)xx[0], bb, (const double*)zz[0]); return; }
-        for (int c = 0; c < na; c++) hipLaunchKernelGGL(k3_axpby, g1(vol), dim3(256), 0, ctx->stream, vol, yy[c], a, (const double*)xx[c], bb, (const double*)zz[c]);
-    };
-    auto zero = [&](double* const* yy) {
-        if (flat3(yy)) { (void)hipMemsetAsync(yy[0], 0, (size_t)na * vol * sizeof(double), ctx->stream); return; }
-        for (int c = 0; c < na; c++) (void)hipMemsetAsync(yy[c], 0, (size_t)vol * sizeof(double), ctx->stream);
-    };
+// ---- right-preconditioned BiCGStab on Krylov vectors (correction form, true-residual stopping) ----------------------------------
+typedef int (*Op3Fn)(pl3_ctx*, const Vec3& in, const Vec3& out);
+struct Stats3 { int iterations, converged; double rel_residual; double error_estimate; };
+enum { K_R, K_RT, K_P, K_V, K_S, K_T, K_Y, K_Z, K_DX, K_R0, K_NW };      // the work vectors of bicgstab3
+static void axpby3(pl3_ctx* ctx, const Vec3& y, double a, const Vec3& x, double b, const Vec3& z) {
+    hipLaunchKernelGGL(k3_axpby, g1(y.n()), dim3(256), 0, ctx->stream, y.n(), y.p, a, (const double*)x.p, b, (const double*)z.p);
+}
+static int zero3(pl3_ctx* ctx, const Vec3& y) { P3_HIP(ctx, hipMemsetAsync(y.p, 0, (size_t)y.n() * sizeof(double), ctx->stream)); return 0; }
+static bool trace3() { static const bool on = getenv("PYLAMP_SOLVER_TRACE") != nullptr; return on; }
+
+// The velocity-error estimate (n |r_cont| + |(M^-1 r)_vel|) / |x_vel| of a Stokes solve, as in pl_solver.hip.  anchor: the component of
+// the residual along the deflated anchor mode has its own amplification |w| / |u|.  a_mom stands for |(M^-1 r)_vel| / |r_mom| between
+// the true-residual checks that measure it.
+// tol, bnorm: the residual test of the iteration (tol tightens while the estimate is above etol); rec: the estimate between the checks;
+// est: that of the last check; resume: the check sends the iteration on.
+struct Est3 { bool on, anchor, resume; double etol, n_amp, a_mom, rec, est, tol, bnorm; int checks; };
+static double anchor_amp3(const pl3_ctx* ctx, double yr, double xx) { return std::fabs(yr / ctx->dfl_yAw) * std::sqrt(ctx->dfl_wvel2 / xx); }
+static int anchor_part3(pl3_ctx* ctx, const Est3& e, const Vec3& res, double xx, double* out) {
+    *out = 0.0;
+    if (!e.anchor || !(xx > 0.0)) return 0;
+    double o;
+    P3_TRY(dot3(ctx, arr3(ctx, ctx->dfl_y), res.prs(), &o));
+    *out = anchor_amp3(ctx, o, xx);
+    return 0;
+}
+// |(x0 + dx)_vel|^2, through t as scratch
+static int vel_norm2_3(pl3_ctx* ctx, const Vec3& x, const Vec3& dx, const Vec3& t, double* xx) {
+    Vec3 src = dx.vel();
+    if (dx.p != x.p) { src = t.vel(); axpby3(ctx, src, 1.0, x.vel(), 1.0, dx.vel()); }
+    return dot3(ctx, src, src, xx);
+}
+// the estimate between the checks: from |r|^2 = rr and |r_cont|^2 = rc of the recurrence residual, |x_vel|^2 = xx and the anchor part ap
+static double est_rec3(const Est3& e, double rr, double rc, double xx, double ap) {
+    if (!(xx > 0.0)) return 0.0;
+    const double rm = rr - rc > 0.0 ? rr - rc : 0.0;
+    return (e.n_amp * std::sqrt(rc > 0.0 ? rc : 0.0) + e.a_mom * std::sqrt(rm)) / std::sqrt(xx) + ap;
+}
+// The true residual s (norm true_norm) has met the tolerance: the estimate from it (e.est), with the velocity norm of the preconditioned
+// residual itself (which also renews a_mom).  Above etol the tolerance tightens and the iteration resumes.
+static int true_check3(pl3_ctx* ctx, Op3Fn M, Est3& e, const Vec3* w, const Vec3& x, const Vec3& dx, double true_norm, int it) {
+    const Vec3 &s = w[K_S], &z = w[K_Z];
+    double rc, zz, xx = 0.0, ap = 0.0;
+    P3_TRY(dot3(ctx, s.prs(), s.prs(), &rc));
+    P3_TRY(M(ctx, s, z));
+    P3_TRY(dot3(ctx, z.vel(), z.vel(), &zz));
+    P3_TRY(vel_norm2_3(ctx, x, dx, w[K_T], &xx));
+    e.checks++;
+    const double rcc = rc > 0.0 ? rc : 0.0, rm = true_norm * true_norm - rcc;
+    P3_TRY(anchor_part3(ctx, e, s, xx, &ap));
+    e.est = (xx > 0.0 ? (e.n_amp * std::sqrt(rcc) + std::sqrt(zz > 0.0 ? zz : 0.0)) / std::sqrt(xx) : 0.0) + ap;
+    if (rm > 0.0 && zz > 0.0) e.a_mom = std::min(std::max(std::sqrt(zz / rm), 1.0), e.n_amp * e.n_amp);
+    if (trace3()) fprintf(stderr, "[pylamp3 bicgstab] it %3d  velocity-error estimate %.3e (etol %.1e)\n", it, e.est, e.etol);
+    e.resume = e.est > e.etol && e.tol > 1e-15;
+    if (e.resume) { e.tol = std::min(e.tol, true_norm / e.bnorm) * std::min(0.5, 0.7 * e.etol / e.est); e.rec = e.est; }
+    return 0;
+}
+
+// Solves A x = b (from x if use_x0, else from zero); w: K_NW work vectors of b's shape.  ref_norm > 0 replaces |b| in the stopping test;
+// etol > 0 (Stokes vectors with M): also bound the velocity-error estimate.
+static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& x, bool use_x0, double rtol, int maxit, const Vec3* w,
+                     Stats3* st, double ref_norm, double etol = 0.0) {
+    const Vec3 &r = w[K_R], &rt = w[K_RT], &p = w[K_P], &v = w[K_V], &s = w[K_S], &t = w[K_T], &y = w[K_Y], &z = w[K_Z];
+    const G3& g = *b.g;
+    const int na = b.na; const long long n = b.n();
     double d[5];
-    { double* const* aa[1] = {b}; P3_TRY(vdots(ctx, vol, na, 1, aa, aa, d)); }
+    P3_TRY(dot3(ctx, b, b, d));
     double bnorm = std::sqrt(d[0]);
     if (ref_norm > 0.0 && bnorm > 0.0) bnorm = ref_norm;
-    st->iterations = 0; st->converged = 0; st->rel_residual = 0.0;
-    if (!(bnorm > 0.0)) { zero(x); st->converged = 1; return 0; }
-    double* const* dx = x; double* const* r0 = b;
-    if (use_x0) { dx = dxb; P3_TRY(A(x, v)); axpby(r0b, 1.0, b, -1.0, v); r0 = r0b; }
-    zero(dx);
-    axpby(r, 1.0, r0, 0.0, r0);
-    for (int c = 0; c < na; c++) hipLaunchKernelGGL(k3_random, grid3(g), dim3(64, 4), 0, ctx->stream, g, rt[c], 1234u + c);
+    st->iterations = 0; st->converged = 0; st->rel_residual = 0.0; st->error_estimate = 0.0;
+    if (!(bnorm > 0.0)) { P3_TRY(zero3(ctx, x)); st->converged = 1; return 0; }
+    Vec3 dx = x, r0 = b;
+    if (use_x0) { dx = w[K_DX]; P3_TRY(A(ctx, x, v)); r0 = w[K_R0]; axpby3(ctx, r0, 1.0, b, -1.0, v); }
+    P3_TRY(zero3(ctx, dx));
+    axpby3(ctx, r, 1.0, r0, 0.0, r0);
+    for (int c = 0; c < na; c++) launch3(ctx, g, k3_random, g, rt[c], 1234u + c);
     int it = 0, restarts = 0; double true_norm = -1.0, last_true = -1.0;
-    static const bool trace3 = getenv("PYLAMP_SOLVER_TRACE") != nullptr;
-    // velocity-error estimate (n |r_cont| + |(M^-1 r)_vel|) / |x_vel| as in pl_solver.hip (na = 4: three velocity arrays + pressure)
-    const bool use_est = etol > 0.0 && na == 4 && M;
-    const double n_amp = (double)std::max(g.gn[0], std::max(g.gn[1], g.gn[2]));
-    double tol = rtol, est_rec = 0.0, a_mom = 1.0;
-    int est_checks = 0;
-    bool resume = false, broke = false, p_fused = false;
-    // one rank, Stokes vectors (4 consecutive arrays each): the fused reduction / update kernels
-    const bool fused = ctx->nranks == 1 && na == 4 && M && flat3(t, s, rt) && flat3(dxb, x, p) && flat3(r, v, y) && flat3(z) &&
-                       !(getenv("PYLAMP_3D_FUSED") && atoi(getenv("PYLAMP_3D_FUSED")) == 0);
+    Est3 e{};
+    e.on = etol > 0.0 && na == 4 && M; e.anchor = e.on && ctx->dfl_active && ctx->dfl_yAw != 0.0;
+    e.etol = etol; e.n_amp = (double)std::max(g.gn[0], std::max(g.gn[1], g.gn[2])); e.a_mom = 1.0;
+    e.tol = rtol; e.bnorm = bnorm;
+    bool broke = false, p_fused = false;
+    // one rank, Stokes vectors: the fused reduction / update kernels
+    const bool fused = ctx->nranks == 1 && na == 4 && M && !(getenv("PYLAMP_3D_FUSED") && atoi(getenv("PYLAMP_3D_FUSED")) == 0);
     double rho = 1.0, alpha = 1.0, omega = 1.0, rho_new = 0.0, rnorm = 0.0, best = 0.0; int best_it = 0;
-    st->error_estimate = 0.0;
-    // the component of the residual along the deflated anchor mode has its own amplification |w| / |u| (see pl_solver.hip)
-    const bool anchor_term = use_est && ctx->dfl_active && ctx->dfl_yAw != 0.0;
-    auto anchor_part = [&](double* const* res, double xx, double& out) -> int {
-        out = 0.0;
-        if (!anchor_term || !(xx > 0.0)) return 0;
-        const double* a1[1] = {ctx->dfl_y}; const double* b1[1] = {res[3]}; double o[1];
-        P3_TRY(dots3(ctx, vol, 1, a1, b1, o));
-        out = std::fabs(o[0] / ctx->dfl_yAw) * std::sqrt(ctx->dfl_wvel2 / xx);
-        return 0;
-    };
-    auto vel_norm2 = [&](double& xx) -> int {        // |(x0 + dx)_vel|^2, through t as scratch
-        double* const* src = dx;
-        if (dx != x) { for (int c = 0; c < 3; c++) hipLaunchKernelGGL(k3_axpby, g1(vol), dim3(256), 0, ctx->stream, vol, t[c], 1.0, (const double*)x[c], 1.0, (const double*)dx[c]); src = t; }
-        double* const* aa[1] = {src}; double o[1];
-        P3_TRY(vdots(ctx, vol, 3, 1, aa, aa, o));
-        xx = o[0];
-        return 0;
-    };
     for (;;) {
-        if (!resume) {
-            zero(p); zero(v);
+        if (!e.resume) {
+            P3_TRY(zero3(ctx, p)); P3_TRY(zero3(ctx, v));
             rho = alpha = omega = 1.0; p_fused = false;
-            { double* const* aa[2] = {rt, r}; double* const* bb[2] = {r, r}; P3_TRY(vdots(ctx, vol, na, 2, aa, bb, d)); }
+            { const Vec3 aa[2] = {rt, r}, bb[2] = {r, r}; P3_TRY(dots3(ctx, 2, aa, bb, d)); }
             rho_new = d[0]; rnorm = std::sqrt(d[1]);
             broke = false;
             best = rnorm; best_it = it;
         }
-        resume = false;
-        while (it < maxit && (rnorm > tol * bnorm || (use_est && est_rec > 0.7 * etol))) {
+        e.resume = false;
+        while (it < maxit && (rnorm > e.tol * bnorm || (e.on && e.rec > 0.7 * etol))) {
             it++;
             if (!(std::fabs(rho_new) > 0.0) || !std::isfinite(rho_new)) { broke = true; break; }
             const double beta = (rho_new / rho) * (alpha / omega);
             if (p_fused) p_fused = false;                   // (written by k3_xrp_update of the previous iteration)
-            else if (flat3(p, r, v)) hipLaunchKernelGGL(k3_p_update, g1(na * vol), dim3(256), 0, ctx->stream, na * vol, p[0], (const double*)r[0], (const double*)v[0], beta, omega);
-            else for (int c = 0; c < na; c++) hipLaunchKernelGGL(k3_p_update, g1(vol), dim3(256), 0, ctx->stream, vol, p[c], (const double*)r[c], (const double*)v[c], beta, omega);
-            double* const* yv = p;
-            if (M) { P3_TRY((*M)(p, y)); yv = y; }
-            P3_TRY(A(yv, v));
-            { double* const* aa[1] = {rt}; double* const* bb[1] = {v}; P3_TRY(vdots(ctx, vol, na, 1, aa, bb, d)); }
+            else hipLaunchKernelGGL(k3_p_update, g1(n), dim3(256), 0, ctx->stream, n, p.p, (const double*)r.p, (const double*)v.p, beta, omega);
+            Vec3 yv = p, zv = s;
+            if (M) { P3_TRY(M(ctx, p, y)); yv = y; }
+            P3_TRY(A(ctx, yv, v));
+            P3_TRY(dot3(ctx, rt, v, d));
             if (!(std::fabs(d[0]) > 0.0) || !std::isfinite(d[0])) { broke = true; break; }
             alpha = rho_new / d[0];
-            axpby(s, 1.0, r, -alpha, v);
-            double* const* zv = s;
-            if (M) { P3_TRY((*M)(s, z)); zv = z; }
-            P3_TRY(A(zv, t));
+            axpby3(ctx, s, 1.0, r, -alpha, v);
+            if (M) { P3_TRY(M(ctx, s, z)); zv = z; }
+            P3_TRY(A(ctx, zv, t));
             // one reduction: t.s, t.t, rt.s, rt.t, s.s  ->  omega, rho' = rt.s - omega rt.t, |r|^2 = s.s - 2 omega t.s + omega^2 t.t
             double f11[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            const bool late = use_est && rnorm <= 1e3 * tol * bnorm;
+            const bool late = e.on && rnorm <= 1e3 * e.tol * bnorm;
             if (fused) {       // ... and, near the end, everything the error estimate of the updated iterate needs, in the same pass
-                Fuse11 fa{}; fa.t = t[0]; fa.s = s[0]; fa.rt = rt[0]; fa.vol = vol;
-                if (late) { fa.x = x[0]; fa.dx = (dx != x) ? dx[0] : nullptr; fa.yw = anchor_term ? ctx->dfl_y : nullptr; }
+                Fuse11 fa{}; fa.t = t.p; fa.s = s.p; fa.rt = rt.p; fa.vol = g.vol;
+                if (late) { fa.x = x.p; fa.dx = (dx.p != x.p) ? dx.p : nullptr; fa.yw = e.anchor ? ctx->dfl_y : nullptr; }
                 hipLaunchKernelGGL(k3_dots11, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, fa, ctx->part);
-                pl3_count_copy(ctx, 11 * D3_BLOCKS * sizeof(double));
-                P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, 11 * D3_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                for (int q = 0; q < 11; q++) { double sm = 0.0; for (int kk = 0; kk < D3_BLOCKS; kk++) sm += ctx->hpart[11 * kk + q]; f11[q] = sm; }
+                P3_TRY(sum_partials3(ctx, 11, 11, f11));
                 for (int q = 0; q < 5; q++) d[q] = f11[q];
-            } else
-            { double* const* aa[5] = {t, t, rt, rt, s}; double* const* bb[5] = {s, t, s, t, s}; P3_TRY(vdots(ctx, vol, na, 5, aa, bb, d)); }
+            } else { const Vec3 aa[5] = {t, t, rt, rt, s}, bb[5] = {s, t, s, t, s}; P3_TRY(dots3(ctx, 5, aa, bb, d)); }
             omega = (d[1] > 0.0) ? d[0] / d[1] : 0.0;
             if (fused) {
                 const double rho_next = d[2] - omega * d[3];
                 const double beta_next = (rho_next / rho_new) * (alpha / omega);
-                hipLaunchKernelGGL(k3_xrp_update, g1(na * vol), dim3(256), 0, ctx->stream, na * vol, dx[0], (const double*)yv[0], (const double*)zv[0], r[0],
-                                   (const double*)s[0], (const double*)t[0], p[0], (const double*)v[0], alpha, omega, beta_next);
+                hipLaunchKernelGGL(k3_xrp_update, g1(n), dim3(256), 0, ctx->stream, n, dx.p, (const double*)yv.p, (const double*)zv.p, r.p,
+                                   (const double*)s.p, (const double*)t.p, p.p, (const double*)v.p, alpha, omega, beta_next);
                 p_fused = std::isfinite(beta_next);
-            }
-            else if (flat3(dx, yv, zv) && flat3(r, s, t))
-                hipLaunchKernelGGL(k3_xr_update, g1(na * vol), dim3(256), 0, ctx->stream, na * vol, dx[0], (const double*)yv[0], (const double*)zv[0], r[0],
-                                   (const double*)s[0], (const double*)t[0], alpha, omega);
-            else for (int c = 0; c < na; c++)
-                hipLaunchKernelGGL(k3_xr_update, g1(vol), dim3(256), 0, ctx->stream, vol, dx[c], (const double*)yv[c], (const double*)zv[c], r[c],
-                                   (const double*)s[c], (const double*)t[c], alpha, omega);
+            } else
+                hipLaunchKernelGGL(k3_xr_update, g1(n), dim3(256), 0, ctx->stream, n, dx.p, (const double*)yv.p, (const double*)zv.p, r.p,
+                                   (const double*)s.p, (const double*)t.p, alpha, omega);
             rho = rho_new; rho_new = d[2] - omega * d[3];
             const double rr = d[4] - 2.0 * omega * d[0] + omega * omega * d[1];
             rnorm = rr > 0.0 ? std::sqrt(rr) : 0.0;
             if (!std::isfinite(rnorm) || !(std::fabs(omega) > 0.0)) { broke = true; break; }
             if (rnorm < best) { best = rnorm; best_it = it; }
-            if (trace3) fprintf(stderr, "[pylamp3 bicgstab] it %3d  |r|/|b| %.3e\n", it, rnorm / bnorm);
-            est_rec = 0.0;
+            if (trace3()) fprintf(stderr, "[pylamp3 bicgstab] it %3d  |r|/|b| %.3e\n", it, rnorm / bnorm);
+            e.rec = 0.0;
             if (fused && late) {                                  // (sums of the fused reduction; |x_vel| of the iterate BEFORE this update: needed to ~10 %)
-                const double rc0 = f11[7] - 2.0 * omega * f11[5] + omega * omega * f11[6], xx = f11[8];
-                const double rcc = rc0 > 0.0 ? rc0 : 0.0, rm = rr - rcc > 0.0 ? rr - rcc : 0.0;
-                const double ap = (anchor_term && xx > 0.0) ? std::fabs((f11[9] - omega * f11[10]) / ctx->dfl_yAw) * std::sqrt(ctx->dfl_wvel2 / xx) : 0.0;
-                if (xx > 0.0) est_rec = (n_amp * std::sqrt(rcc) + a_mom * std::sqrt(rm)) / std::sqrt(xx) + ap;
-            } else
-            if (use_est && rnorm <= 1e3 * tol * bnorm) {          // near the end: the estimate from the recurrence residual
-                double rc[1], xx = 0.0;
-                { double* const* aa[1] = {r + 3}; P3_TRY(vdots(ctx, vol, 1, 1, aa, aa, rc)); }
-                P3_TRY(vel_norm2(xx));
-                const double rm = rr - rc[0] > 0.0 ? rr - rc[0] : 0.0;
-                double ap = 0.0;
-                P3_TRY(anchor_part(r, xx, ap));
-                if (xx > 0.0) est_rec = (n_amp * std::sqrt(rc[0] > 0.0 ? rc[0] : 0.0) + a_mom * std::sqrt(rm)) / std::sqrt(xx) + ap;
+                const double rc = f11[7] - 2.0 * omega * f11[5] + omega * omega * f11[6], xx = f11[8];
+                const double ap = (e.anchor && xx > 0.0) ? anchor_amp3(ctx, f11[9] - omega * f11[10], xx) : 0.0;
+                e.rec = est_rec3(e, rr, rc > 0.0 ? rc : 0.0, xx, ap);
+            } else if (e.on && rnorm <= 1e3 * e.tol * bnorm) {    // near the end: the estimate from the recurrence residual
+                double rc, xx = 0.0, ap = 0.0;
+                P3_TRY(dot3(ctx, r.prs(), r.prs(), &rc));
+                P3_TRY(vel_norm2_3(ctx, x, dx, t, &xx));
+                P3_TRY(anchor_part3(ctx, e, r, xx, &ap));
+                e.rec = est_rec3(e, rr, rc, xx, ap);
             }
             if (it - best_it > 80 || rnorm > 1e8 * best) { broke = true; break; }
         }
-        P3_TRY(A(dx, t));
-        axpby(s, 1.0, r0, -1.0, t);
-        { double* const* aa[1] = {s}; P3_TRY(vdots(ctx, vol, na, 1, aa, aa, d)); }
+        P3_TRY(A(ctx, dx, t));
+        axpby3(ctx, s, 1.0, r0, -1.0, t);
+        P3_TRY(dot3(ctx, s, s, d));
         last_true = true_norm; true_norm = std::sqrt(d[0]);
-        if (true_norm <= tol * bnorm && !broke && it < maxit && use_est && est_checks < 6) {
-            double rc[1], zz[1], xx = 0.0;
-            { double* const* aa[1] = {s + 3}; P3_TRY(vdots(ctx, vol, 1, 1, aa, aa, rc)); }
-            P3_TRY((*M)(s, z));
-            { double* const* aa[1] = {z}; P3_TRY(vdots(ctx, vol, 3, 1, aa, aa, zz)); }
-            P3_TRY(vel_norm2(xx));
-            est_checks++;
-            const double rcc = rc[0] > 0.0 ? rc[0] : 0.0, rm = true_norm * true_norm - rcc;
-            double ap = 0.0;
-            P3_TRY(anchor_part(s, xx, ap));
-            const double est = (xx > 0.0 ? (n_amp * std::sqrt(rcc) + std::sqrt(zz[0] > 0.0 ? zz[0] : 0.0)) / std::sqrt(xx) : 0.0) + ap;
-            if (rm > 0.0 && zz[0] > 0.0) a_mom = std::min(std::max(std::sqrt(zz[0] / rm), 1.0), n_amp * n_amp);
-            st->error_estimate = est;
-            if (trace3) fprintf(stderr, "[pylamp3 bicgstab] it %3d  velocity-error estimate %.3e (etol %.1e)\n", it, est, etol);
-            if (est > etol && tol > 1e-15) {
-                tol = std::min(tol, true_norm / bnorm) * std::min(0.5, 0.7 * etol / est);
-                est_rec = est; resume = true;
-                continue;
-            }
+        if (true_norm <= e.tol * bnorm && !broke && it < maxit && e.on && e.checks < 6) {
+            P3_TRY(true_check3(ctx, M, e, w, x, dx, true_norm, it));
+            st->error_estimate = e.est;
+            if (e.resume) continue;
         }
-        if (true_norm <= tol * bnorm || broke || it >= maxit || restarts >= 4) break;
+        if (true_norm <= e.tol * bnorm || broke || it >= maxit || restarts >= 4) break;
         if (last_true >= 0.0 && !(true_norm < 0.5 * last_true)) break;
         restarts++;
-        axpby(r, 1.0, s, 0.0, s);
+        axpby3(ctx, r, 1.0, s, 0.0, s);
     }
-    if (dx != x) axpby(x, 1.0, x, 1.0, dx);
+    if (dx.p != x.p) axpby3(ctx, x, 1.0, x, 1.0, dx);
     st->iterations = it; st->rel_residual = true_norm / bnorm;
-    st->converged = (st->rel_residual <= rtol && !(use_est && st->error_estimate > 1.5 * etol)) ? 1 : 0;
+    st->converged = (st->rel_residual <= rtol && !(e.on && st->error_estimate > 1.5 * etol)) ? 1 : 0;
     return 0;
 }
 
@@ -2002,6 +1978,124 @@ __global__ __launch_bounds__(256) void k3_shift(G3 g, double* __restrict__ P, co
     if (i < g.gn[0] - 1 && j < g.gn[1] - 1 && k < g.gn[2] - 1) P[c] -= *anchor_val;
 }
 
+
+// ---- the Stokes solve: operator, preconditioner, hydrostatic start, deflation vector ---------------------------------------------
+static int stokes_A3(pl3_ctx* ctx, const Vec3& in, const Vec3& out) {
+    P3_TRY(halo3(ctx, in));
+    launch_apply3<true>(ctx, ctx->op, in, out);
+    ctx->napply++;
+    return 0;
+}
+// block-triangular [[A_vv, A_vp], [0, S^]]: the pressure by S^-1, one V-cycle for the velocities, then the deflation correction
+static int stokes_M3(pl3_ctx* ctx, const Vec3& in, const Vec3& out) {
+    const G3& g = ctx->geom.d;
+    Lev3* L0 = ctx->levels[0];
+    P3_TRY(halo3(ctx, in.prs()));                // S^-1 r_p of the neighbour cell (A_vp z_p) reads the pressure residual one node beyond the block
+    launch3(ctx, g, k3_stage1, ctx->op, cv4(in), out[3], wv3(L0->f));
+    int ob = 0;
+    if (ctx->levels.size() > 1) {           // the post-smoothing sweep of the finest level writes the velocities into out[0..2] itself
+        const W3 fo = wv3(out);
+        P3_TRY(vcycle3(ctx, 0, L0->f, ob, &fo));
+    } else {
+        P3_TRY(vcycle3(ctx, 0, L0->f, ob));
+        for (int q = 0; q < 3; q++) P3_HIP(ctx, hipMemcpyAsync(out[q], L0->v[ob][q], (size_t)g.vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    ctx->nprec++;
+    if (ctx->dfl_active) {                  // z += w yw.(r - A z) / yw.(A w); the continuity rows of A z come from z's velocities alone
+        const Vec3 W = svec(ctx, 13), yw = arr3(ctx, ctx->dfl_y);
+        const Vec3 a1[2] = {yw, yw}, b1[2] = {in.prs(), arr3(ctx, ctx->dfl_t)}; double o[2];
+        P3_TRY(halo3(ctx, out.vel()));
+        launch3(ctx, g, k3_cont_rows, ctx->op, cv3(out), ctx->dfl_t);
+        P3_TRY(dots3(ctx, 2, a1, b1, o));
+        const double coef = (o[0] - o[1]) / ctx->dfl_yAw;
+        for (int c = 0; c < 4; c++) axpby3(ctx, out.part(c, 1), 1.0, out.part(c, 1), coef, W.part(c, 1));
+    }
+    return 0;
+}
+// The hydrostatic pressure x_h (zero velocities) into XH, and the dynamic-load reference norm |b - A x_h| (0: not usable) into ref.
+// vec[4], vec[5]: work vectors of the iteration, free before it starts.
+static int hydrostatic_start3(pl3_ctx* ctx, const Vec3& B, const Vec3& XH, double* ref) {
+    const G3& g = ctx->geom.d;
+    const Vec3 res = svec(ctx, 4), AX = svec(ctx, 5);
+    double* P = XH[3];
+    double* coltot = ctx->nranks > 1 ? AX.p : nullptr;      // several ranks: the column totals of this block
+    P3_TRY(zero3(ctx, XH.vel()));
+    hipLaunchKernelGGL(k3_hydro, dim3((g.n[2] + 63) / 64, (g.n[1] + 3) / 4), dim3(64, 4), 0, ctx->stream, ctx->op, P, coltot);
+    if (ctx->nranks == 1)
+        P3_HIP(ctx, hipMemcpyAsync(ctx->part, P + i3(g, 3, 2, 2), sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));     // anchor value
+    else {
+        // every block integrated from zero at its top: add the column totals of the blocks above (same block column), then the anchor
+        // value -- one table [Pz][nx][ny] and one scalar summed over the ranks on the host (once per solve)
+        const long long cols = (long long)g.n[1] * g.n[2], gcols = (long long)g.gn[1] * g.gn[2];
+        std::vector<double> mine((size_t)cols), tab((size_t)ctx->P[0] * gcols, 0.0);
+        P3_HIP(ctx, hipMemcpyAsync(mine.data(), coltot, (size_t)cols * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int jj = 0; jj < g.n[1]; jj++) for (int kk = 0; kk < g.n[2]; kk++)
+            tab[(size_t)ctx->pc[0] * gcols + (size_t)(g.o[1] + jj) * g.gn[2] + (g.o[2] + kk)] = mine[(size_t)jj * g.n[2] + kk];
+        P3_TRY(allreduce3(ctx, tab.data(), (int)tab.size(), 0));
+        for (int jj = 0; jj < g.n[1]; jj++) for (int kk = 0; kk < g.n[2]; kk++) {
+            double a = 0.0;
+            for (int q = 0; q < ctx->pc[0]; q++) a += tab[(size_t)q * gcols + (size_t)(g.o[1] + jj) * g.gn[2] + (g.o[2] + kk)];
+            mine[(size_t)jj * g.n[2] + kk] = a;
+        }
+        P3_HIP(ctx, hipMemcpyAsync(coltot, mine.data(), (size_t)cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        launch3(ctx, g, k3_hydro_add, g, P, coltot);
+        double av[1] = {0.0};
+        const int ai = ctx->op.anchor[0] - g.o[0], aj = ctx->op.anchor[1] - g.o[1], ak = ctx->op.anchor[2] - g.o[2];
+        if (ai >= 0 && ai < g.n[0] && aj >= 0 && aj < g.n[1] && ak >= 0 && ak < g.n[2])
+            P3_HIP(ctx, hipMemcpyAsync(av, P + i3(g, ai, aj, ak), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        P3_TRY(allreduce3(ctx, av, 1, 0));
+        P3_HIP(ctx, hipMemcpyAsync(ctx->part, av, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        P3_HIP(ctx, hipMemsetAsync(coltot, 0, (size_t)cols * sizeof(double), ctx->stream));
+    }
+    launch3(ctx, g, k3_shift, g, P, ctx->part);
+    P3_TRY(stokes_A3(ctx, XH, AX));
+    axpby3(ctx, res, 1.0, B, -1.0, AX);
+    const Vec3 aa[2] = {res, B}; double d[2];
+    P3_TRY(dots3(ctx, 2, aa, aa, d));
+    *ref = std::sqrt(d[0]);
+    if (!(*ref > 1e-9 * std::sqrt(d[1]))) *ref = 0.0;
+    return 0;
+}
+// The deflation vector w = A^-1 u (pl_solver.hip, "deflation of the pressure-anchor mode"), kept in vec[13] between solves: tested
+// against this operator, improved or solved for anew, and switched on (ctx->dfl_active, dfl_yAw, dfl_wvel2) if it is good.
+// U: scratch for u; w: the work vectors of bicgstab3.
+static int deflation_setup3(pl3_ctx* ctx, const Vec3& U, const Vec3* w) {
+    const G3& g = ctx->geom.d;
+    const Vec3 W = svec(ctx, 13);
+    if (!ctx->dfl_y) { P3_TRY(dmal(ctx, &ctx->dfl_y, g.vol)); P3_TRY(dmal(ctx, &ctx->dfl_t, g.vol)); ctx->dfl_valid = false; }
+    launch3(ctx, g, k3_defl_setup, ctx->op, wv4(U), ctx->dfl_y);
+    auto activate = [&]() -> int {          // yw.(A w), from the continuity rows of w's velocities
+        P3_TRY(halo3(ctx, W.vel()));
+        launch3(ctx, g, k3_cont_rows, ctx->op, cv3(W), ctx->dfl_t);
+        P3_TRY(dot3(ctx, arr3(ctx, ctx->dfl_y), arr3(ctx, ctx->dfl_t), &ctx->dfl_yAw));
+        ctx->dfl_active = ctx->dfl_yAw != 0.0 && std::isfinite(ctx->dfl_yAw);
+        return 0;
+    };
+    double q = 1.0;
+    if (ctx->dfl_valid) {                   // quality of the kept vector for this operator: ||u - A w|| / ||u||
+        const Vec3 res = w[K_S], AW = w[K_T]; double dq[2];
+        P3_TRY(stokes_A3(ctx, W, AW));
+        axpby3(ctx, res, 1.0, U, -1.0, AW);
+        const Vec3 aa[2] = {res, U};
+        P3_TRY(dots3(ctx, 2, aa, aa, dq));
+        q = (dq[1] > 0.0 && std::isfinite(dq[0])) ? std::sqrt(dq[0] / dq[1]) : 1.0;
+    }
+    const bool reuse = ctx->dfl_valid && q < 0.5;
+    if (reuse) P3_TRY(activate());
+    if (!reuse || q > 0.1) {
+        if (!reuse) P3_TRY(zero3(ctx, W));
+        Stats3 st{};
+        P3_TRY(bicgstab3(ctx, stokes_A3, stokes_M3, U, W, reuse, 1e-3, 80, w, &st, 0.0));
+        ctx->dfl_valid = st.rel_residual < 0.05 && std::isfinite(st.rel_residual);
+        ctx->dfl_active = false;
+        if (ctx->dfl_valid) P3_TRY(activate());
+    }
+    if (ctx->dfl_active) P3_TRY(dot3(ctx, W.vel(), W.vel(), &ctx->dfl_wvel2));
+    return 0;
+}
 extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int use_x0, double rtol, int maxit, pl_solve_stats* stats) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     // x == NULL: device-resident solve -- the solution stays in the context (pl3_get_solution fetches it), use_x0 starts from the
@@ -2009,143 +2103,37 @@ extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int 
     if (!x && use_x0 && !ctx->have_x) return p3_fail(ctx, "pl3_stokes_solve: no resident solution to start from");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 14));
-    ctx->halo_failed = false;
     if (rtol <= 0) rtol = 1e-7;
     if (maxit <= 0) maxit = 600;
     const G3& g = ctx->geom.d;
-    const long long vol = g.vol;
     P3_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     P3_TRY(build_levels3(ctx));
-    double* const* B = ctx->vec[10]; double* const* X = ctx->vec[11]; double* const* XH = ctx->vec[12];
-    if (rhs) { P3_TRY(upload3(ctx, rhs, 4, B)); hipLaunchKernelGGL(k3_scale_rows, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(B)); }
-    else hipLaunchKernelGGL(k3_rhs, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(B), 1, ctx->wallvel);
-    int napply = 0, nprec = 0;
-    bool defl_active = false; double yAw = 1.0;
-    double* const* W = ctx->vec[13];
-    Op3Fn A = [&](double* const* in, double* const* out) -> int {
-        P3_TRY(halo3(ctx, g, in, 4));
-        launch_apply3<true>(ctx, ctx->op, in, out);
-        napply++; return 0;
-    };
-    Op3Fn M = [&](double* const* in, double* const* out) -> int {
-        Lev3* L0 = ctx->levels[0];
-        P3_TRY(halo3_1(ctx, g, in[3]));             // S^-1 r_p of the neighbour cell (A_vp z_p) reads the pressure residual one node beyond the block
-        hipLaunchKernelGGL(k3_stage1, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, cv4(in), out[3], wv3(L0->f));
-        int ob = 0;
-        if (ctx->levels.size() > 1) {           // the post-smoothing sweep of the finest level writes the velocities into out[0..2] itself
-            const W3 fo = wv3(out);
-            vcycle3(ctx, 0, L0->f, ob, &fo);
-        } else {
-            vcycle3(ctx, 0, L0->f, ob);
-            for (int q = 0; q < 3; q++) P3_HIP(ctx, hipMemcpyAsync(out[q], L0->v[ob][q], (size_t)vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        nprec++;
-        if (ctx->halo_failed) return 1;      // (an exchange inside the V-cycle; ctx->err says which)
-        if (defl_active) {                  // z += w yw.(r - A z) / yw.(A w); the continuity rows of A z come from z's velocities alone
-            const double* a1[2] = {ctx->dfl_y, ctx->dfl_y}; const double* b1[2] = {in[3], ctx->dfl_t}; double o[2];
-            P3_TRY(halo3(ctx, g, out, 3));
-            hipLaunchKernelGGL(k3_cont_rows, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, cv3(out), ctx->dfl_t);
-            P3_TRY(dots3(ctx, vol, 2, a1, b1, o));
-            const double coef = (o[0] - o[1]) / yAw;
-            for (int c = 0; c < 4; c++) hipLaunchKernelGGL(k3_axpby, g1(vol), dim3(256), 0, ctx->stream, vol, out[c], 1.0, (const double*)out[c], coef, (const double*)W[c]);
-        }
-        return 0;
-    };
-    // hydrostatic start and the dynamic-load reference norm
+    Vec3 w[K_NW];
+    for (int q = 0; q < K_NW; q++) w[q] = svec(ctx, q);
+    const Vec3 B = svec(ctx, 10), X = svec(ctx, 11), XH = svec(ctx, 12);
+    if (rhs) { P3_TRY(upload3(ctx, rhs, 4, wv4(B).p)); launch3(ctx, g, k3_scale_rows, ctx->op, wv4(B)); }
+    else launch3(ctx, g, k3_rhs, ctx->op, wv4(B), 1, ctx->wallvel);
+    ctx->napply = ctx->nprec = 0;
+    ctx->dfl_active = false; ctx->dfl_yAw = 1.0; ctx->dfl_wvel2 = 0.0;
     double ref = 0.0;
-    {
-        for (int q = 0; q < 3; q++) P3_HIP(ctx, hipMemsetAsync(XH[q], 0, (size_t)vol * sizeof(double), ctx->stream));
-        if (ctx->nranks == 1) {
-            hipLaunchKernelGGL(k3_hydro, dim3((g.n[2] + 63) / 64, (g.n[1] + 3) / 4), dim3(64, 4), 0, ctx->stream, ctx->op, XH[3], (double*)nullptr);
-            P3_HIP(ctx, hipMemcpyAsync(ctx->part, XH[3] + i3(g, 3, 2, 2), sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));   // anchor value
-        } else {
-            // every block integrated from zero at its top: add the column totals of the blocks above (same block column), then the anchor
-            // value -- one table [Pz][nx][ny] and one scalar summed over the ranks on the host (once per solve)
-            const long long cols = (long long)g.n[1] * g.n[2], gcols = (long long)g.gn[1] * g.gn[2];
-            double* coltot = ctx->vec[5][0];                    // scratch (a work vector of the iteration, free before it starts)
-            hipLaunchKernelGGL(k3_hydro, dim3((g.n[2] + 63) / 64, (g.n[1] + 3) / 4), dim3(64, 4), 0, ctx->stream, ctx->op, XH[3], coltot);
-            std::vector<double> mine((size_t)cols), tab((size_t)ctx->P[0] * gcols, 0.0);
-            P3_HIP(ctx, hipMemcpyAsync(mine.data(), coltot, (size_t)cols * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (int jj = 0; jj < g.n[1]; jj++) for (int kk = 0; kk < g.n[2]; kk++)
-                tab[(size_t)ctx->pc[0] * gcols + (size_t)(g.o[1] + jj) * g.gn[2] + (g.o[2] + kk)] = mine[(size_t)jj * g.n[2] + kk];
-            P3_TRY(allreduce3(ctx, tab.data(), (int)tab.size(), 0));
-            for (int jj = 0; jj < g.n[1]; jj++) for (int kk = 0; kk < g.n[2]; kk++) {
-                double a = 0.0;
-                for (int q = 0; q < ctx->pc[0]; q++) a += tab[(size_t)q * gcols + (size_t)(g.o[1] + jj) * g.gn[2] + (g.o[2] + kk)];
-                mine[(size_t)jj * g.n[2] + kk] = a;
-            }
-            P3_HIP(ctx, hipMemcpyAsync(coltot, mine.data(), (size_t)cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k3_hydro_add, grid3(g), dim3(64, 4), 0, ctx->stream, g, XH[3], (const double*)coltot);
-            double av[1] = {0.0};
-            const int ai = ctx->op.anchor[0] - g.o[0], aj = ctx->op.anchor[1] - g.o[1], ak = ctx->op.anchor[2] - g.o[2];
-            if (ai >= 0 && ai < g.n[0] && aj >= 0 && aj < g.n[1] && ak >= 0 && ak < g.n[2])
-                P3_HIP(ctx, hipMemcpyAsync(av, XH[3] + i3(g, ai, aj, ak), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            P3_TRY(allreduce3(ctx, av, 1, 0));
-            P3_HIP(ctx, hipMemcpyAsync(ctx->part, av, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            P3_HIP(ctx, hipMemsetAsync(coltot, 0, (size_t)cols * sizeof(double), ctx->stream));
-        }
-        hipLaunchKernelGGL(k3_shift, grid3(g), dim3(64, 4), 0, ctx->stream, g, XH[3], (const double*)ctx->part);
-        P3_TRY(A(XH, ctx->vec[5]));
-        for (int c = 0; c < 4; c++) hipLaunchKernelGGL(k3_axpby, g1(vol), dim3(256), 0, ctx->stream, vol, ctx->vec[4][c], 1.0, (const double*)B[c], -1.0, (const double*)ctx->vec[5][c]);
-        double d[2];
-        double* const* aa[2] = {ctx->vec[4], B}; P3_TRY(vdots(ctx, vol, 4, 2, aa, aa, d));
-        ref = std::sqrt(d[0]);
-        if (!(ref > 1e-9 * std::sqrt(d[1]))) ref = 0.0;
-    }
-    if (use_x0) { if (x) P3_TRY(upload3(ctx, x, 4, X)); }
-    else for (int c = 0; c < 4; c++) P3_HIP(ctx, hipMemcpyAsync(X[c], XH[c], (size_t)vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    P3_TRY(halo3(ctx, g, X, 3));
-    hipLaunchKernelGGL(k3_close, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv3(X), cv3(B));
-    double* const* w[10] = {ctx->vec[0], ctx->vec[1], ctx->vec[2], ctx->vec[3], ctx->vec[4], ctx->vec[5], ctx->vec[6], ctx->vec[7], ctx->vec[8], ctx->vec[9]};
+    P3_TRY(hydrostatic_start3(ctx, B, XH, &ref));
+    if (use_x0) { if (x) P3_TRY(upload3(ctx, x, 4, wv4(X).p)); }
+    else P3_HIP(ctx, hipMemcpyAsync(X.p, XH.p, (size_t)X.n() * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    P3_TRY(halo3(ctx, X.vel()));
+    launch3(ctx, g, k3_close, ctx->op, wv3(X), cv3(B));
     static const bool defl_on = !(getenv("PYLAMP_DEFLATE") && atoi(getenv("PYLAMP_DEFLATE")) == 0);
     if (const char* e = getenv("PYLAMP_STOKES_ETOL")) { const double v = atof(e); if (v >= 0.0) ctx->etol = v; }
-    if (defl_on && ctx->levels.size() > 1) {
-        // the deflation vector w = A^-1 u (pl_solver.hip, "deflation of the pressure-anchor mode"), kept in vec[13] between solves
-        if (!ctx->dfl_y) { P3_TRY(dmal(ctx, &ctx->dfl_y, vol)); P3_TRY(dmal(ctx, &ctx->dfl_t, vol)); ctx->dfl_valid = false; }
-        double* const* U = XH;               // the hydrostatic vector is not needed any more
-        hipLaunchKernelGGL(k3_defl_setup, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, wv4(U), ctx->dfl_y);
-        auto denominator = [&]() -> int {
-            const double* a1[1] = {ctx->dfl_y}; const double* b1[1] = {ctx->dfl_t}; double o[1];
-            P3_TRY(halo3(ctx, g, W, 3));
-            hipLaunchKernelGGL(k3_cont_rows, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->op, cv3(W), ctx->dfl_t);
-            P3_TRY(dots3(ctx, vol, 1, a1, b1, o));
-            yAw = o[0];
-            return 0;
-        };
-        double q = 1.0;
-        if (ctx->dfl_valid) {               // quality of the kept vector for this operator: ||u - A w|| / ||u||
-            double dq[2];
-            P3_TRY(A(W, ctx->vec[5]));
-            for (int c = 0; c < 4; c++) hipLaunchKernelGGL(k3_axpby, g1(vol), dim3(256), 0, ctx->stream, vol, ctx->vec[4][c], 1.0, (const double*)U[c], -1.0, (const double*)ctx->vec[5][c]);
-            double* const* aa[2] = {ctx->vec[4], U}; P3_TRY(vdots(ctx, vol, 4, 2, aa, aa, dq));
-            q = (dq[1] > 0.0 && std::isfinite(dq[0])) ? std::sqrt(dq[0] / dq[1]) : 1.0;
-        }
-        const bool reuse = ctx->dfl_valid && q < 0.5;
-        if (reuse) { P3_TRY(denominator()); defl_active = yAw != 0.0 && std::isfinite(yAw); }
-        if (!reuse || q > 0.1) {
-            if (!reuse) for (int c = 0; c < 4; c++) P3_HIP(ctx, hipMemsetAsync(W[c], 0, (size_t)vol * sizeof(double), ctx->stream));
-            Stats3 st2{};
-            P3_TRY(bicgstab3(ctx, vol, 4, A, &M, U, W, reuse, 1e-3, 80, w, g, &st2, 0.0));
-            ctx->dfl_valid = st2.rel_residual < 0.05 && std::isfinite(st2.rel_residual);
-            defl_active = false;
-            if (ctx->dfl_valid) { P3_TRY(denominator()); defl_active = yAw != 0.0 && std::isfinite(yAw); }
-        }
-    }
-    ctx->dfl_active = defl_active; ctx->dfl_yAw = yAw; ctx->dfl_wvel2 = 0.0;
-    if (defl_active) { double* const* aa[1] = {W}; double o[1]; P3_TRY(vdots(ctx, vol, 3, 1, aa, aa, o)); ctx->dfl_wvel2 = o[0]; }
+    if (defl_on && ctx->levels.size() > 1) P3_TRY(deflation_setup3(ctx, XH, w));        // (the hydrostatic vector is not needed any more)
     Stats3 st{};
-    P3_TRY(bicgstab3(ctx, vol, 4, A, &M, B, X, true, rtol, maxit, w, g, &st, ref, ctx->etol));
+    P3_TRY(bicgstab3(ctx, stokes_A3, stokes_M3, B, X, true, rtol, maxit, w, &st, ref, ctx->etol));
     ctx->dfl_active = false;
     P3_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     P3_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0; P3_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->have_x = true;
-    if (x) P3_TRY(download3(ctx, X, 4, x));
+    if (x) P3_TRY(download3(ctx, wv4(X).p, 4, x));
     if (stats) { stats->iterations = st.iterations; stats->converged = st.converged; stats->rel_residual = st.rel_residual; stats->solve_ms = ms;
-                 stats->operator_applies = napply; stats->precond_applies = nprec; stats->used_direct = 0; stats->error_estimate = st.error_estimate; }
+                 stats->operator_applies = ctx->napply; stats->precond_applies = ctx->nprec; stats->used_direct = 0; stats->error_estimate = st.error_estimate; }
     return 0;
 }
 extern "C" int pl3_stokes_mg_info(pl3_ctx* ctx, int* nlevels, double* lmax, int max_levels) {
@@ -2164,7 +2152,7 @@ static int heat_set3(pl3_ctx* ctx, const double* const mp[3], const double* cons
     double* dst[7] = {ctx->hk[0], ctx->hk[1], ctx->hk[2], ctx->hT, ctx->hH, ctx->hrho, ctx->hcp};
     for (int q = 0; q < 7; q++) {
         if (dev) P3_TRY(ring3(ctx, src[q], dst[q]));
-        else { double* d1[1] = {dst[q]}; P3_TRY(upload3(ctx, src[q], 1, d1)); }
+        else P3_TRY(upload3(ctx, src[q], 1, &dst[q]));
     }
     size_t len[3], tot = 0;
     for (int a = 0; a < 3; a++) { len[a] = (size_t)g.gn[a] + 2 * PL_TOFF + 2; tot += len[a]; }
@@ -2180,7 +2168,7 @@ static int heat_set3(pl3_ctx* ctx, const double* const mp[3], const double* cons
     Heat3& op = ctx->hop;
     op.g = g; for (int a = 0; a < 3; a++) { op.kk[a] = ctx->hk[a]; op.rdb[a] = ctx->htab + offs[a]; }
     op.cdt = ctx->hcdt; for (int w = 0; w < 6; w++) op.bc[w] = bc[w];
-    hipLaunchKernelGGL(k3_heat_coef, grid3(g), dim3(64, 4), 0, ctx->stream, g, (const double*)ctx->hrho, (const double*)ctx->hcp, tstep, ctx->hcdt);
+    launch3(ctx, g, k3_heat_coef, g, ctx->hrho, ctx->hcp, tstep, ctx->hcdt);
     P3_HIP(ctx, hipGetLastError());
     ctx->hop_ready = true;
     return 0;
@@ -2205,20 +2193,24 @@ extern "C" int pl3_heat_apply(pl3_ctx* ctx, const double* x, double* y) {
     if (!ctx->hop_ready) return p3_fail(ctx, "heat operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_hvecs(ctx));
-    double* a[1] = {ctx->hvec[0]}; double* b[1] = {ctx->hvec[1]};
-    P3_TRY(upload3(ctx, x, 1, a));
-    hipLaunchKernelGGL(k3_heat_apply<false>, grid3(ctx->hop.g), dim3(64, 4), 0, ctx->stream, ctx->hop, (const double*)a[0], b[0]);
+    P3_TRY(upload3(ctx, x, 1, &ctx->hvec[0]));
+    launch3(ctx, ctx->hop.g, k3_heat_apply<false>, ctx->hop, ctx->hvec[0], ctx->hvec[1]);
     P3_HIP(ctx, hipGetLastError());
-    return download3(ctx, b, 1, y);
+    return download3(ctx, &ctx->hvec[1], 1, y);
 }
 extern "C" int pl3_heat_rhs(pl3_ctx* ctx, double* rhs) {
     if (!ctx->hop_ready) return p3_fail(ctx, "heat operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_hvecs(ctx));
-    double* b[1] = {ctx->hvec[1]};
-    hipLaunchKernelGGL(k3_heat_rhs, grid3(ctx->hop.g), dim3(64, 4), 0, ctx->stream, ctx->hop, (const double*)ctx->hT, (const double*)ctx->hH, (const double*)ctx->hbcv, b[0], 0);
+    launch3(ctx, ctx->hop.g, k3_heat_rhs, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, ctx->hvec[1], 0);
     P3_HIP(ctx, hipGetLastError());
-    return download3(ctx, b, 1, rhs);
+    return download3(ctx, &ctx->hvec[1], 1, rhs);
+}
+static int heat_A3(pl3_ctx* ctx, const Vec3& in, const Vec3& out) {
+    P3_TRY(halo3(ctx, in));
+    launch3(ctx, *in.g, k3_heat_apply<true>, ctx->hop, in.p, out.p);
+    ctx->napply++;
+    return 0;
 }
 extern "C" int pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double rtol, int maxit, pl_solve_stats* stats) {
     if (!ctx->hop_ready) return p3_fail(ctx, "heat operator not set");
@@ -2228,26 +2220,21 @@ extern "C" int pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double
     if (maxit <= 0) maxit = 2000;
     const G3& g = ctx->geom.d;
     P3_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    double* B[1] = {ctx->hvec[10]}; double* X[1] = {ctx->hvec[11]};
+    const Vec3 B = hvec(ctx, 10), X = hvec(ctx, 11);
     if (rhs) return p3_fail(ctx, "pl3_heat_solve: rhs must be NULL -- the system is solved for the operator's own right-hand side (pl3_heat_rhs)");
-    hipLaunchKernelGGL(k3_heat_rhs, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->hop, (const double*)ctx->hT, (const double*)ctx->hH, (const double*)ctx->hbcv, B[0], 1);
-    int napply = 0;
-    Op3Fn A = [&](double* const* in, double* const* out) -> int {
-        P3_TRY(halo3(ctx, g, in, 1));
-        hipLaunchKernelGGL(k3_heat_apply<true>, grid3(g), dim3(64, 4), 0, ctx->stream, ctx->hop, (const double*)in[0], out[0]);
-        napply++; return 0;
-    };
-    double* wv[10][1]; double* const* w[10];
-    for (int q = 0; q < 10; q++) { wv[q][0] = ctx->hvec[q]; w[q] = wv[q]; }
+    launch3(ctx, g, k3_heat_rhs, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, B.p, 1);
+    ctx->napply = 0;
+    Vec3 w[K_NW];
+    for (int q = 0; q < K_NW; q++) w[q] = hvec(ctx, q);
     Stats3 st{};
-    P3_TRY(bicgstab3(ctx, g.vol, 1, A, nullptr, B, X, false, rtol, maxit, w, g, &st, 0.0));
+    P3_TRY(bicgstab3(ctx, heat_A3, nullptr, B, X, false, rtol, maxit, w, &st, 0.0));
     P3_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     P3_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0; P3_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->have_T = true;
-    if (x) P3_TRY(download3(ctx, X, 1, x));
+    if (x) P3_TRY(download3(ctx, &ctx->hvec[11], 1, x));
     if (stats) { stats->iterations = st.iterations; stats->converged = st.converged; stats->rel_residual = st.rel_residual; stats->solve_ms = ms;
-                 stats->operator_applies = napply; stats->precond_applies = 0; }
+                 stats->operator_applies = ctx->napply; stats->precond_applies = 0; }
     return 0;
 }
 
@@ -2257,11 +2244,10 @@ extern "C" int pl3_get_solution(pl3_ctx* ctx, int which, double* out) {
     P3_HIP(ctx, hipSetDevice(ctx->device));
     if (which == 0) {
         if (!ctx->have_x) return p3_fail(ctx, "pl3_get_solution: no Stokes solution yet");
-        return download3(ctx, ctx->vec[11], 4, out);
+        return download3(ctx, wv4(svec(ctx, 11)).p, 4, out);
     }
     if (!ctx->have_T) return p3_fail(ctx, "pl3_get_solution: no heat solution yet");
-    double* X[1] = {ctx->hvec[11]};
-    return download3(ctx, X, 1, out);
+    return download3(ctx, &ctx->hvec[11], 1, out);
 }
 
 // ---- what the device-resident step (pl_step3.hip) needs of a context ----------------------------------------------------------
@@ -2271,7 +2257,7 @@ int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     P3_TRY(need_hvecs(ctx));
     const G3& g = ctx->geom.d;
     v->s0 = g.s[0]; v->s1 = g.s[1]; v->pad = P3_PAD; v->stream = ctx->stream; v->slot = &ctx->step3;
-    for (int q = 0; q < 4; q++) { v->X[q] = ctx->vec[11][q]; v->scratch[q] = ctx->vec[0][q]; }
+    for (int q = 0; q < 4; q++) { v->X[q] = svec(ctx, 11)[q]; v->scratch[q] = svec(ctx, 0)[q]; }
     v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T; v->noslip = ctx->noslip; v->wallvel = ctx->wallvel;
     return 0;
 }
