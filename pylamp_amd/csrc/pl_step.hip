@@ -3,9 +3,10 @@
 // to tracers + subgrid diffusion, velocity re-centring + ghost fill, RK4 advection, fence).
 // plus the end-of-step cell sort, slab migration and census / injection (pylamp2.py:588-633).
 // Tracers and every grid field stay in HBM across steps; the host only sees scalars.
-// Not included: tracer deletion (pylamp2.py:574-581) - it cannot trigger with the supported walls.
+// Tracer deletion (pylamp2.py:574-581, fence off) is part of the sort: the trash bucket and compact_deleted.
 #include "pl_internal.h"
 #include "pl_mic.h"
+#include "pl_x0.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -16,7 +17,7 @@ enum { TR_RHO = 0, TR_ETA, TR_MRK, TR_TMP, TR_HCD, TR_HCP, TR_RH0, TR_ALP, TR_MA
 #define GASR 8.31446
 #define PL_EPS (1.0 / 1024.0)      // pylamp_const.py:46
 
-constexpr int X0_HIST = 5;                     // older Stokes solutions kept at most for the extrapolated initial guess
+constexpr int NTCOLS = NFTRAC + 4;              // columns that travel with a tracer (TracerCols)
 struct PlStepState {
     long long n = 0, cap = 0;
     double* tz = nullptr; double* tx = nullptr;      // positions (SoA)
@@ -66,15 +67,27 @@ static PlStepState* state_of(pl_ctx* ctx) {
     return (PlStepState*)ctx->step;
 }
 
+// Every per-tracer array: grow_tracers (re)allocates them, pl_step_free frees them.  kept: the contents survive a growth
+// (the tracer columns, and the sort keys of a sort in progress); the others are scratch.
+struct TracerArray { void** p; size_t elem; bool kept; };
+static std::vector<TracerArray> tracer_arrays(PlStepState* S) {
+    std::vector<TracerArray> v;              // (in the order they have always been allocated in: another order cost the advection stage 2.5 % at 2049^2)
+    for (double** q : {&S->tz, &S->tx, &S->tz2, &S->tx2, &S->vtz, &S->vtx, &S->tmp[0], &S->tmp[1], &S->tmp[2]})
+        v.push_back({(void**)q, sizeof(double), q == &S->tz || q == &S->tx || q == &S->vtz || q == &S->vtx});
+    for (int k = 0; k < NFTRAC; k++) { v.push_back({(void**)&S->f[k], sizeof(double), true}); v.push_back({(void**)&S->f2[k], sizeof(double), false}); }
+    for (int** q : {&S->cell, &S->dest, &S->orig, &S->orig2, &S->slot, &S->slot2})
+        v.push_back({(void**)q, sizeof(int), q == &S->cell || q == &S->orig || q == &S->slot});
+    return v;
+}
+// the tables of the sort grid (sort_tables): ints per sort bucket; block_sums, the last, holds the partial sums of their scans
+static std::vector<int**> sort_table_arrays(PlStepState* S) { return {&S->cell_count, &S->cell_start, &S->need, &S->need_off, &S->need_flag, &S->need_rank, &S->cell_res, &S->block_sums}; }
+
 void pl_step_free(pl_ctx* ctx) {
     PlStepState* s = (PlStepState*)ctx->step;
     if (!s) return;
-    for (double* q : {s->tz, s->tx, s->tz2, s->tx2, s->vtz, s->vtx, s->tmp[0], s->tmp[1], s->tmp[2], s->partial, s->gcoords})
-        if (q) (void)hipFree(q);
-    for (double* q : s->f) if (q) (void)hipFree(q);
-    for (double* q : s->f2) if (q) (void)hipFree(q);
-    for (double* q : {s->flags, s->counts_dev}) if (q) (void)hipFree(q);
-    for (int* q : {s->slot, s->slot2, s->cell, s->dest, s->orig, s->orig2, s->cell_count, s->cell_start, s->block_sums, s->need, s->need_off, s->need_flag, s->need_rank, s->cell_res}) if (q) (void)hipFree(q);
+    for (const TracerArray& a : tracer_arrays(s)) if (*a.p) (void)hipFree(*a.p);
+    for (int** q : sort_table_arrays(s)) if (*q) (void)hipFree(*q);
+    for (double* q : {s->partial, s->gcoords, s->flags, s->counts_dev}) if (q) (void)hipFree(q);
     delete s;
     ctx->step = nullptr;
 }
@@ -482,58 +495,43 @@ static int reduce_minmax_multi(pl_ctx* ctx, PlStepState* S, const PlGeom& g, int
     return 0;
 }
 
-// grow every tracer array to hold n tracers, keeping the first `keep` entries
+// Grow every tracer array (tracer_arrays) to hold n tracers.  The first `keep` entries of the kept arrays are carried over
+// (allocate, copy, free); an array with nothing to carry over is freed BEFORE its successor is allocated (peak memory).
 static int grow_tracers(pl_ctx* ctx, PlStepState* S, long long n, long long keep) {
     if (n <= S->cap) return 0;
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const long long cap = n + n / 8 + 1024;
-    auto regrow = [&](double** p, bool copy) -> int {
-        double* q = nullptr;
-        PL_HIP(ctx, hipMalloc((void**)&q, (size_t)cap * sizeof(double)));
-        if (copy && *p && keep > 0) PL_HIP(ctx, hipMemcpy(q, *p, (size_t)keep * sizeof(double), hipMemcpyDeviceToDevice));
-        if (*p) (void)hipFree(*p);
-        *p = q;
-        return 0;
-    };
-    PL_TRY(regrow(&S->tz, true)); PL_TRY(regrow(&S->tx, true));
-    for (int k = 0; k < NFTRAC; k++) { PL_TRY(regrow(&S->f[k], true)); PL_TRY(regrow(&S->f2[k], false)); }
-    PL_TRY(regrow(&S->vtz, true)); PL_TRY(regrow(&S->vtx, true));
-    for (double** q : {&S->tz2, &S->tx2, &S->tmp[0], &S->tmp[1], &S->tmp[2]}) PL_TRY(regrow(q, false));
-    for (int** q : {&S->dest, &S->orig2, &S->slot2}) {
-        if (*q) (void)hipFree(*q);
-        PL_HIP(ctx, hipMalloc((void**)q, (size_t)cap * sizeof(int)));
-    }
-    for (int** pq : {&S->orig, &S->cell, &S->slot}) {        // the sort keys of a sort in progress are kept as well
-        int* q = nullptr; PL_HIP(ctx, hipMalloc((void**)&q, (size_t)cap * sizeof(int)));
-        if (*pq && keep > 0) PL_HIP(ctx, hipMemcpy(q, *pq, (size_t)keep * sizeof(int), hipMemcpyDeviceToDevice));
-        if (*pq) (void)hipFree(*pq);
-        *pq = q;
+    for (const TracerArray& a : tracer_arrays(S)) {
+        const bool carry = a.kept && keep > 0 && *a.p;
+        if (!carry && *a.p) { (void)hipFree(*a.p); *a.p = nullptr; }
+        void* q = nullptr;
+        PL_HIP(ctx, hipMalloc(&q, (size_t)cap * a.elem));
+        if (carry) { PL_HIP(ctx, hipMemcpy(q, *a.p, (size_t)keep * a.elem, hipMemcpyDeviceToDevice)); (void)hipFree(*a.p); }
+        *a.p = q;
     }
     S->cap = cap;
     return 0;
 }
-
-static int ensure_tracers(pl_ctx* ctx, PlStepState* S, long long n) {
-    if (n <= S->cap) return 0;
-    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    long long cap = n + n / 8 + 1024;
-    auto re = [&](double** p) -> int {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        PL_HIP(ctx, hipMalloc((void**)p, (size_t)cap * sizeof(double)));
-        return 0;
-    };
-    for (double** q : {&S->tz, &S->tx, &S->tz2, &S->tx2, &S->vtz, &S->vtx, &S->tmp[0], &S->tmp[1], &S->tmp[2]}) PL_TRY(re(q));
-    for (int k = 0; k < NFTRAC; k++) { PL_TRY(re(&S->f[k])); PL_TRY(re(&S->f2[k])); }
-    for (int** q : {&S->cell, &S->dest, &S->orig, &S->orig2, &S->slot, &S->slot2}) {
-        if (*q) (void)hipFree(*q);
-        PL_HIP(ctx, hipMalloc((void**)q, (size_t)cap * sizeof(int)));
-    }
-    S->cap = cap;
-    return 0;
+// The columns that travel with a tracer -- positions, the 13 fields, the velocities of the last advection -- and the spare
+// each one is permuted / received into; the order is that of LeaverArgs / ArrivalArgs.
+struct TracerCols { double* col[NTCOLS]; double* spare[NTCOLS]; };
+static_assert(NTCOLS == 17, "LeaverArgs / ArrivalArgs hold 17 columns");
+static TracerCols tracer_cols(const PlStepState* S) {
+    TracerCols c; int k = 0;
+    c.col[k] = S->tz; c.spare[k++] = S->tz2; c.col[k] = S->tx; c.spare[k++] = S->tx2;
+    for (int f = 0; f < NFTRAC; f++) { c.col[k] = S->f[f]; c.spare[k++] = S->f2[f]; }
+    c.col[k] = S->vtz; c.spare[k++] = S->tmp[0]; c.col[k] = S->vtx; c.spare[k++] = S->tmp[1];
+    return c;
 }
 
-static void unpermute(pl_ctx* ctx, PlStepState* S, int na, const double* const* in, double* const* out);
+// un-permute resident arrays into the spare buffers so that downloads come out in the caller's order
+static void unpermute(pl_ctx* ctx, PlStepState* S, int na, const double* const* in, double* const* out) {
+    for (int k0 = 0; k0 < na; k0 += 5) {
+        PermArgs pa{}; pa.na = std::min(5, na - k0);
+        for (int k = 0; k < pa.na; k++) { pa.in[k] = in[k0 + k]; pa.out[k] = out[k0 + k]; }
+        hipLaunchKernelGGL(k_permute, grid1d(S->n), dim3(256), 0, ctx->stream, S->n, S->orig, pa);
+    }
+}
 static bool scatter_cells_on() { const char* e = getenv("PYLAMP_SCATTER"); return !(e && atoi(e) == 0); }    // read per call: tests switch it
 static int ensure_current(pl_ctx* ctx, PlStepState* S);
 struct SortOpts {
@@ -544,7 +542,15 @@ struct SortOpts {
     bool premigrated = false;         // several ranks: leavers have been sent and re-keyed as trash, arrivals appended with their keys (migrate_presort)
     bool drop_trash = false;          // the trash bucket behind the sorted tracers is dropped (S->n = everything before it)
 };
-static int sort_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, double x0, double hx, const SortOpts& o = SortOpts());
+// the regular node grid as the marker kernels take it: first node and spacing per axis
+struct StepGrid { double z0, hz, x0, hx; };
+static StepGrid step_grid(pl_ctx* ctx) {
+    const int nz = ctx->nz, nx = ctx->nx;
+    StepGrid q; q.z0 = ctx->geom.zc[0]; q.x0 = ctx->geom.xc[0];
+    q.hz = (ctx->geom.zc[nz - 1] - q.z0) / (nz - 1); q.hx = (ctx->geom.xc[nx - 1] - q.x0) / (nx - 1);
+    return q;
+}
+static int sort_tracers(pl_ctx* ctx, PlStepState* S, const StepGrid& q, const SortOpts& o = SortOpts());
 // Host midpoint grids (pylamp2.py:92-95) and device copies of all coordinate arrays the marker kernels use:
 // gcoords = [ node z (nz) | node x (nx) | padded centres z (nz+1) | padded centres x (nx+1) ]; the centre
 // (midpoint) grids of the staggered targets are the padded ones without their first entry.
@@ -576,13 +582,13 @@ static const double* coords_x(pl_ctx* ctx, PlStepState* S, int stag) {
     if (ctx->geom.uniform) return nullptr;
     return stag ? S->gcoords + ctx->nz + ctx->nx + (ctx->nz + 1) + 1 : S->gcoords + ctx->nz;
 }
-static int migrate_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, double x0, double hx, const SortOpts& o = SortOpts());
+static int migrate_tracers(pl_ctx* ctx, PlStepState* S, const StepGrid& q, const SortOpts& o = SortOpts());
 
 extern "C" int pl_tracers_upload(pl_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f) {
     if (n < 0 || !tr_x || !tr_f) return pl_fail(ctx, "pl_tracers_upload: bad argument");
     PL_HIP(ctx, hipSetDevice(ctx->device));
     PlStepState* S = state_of(ctx);
-    PL_TRY(ensure_tracers(ctx, S, n));
+    PL_TRY(grow_tracers(ctx, S, n, 0));
     S->epoch_on = false; S->epoch_age = 0; S->lazy_pending = false; S->cols_undefined = false;
     // stream the AoS rows through the staging buffer in chunks
     const long long chunk = 1 << 22;
@@ -608,11 +614,9 @@ extern "C" int pl_tracers_upload(pl_ctx* ctx, int64_t n, const double* tr_x, con
     S->max_id = idmax[0]; S->max_id_valid = true;
     // cell-sort (and, on a slab, hand over anything that does not belong here)
     PL_TRY(ensure_coords(ctx, S));
-    const int nz = ctx->nz, nx = ctx->nx;
-    const double z0 = ctx->geom.zc[0], x0 = ctx->geom.xc[0];
-    const double hz = (ctx->geom.zc[nz - 1] - z0) / (nz - 1), hx = (ctx->geom.xc[nx - 1] - x0) / (nx - 1);
-    { SortOpts so; so.full = true; PL_TRY(sort_tracers(ctx, S, z0, hz, x0, hx, so)); }     // (an epoch opened on the caller's random order would scatter every read of the constant columns)
-    PL_TRY(migrate_tracers(ctx, S, z0, hz, x0, hx));
+    const StepGrid q = step_grid(ctx);
+    { SortOpts so; so.full = true; PL_TRY(sort_tracers(ctx, S, q, so)); }     // (an epoch opened on the caller's random order would scatter every read of the constant columns)
+    PL_TRY(migrate_tracers(ctx, S, q));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     S->sorted = true;
     return 0;
@@ -625,12 +629,8 @@ extern "C" int pl_tracers_download(pl_ctx* ctx, int64_t n, double* tr_x, double*
     PL_TRY(ensure_current(ctx, S));
     const long long chunk = 1 << 22;
     PL_TRY(pl_stage(ctx, (size_t)chunk * NFTRAC * sizeof(double)));
-    {   // caller's order
-        const double* in[15]; double* out[15];
-        in[0] = S->tz; out[0] = S->tz2; in[1] = S->tx; out[1] = S->tx2;
-        for (int k = 0; k < NFTRAC; k++) { in[2 + k] = S->f[k]; out[2 + k] = S->f2[k]; }
-        unpermute(ctx, S, 15, in, out);
-    }
+    const TracerCols c = tracer_cols(S);
+    unpermute(ctx, S, NTCOLS - 2, c.col, c.spare);      // caller's order: positions and fields (the velocities have their own download)
     double* const uz = S->tz2; double* const ux = S->tx2; double* const* uf = S->f2;
     for (long long t0 = 0; t0 < n; t0 += chunk) {
         long long m = std::min<long long>(chunk, n - t0);
@@ -777,11 +777,13 @@ __global__ __launch_bounds__(256) void k_add_need(int nc, int m, const int* __re
     if (c < m) total[c] = count[c] + (c < nc ? need[c] : 0);
 }
 
-static int scan_ints(pl_ctx* ctx, PlStepState* S, int m, const int* in, int* out) {
+// exclusive scan of m ints; bsum: (m + 1023) / 1024 + 1 ints for the block sums (NULL: the sort tables' block_sums)
+static int scan_ints(pl_ctx* ctx, PlStepState* S, int m, const int* in, int* out, int* bsum = nullptr) {
     const int nb = (m + 1023) / 1024;
-    hipLaunchKernelGGL(k_scan_block, dim3(nb), dim3(256), 0, ctx->stream, m, in, out, S->block_sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, nb, S->block_sums);
-    hipLaunchKernelGGL(k_scan_add, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, m, out, S->block_sums, 0);
+    if (!bsum) bsum = S->block_sums;
+    hipLaunchKernelGGL(k_scan_block, dim3(nb), dim3(256), 0, ctx->stream, m, in, out, bsum);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, nb, bsum);
+    hipLaunchKernelGGL(k_scan_add, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, m, out, bsum, 0);
     return 0;
 }
 
@@ -843,6 +845,148 @@ static int ensure_current(pl_ctx* ctx, PlStepState* S) {
     return relayout(ctx, S);
 }
 
+// ---- the parts of sort_tracers (below), in the order it runs them ------------------------------------------------------------------
+// cells of this rank's block = its nodes (the last block owns one more node)
+static void block_cells(const PlGeom& g, int& ncz, int& ncx) {
+    ncz = (g.gi0 + g.lnz >= g.nz) ? g.lnz - 1 : g.lnz;
+    ncx = (g.gj0 + g.lnx >= g.nx) ? g.lnx - 1 : g.lnx;
+}
+// the tables of the sort grid, (re)allocated when the grid has changed: ncz * ncx cells + 8 leaver buckets + trash + total
+static int sort_tables(pl_ctx* ctx, PlStepState* S, int ncz, int ncx, bool keys_ready) {
+    if (S->cell_count && S->ncz == ncz && S->ncx == ncx) return 0;
+    if (keys_ready) return pl_fail(ctx, "sort_tracers: sort keys announced for another sort grid (internal error)");
+    for (int** q : sort_table_arrays(S)) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    const int m = ncz * ncx + 10, nb = (m + 1023) / 1024;
+    for (int** q : sort_table_arrays(S)) PL_HIP(ctx, hipMalloc((void**)q, (size_t)(q == &S->block_sums ? nb + 1 : m) * sizeof(int)));
+    S->ncz = ncz; S->ncx = ncx;
+    return 0;
+}
+// current maximum of TR__ID over all ranks, from the device (a deletion may have removed the holder of the cached one)
+static int recompute_max_id(pl_ctx* ctx, PlStepState* S, long long n) {
+    double mx[1] = {-1.0};
+    if (n > 0) {
+        const int nbm = 256;
+        if (!S->partial || S->hpartial.size() < (size_t)3 * 4096) {
+            if (S->partial) (void)hipFree(S->partial);
+            PL_HIP(ctx, hipMalloc((void**)&S->partial, 3 * 4096 * sizeof(double)));
+            S->hpartial.resize(3 * 4096);
+        }
+        hipLaunchKernelGGL(k_max1d, dim3(nbm), dim3(256), 0, ctx->stream, n, S->f[TR__ID], S->partial);
+        PL_HIP(ctx, hipMemcpyAsync(S->hpartial.data(), S->partial, nbm * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int k = 0; k < nbm; k++) mx[0] = std::fmax(mx[0], S->hpartial[k]);
+    }
+    PL_TRY(pl_allreduce_host(ctx, mx, 1, 2));
+    S->max_id = mx[0]; S->max_id_valid = true;
+    return 0;
+}
+// Census + deficits (the counts ARE the census) and the IDs of the new tracers; grows the arrays to hold them.
+struct Census { long long ninj = 0; double id0 = 0.0; bool strict = false; };      // new tracers of this rank, its first new ID, the reference's ID rule
+static int census_and_ids(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, int nc, long long n, bool epoch_ok, Census& cs) {
+    const int m = nc + 10, ncx = S->ncx, ncz = S->ncz;
+    // resident counts of the cells as the deficit kernel expects them (start[c+1]-start[c]): scan the counts first
+    scan_ints(ctx, S, m, S->cell_count, S->cell_res);
+    hipLaunchKernelGGL(k_deficit, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream, nc, ncx, 0, ncz, S->cell_res, cfg->tracdens,
+                       cfg->tracdens_min, S->need, S->need_flag);
+    scan_ints(ctx, S, nc + 1, S->need, S->need_off);
+    scan_ints(ctx, S, nc + 1, S->need_flag, S->need_rank);
+    int h2[2] = {0, 0};
+    PL_HIP(ctx, hipMemcpyAsync(&h2[0], S->need_off + nc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipMemcpyAsync(&h2[1], S->need_rank + nc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    cs.ninj = h2[0];
+    // new IDs in global (rank-major) cell order: rank r continues after the ranks before it
+    const int R = ctx->nranks;
+    std::vector<double> cnt((size_t)2 * R, 0.0);
+    cnt[2 * ctx->rank] = (double)cs.ninj; cnt[2 * ctx->rank + 1] = h2[1];      // (new tracers, refilled cells)
+    if (R > 1) {                                              // every rank's (new tracers, refilled cells): summed on the device
+        PL_TRY(step_counts(ctx, S, 2 * R));
+        hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 1, (const int*)(S->need_off + nc), 0, S->counts_dev, 2 * ctx->rank);
+        hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 1, (const int*)(S->need_rank + nc), 0, S->counts_dev, 2 * ctx->rank + 1);
+        PL_TRY(pl_comm_allreduce_dev(ctx, S->counts_dev, 2 * R, 0));
+        PL_HIP(ctx, hipMemcpyAsync(cnt.data(), S->counts_dev, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    double before = 0.0, total = 0.0, def_before = 0.0, def_total = 0.0;
+    for (int q = 0; q < R; q++) {
+        if (q < ctx->rank) { before += cnt[2 * q]; def_before += cnt[2 * q + 1]; }
+        total += cnt[2 * q]; def_total += cnt[2 * q + 1];
+    }
+    if (total > 0.0) {
+        if (!S->max_id_valid) PL_TRY(recompute_max_id(ctx, S, n));
+        cs.strict = cfg->inject_unique_ids == 0;
+        // strict: IDs start AT the current maximum and every refilled cell repeats one (pylamp2.py:621-622)
+        cs.id0 = cs.strict ? S->max_id + before - def_before : S->max_id + 1.0 + before;
+        S->max_id += cs.strict ? total - def_total : total;
+    }
+    if (cs.ninj > 0) {
+        const long long used = std::max(n, (epoch_ok && S->epoch_on) ? S->epoch_len : n);
+        PL_TRY(grow_tracers(ctx, S, used + cs.ninj, used));
+    }
+    return 0;
+}
+// positions, temperature and slot: placement and permutation in ONE pass; RHO, ETA and the tracer velocities stay behind (lazy)
+static void permute_epoch(pl_ctx* ctx, PlStepState* S, long long n) {
+    PermArgs pa{}; pa.na = 3;
+    pa.in[0] = S->tz; pa.out[0] = S->tz2; pa.in[1] = S->tx; pa.out[1] = S->tx2; pa.in[2] = S->f[TR_TMP]; pa.out[2] = S->f2[TR_TMP];
+    hipLaunchKernelGGL(k_place_permute, grid1d(n), dim3(256), 0, ctx->stream, n, S->cell, S->cell_start, S->cell_count, S->dest, pa,
+                       S->epoch_on ? (const int*)S->slot : (const int*)nullptr, S->slot2);
+    std::swap(S->tz, S->tz2); std::swap(S->tx, S->tx2);
+    std::swap(S->vtz, S->tmp[0]); std::swap(S->vtx, S->tmp[1]);         // (lazy: the old values stay in tmp[0..1] / f2[RHO], f2[ETA])
+    std::swap(S->slot, S->slot2);
+    for (int k : {(int)TR_TMP, (int)TR_RHO, (int)TR_ETA}) std::swap(S->f[k], S->f2[k]);
+}
+// classic: positions, the 13 fields and the velocities of the last advection travel together
+static void permute_classic(pl_ctx* ctx, PlStepState* S, long long n) {
+    hipLaunchKernelGGL(k_cell_place, grid1d(n), dim3(256), 0, ctx->stream, n, S->cell, S->cell_start, S->cell_count, S->dest);
+    const TracerCols c = tracer_cols(S);
+    for (int k0 = 0; k0 < NTCOLS; k0 += 5) {
+        PermArgs pa{}; pa.na = std::min(5, NTCOLS - k0);
+        for (int k = 0; k < pa.na; k++) { pa.in[k] = c.col[k0 + k]; pa.out[k] = c.spare[k0 + k]; }
+        hipLaunchKernelGGL(k_permute, grid1d(n), dim3(256), 0, ctx->stream, n, S->dest, pa);
+    }
+    hipLaunchKernelGGL(k_permute_int, grid1d(n), dim3(256), 0, ctx->stream, n, S->dest, S->orig, S->orig2);
+    std::swap(S->tz, S->tz2); std::swap(S->tx, S->tx2); std::swap(S->orig, S->orig2);
+    std::swap(S->vtz, S->tmp[0]); std::swap(S->vtx, S->tmp[1]);
+    for (int k = 0; k < NFTRAC; k++) std::swap(S->f[k], S->f2[k]);
+}
+// the new tracers of the census, written into the room the permutation left behind the residents of their cell
+static void launch_inject(pl_ctx* ctx, PlStepState* S, const StepGrid& q, const SortOpts& o, const Census& cs, int nc, long long n, bool epoch_ok) {
+    InjectSorted a{};
+    a.nc = nc; a.ncx = S->ncx; a.crow0 = S->crow0; a.ccol0 = S->ccol0; a.start = S->cell_start; a.count = S->cell_res;
+    a.need = S->need; a.off = S->need_off; a.rank = cs.strict ? S->need_rank : nullptr;
+    a.tz = S->tz; a.tx = S->tx; for (int k = 0; k < NFTRAC; k++) a.f[k] = S->f[k];
+    a.vtz = S->vtz; a.vtx = S->vtx; a.orig = S->orig;
+    a.slot = epoch_ok ? S->slot : nullptr; a.lazy = epoch_ok ? 1 : 0;
+    a.z0 = q.z0; a.hz = q.hz; a.x0 = q.x0; a.hx = q.hx; a.seed = o.inject->inject_seed; a.step = (unsigned)o.it; a.id0 = cs.id0;
+    a.n_old = (int)(epoch_ok ? S->epoch_len : n);        // epoch layout: the constants of new tracers go behind everything the epoch holds
+    if (epoch_ok) S->epoch_len += cs.ninj;
+    a.zc = coords_z(ctx, S, 0); a.xc = coords_x(ctx, S, 0);
+    hipLaunchKernelGGL(k_inject_sorted, dim3((nc + 63) / 64), dim3(64), 0, ctx->stream, a);
+    S->n = n + cs.ninj;
+}
+// Deletion (o.del_outside): the sort has put the deleted tracers into the trash bucket behind everything else; drop them and
+// renumber `orig` so that downloads keep the caller's relative order (np.delete keeps it, pylamp2.py:578-580).
+static int compact_deleted(pl_ctx* ctx, PlStepState* S, int nc, long long* removed) {
+    int h[2] = {0, 0};
+    PL_HIP(ctx, hipMemcpyAsync(h, S->cell_start + nc + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int alive_n = h[0], all_n = h[1];
+    if (alive_n >= all_n) return 0;
+    // the survivors are the first alive_n entries; cell / dest are free after the sort: alive flag per caller's index and its scan
+    PL_HIP(ctx, hipMemsetAsync(S->cell, 0, (size_t)all_n * sizeof(int), ctx->stream));
+    if (alive_n > 0) hipLaunchKernelGGL(k_mark_alive, grid1d(alive_n), dim3(256), 0, ctx->stream, (long long)alive_n, S->orig, S->cell);
+    int* bs = nullptr;
+    PL_HIP(ctx, hipMalloc((void**)&bs, (size_t)((all_n + 1023) / 1024 + 1) * sizeof(int)));
+    scan_ints(ctx, S, all_n, S->cell, S->dest, bs);
+    if (alive_n > 0) hipLaunchKernelGGL(k_remap_orig, grid1d(alive_n), dim3(256), 0, ctx->stream, (long long)alive_n, S->orig, S->dest);
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(bs);
+    if (removed) *removed = all_n - alive_n;
+    S->n = alive_n; S->max_id_valid = false;
+    return 0;
+}
+
 // Counting sort of all tracer arrays by the cells of this rank's block; leaves cell_start valid:
 //   [0, nc] cells (cell_start[nc] = number of stayers), [nc, nc+8] the leaver buckets per neighbour block,
 //   [nc+8] the trash bucket (deleted tracers), [nc+9] = all.
@@ -850,103 +994,33 @@ static int ensure_current(pl_ctx* ctx, PlStepState* S) {
 // o.inject: census + refill (pylamp2.py:588-633) in the SAME pass -- the deficits follow from the counts, the
 // permutation leaves room for the new tracers behind the residents of their cell, and they are written straight
 // into their sorted slots (no second sort: re-sorting 67 M tracers for a few thousand new ones took 4.4 ms).
-static int sort_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, double x0, double hx, const SortOpts& o) {
+static int sort_tracers(pl_ctx* ctx, PlStepState* S, const StepGrid& q, const SortOpts& o) {
     const PlGeom& g = ctx->geom.d;
-    const int ncz = (g.gi0 + g.lnz >= g.nz) ? g.lnz - 1 : g.lnz;        // cells of the block = its nodes (the last block owns one more node)
-    const int ncx = (g.gj0 + g.lnx >= g.nx) ? g.lnx - 1 : g.lnx;
+    int ncz, ncx; block_cells(g, ncz, ncx);
     const int nc = ncz * ncx, m = nc + 10;
     S->crow0 = g.gi0; S->ccol0 = g.gj0;
-    long long n = S->n;
+    const long long n = S->n;
     if (n >= (1LL << 31)) return pl_fail(ctx, "sort_tracers: more than 2^31 tracers per GPU");
-    // epoch layout + lazy columns (see above) where the resident step is the only reader until the next sort
+    // ---- layout: epoch layout + lazy columns (see above) where the resident step is the only reader until the next sort
     const bool epoch_ok = !o.full && epoch_length() > 0 && (ctx->nranks == 1 || o.premigrated) && !o.del_outside && ctx->geom.uniform && scatter_cells_on();
     if (!epoch_ok) PL_TRY(ensure_current(ctx, S));
     else {
         PL_TRY(flush_lazy(ctx, S));                     // (pl_step has dropped them already: rewritten before anything reads them)
         if (S->epoch_on && S->epoch_age >= epoch_length()) PL_TRY(relayout(ctx, S));
     }
-    if (!S->cell_count || S->ncz != ncz || S->ncx != ncx) {
-        if (o.keys_ready) return pl_fail(ctx, "sort_tracers: sort keys announced for another sort grid (internal error)");
-        for (int** q : {&S->cell_count, &S->cell_start, &S->block_sums, &S->need, &S->need_off, &S->need_flag, &S->need_rank, &S->cell_res}) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-        const int nb = (m + 1023) / 1024;
-        for (int** q : {&S->cell_count, &S->cell_start, &S->need, &S->need_off, &S->need_flag, &S->need_rank, &S->cell_res})
-            PL_HIP(ctx, hipMalloc((void**)q, (size_t)m * sizeof(int)));
-        PL_HIP(ctx, hipMalloc((void**)&S->block_sums, (size_t)(nb + 1) * sizeof(int)));
-        S->ncz = ncz; S->ncx = ncx;
-    }
+    // ---- tables and keys
+    PL_TRY(sort_tables(ctx, S, ncz, ncx, o.keys_ready));
     S->sort_cells = nc;
     if (!o.keys_ready) {
         PL_HIP(ctx, hipMemsetAsync(S->cell_count, 0, (size_t)m * sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(k_cell_count, grid1d(n), dim3(256), 0, ctx->stream, n, S->tz, S->tx, z0, hz, x0, hx, coords_z(ctx, S, 0),
+        hipLaunchKernelGGL(k_cell_count, grid1d(n), dim3(256), 0, ctx->stream, n, S->tz, S->tx, q.z0, q.hz, q.x0, q.hx, coords_z(ctx, S, 0),
                            coords_x(ctx, S, 0), ncz, ncx, S->crow0, S->ccol0, g.nz - 1, g.nx - 1, S->cell, S->cell_count, o.del_outside, o.Lz, o.Lx);
     }
-    // ---- census + deficits (the counts ARE the census)
-    long long ninj = 0; int ndef = 0;
-    double id0 = 0.0; bool strict = false;
-    const bool inj = o.inject && o.inject->tracdens_min > 0 && o.inject->tracdens > 0;
-    if (inj) {
-        const pl_step_config* cfg = o.inject;
-        // resident counts of the cells as the deficit kernel expects them (start[c+1]-start[c]): scan the counts first
-        scan_ints(ctx, S, m, S->cell_count, S->cell_res);
-        hipLaunchKernelGGL(k_deficit, dim3((nc + 1 + 255) / 256), dim3(256), 0, ctx->stream, nc, ncx, 0, ncz, S->cell_res, cfg->tracdens,
-                           cfg->tracdens_min, S->need, S->need_flag);
-        scan_ints(ctx, S, nc + 1, S->need, S->need_off);
-        scan_ints(ctx, S, nc + 1, S->need_flag, S->need_rank);
-        int h2[2] = {0, 0};
-        PL_HIP(ctx, hipMemcpyAsync(&h2[0], S->need_off + nc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        PL_HIP(ctx, hipMemcpyAsync(&h2[1], S->need_rank + nc, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ninj = h2[0]; ndef = h2[1];
-        // new IDs in global (rank-major) cell order: rank r continues after the ranks before it
-        const int R = ctx->nranks;
-        std::vector<double> cnt((size_t)2 * R, 0.0);
-        cnt[2 * ctx->rank] = (double)ninj; cnt[2 * ctx->rank + 1] = ndef;
-        if (R > 1) {                                              // every rank's (new tracers, refilled cells): summed on the device
-            PL_TRY(step_counts(ctx, S, 2 * R));
-            hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 1, (const int*)(S->need_off + nc), 0, S->counts_dev, 2 * ctx->rank);
-            hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 1, (const int*)(S->need_rank + nc), 0, S->counts_dev, 2 * ctx->rank + 1);
-            PL_TRY(pl_comm_allreduce_dev(ctx, S->counts_dev, 2 * R, 0));
-            PL_HIP(ctx, hipMemcpyAsync(cnt.data(), S->counts_dev, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        double before = 0.0, total = 0.0, def_before = 0.0, def_total = 0.0;
-        for (int q = 0; q < R; q++) {
-            if (q < ctx->rank) { before += cnt[2 * q]; def_before += cnt[2 * q + 1]; }
-            total += cnt[2 * q]; def_total += cnt[2 * q + 1];
-        }
-        if (total > 0.0) {
-            if (!S->max_id_valid) {                                // a deletion may have removed the holder of the maximum
-                double mx[1] = {-1.0};
-                if (n > 0) {
-                    const int nbm = 256;
-                    if (!S->partial || S->hpartial.size() < (size_t)3 * 4096) {
-                        if (S->partial) (void)hipFree(S->partial);
-                        PL_HIP(ctx, hipMalloc((void**)&S->partial, 3 * 4096 * sizeof(double)));
-                        S->hpartial.resize(3 * 4096);
-                    }
-                    hipLaunchKernelGGL(k_max1d, dim3(nbm), dim3(256), 0, ctx->stream, n, S->f[TR__ID], S->partial);
-                    PL_HIP(ctx, hipMemcpyAsync(S->hpartial.data(), S->partial, nbm * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    for (int k = 0; k < nbm; k++) mx[0] = std::fmax(mx[0], S->hpartial[k]);
-                }
-                PL_TRY(pl_allreduce_host(ctx, mx, 1, 2));
-                S->max_id = mx[0]; S->max_id_valid = true;
-            }
-            strict = cfg->inject_unique_ids == 0;
-            // strict: IDs start AT the current maximum and every refilled cell repeats one (pylamp2.py:621-622)
-            id0 = strict ? S->max_id + before - def_before : S->max_id + 1.0 + before;
-            S->max_id += strict ? total - def_total : total;
-        }
-        if (ninj > 0) {
-            const long long used = std::max(n, (epoch_ok && S->epoch_on) ? S->epoch_len : n);
-            PL_TRY(grow_tracers(ctx, S, used + ninj, used));
-        }
-    }
+    // ---- census
+    Census cs;
+    if (o.inject && o.inject->tracdens_min > 0 && o.inject->tracdens > 0) PL_TRY(census_and_ids(ctx, S, o.inject, nc, n, epoch_ok, cs));
     // ---- offsets of the sorted arrays: residents (+ room for the new tracers of a cell right behind them)
-    if (ninj > 0) {
+    if (cs.ninj > 0) {
         hipLaunchKernelGGL(k_add_need, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, nc, m, S->cell_count, S->need, S->cell_res);
         scan_ints(ctx, S, m, S->cell_res, S->cell_start);
         PL_HIP(ctx, hipMemcpyAsync(S->cell_res, S->cell_count, (size_t)m * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));   // residents per cell
@@ -954,53 +1028,19 @@ static int sort_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, doubl
         scan_ints(ctx, S, m, S->cell_count, S->cell_start);
     }
     PL_HIP(ctx, hipMemsetAsync(S->cell_count, 0, (size_t)m * sizeof(int), ctx->stream));   // reused as fill counters
-    if (n > 0 && epoch_ok) {                                // positions, temperature and slot: placement and permutation in ONE pass
-        PermArgs pa{}; pa.na = 3;
-        pa.in[0] = S->tz; pa.out[0] = S->tz2; pa.in[1] = S->tx; pa.out[1] = S->tx2; pa.in[2] = S->f[TR_TMP]; pa.out[2] = S->f2[TR_TMP];
-        hipLaunchKernelGGL(k_place_permute, grid1d(n), dim3(256), 0, ctx->stream, n, S->cell, S->cell_start, S->cell_count, S->dest, pa,
-                           S->epoch_on ? (const int*)S->slot : (const int*)nullptr, S->slot2);
-        std::swap(S->tz, S->tz2); std::swap(S->tx, S->tx2);
-        std::swap(S->vtz, S->tmp[0]); std::swap(S->vtx, S->tmp[1]);         // (lazy: the old values stay in tmp[0..1] / f2[RHO], f2[ETA])
-        std::swap(S->slot, S->slot2);
-        for (int k : {(int)TR_TMP, (int)TR_RHO, (int)TR_ETA}) std::swap(S->f[k], S->f2[k]);
-    } else if (n > 0) {
-        hipLaunchKernelGGL(k_cell_place, grid1d(n), dim3(256), 0, ctx->stream, n, S->cell, S->cell_start, S->cell_count, S->dest);
-        // classic: positions, the 13 fields and the velocities of the last advection travel together
-        const double* src[17]; double* dst[17];
-        src[0] = S->tz; dst[0] = S->tz2; src[1] = S->tx; dst[1] = S->tx2;
-        for (int k = 0; k < NFTRAC; k++) { src[2 + k] = S->f[k]; dst[2 + k] = S->f2[k]; }
-        src[15] = S->vtz; dst[15] = S->tmp[0]; src[16] = S->vtx; dst[16] = S->tmp[1];
-        for (int k0 = 0; k0 < 17; k0 += 5) {
-            PermArgs pa{}; pa.na = std::min(5, 17 - k0);
-            for (int k = 0; k < pa.na; k++) { pa.in[k] = src[k0 + k]; pa.out[k] = dst[k0 + k]; }
-            hipLaunchKernelGGL(k_permute, grid1d(n), dim3(256), 0, ctx->stream, n, S->dest, pa);
-        }
-        hipLaunchKernelGGL(k_permute_int, grid1d(n), dim3(256), 0, ctx->stream, n, S->dest, S->orig, S->orig2);
-        std::swap(S->tz, S->tz2); std::swap(S->tx, S->tx2); std::swap(S->orig, S->orig2);
-        std::swap(S->vtz, S->tmp[0]); std::swap(S->vtx, S->tmp[1]);
-        for (int k = 0; k < NFTRAC; k++) std::swap(S->f[k], S->f2[k]);
-    }
+    // ---- permute
+    if (n > 0 && epoch_ok) permute_epoch(ctx, S, n);
+    else if (n > 0) permute_classic(ctx, S, n);
     if (epoch_ok) {
         if (!S->epoch_on) S->epoch_len = n;                 // the sort has just opened the epoch: slot = the index before it
         S->epoch_age = S->epoch_on ? S->epoch_age + 1 : 1; S->epoch_on = true;
-        S->lazy_pending = true; S->lazy_n = n; S->lazy_inject = ninj > 0;
+        S->lazy_pending = true; S->lazy_n = n; S->lazy_inject = cs.ninj > 0;
     }
-    if (ninj > 0) {
-        InjectSorted a{};
-        a.nc = nc; a.ncx = ncx; a.crow0 = S->crow0; a.ccol0 = S->ccol0; a.start = S->cell_start; a.count = S->cell_res;
-        a.need = S->need; a.off = S->need_off; a.rank = strict ? S->need_rank : nullptr;
-        a.tz = S->tz; a.tx = S->tx; for (int k = 0; k < NFTRAC; k++) a.f[k] = S->f[k];
-        a.vtz = S->vtz; a.vtx = S->vtx; a.orig = S->orig;
-        a.slot = epoch_ok ? S->slot : nullptr; a.lazy = epoch_ok ? 1 : 0;
-        a.z0 = z0; a.hz = hz; a.x0 = x0; a.hx = hx; a.seed = o.inject->inject_seed; a.step = (unsigned)o.it; a.id0 = id0;
-        a.n_old = (int)(epoch_ok ? S->epoch_len : n);        // epoch layout: the constants of new tracers go behind everything the epoch holds
-        if (epoch_ok) S->epoch_len += ninj;
-        a.zc = coords_z(ctx, S, 0); a.xc = coords_x(ctx, S, 0);
-        hipLaunchKernelGGL(k_inject_sorted, dim3((nc + 63) / 64), dim3(64), 0, ctx->stream, a);
-        S->n = n + ninj;
-    }
-    if (o.ninjected) *o.ninjected = ninj;
+    // ---- inject
+    if (cs.ninj > 0) launch_inject(ctx, S, q, o, cs, nc, n, epoch_ok);
+    if (o.ninjected) *o.ninjected = cs.ninj;
     PL_HIP(ctx, hipGetLastError());
+    // ---- trash / deletion
     if (o.removed) *o.removed = 0;
     if (o.drop_trash) {                                   // (several ranks: the tracers that have left for a neighbour block)
         int keep = 0;
@@ -1008,34 +1048,36 @@ static int sort_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, doubl
         PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         S->n = keep;
     }
-    if (o.del_outside && n > 0) {
-        int h[2] = {0, 0};
-        PL_HIP(ctx, hipMemcpyAsync(h, S->cell_start + nc + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const int alive_n = h[0], all_n = h[1];
-        if (alive_n < all_n) {
-            // the survivors are the first alive_n entries; renumber `orig` so that downloads keep the caller's
-            // relative order (np.delete keeps it, pylamp2.py:578-580).  cell / dest are free after the sort.
-            PL_HIP(ctx, hipMemsetAsync(S->cell, 0, (size_t)all_n * sizeof(int), ctx->stream));
-            if (alive_n > 0) hipLaunchKernelGGL(k_mark_alive, grid1d(alive_n), dim3(256), 0, ctx->stream, (long long)alive_n, S->orig, S->cell);
-            const int nbb = (all_n + 1023) / 1024;
-            int* bs = nullptr;
-            PL_HIP(ctx, hipMalloc((void**)&bs, (size_t)(nbb + 1) * sizeof(int)));
-            hipLaunchKernelGGL(k_scan_block, dim3(nbb), dim3(256), 0, ctx->stream, all_n, S->cell, S->dest, bs);
-            hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, nbb, bs);
-            hipLaunchKernelGGL(k_scan_add, dim3((all_n + 255) / 256), dim3(256), 0, ctx->stream, all_n, S->dest, bs, 0);
-            if (alive_n > 0) hipLaunchKernelGGL(k_remap_orig, grid1d(alive_n), dim3(256), 0, ctx->stream, (long long)alive_n, S->orig, S->dest);
-            PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(bs);
-            if (o.removed) *o.removed = all_n - alive_n;
-            S->n = alive_n;
-            S->max_id_valid = false;
-        }
-    }
+    if (o.del_outside && n > 0) PL_TRY(compact_deleted(ctx, S, nc, o.removed));
     if (o.del_outside && ctx->nranks > 1) {        // collective: a deletion anywhere invalidates the cached maximum ID everywhere
         double v[1] = {S->max_id_valid ? 0.0 : 1.0};
         PL_TRY(pl_allreduce_host(ctx, v, 1, 2));
         if (v[0] > 0.0) S->max_id_valid = false;
+    }
+    return 0;
+}
+// Several ranks: who sends how many tracers to whom.  Per direction k (N S W E NW NE SW SE as in pl_comm.hip): the neighbour
+// block (-1: a domain wall), the tracers leaving towards it and arriving from it, and their offsets in a send / receive buffer.
+struct Route { int peer[8]; long long nsend[8], nrecv[8], soff[8], roff[8], outgoing, incoming; };
+// counts_src: this rank's 8 leaver counts on the device (diff = 1: 9 bucket offsets), summed over the ranks on the device as slot
+// [r*8 + k] of a table; bucket_off: the same offsets on the host where the caller has them (NULL: read from the table); who: the caller
+static int migration_route(pl_ctx* ctx, PlStepState* S, const int* counts_src, int diff, const int* bucket_off, const char* who, Route& r) {
+    static const int DZ[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, DX[8] = {0, 0, -1, 1, -1, 1, -1, 1}, OPP[8] = {1, 0, 3, 2, 7, 6, 5, 4};
+    const int R = ctx->nranks;
+    std::vector<double> cnt((size_t)8 * R, 0.0);
+    PL_TRY(step_counts(ctx, S, 8 * R));
+    hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 8, counts_src, diff, S->counts_dev, 8 * ctx->rank);
+    PL_TRY(pl_comm_allreduce_dev(ctx, S->counts_dev, 8 * R, 0));
+    PL_HIP(ctx, hipMemcpyAsync(cnt.data(), S->counts_dev, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    r.outgoing = 0; r.incoming = 0;
+    for (int k = 0; k < 8; k++) {
+        const int qz = ctx->pz + DZ[k], qx = ctx->px + DX[k];
+        r.peer[k] = (qz < 0 || qz >= ctx->Pz || qx < 0 || qx >= ctx->Px) ? -1 : qz * ctx->Px + qx;
+        r.nsend[k] = bucket_off ? bucket_off[k + 1] - bucket_off[k] : (long long)cnt[(size_t)8 * ctx->rank + k];
+        r.nrecv[k] = r.peer[k] < 0 ? 0 : (long long)cnt[(size_t)8 * r.peer[k] + OPP[k]];
+        if (r.peer[k] < 0 && r.nsend[k] > 0) return pl_fail(ctx, std::string(who) + ": a tracer left through a domain wall (internal error)");
+        r.soff[k] = r.outgoing; r.outgoing += r.nsend[k]; r.roff[k] = r.incoming; r.incoming += r.nrecv[k];
     }
     return 0;
 }
@@ -1044,49 +1086,30 @@ static int sort_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, doubl
 // again.  (Tracers move less than a cell per step, so a neighbour block is always the destination; one that jumps
 // further is simply forwarded again at the next step.)  The arrays grow when the arrivals do not fit.
 // The census + refill of o.inject happens in the final sort, when every tracer is on its owner.
-static int migrate_tracers(pl_ctx* ctx, PlStepState* S, double z0, double hz, double x0, double hx, const SortOpts& o) {
+static int migrate_tracers(pl_ctx* ctx, PlStepState* S, const StepGrid& q, const SortOpts& o) {
     if (ctx->nranks <= 1) return 0;
-    static const int DZ[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, DX[8] = {0, 0, -1, 1, -1, 1, -1, 1}, OPP[8] = {1, 0, 3, 2, 7, 6, 5, 4};
-    const int nc = S->sort_cells, R = ctx->nranks;
+    const int nc = S->sort_cells;
     int h[10];
     PL_HIP(ctx, hipMemcpyAsync(h, S->cell_start + nc, 10 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const long long stay = h[0];
-    // who sends how many to whom: slot [r*8 + k] = tracers rank r sends towards direction k
-    std::vector<double> cnt((size_t)8 * R, 0.0);
-    PL_TRY(step_counts(ctx, S, 8 * R));
-    hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 8, (const int*)(S->cell_start + nc), 1, S->counts_dev, 8 * ctx->rank);
-    PL_TRY(pl_comm_allreduce_dev(ctx, S->counts_dev, 8 * R, 0));
-    PL_HIP(ctx, hipMemcpyAsync(cnt.data(), S->counts_dev, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int peer[8]; long long nsend[8], nrecv[8], roff[8]; long long incoming = 0;
-    for (int k = 0; k < 8; k++) {
-        const int qz = ctx->pz + DZ[k], qx = ctx->px + DX[k];
-        peer[k] = (qz < 0 || qz >= ctx->Pz || qx < 0 || qx >= ctx->Px) ? -1 : qz * ctx->Px + qx;
-        nsend[k] = h[k + 1] - h[k];
-        nrecv[k] = peer[k] < 0 ? 0 : (long long)cnt[(size_t)8 * peer[k] + OPP[k]];
-        if (peer[k] < 0 && nsend[k] > 0) return pl_fail(ctx, "migrate_tracers: a tracer left through a domain wall (internal error)");
-        roff[k] = incoming; incoming += nrecv[k];
-    }
+    Route r;
+    PL_TRY(migration_route(ctx, S, S->cell_start + nc, 1, h, "migrate_tracers", r));
     const long long n_all = S->n;
-    PL_TRY(grow_tracers(ctx, S, std::max(stay + incoming, n_all), n_all));    // collective decision: every rank knows its own need
-    const int NC = 17;
-    double* cols[NC]; double* spare[NC];
-    cols[0] = S->tz; cols[1] = S->tx; spare[0] = S->tz2; spare[1] = S->tx2;
-    for (int k = 0; k < NFTRAC; k++) { cols[2 + k] = S->f[k]; spare[2 + k] = S->f2[k]; }
-    cols[15] = S->vtz; spare[15] = S->tmp[0]; cols[16] = S->vtx; spare[16] = S->tmp[1];
+    PL_TRY(grow_tracers(ctx, S, std::max(stay + r.incoming, n_all), n_all));    // collective decision: every rank knows its own need
+    const TracerCols tc = tracer_cols(S);
     std::vector<PlMsg> msgs;
     for (int k = 0; k < 8; k++) {
-        if (peer[k] < 0 || (nsend[k] == 0 && nrecv[k] == 0)) continue;
-        for (int c = 0; c < NC; c++) msgs.push_back(PlMsg{peer[k], cols[c] + h[k], nsend[k], spare[c] + roff[k], nrecv[k]});
+        if (r.peer[k] < 0 || (r.nsend[k] == 0 && r.nrecv[k] == 0)) continue;
+        for (int c = 0; c < NTCOLS; c++) msgs.push_back(PlMsg{r.peer[k], tc.col[c] + h[k], r.nsend[k], tc.spare[c] + r.roff[k], r.nrecv[k]});
     }
     PL_TRY(pl_comm_sendrecv(ctx, msgs.data(), (int)msgs.size()));
-    if (incoming > 0)
-        for (int c = 0; c < NC; c++)
-            PL_HIP(ctx, hipMemcpyAsync(cols[c] + stay, spare[c], (size_t)incoming * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    S->n = stay + incoming;
+    if (r.incoming > 0)
+        for (int c = 0; c < NTCOLS; c++)
+            PL_HIP(ctx, hipMemcpyAsync(tc.col[c] + stay, tc.spare[c], (size_t)r.incoming * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    S->n = stay + r.incoming;
     hipLaunchKernelGGL(k_iota, grid1d(S->n), dim3(256), 0, ctx->stream, S->n, S->orig, 0);
-    return sort_tracers(ctx, S, z0, hz, x0, hx, o);
+    return sort_tracers(ctx, S, q, o);
 }
 
 // ---- several ranks, regular grid: migration BEFORE the sort ---------------------------------------------------------------------------
@@ -1140,61 +1163,46 @@ __global__ __launch_bounds__(256) void k_unpack_arrivals(ArrivalArgs a, long lon
     if (a.slot) a.slot[t] = (int)e;
     a.orig[a.slot ? e : t] = (int)(a.slot ? e : t);
 }
-static int migrate_presort(pl_ctx* ctx, PlStepState* S, double z0, double hz, double x0, double hx) {
-    static const int DZ[8] = {-1, 1, 0, 0, -1, -1, 1, 1}, DX[8] = {0, 0, -1, 1, -1, 1, -1, 1}, OPP[8] = {1, 0, 3, 2, 7, 6, 5, 4};
+static int migrate_presort(pl_ctx* ctx, PlStepState* S, const StepGrid& q) {
     const PlGeom& g = ctx->geom.d;
-    const int nc = S->sort_cells, R = ctx->nranks;
+    const int nc = S->sort_cells;
     const long long n_all = S->n;
-    // who sends how many to whom (slot [r*8 + k] = tracers rank r sends towards direction k): summed over the ranks on the device
-    std::vector<double> cnt((size_t)8 * R, 0.0);
-    PL_TRY(step_counts(ctx, S, 8 * R));
-    hipLaunchKernelGGL(k_counts_from_ints, dim3(1), dim3(64), 0, ctx->stream, 8, (const int*)(S->cell_count + nc), 0, S->counts_dev, 8 * ctx->rank);
-    PL_TRY(pl_comm_allreduce_dev(ctx, S->counts_dev, 8 * R, 0));
-    PL_HIP(ctx, hipMemcpyAsync(cnt.data(), S->counts_dev, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int peer[8]; long long nsend[8], nrecv[8], soff[8], roff[8], outgoing = 0, incoming = 0;
-    for (int k = 0; k < 8; k++) {
-        const int qz = ctx->pz + DZ[k], qx = ctx->px + DX[k];
-        peer[k] = (qz < 0 || qz >= ctx->Pz || qx < 0 || qx >= ctx->Px) ? -1 : qz * ctx->Px + qx;
-        nsend[k] = (long long)cnt[(size_t)8 * ctx->rank + k];
-        nrecv[k] = peer[k] < 0 ? 0 : (long long)cnt[(size_t)8 * peer[k] + OPP[k]];
-        if (peer[k] < 0 && nsend[k] > 0) return pl_fail(ctx, "migrate_presort: a tracer left through a domain wall (internal error)");
-        soff[k] = outgoing; outgoing += nsend[k]; roff[k] = incoming; incoming += nrecv[k];
-    }
+    Route r;
+    PL_TRY(migration_route(ctx, S, S->cell_count + nc, 0, nullptr, "migrate_presort", r));
+    const long long outgoing = r.outgoing, incoming = r.incoming;
     double *sb = nullptr, *rb = nullptr;
-    PL_TRY(pl_buf(ctx, "mig_send", (size_t)std::max<long long>(17 * outgoing, 1) * sizeof(double), &sb, false));
-    PL_TRY(pl_buf(ctx, "mig_recv", (size_t)std::max<long long>(17 * incoming, 1) * sizeof(double), &rb, false));
+    PL_TRY(pl_buf(ctx, "mig_send", (size_t)std::max<long long>(NTCOLS * outgoing, 1) * sizeof(double), &sb, false));
+    PL_TRY(pl_buf(ctx, "mig_recv", (size_t)std::max<long long>(NTCOLS * incoming, 1) * sizeof(double), &rb, false));
     const long long used = std::max(n_all, S->epoch_on ? S->epoch_len : n_all);
     PL_TRY(grow_tracers(ctx, S, used + incoming, used));         // (collective in effect: every rank knows its own need)
-    double* cols[17];
-    cols[0] = S->tz; cols[1] = S->tx; for (int k = 0; k < NFTRAC; k++) cols[2 + k] = S->f[k]; cols[15] = S->vtz; cols[16] = S->vtx;
+    const TracerCols tc = tracer_cols(S);
     if (outgoing > 0) {
         double* fc;
         PL_TRY(pl_buf(ctx, "mig_fill", 64, &fc, false));
         PL_HIP(ctx, hipMemsetAsync(fc, 0, 64, ctx->stream));
         LeaverArgs a{};
         a.n = n_all; a.nc = nc; a.cell = S->cell; a.count = S->cell_count; a.slot = S->epoch_on ? S->slot : nullptr;
-        for (int m = 0; m < 17; m++) a.col[m] = cols[m];
+        for (int m = 0; m < NTCOLS; m++) a.col[m] = tc.col[m];
         a.fill = (int*)fc; a.buf = sb;
-        for (int k = 0; k < 8; k++) { a.off[k] = soff[k]; a.cnt[k] = nsend[k]; }
+        for (int k = 0; k < 8; k++) { a.off[k] = r.soff[k]; a.cnt[k] = r.nsend[k]; }
         hipLaunchKernelGGL(k_pack_leavers, grid1d(n_all), dim3(256), 0, ctx->stream, a);
     }
     std::vector<PlMsg> msgs;
     for (int k = 0; k < 8; k++) {
-        if (peer[k] < 0 || (nsend[k] == 0 && nrecv[k] == 0)) continue;
-        msgs.push_back(PlMsg{peer[k], sb + 17 * soff[k], 17 * nsend[k], rb + 17 * roff[k], 17 * nrecv[k]});
+        if (r.peer[k] < 0 || (r.nsend[k] == 0 && r.nrecv[k] == 0)) continue;
+        msgs.push_back(PlMsg{r.peer[k], sb + NTCOLS * r.soff[k], NTCOLS * r.nsend[k], rb + NTCOLS * r.roff[k], NTCOLS * r.nrecv[k]});
     }
     PL_TRY(pl_comm_sendrecv(ctx, msgs.data(), (int)msgs.size()));
     if (incoming > 0) {
         ArrivalArgs a{};
         a.first = n_all; a.e0 = S->epoch_on ? S->epoch_len : n_all;
-        for (int m = 0; m < 17; m++) a.col[m] = cols[m];
+        for (int m = 0; m < NTCOLS; m++) a.col[m] = tc.col[m];
         a.slot = S->epoch_on ? S->slot : nullptr; a.orig = S->orig; a.buf = rb;
-        for (int k = 0; k < 8; k++) { a.off[k] = roff[k]; a.cnt[k] = nrecv[k]; }
+        for (int k = 0; k < 8; k++) { a.off[k] = r.roff[k]; a.cnt[k] = r.nrecv[k]; }
         hipLaunchKernelGGL(k_unpack_arrivals, grid1d(incoming), dim3(256), 0, ctx->stream, a, incoming);
         // their sort keys, counted into the same table (the arrivals may lie one block further already: forwarded at the next step)
         hipLaunchKernelGGL(k_cell_count, grid1d(incoming), dim3(256), 0, ctx->stream, incoming, (const double*)(S->tz + n_all), (const double*)(S->tx + n_all),
-                           z0, hz, x0, hx, (const double*)nullptr, (const double*)nullptr, S->ncz, S->ncx, S->crow0, S->ccol0, g.nz - 1, g.nx - 1,
+                           q.z0, q.hz, q.x0, q.hx, (const double*)nullptr, (const double*)nullptr, S->ncz, S->ncx, S->crow0, S->ccol0, g.nz - 1, g.nx - 1,
                            S->cell + n_all, S->cell_count, 0, 0.0, 0.0);
         if (S->epoch_on) S->epoch_len += incoming;
     }
@@ -1203,27 +1211,16 @@ static int migrate_presort(pl_ctx* ctx, PlStepState* S, double z0, double hz, do
     return 0;
 }
 
-// un-permute resident arrays into the spare buffers so that downloads come out in the caller's order
-static void unpermute(pl_ctx* ctx, PlStepState* S, int na, const double* const* in, double* const* out) {
-    for (int k0 = 0; k0 < na; k0 += 5) {
-        PermArgs pa{}; pa.na = std::min(5, na - k0);
-        for (int k = 0; k < pa.na; k++) { pa.in[k] = in[k0 + k]; pa.out[k] = out[k0 + k]; }
-        hipLaunchKernelGGL(k_permute, grid1d(S->n), dim3(256), 0, ctx->stream, S->n, S->orig, pa);
-    }
-}
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-static double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// scatter a set of tracer fields onto a staggered node set, writing ring planes
-static int scatter_to_planes(pl_ctx* ctx, PlStepState* S, int nf, const int* fidx, const int* schemes, double z0, double hz,
-                             double x0, double hx, double* const* planes, int stag_z = 0, int stag_x = 0) {
+// scatter a set of tracer fields onto a node set (stag_*: the one half a spacing further along that axis), writing ring planes
+static int scatter_to_planes(pl_ctx* ctx, PlStepState* S, int nf, const int* fidx, const int* schemes, const StepGrid& q,
+                             double* const* planes, int stag_z = 0, int stag_x = 0) {
     const PlGeom& g = ctx->geom.d;
     PlScatterArgs a{};
     a.n = S->n; a.tz = S->tz; a.tx = S->tx; a.nf = nf;
     for (int k = 0; k < nf; k++) { a.f[k] = fidx[k] >= 0 ? S->f[fidx[k]] : S->tmp[-fidx[k] - 1]; a.scheme[k] = schemes[k]; }
-    a.z0 = z0; a.hz = hz; a.x0 = x0; a.hx = hx; a.nz = g.nz; a.nx = g.nx;
+    a.z0 = stag_z ? q.z0 + 0.5 * q.hz : q.z0; a.hz = q.hz; a.x0 = stag_x ? q.x0 + 0.5 * q.hx : q.x0; a.hx = q.hx; a.nz = g.nz; a.nx = g.nx;
     a.zc = coords_z(ctx, S, stag_z); a.xc = coords_x(ctx, S, stag_x);
     a.cell_start = S->cell_start; a.ncz = S->ncz; a.ncx = S->ncx; a.crow0 = S->crow0; a.ccol0 = S->ccol0;     // cell-sorted (sort_tracers)
     a.stag_z = stag_z; a.stag_x = stag_x;
@@ -1236,8 +1233,8 @@ static int scatter_to_planes(pl_ctx* ctx, PlStepState* S, int nf, const int* fid
 //   variant 1 (heat off): nodes {rho AW, log eta GW} -> out[0..1], centres {log eta, UNWEIGHTED} -> out[2]   (pylamp2.py:316-319)
 //   variant 2:            nodes {fn[0] AW} -> out[0]                                          (subgrid diffusion, pylamp2.py:477)
 // PYLAMP_SCATTER=0 keeps the one-set-per-pass kernels (k_scatter_binned) -- the cross-check of the tests.
-static int scatter_cells(pl_ctx* ctx, PlStepState* S, int variant, const double* const* fn, const double* fm, double z0, double hz,
-                         double x0, double hx, double* const* out, const int* ix = nullptr, unsigned ind = 0u) {
+static int scatter_cells(pl_ctx* ctx, PlStepState* S, int variant, const double* const* fn, const double* fm, const StepGrid& q,
+                         double* const* out, const int* ix = nullptr, unsigned ind = 0u) {
     const PlGeom& g = ctx->geom.d;
     const int AW = PL_AVG_ARITHMETIC | PL_AVG_WEIGHTED, GW = PL_AVG_GEOMETRIC | PL_AVG_WEIGHTED, G0 = PL_AVG_GEOMETRIC;
     const int nfn = variant == 0 ? 6 : (variant == 1 ? 2 : 1);
@@ -1247,7 +1244,7 @@ static int scatter_cells(pl_ctx* ctx, PlStepState* S, int variant, const double*
     a.tz = S->tz; a.tx = S->tx;
     for (int k = 0; k < nfn; k++) a.fn[k] = fn[k];
     a.fm = fm; a.ix = ind ? ix : nullptr; a.ind = ix ? ind : 0u;
-    a.z0 = z0; a.hz = hz; a.x0 = x0; a.hx = hx; a.nz = g.nz; a.nx = g.nx;
+    a.z0 = q.z0; a.hz = q.hz; a.x0 = q.x0; a.hx = q.hx; a.nz = g.nz; a.nx = g.nx;
     a.row0 = g.gi0 - 1; a.nrows = g.lnz + 2; a.col0 = g.gj0 - 1; a.ncols = g.lnx + 2;
     a.cell_start = S->cell_start; a.ncz = S->ncz; a.ncx = S->ncx; a.crow0 = S->crow0; a.ccol0 = S->ccol0;
     const size_t N = (size_t)a.nrows * a.ncols;
@@ -1301,13 +1298,6 @@ static int step_planes(pl_ctx* ctx, StepPlanes& P) {
     PL_TRY(pl_buf(ctx, "dT", pb, &P.dT));
     return 0;
 }
-struct StepGrid { double z0, hz, x0, hx; };
-static StepGrid step_grid(pl_ctx* ctx) {
-    const int nz = ctx->nz, nx = ctx->nx;
-    StepGrid q; q.z0 = ctx->geom.zc[0]; q.x0 = ctx->geom.xc[0];
-    q.hz = (ctx->geom.zc[nz - 1] - q.z0) / (nz - 1); q.hx = (ctx->geom.xc[nx - 1] - q.x0) / (nx - 1);
-    return q;
-}
 
 // stage 1: tracer properties (pylamp2.py:291-303)
 static int stage_props(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg) {
@@ -1323,7 +1313,6 @@ static int stage_props(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg) {
 static int stage_scatter(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, int it, const StepPlanes& P) {
     const PlGeom& g = ctx->geom.d;
     const StepGrid q = step_grid(ctx);
-    const double z0 = q.z0, hz = q.hz, x0 = q.x0, hx = q.hx;
     const int AW = PL_AVG_ARITHMETIC | PL_AVG_WEIGHTED, GW = PL_AVG_GEOMETRIC | PL_AVG_WEIGHTED | PL_AVG_PRELOG;
     const int ETA_LOG = -3;                     // S->tmp[2]: log(eta) written by k_property_update
     const bool cells = scatter_cells_on() && ctx->geom.uniform;
@@ -1333,33 +1322,33 @@ static int stage_scatter(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg,
             const double* fn[6] = {S->f[TR_RHO], S->tmp[2], S->f[TR_HCP], S->f[TR_TMP], S->f[TR_IHT], S->f[TR_MAT]};
             double* out[9] = {P.rho, P.etas, P.cp, P.T, P.H, P.mat, P.etan, P.kz, P.kx};
             // epoch layout: cp, H, mat (fields 2, 4, 5) and the conductivity of the mid-face sets are constant columns
-            PL_TRY(scatter_cells(ctx, S, 0, fn, S->f[TR_HCD], z0, hz, x0, hx, out, S->epoch_on ? (const int*)S->slot : (const int*)nullptr,
+            PL_TRY(scatter_cells(ctx, S, 0, fn, S->f[TR_HCD], q, out, S->epoch_on ? (const int*)S->slot : (const int*)nullptr,
                                  (1u << 2) | (1u << 4) | (1u << 5) | (1u << 31)));
         } else {
             const int fi[6] = {TR_RHO, ETA_LOG, TR_HCP, TR_TMP, TR_IHT, TR_MAT};
             const int sc[6] = {AW, GW, AW, AW, AW, AW};
             double* pl6[6] = {P.rho, P.etas, P.cp, P.T, P.H, P.mat};
-            PL_TRY(scatter_to_planes(ctx, S, 6, fi, sc, z0, hz, x0, hx, pl6));
+            PL_TRY(scatter_to_planes(ctx, S, 6, fi, sc, q, pl6));
             const int f1[1] = {ETA_LOG}; const int s1[1] = {GW}; double* pn[1] = {P.etan};
-            PL_TRY(scatter_to_planes(ctx, S, 1, f1, s1, z0 + 0.5 * hz, hz, x0 + 0.5 * hx, hx, pn, 1, 1));
+            PL_TRY(scatter_to_planes(ctx, S, 1, f1, s1, q, pn, 1, 1));
             const int f2[1] = {TR_HCD}; const int s2[1] = {AW};
             double* pk[1] = {P.kz};
-            PL_TRY(scatter_to_planes(ctx, S, 1, f2, s2, z0 + 0.5 * hz, hz, x0, hx, pk, 1, 0));
+            PL_TRY(scatter_to_planes(ctx, S, 1, f2, s2, q, pk, 1, 0));
             pk[0] = P.kx;
-            PL_TRY(scatter_to_planes(ctx, S, 1, f2, s2, z0, hz, x0 + 0.5 * hx, hx, pk, 0, 1));
+            PL_TRY(scatter_to_planes(ctx, S, 1, f2, s2, q, pk, 0, 1));
         }
         if (it > 1 && S->have_newtemp)
             hipLaunchKernelGGL(k_copy_boundary, grid2d(g), dim3(64, 4), 0, ctx->stream, g, P.newT, P.T);
     } else if (cells) {
         const double* fn[2] = {S->f[TR_RHO], S->tmp[2]};
         double* out[3] = {P.rho, P.etas, P.etan};
-        PL_TRY(scatter_cells(ctx, S, 1, fn, nullptr, z0, hz, x0, hx, out));
+        PL_TRY(scatter_cells(ctx, S, 1, fn, nullptr, q, out));
     } else {
         const int fi[2] = {TR_RHO, ETA_LOG}; const int sc[2] = {AW, GW};
         double* pl2[2] = {P.rho, P.etas};
-        PL_TRY(scatter_to_planes(ctx, S, 2, fi, sc, z0, hz, x0, hx, pl2));
+        PL_TRY(scatter_to_planes(ctx, S, 2, fi, sc, q, pl2));
         const int f1[1] = {ETA_LOG}; const int s1[1] = {PL_AVG_GEOMETRIC | PL_AVG_PRELOG}; double* pn[1] = {P.etan};   // pylamp2.py:319 (unweighted)
-        PL_TRY(scatter_to_planes(ctx, S, 1, f1, s1, z0 + 0.5 * hz, hz, x0 + 0.5 * hx, hx, pn, 1, 1));
+        PL_TRY(scatter_to_planes(ctx, S, 1, f1, s1, q, pn, 1, 1));
     }
     PL_HIP(ctx, hipGetLastError());
     return 0;
@@ -1412,10 +1401,10 @@ static int stage_temp_to_tracers(pl_ctx* ctx, PlStepState* S, const pl_step_conf
             // T currently holds Told for the subgrid branch; dTs = tmp[2] -> nodes -> back to tracers
             if (scatter_cells_on() && ctx->geom.uniform) {
                 const double* fn[1] = {S->tmp[2]}; double* out[1] = {P.sgc};
-                PL_TRY(scatter_cells(ctx, S, 2, fn, nullptr, q.z0, q.hz, q.x0, q.hx, out));
+                PL_TRY(scatter_cells(ctx, S, 2, fn, nullptr, q, out));
             } else {
                 const int fs[1] = {-3}; const int ss[1] = {AW}; double* ps[1] = {P.sgc};
-                PL_TRY(scatter_to_planes(ctx, S, 1, fs, ss, q.z0, q.hz, q.x0, q.hx, ps));
+                PL_TRY(scatter_to_planes(ctx, S, 1, fs, ss, q, ps));
             }
             ga.fields[0] = P.sgc; ga.out[0] = S->tmp[0];
             if (fuse) ga.epi = 2;
@@ -1463,9 +1452,9 @@ static int stage_rk4(pl_ctx* ctx, PlStepState* S, const double* V, int I0, int I
         // since the last sort): no separate pass over the new positions
         *keys_ready = false;
         const PlGeom& g = ctx->geom.d;
-        const int ncz = (g.gi0 + g.lnz >= g.nz) ? g.lnz - 1 : g.lnz, ncx = (g.gj0 + g.lnx >= g.nx) ? g.lnx - 1 : g.lnx;
-        const bool fuse_keys = true;           // (the sort keys as a pass of their own cost 0.35 ms at 2049^2 / 68 M tracers)
-        if (fuse_keys && ctx->geom.uniform && S->cell_count && S->ncz == ncz && S->ncx == ncx && S->cell && S->n < (1LL << 31)) {
+        int ncz, ncx; block_cells(g, ncz, ncx);
+        // (the sort keys as a pass of their own cost 0.35 ms at 2049^2 / 68 M tracers)
+        if (ctx->geom.uniform && S->cell_count && S->ncz == ncz && S->ncx == ncx && S->cell && S->n < (1LL << 31)) {
             PlSortKey& k = ra.key;
             k.on = 1; k.z0 = q.z0; k.rhz = 1.0 / q.hz; k.x0 = q.x0; k.rhx = 1.0 / q.hx;
             k.ncz = ncz; k.ncx = ncx; k.crow0 = g.gi0; k.ccol0 = g.gj0; k.gcz = g.nz - 1; k.gcx = g.nx - 1;
@@ -1499,6 +1488,187 @@ static int stage_rk4(pl_ctx* ctx, PlStepState* S, const double* V, int I0, int I
     return 0;
 }
 
+// ---- the grid stages of a time step, and its end ------------------------------------------------------------------------------------
+// min(hi, v) then max(lo, v) in the reference's order of comparisons (a NaN stays a NaN)
+static double clamp_tstep(double v, double lo, double hi) { v = (hi < v) ? hi : v; return (lo > v) ? lo : v; }
+static double min_spacing(pl_ctx* ctx, const pl_step_config* cfg) { return std::fmin(cfg->length[0] / (ctx->geom.d.nz - 1), cfg->length[1] / (ctx->geom.d.nx - 1)); }    // pylamp2.py:87
+// stage 3: heat time step (pylamp2.py:339-343), the viscosity minima of the Stokes scaling (pylamp_stokes.py:116-118) and the
+// viscosity contrast the solver chooses its method by: ONE reduction
+struct StepLimits { double mes, men, tstep_temp; };
+static int stage_limits(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, const StepPlanes& P, StepLimits& L) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    MinMaxSpec sp[3] = {{P.etas, nullptr, nullptr, 0}, {P.etan, nullptr, nullptr, 0}, {P.kz, P.rho, P.cp, 1}};
+    MinMaxOut mm[3];
+    PL_TRY(reduce_minmax_multi(ctx, S, ctx->geom.d, cfg->do_heatdiff ? 3 : 2, sp, mm));
+    L.mes = mm[0].has_nan ? nan : mm[0].mn; L.men = mm[1].has_nan ? nan : mm[1].mn;
+    const double lo = std::fmin(mm[0].mn, mm[1].mn), hi = std::fmax(mm[0].mx, mm[1].mx);
+    ctx->visc_contrast = (lo > 0.0 && hi > 0.0 && std::isfinite(hi / lo)) ? hi / lo : 1.0;
+    L.tstep_temp = 0.0;
+    if (cfg->do_heatdiff) {
+        const double mx = mm[2].has_nan ? nan : mm[2].mx, mindx = min_spacing(ctx, cfg);
+        L.tstep_temp = clamp_tstep(cfg->tstep_modifier * mindx * mindx / mx, cfg->tstep_dif_min, cfg->tstep_dif_max);
+    }
+    return 0;
+}
+// Initial guess of the Stokes solve, extrapolated in model time from the last solutions (polynomial through up to PYLAMP_X0_ORDER
+// + 1 of them, default 2 = quadratic; PYLAMP_X0_EXTRAP scales the target time, 0 switches the extrapolation off; the weights:
+// pl_x0.h).  Every factor 3 in the initial residual is an iteration; at 2049^2: none 15.3 iterations / 38.6 ms per solve, linear
+// 13.3 / 33.5 ms, quadratic 11.5 / 29.9 ms.  Only the iteration count depends on it: the stopping rule is the same whatever the start.
+static int stokes_start(pl_ctx* ctx, PlStepState* S) {
+    static const double wx = getenv("PYLAMP_X0_EXTRAP") ? atof(getenv("PYLAMP_X0_EXTRAP")) : 1.0;
+    if (wx == 0.0 || !S->have_solution) return 0;
+    double* xs = pl_stokes_solution_device(ctx);
+    const long long n3 = 3 * ctx->geom.d.plane;
+    static const int order = std::max(1, std::min(3, getenv("PYLAMP_X0_ORDER") ? atoi(getenv("PYLAMP_X0_ORDER")) : 2));
+    static const int keep = std::max(order, std::min((int)X0_HIST, getenv("PYLAMP_X0_POINTS") ? atoi(getenv("PYLAMP_X0_POINTS")) : order));
+    if (!S->x_hist[0]) {
+        const char* nm[X0_HIST] = {"x_prev", "x_prev2", "x_prev3", "x_prev4", "x_prev5"};
+        for (int k = 0; k < keep; k++) PL_TRY(pl_buf(ctx, nm[k], (size_t)n3 * sizeof(double), &S->x_hist[k]));
+    }
+    const X0Weights w = pl_x0_weights(S->dt_hist, S->n_prev, keep, order, wx);
+    ExtrapArgs ea{};
+    ea.nk = keep; ea.nh = w.nh; ea.l0 = w.l0;
+    for (int k = 0; k < keep; k++) ea.h[k] = S->x_hist[k];
+    for (int k = 0; k < X0_HIST; k++) ea.l[k] = w.l[k];
+    hipLaunchKernelGGL(k_extrap_x0, grid1d(n3), dim3(256), 0, ctx->stream, n3, xs, ea);
+    // the slot that took the old x becomes the newest
+    double* newest = S->x_hist[keep - 1];
+    for (int k = keep - 1; k > 0; k--) S->x_hist[k] = S->x_hist[k - 1];
+    S->x_hist[0] = newest;
+    S->n_prev = std::min(keep, S->n_prev + 1);
+    return 0;
+}
+static int solve_stokes(pl_ctx* ctx, const pl_step_config* cfg, double* b, bool warm, pl_solve_stats* st) {
+    return pl_stokes_solve_device(ctx, b, warm, cfg->stokes_rtol > 0 ? cfg->stokes_rtol : 1e-10, cfg->stokes_maxit > 0 ? cfg->stokes_maxit : 400, st);
+}
+// signed np.max over both velocity arrays (pylamp2.py:364)
+static int velocity_max(pl_ctx* ctx, PlStepState* S, double& vmax) {
+    double* x = pl_stokes_solution_device(ctx);
+    MinMaxSpec sp[2] = {{x, nullptr, nullptr, 0}, {x + ctx->geom.d.plane, nullptr, nullptr, 0}};
+    MinMaxOut mm[2];
+    PL_TRY(reduce_minmax_multi(ctx, S, ctx->geom.d, 2, sp, mm));
+    vmax = std::fmax(mm[0].mx, mm[1].mx);
+    return 0;
+}
+// the smaller of the two limits and the letter of the limiter (pylamp2.py:374-380)
+static double choose_tstep(const pl_step_config* cfg, double tstep_temp, double tstep_stokes, int& limiter) {
+    limiter = (cfg->do_heatdiff && tstep_temp < tstep_stokes) ? 'H' : 'S';
+    if (!cfg->do_heatdiff) return tstep_stokes;
+    return (tstep_stokes < tstep_temp) ? tstep_stokes : tstep_temp;
+}
+// stage 4: Stokes (pylamp2.py:349-405): solve, advective time step, the step and its limiter -> rep
+static int stage_stokes(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, const StepPlanes& P, const StepLimits& L, pl_step_report* rep) {
+    double Kc, Kb;
+    pl_stokes_scaling_host(ctx->geom, L.mes, L.men, &Kc, &Kb);
+    const bool ss = cfg->surface_stabilization != 0;
+    if (!ss || cfg->surfstab_tstep < 0) pl_stokes_fill_op(ctx, P.etas, P.etan, P.rho, cfg->bcstokes, 0, 0.0, 0.5, Kc, Kb);
+    else pl_stokes_fill_op(ctx, P.etas, P.etan, P.rho, cfg->bcstokes, 1, cfg->surfstab_tstep, cfg->surfstab_theta, Kc, Kb);
+    double* b = pl_stokes_rhs_buffer_device(ctx);
+    if (!b) return 1;
+    pl_launch_stokes_rhs(ctx, ctx->sop, b);
+    pl_stokes_deflation(ctx, true);
+    PL_TRY(stokes_start(ctx, S));
+    PL_TRY(solve_stokes(ctx, cfg, b, S->have_solution, &rep->stokes));
+    S->have_solution = true;
+    const double mindx = min_spacing(ctx, cfg);
+    double vmax;
+    PL_TRY(velocity_max(ctx, S, vmax));
+    double tstep_stokes = clamp_tstep(cfg->tstep_modifier * mindx / vmax, cfg->tstep_adv_min, cfg->tstep_adv_max);
+    if (cfg->surfstab_tstep > 0) tstep_stokes = cfg->surfstab_tstep;          // pylamp2.py:368-372
+    int limiter;
+    double tstep = choose_tstep(cfg, L.tstep_temp, tstep_stokes, limiter);
+    // surface stabilisation: re-assemble with the chosen step and re-solve until the step stops shrinking (pylamp2.py:387-405)
+    for (int guard = 0; ss && cfg->surfstab_tstep < 0 && guard < 50; guard++) {
+        pl_stokes_fill_op(ctx, P.etas, P.etan, P.rho, cfg->bcstokes, 1, tstep, cfg->surfstab_theta, Kc, Kb);
+        pl_launch_stokes_rhs(ctx, ctx->sop, b);
+        pl_solve_stats st2{};
+        PL_TRY(solve_stokes(ctx, cfg, b, true, &st2));
+        rep->stokes_resolves++;
+        rep->stokes.iterations += st2.iterations; rep->stokes.converged &= st2.converged;
+        rep->stokes.rel_residual = st2.rel_residual; rep->stokes.error_estimate = st2.error_estimate; rep->stokes.solve_ms += st2.solve_ms;
+        rep->stokes.operator_applies += st2.operator_applies; rep->stokes.precond_applies += st2.precond_applies;
+        rep->stokes.used_direct |= st2.used_direct;
+        PL_TRY(velocity_max(ctx, S, vmax));
+        const double check = cfg->tstep_modifier * mindx / vmax;
+        if (!(check < tstep)) break;
+        tstep = check; limiter = 's';
+    }
+    rep->tstep = tstep; rep->limiter = limiter; rep->tstep_heat = L.tstep_temp; rep->tstep_stokes = tstep_stokes;
+    return 0;
+}
+// stage 5a: heat (pylamp2.py:412-434): the new nodal temperature -> P.newT (halo filled)
+static int stage_heat(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, const StepPlanes& P, double tstep, pl_step_report* rep) {
+    const PlGeom& g = ctx->geom.d;
+    const size_t pb = (size_t)g.plane * sizeof(double);
+    PL_TRY(pl_heat_tables(ctx, S->gmz.data(), S->gmx.data()));
+    PlHeatOp& hop = ctx->hop;
+    hop.g = g; hop.kz = P.kz; hop.kx = P.kx; hop.rhocp_inv_dt = P.c; hop.dt = tstep;
+    for (int w = 0; w < 4; w++) { hop.bc[w] = cfg->bcheat[w]; ctx->heat_bcvalue[w] = cfg->bcheatvals[w]; }
+    ctx->hop_ready = true;
+    pl_launch_heat_coef(ctx, g, P.rho, P.cp, tstep, P.c);
+    double* hb;
+    PL_TRY(pl_buf(ctx, "api_hx", pb, &hb));
+    pl_launch_heat_rhs(ctx, hop, P.T, P.H, hb);
+    double* xs = nullptr;
+    // Initial guess: the nodal temperature the right-hand side was built from, plus (from the third step on) the last step's
+    // implicit increment scaled to this step's length -- instead of zero (PYLAMP_HEAT_X0 = 0: zero, 1: the old temperature only).
+    static const int hx0 = getenv("PYLAMP_HEAT_X0") ? atoi(getenv("PYLAMP_HEAT_X0")) : 2;
+    const double* guess = nullptr;
+    if (hx0 >= 1) {
+        guess = P.T;
+        if (hx0 >= 2 && S->have_dT && S->dt_hist[1] > 0.0 && tstep <= 2.0 * S->dt_hist[1]) {
+            double* hg;
+            PL_TRY(pl_buf(ctx, "heat_x0", pb, &hg));
+            const long long np1 = g.plane;
+            hipLaunchKernelGGL(k_plane_axpy, grid1d(np1), dim3(256), 0, ctx->stream, np1, hg, P.T, P.dT, tstep / S->dt_hist[1]);
+            guess = hg;
+        }
+    }
+    PL_TRY(pl_heat_solve_device(ctx, hb, cfg->heat_rtol > 0 ? cfg->heat_rtol : 1e-12,
+                                cfg->heat_maxit > 0 ? cfg->heat_maxit : 2000, &rep->heat, &xs, guess));
+    PL_HIP(ctx, hipMemcpyAsync(P.newT, xs, pb, hipMemcpyDeviceToDevice, ctx->stream));
+    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PL_TRY(pl_halo(ctx, g, P.newT, 1, g.plane));
+    return 0;
+}
+// stage 6: advection (pylamp2.py:484-572).  The window of the padded centre grid the RK4 stages of this rank's tracers can reach:
+// a tracer moves less than a cell per stage (the time step is CFL-limited, pylamp2.py:364), so cells [gi0-1, gi0+lnz+1] of the
+// padded grid, i.e. its nodes I in [gi0-1, gi0+lnz+2], computed from the velocity planes with a halo 3 nodes deep -- no all-gather.
+static int stage_advect(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, double tstep, bool* keys_ready) {
+    const PlGeom& g = ctx->geom.d;
+    double* xsol = pl_stokes_solution_device(ctx);
+    const double* vz = xsol; const double* vx = xsol + g.plane;
+    const int I0 = std::max(g.gi0 - 1, 0), I1 = std::min(g.gi0 + g.lnz + 2, g.nz), J0 = std::max(g.gj0 - 1, 0), J1 = std::min(g.gj0 + g.lnx + 2, g.nx);
+    const int nVr = I1 - I0 + 1, nVc = J1 - J0 + 1;
+    const size_t VN = (size_t)nVr * nVc;
+    double* V;
+    PL_TRY(pl_buf(ctx, "advect_vel", 2 * VN * sizeof(double), &V, false));
+    PL_TRY(pl_halo(ctx, g, xsol, 2, g.plane, 3));
+    dim3 gr((nVc + 63) / 64, (nVr + 3) / 4);
+    hipLaunchKernelGGL(k_advection_velocity, gr, dim3(64, 4), 0, ctx->stream, g, vz, vx,
+                       (cfg->bcstokes[0] & PL_BC_FREESLIP) ? 1 : 0, (cfg->bcstokes[1] & PL_BC_FREESLIP) ? 1 : 0,
+                       (cfg->bcstokes[2] & PL_BC_FREESLIP) ? 1 : 0, (cfg->bcstokes[3] & PL_BC_FREESLIP) ? 1 : 0, I0, J0, nVr, nVc, V, V + VN);
+    return stage_rk4(ctx, S, V, I0, I1, J0, J1, tstep, cfg->tracs_fence_disabled ? 0 : 1, cfg->length[0], cfg->length[1], keys_ready);
+}
+// stage 7: cell sort of the advected tracers, migration between the blocks, census + injection (pylamp2.py:574-633)
+static int stage_sort(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, int it, bool keys_ready, pl_step_report* rep) {
+    const StepGrid q = step_grid(ctx);
+    long long removed = 0;
+    SortOpts so; so.del_outside = cfg->tracs_fence_disabled ? 1 : 0; so.Lz = cfg->length[0]; so.Lx = cfg->length[1]; so.removed = &removed; so.keys_ready = keys_ready;
+    SortOpts si; si.inject = cfg; si.it = it; si.ninjected = &rep->ninjected;
+    static const bool presort_env = !(getenv("PYLAMP_MIGRATE_PRESORT") && atoi(getenv("PYLAMP_MIGRATE_PRESORT")) == 0);
+    const bool presort = ctx->nranks > 1 && presort_env && keys_ready && !so.del_outside && ctx->geom.uniform && scatter_cells_on() && epoch_length() > 0;
+    if (ctx->nranks == 1 || presort) { so.inject = si.inject; so.it = it; so.ninjected = si.ninjected; }     // one pass does it all
+    if (presort) {                // several ranks: leavers out / arrivals in BEFORE the one sort (epoch layout, as on one rank)
+        PL_TRY(migrate_presort(ctx, S, q));
+        so.premigrated = true; so.drop_trash = true;
+    }
+    PL_TRY(sort_tracers(ctx, S, q, so));
+    rep->nremoved = removed;
+    if (!presort) PL_TRY(migrate_tracers(ctx, S, q, si));          // classic: sort, send the leaver buckets, append, sort again
+    return 0;
+}
+
 extern "C" int pl_step(pl_ctx* ctx, const pl_step_config* cfg, int it, pl_step_report* rep) {
     if (!cfg || !rep) return pl_fail(ctx, "pl_step: NULL argument");
     PL_HIP(ctx, hipSetDevice(ctx->device));
@@ -1508,189 +1678,35 @@ extern "C" int pl_step(pl_ctx* ctx, const pl_step_config* cfg, int it, pl_step_r
     PL_TRY(ensure_coords(ctx, S));
     PL_TRY(pl_stokes_check_bc(ctx, cfg->bcstokes));
     if (cfg->do_heatdiff) PL_TRY(pl_heat_check_bc(ctx, cfg->bcheat));
-    const PlGeom& g = ctx->geom.d;
-    const int nz = g.nz, nx = g.nx;
-    const size_t pb = (size_t)g.plane * sizeof(double);
     memset(rep, 0, sizeof(*rep));
-    const double Lz = cfg->length[0], Lx = cfg->length[1];
-    const double dz = Lz / (nz - 1), dx = Lx / (nx - 1);           // pylamp2.py:87
-    const double z0 = ctx->geom.zc[0], x0 = ctx->geom.xc[0];
-    const double hz = (ctx->geom.zc[nz - 1] - z0) / (nz - 1), hx = (ctx->geom.xc[nx - 1] - x0) / (nx - 1);
     double t_all = now_ms(), t0;
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-
     StepPlanes P;
     PL_TRY(step_planes(ctx, P));
-    double* const p_rho = P.rho; double* const p_etas = P.etas; double* const p_etan = P.etan; double* const p_cp = P.cp;
-    double* const p_T = P.T; double* const p_H = P.H; double* const p_kz = P.kz; double* const p_kx = P.kx;
-    double* const p_newT = P.newT; double* const p_c = P.c; double* const p_dT = P.dT;
-
     // tracers arrive cell-sorted (pl_tracers_upload / end of the previous step)
     if (!S->sorted) return pl_fail(ctx, "pl_step: tracers are not sorted (internal error)");
     // the columns the last sort left behind (RHO, ETA, tracer velocities) are rewritten below before anything reads them -- unless
     // this configuration does not run the stage that rewrites them
     if (S->cols_undefined) return pl_fail(ctx, "pl_step: the previous step failed half-way; upload the tracers again");
-    if (ctx->geom.uniform && scatter_cells_on()) { S->cols_undefined = S->lazy_pending; S->lazy_pending = false; }     // (defined again behind stage_rk4)
+    if (ctx->geom.uniform && scatter_cells_on()) { S->cols_undefined = S->lazy_pending; S->lazy_pending = false; }     // (defined again behind stage_advect)
     else PL_TRY(ensure_current(ctx, S));
-
-    // ---- 1. tracer properties --------------------------------------------------------------
+    // ---- 1. tracer properties (pylamp2.py:291-303)
     t0 = now_ms();
     PL_TRY(stage_props(ctx, S, cfg));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rep->ms_props = now_ms() - t0;
-
-    // ---- 2. tracer -> grid (pylamp2.py:307-319) ------------------------------------------------
+    // ---- 2. tracer -> grid (pylamp2.py:307-319)
     t0 = now_ms();
     PL_TRY(stage_scatter(ctx, S, cfg, it, P));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rep->ms_scatter = now_ms() - t0;
-
-    // ---- 3. heat time step (pylamp2.py:339-343) and the viscosity minima of the Stokes scaling (pylamp_stokes.py:116-118): ONE reduction
-    double tstep_temp = 0.0, mx;
-    double mes, men;
-    {
-        MinMaxSpec sp[3] = {{p_etas, nullptr, nullptr, 0}, {p_etan, nullptr, nullptr, 0}, {p_kz, p_rho, p_cp, 1}};
-        MinMaxOut mm[3];
-        PL_TRY(reduce_minmax_multi(ctx, S, g, cfg->do_heatdiff ? 3 : 2, sp, mm));
-        mes = mm[0].has_nan ? std::numeric_limits<double>::quiet_NaN() : mm[0].mn;
-        men = mm[1].has_nan ? std::numeric_limits<double>::quiet_NaN() : mm[1].mn;
-        {
-            const double lo = std::fmin(mm[0].mn, mm[1].mn), hi = std::fmax(mm[0].mx, mm[1].mx);
-            ctx->visc_contrast = (lo > 0.0 && hi > 0.0 && std::isfinite(hi / lo)) ? hi / lo : 1.0;
-        }
-        if (cfg->do_heatdiff) {
-            mx = mm[2].has_nan ? std::numeric_limits<double>::quiet_NaN() : mm[2].mx;
-            const double mindx = std::fmin(dz, dx);
-            tstep_temp = cfg->tstep_modifier * mindx * mindx / mx;
-            tstep_temp = (cfg->tstep_dif_max < tstep_temp) ? cfg->tstep_dif_max : tstep_temp;   // python min/max order
-            tstep_temp = (cfg->tstep_dif_min > tstep_temp) ? cfg->tstep_dif_min : tstep_temp;
-        }
-    }
-
-    // ---- 4. Stokes (pylamp2.py:349-366) -----------------------------------------------------------
+    // ---- 3. heat time step and the viscosity scales; 4. Stokes and the time step (pylamp2.py:339-405)
+    StepLimits L;
+    PL_TRY(stage_limits(ctx, S, cfg, P, L));
     t0 = now_ms();
-    double Kc, Kb;
-    pl_stokes_scaling_host(ctx->geom, mes, men, &Kc, &Kb);
-    const bool ss = cfg->surface_stabilization != 0;
-    if (!ss || cfg->surfstab_tstep < 0) pl_stokes_fill_op(ctx, p_etas, p_etan, p_rho, cfg->bcstokes, 0, 0.0, 0.5, Kc, Kb);
-    else pl_stokes_fill_op(ctx, p_etas, p_etan, p_rho, cfg->bcstokes, 1, cfg->surfstab_tstep, cfg->surfstab_theta, Kc, Kb);
-    double* b = pl_stokes_rhs_buffer_device(ctx);
-    if (!b) return 1;
-    pl_launch_stokes_rhs(ctx, ctx->sop, b);
-    pl_stokes_deflation(ctx, true);
-    {   // Initial guess extrapolated in model time from the last solutions (Lagrange polynomial through up to PYLAMP_X0_ORDER + 1
-        // of them, default 2 = quadratic; PYLAMP_X0_EXTRAP scales the target time, 0 switches the extrapolation off).  With the
-        // plateau of the pressure-anchor mode gone (pl_solver.hip) every factor 3 in the initial residual is an iteration; at 2049^2:
-        // none 15.3 iterations / 38.6 ms per solve, linear 13.3 / 33.5 ms, quadratic 11.5 / 29.9 ms.  In round 1 the same
-        // extrapolation changed nothing -- the plateau ate whatever the start gained.  Only the iteration count depends on it: the
-        // stopping rule is the same whatever the start.
-        static const double wx = getenv("PYLAMP_X0_EXTRAP") ? atof(getenv("PYLAMP_X0_EXTRAP")) : 1.0;
-        if (wx != 0.0 && S->have_solution) {
-            double* xs = pl_stokes_solution_device(ctx);
-            const long long n3 = 3 * g.plane;
-            static const int order = std::max(1, std::min(3, getenv("PYLAMP_X0_ORDER") ? atoi(getenv("PYLAMP_X0_ORDER")) : 2));
-            static const int keep = std::max(order, std::min((int)X0_HIST, getenv("PYLAMP_X0_POINTS") ? atoi(getenv("PYLAMP_X0_POINTS")) : order));
-            if (!S->x_hist[0]) {
-                const char* nm[X0_HIST] = {"x_prev", "x_prev2", "x_prev3", "x_prev4", "x_prev5"};
-                for (int k = 0; k < keep; k++) PL_TRY(pl_buf(ctx, nm[k], (size_t)n3 * sizeof(double), &S->x_hist[k]));
-            }
-            // Weights of the polynomial of degree `order` fitted (least squares when more than order + 1 solutions are kept, else
-            // interpolating) to the solutions at model times 0, -dt1, -dt1-dt2, ... and evaluated at +dt0.  A time step that more
-            // than doubled (or a missing history) falls back to the linear formula with its weight capped at 2.
-            const double* d = S->dt_hist;
-            int np = std::min(keep, S->n_prev);                // older solutions used
-            for (int k = 0; k <= np; k++) if (!(d[k] > 0.0)) np = std::min(np, std::max(0, k - 1));
-            if (np >= 2 && d[0] > 2.0 * d[1]) np = 1;
-            ExtrapArgs ea{};
-            ea.nk = keep; ea.nh = np; ea.l0 = 1.0;
-            for (int k = 0; k < keep; k++) ea.h[k] = S->x_hist[k];
-            if (np == 1) {
-                const double w = std::min(2.0, wx * d[0] / d[1]);
-                ea.l0 = 1.0 + w; ea.l[0] = -w;
-            } else if (np >= 2) {
-                const int deg = std::min(order, np), m = np + 1;
-                double tau[X0_HIST + 1] = {}, G[4][5] = {};              // times in units of dt0; normal equations (V^T V) c = t
-                for (int k = 1; k <= np; k++) tau[k] = tau[k - 1] - d[k] / d[0];
-                const double T = wx;
-                for (int a2 = 0; a2 <= deg; a2++) {
-                    for (int b2 = 0; b2 <= deg; b2++) for (int i = 0; i < m; i++) G[a2][b2] += std::pow(tau[i], a2 + b2);
-                    G[a2][deg + 1] = std::pow(T, a2);
-                }
-                bool ok = true;
-                for (int c = 0; c <= deg && ok; c++) {                    // Gauss-Jordan with partial pivoting on the (deg+1) system
-                    int pv = c;
-                    for (int r = c + 1; r <= deg; r++) if (std::fabs(G[r][c]) > std::fabs(G[pv][c])) pv = r;
-                    if (!(std::fabs(G[pv][c]) > 1e-300)) { ok = false; break; }
-                    for (int k = 0; k <= deg + 1; k++) std::swap(G[c][k], G[pv][k]);
-                    for (int r = 0; r <= deg; r++) if (r != c) {
-                        const double f = G[r][c] / G[c][c];
-                        for (int k = c; k <= deg + 1; k++) G[r][k] -= f * G[c][k];
-                    }
-                }
-                if (ok) {
-                    double L[X0_HIST + 1];
-                    for (int i = 0; i < m; i++) {
-                        L[i] = 0.0;
-                        for (int a2 = 0; a2 <= deg; a2++) L[i] += std::pow(tau[i], a2) * G[a2][deg + 1] / G[a2][a2];
-                    }
-                    ea.l0 = L[0];
-                    for (int k = 0; k < np; k++) ea.l[k] = L[k + 1];
-                } else ea.nh = 0;
-            }
-            hipLaunchKernelGGL(k_extrap_x0, grid1d(n3), dim3(256), 0, ctx->stream, n3, xs, ea);
-            {   // the slot that took the old x becomes the newest
-                double* newest = S->x_hist[keep - 1];
-                for (int k = keep - 1; k > 0; k--) S->x_hist[k] = S->x_hist[k - 1];
-                S->x_hist[0] = newest;
-            }
-            S->n_prev = std::min(keep, S->n_prev + 1);
-        }
-    }
-    PL_TRY(pl_stokes_solve_device(ctx, b, S->have_solution, cfg->stokes_rtol > 0 ? cfg->stokes_rtol : 1e-10,
-                                  cfg->stokes_maxit > 0 ? cfg->stokes_maxit : 400, &rep->stokes));
-    S->have_solution = true;
-    double* xsol = pl_stokes_solution_device(ctx);
-    double* p_vz = xsol; double* p_vx = xsol + g.plane;
-    double vmax_z, vmax_x;
-    auto velocity_max = [&]() -> int {
-        MinMaxSpec sp[2] = {{p_vz, nullptr, nullptr, 0}, {p_vx, nullptr, nullptr, 0}};
-        MinMaxOut mm[2];
-        PL_TRY(reduce_minmax_multi(ctx, S, g, 2, sp, mm));
-        vmax_z = mm[0].mx; vmax_x = mm[1].mx;
-        return 0;
-    };
-    PL_TRY(velocity_max());
-    const double vmax = std::fmax(vmax_z, vmax_x);                  // signed np.max over both arrays (pylamp2.py:364)
-    double tstep_stokes = cfg->tstep_modifier * std::fmin(dz, dx) / vmax;
-    tstep_stokes = (cfg->tstep_adv_max < tstep_stokes) ? cfg->tstep_adv_max : tstep_stokes;
-    tstep_stokes = (cfg->tstep_adv_min > tstep_stokes) ? cfg->tstep_adv_min : tstep_stokes;
-    if (cfg->surfstab_tstep > 0) tstep_stokes = cfg->surfstab_tstep;          // pylamp2.py:368-372
-    double tstep; int limiter;
-    if (cfg->do_heatdiff) {
-        limiter = (tstep_temp < tstep_stokes) ? 'H' : 'S';
-        tstep = (tstep_stokes < tstep_temp) ? tstep_stokes : tstep_temp;
-    } else { tstep = tstep_stokes; limiter = 'S'; }
-    if (ss && cfg->surfstab_tstep < 0) {
-        // re-assemble with the chosen step and re-solve until the step stops shrinking (pylamp2.py:387-405)
-        for (int guard = 0; guard < 50; guard++) {
-            pl_stokes_fill_op(ctx, p_etas, p_etan, p_rho, cfg->bcstokes, 1, tstep, cfg->surfstab_theta, Kc, Kb);
-            pl_launch_stokes_rhs(ctx, ctx->sop, b);
-            pl_solve_stats st2{};
-            PL_TRY(pl_stokes_solve_device(ctx, b, true, cfg->stokes_rtol > 0 ? cfg->stokes_rtol : 1e-10,
-                                          cfg->stokes_maxit > 0 ? cfg->stokes_maxit : 400, &st2));
-            rep->stokes_resolves++;
-            rep->stokes.iterations += st2.iterations; rep->stokes.converged &= st2.converged;
-            rep->stokes.rel_residual = st2.rel_residual; rep->stokes.error_estimate = st2.error_estimate; rep->stokes.solve_ms += st2.solve_ms;
-            rep->stokes.operator_applies += st2.operator_applies; rep->stokes.precond_applies += st2.precond_applies;
-            rep->stokes.used_direct |= st2.used_direct;
-            PL_TRY(velocity_max());
-            const double check = cfg->tstep_modifier * std::fmin(dz, dx) / std::fmax(vmax_z, vmax_x);
-            if (check < tstep) { tstep = check; limiter = 's'; }
-            else break;
-        }
-    }
+    PL_TRY(stage_stokes(ctx, S, cfg, P, L, rep));
     rep->ms_stokes = now_ms() - t0;
-    rep->tstep = tstep; rep->limiter = limiter; rep->tstep_heat = tstep_temp; rep->tstep_stokes = tstep_stokes;
+    const double tstep = rep->tstep;
     for (int k = X0_HIST; k > 0; k--) S->dt_hist[k] = S->dt_hist[k - 1];
     S->dt_hist[0] = tstep;
     // the reference would carry a NaN time step on (NaN positions from the next advection); say what happened instead
@@ -1698,89 +1714,26 @@ extern "C" int pl_step(pl_ctx* ctx, const pl_step_config* cfg, int it, pl_step_r
         return pl_fail(ctx, "pl_step: the time step is not finite - a grid node without any marker in reach makes the interpolated "
                             "fields NaN, and so do tracers injected into a cell without residents (their fields are 0/0 as in "
                             "pylamp2.py:624-629): raise the marker density or enable injection before cells run empty");
-
-    // ---- 5. heat (pylamp2.py:412-480) ----------------------------------------------------------------
+    // ---- 5. heat and temperature to the tracers (pylamp2.py:412-480)
     if (cfg->do_heatdiff) {
         t0 = now_ms();
-        PL_TRY(pl_heat_tables(ctx, S->gmz.data(), S->gmx.data()));
-        PlHeatOp& hop = ctx->hop;
-        hop.g = g; hop.kz = p_kz; hop.kx = p_kx; hop.rhocp_inv_dt = p_c; hop.dt = tstep;
-        for (int w = 0; w < 4; w++) { hop.bc[w] = cfg->bcheat[w]; ctx->heat_bcvalue[w] = cfg->bcheatvals[w]; }
-        ctx->hop_ready = true;
-        pl_launch_heat_coef(ctx, g, p_rho, p_cp, tstep, p_c);
-        double* hb;
-        PL_TRY(pl_buf(ctx, "api_hx", pb, &hb));
-        pl_launch_heat_rhs(ctx, hop, p_T, p_H, hb);
-        double* xs = nullptr;
-        // Initial guess: the nodal temperature the right-hand side was built from, plus (from the third step on) the last step's
-        // implicit increment scaled to this step's length -- instead of zero (PYLAMP_HEAT_X0 = 0: zero, 1: the old temperature only).
-        static const int hx0 = getenv("PYLAMP_HEAT_X0") ? atoi(getenv("PYLAMP_HEAT_X0")) : 2;
-        const double* guess = nullptr;
-        if (hx0 >= 1) {
-            guess = p_T;
-            if (hx0 >= 2 && S->have_dT && S->dt_hist[1] > 0.0 && tstep <= 2.0 * S->dt_hist[1]) {
-                double* hg;
-                PL_TRY(pl_buf(ctx, "heat_x0", pb, &hg));
-                const long long np1 = g.plane;
-                hipLaunchKernelGGL(k_plane_axpy, grid1d(np1), dim3(256), 0, ctx->stream, np1, hg, p_T, p_dT, tstep / S->dt_hist[1]);
-                guess = hg;
-            }
-        }
-        PL_TRY(pl_heat_solve_device(ctx, hb, cfg->heat_rtol > 0 ? cfg->heat_rtol : 1e-12,
-                                    cfg->heat_maxit > 0 ? cfg->heat_maxit : 2000, &rep->heat, &xs, guess));
-        PL_HIP(ctx, hipMemcpyAsync(p_newT, xs, pb, hipMemcpyDeviceToDevice, ctx->stream));
-        PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        PL_TRY(pl_halo(ctx, g, p_newT, 1, g.plane));
+        PL_TRY(stage_heat(ctx, S, cfg, P, tstep, rep));
         rep->ms_heat = now_ms() - t0;
-
-        // temperature to tracers
         t0 = now_ms();
         PL_TRY(stage_temp_to_tracers(ctx, S, cfg, it == 1 || !S->have_newtemp, P, tstep));
         S->have_newtemp = true;
         rep->ms_gather = now_ms() - t0;
     }
-
-    // ---- 6. advection (pylamp2.py:484-572) ------------------------------------------------------------
+    // ---- 6. advection (pylamp2.py:484-572)
     t0 = now_ms();
-    // window of the padded centre grid the RK4 stages of this rank's tracers can reach: a tracer moves less than a cell
-    // per stage (the time step is CFL-limited, pylamp2.py:364), so cells [gi0-1, gi0+lnz+1] of the padded grid, i.e.
-    // its nodes I in [gi0-1, gi0+lnz+2], computed from the velocity planes with a halo 3 nodes deep -- no all-gather.
-    const int I0 = std::max(g.gi0 - 1, 0), I1 = std::min(g.gi0 + g.lnz + 2, nz), J0 = std::max(g.gj0 - 1, 0), J1 = std::min(g.gj0 + g.lnx + 2, nx);
-    const int nVr = I1 - I0 + 1, nVc = J1 - J0 + 1;
-    const size_t VN = (size_t)nVr * nVc;
-    double* V;
-    PL_TRY(pl_buf(ctx, "advect_vel", 2 * VN * sizeof(double), &V, false));
-    PL_TRY(pl_halo(ctx, g, xsol, 2, g.plane, 3));
-    {
-        dim3 gr((nVc + 63) / 64, (nVr + 3) / 4);
-        hipLaunchKernelGGL(k_advection_velocity, gr, dim3(64, 4), 0, ctx->stream, g, (const double*)p_vz, (const double*)p_vx,
-                           (cfg->bcstokes[0] & PL_BC_FREESLIP) ? 1 : 0, (cfg->bcstokes[1] & PL_BC_FREESLIP) ? 1 : 0,
-                           (cfg->bcstokes[2] & PL_BC_FREESLIP) ? 1 : 0, (cfg->bcstokes[3] & PL_BC_FREESLIP) ? 1 : 0, I0, J0, nVr, nVc, V, V + VN);
-    }
     bool keys_ready = false;
-    PL_TRY(stage_rk4(ctx, S, V, I0, I1, J0, J1, tstep, cfg->tracs_fence_disabled ? 0 : 1, Lz, Lx, &keys_ready));
+    PL_TRY(stage_advect(ctx, S, cfg, tstep, &keys_ready));
     S->cols_undefined = false;        // RHO / ETA (stage 1) and the tracer velocities (here) have been rewritten
     rep->ms_advect = now_ms() - t0;
-
-    // ---- 7. cell sort of the advected tracers, slab migration, census + injection --------------------
+    // ---- 7. cell sort, migration, census + injection (pylamp2.py:574-633)
     t0 = now_ms();
     S->sorted = false;
-    {
-        long long removed = 0;
-        SortOpts so; so.del_outside = cfg->tracs_fence_disabled ? 1 : 0; so.Lz = Lz; so.Lx = Lx; so.removed = &removed;
-        so.keys_ready = keys_ready;
-        SortOpts si; si.inject = cfg; si.it = it; si.ninjected = &rep->ninjected;
-        static const bool presort_env = !(getenv("PYLAMP_MIGRATE_PRESORT") && atoi(getenv("PYLAMP_MIGRATE_PRESORT")) == 0);
-        const bool presort = ctx->nranks > 1 && presort_env && keys_ready && !so.del_outside && ctx->geom.uniform && scatter_cells_on() && epoch_length() > 0;
-        if (ctx->nranks == 1 || presort) { so.inject = si.inject; so.it = it; so.ninjected = si.ninjected; }     // one pass does it all
-        if (presort) {                // several ranks: leavers out / arrivals in BEFORE the one sort (epoch layout, as on one rank)
-            PL_TRY(migrate_presort(ctx, S, z0, hz, x0, hx));
-            so.premigrated = true; so.drop_trash = true;
-        }
-        PL_TRY(sort_tracers(ctx, S, z0, hz, x0, hx, so));
-        rep->nremoved = removed;
-        if (!presort) PL_TRY(migrate_tracers(ctx, S, z0, hz, x0, hx, si));          // classic: sort, send the leaver buckets, append, sort again
-    }
+    PL_TRY(stage_sort(ctx, S, cfg, it, keys_ready, rep));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     S->sorted = true;
     rep->ms_sort = now_ms() - t0;
@@ -1790,19 +1743,20 @@ extern "C" int pl_step(pl_ctx* ctx, const pl_step_config* cfg, int it, pl_step_r
 }
 
 // ---- the marker stages one at a time (tests pin the kernels the timed step launches against the reference's fixtures) -----
-static int resident_ready(pl_ctx* ctx, PlStepState* S, const char* who) {
+// what every one of them begins with: the cell-sorted tracers of the one rank, every column current, the coordinates on the device
+static int resident_ready(pl_ctx* ctx, const char* who, PlStepState*& S) {
+    PL_HIP(ctx, hipSetDevice(ctx->device));
+    S = state_of(ctx);
     if (ctx->nranks != 1) return pl_fail(ctx, std::string(who) + ": single-rank entry point (several ranks run pl_step)");
     if (!S->cell_start || !S->sorted) return pl_fail(ctx, std::string(who) + ": no cell-sorted tracers resident (call pl_tracers_upload)");
-    return 0;
+    PL_TRY(flush_lazy(ctx, S));
+    return ensure_coords(ctx, S);
 }
 
 extern "C" int pl_resident_scatter(pl_ctx* ctx, const pl_step_config* cfg, int it) {
     if (!cfg) return pl_fail(ctx, "pl_resident_scatter: NULL argument");
-    PL_HIP(ctx, hipSetDevice(ctx->device));
-    PlStepState* S = state_of(ctx);
-    PL_TRY(resident_ready(ctx, S, "pl_resident_scatter"));
-    PL_TRY(flush_lazy(ctx, S));
-    PL_TRY(ensure_coords(ctx, S));
+    PlStepState* S;
+    PL_TRY(resident_ready(ctx, "pl_resident_scatter", S));
     StepPlanes P;
     PL_TRY(step_planes(ctx, P));
     PL_TRY(stage_props(ctx, S, cfg));
@@ -1813,11 +1767,8 @@ extern "C" int pl_resident_scatter(pl_ctx* ctx, const pl_step_config* cfg, int i
 
 extern "C" int pl_resident_temp_to_tracers(pl_ctx* ctx, const pl_step_config* cfg, int first, const double* newtemp, double tstep) {
     if (!cfg || !newtemp) return pl_fail(ctx, "pl_resident_temp_to_tracers: NULL argument");
-    PL_HIP(ctx, hipSetDevice(ctx->device));
-    PlStepState* S = state_of(ctx);
-    PL_TRY(resident_ready(ctx, S, "pl_resident_temp_to_tracers"));
-    PL_TRY(flush_lazy(ctx, S));
-    PL_TRY(ensure_coords(ctx, S));
+    PlStepState* S;
+    PL_TRY(resident_ready(ctx, "pl_resident_temp_to_tracers", S));
     StepPlanes P;
     PL_TRY(step_planes(ctx, P));
     PL_TRY(pl_plane_upload(ctx, ctx->geom.d, newtemp, P.newT));
@@ -1828,11 +1779,8 @@ extern "C" int pl_resident_temp_to_tracers(pl_ctx* ctx, const pl_step_config* cf
 
 extern "C" int pl_resident_rk4(pl_ctx* ctx, const double* vz_pad, const double* vx_pad, double tstep, int fence, const double length[2]) {
     if (!vz_pad || !vx_pad || !length) return pl_fail(ctx, "pl_resident_rk4: NULL argument");
-    PL_HIP(ctx, hipSetDevice(ctx->device));
-    PlStepState* S = state_of(ctx);
-    PL_TRY(resident_ready(ctx, S, "pl_resident_rk4"));
-    PL_TRY(flush_lazy(ctx, S));
-    PL_TRY(ensure_coords(ctx, S));
+    PlStepState* S;
+    PL_TRY(resident_ready(ctx, "pl_resident_rk4", S));
     const int nz = ctx->nz, nx = ctx->nx;
     const size_t VN = (size_t)(nz + 1) * (nx + 1);
     double* V;
@@ -1841,8 +1789,7 @@ extern "C" int pl_resident_rk4(pl_ctx* ctx, const double* vz_pad, const double* 
     PL_HIP(ctx, hipMemcpyAsync(V + VN, vx_pad, VN * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PL_TRY(stage_rk4(ctx, S, V, 0, nz, 0, nx, tstep, fence ? 1 : 0, length[0], length[1]));
     S->sorted = false;
-    const StepGrid q = step_grid(ctx);
-    PL_TRY(sort_tracers(ctx, S, q.z0, q.hz, q.x0, q.hx));
+    PL_TRY(sort_tracers(ctx, S, step_grid(ctx)));
     PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     S->sorted = true;
     return 0;
