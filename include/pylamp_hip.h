@@ -232,6 +232,9 @@ int  pl_heat_rhs(pl_ctx* ctx, double* rhs);
 int  pl_heat_solve(pl_ctx* ctx, const double* rhs, double* x, double rtol, int maxit,
                    pl_solve_stats* stats);
 int  pl_heat_apply_bench(pl_ctx* ctx, int reps, double* avg_ms);
+/* Launches of the several-sweeps-per-launch Chebyshev kernel (k_heat_cheb_fused; one rank, PYLAMP_HEAT_FUSE unset or non-zero) by the
+ * heat solves of this context so far, pl_step's included: 0 where every sweep was a launch of its own. */
+int  pl_heat_fused_launches(pl_ctx* ctx, long long* n);
 
 /* ---- Marker-in-cell: replaces pylamp_trac.trac2grid / grid2trac / RK ----------------- */
 /* Tracer -> grid (pylamp_trac.py:161-318, method ELEM).  tr_x is (n,2) [z,x]; tr_f is

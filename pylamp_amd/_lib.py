@@ -168,6 +168,7 @@ SIGNATURES = {
     "pl_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),
     "pl_heat_solve": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int, C.POINTER(SolveStats)]),
     "pl_heat_apply_bench": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "pl_heat_fused_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     "pl_trac2grid": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int, c_int_p,
                                C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(c_double_p)]),
     "pl_trac2grid_rect": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int, c_int_p,

@@ -1605,6 +1605,7 @@ struct PlSolver {
     double* hc3 = nullptr;                    // several ranks: the three Chebyshev iterates of the heat solve, contiguous (one halo exchange)
     double* hc[9] = {nullptr}; double* hc_part = nullptr; int hc_nb = 0, hc_last_its = 0;      // CG work planes (wall entries of d, r, z, p, q stay 0)
     int napply = 0, nprec = 0;
+    long long heat_fused_launches = 0;        // k_heat_cheb_fused launches on this context so far (pl_heat_fused_launches)
 };
 
 static PlSolver* solver_of(pl_ctx* ctx) {
@@ -4650,6 +4651,15 @@ __global__ __launch_bounds__(256) void k_heat_mass_norm(PlHeatOp op, const doubl
 //     d_next = d + c1 (d - d_prev) + c2 dinv (r0 - A_red d)        -- no reduction, one launch per sweep
 // Several ranks: launched on the block EXTENDED into the halo (op.g is the extended view, every pointer shifted accordingly), one
 // node less per sweep, so that a round of sweeps needs ONE exchange (deep halo, as the multigrid smoother's)
+__device__ inline double heat_red_rdiag(const HeatRed& h) { return pl_rcp(h.w[0] + h.w[1] + h.w[2] + h.w[3] + h.m); }
+// the sweep at one node: its iterate dc, the four neighbours' (E, W, N, S), its previous iterate dp (not used where c1 = 0: the first
+// sweep of a round) and its right-hand side -- the ONE expression both Chebyshev kernels evaluate
+__device__ inline double heat_cheb_node(const HeatRed& h, double di, double dc, double dE, double dW, double dN, double dS, double dp, double r0,
+                                        double c1, double c2) {
+    const double Ad = h.w[0] * (dc - dE) + h.w[1] * (dc - dW) + h.w[2] * (dc - dN) + h.w[3] * (dc - dS) + h.m * dc;
+    return dc + (c1 != 0.0 ? c1 * (dc - dp) : 0.0) + c2 * di * (r0 - Ad);
+}
+#define PL_HEAT_KMAX 5       // most sweeps one k_heat_cheb_fused launch performs (measured at 2049^2, 15 sweeps: 4 -> 0.62, 5 -> 0.56 ms per solve)
 __global__ __launch_bounds__(256) void k_heat_cheb(PlHeatOp op, const double* __restrict__ dcur, const double* __restrict__ dprev, const double* __restrict__ r0,
                                                    const double* __restrict__ dinv, double* __restrict__ dnext, double c1, double c2) {
     const PlGeom& g = op.g;
@@ -4658,11 +4668,81 @@ __global__ __launch_bounds__(256) void k_heat_cheb(PlHeatOp op, const double* __
     const long long c = pl_idx(g, li, lj);
     const int p = g.pitch;
     const HeatRed h = heat_red(op, i, j, c);
-    const double dc = dcur[c];
-    const double Ad = h.w[0] * (dc - dcur[c + 1]) + h.w[1] * (dc - dcur[c - 1]) + h.w[2] * (dc - dcur[c + p]) + h.w[3] * (dc - dcur[c - p]) + h.m * dc;
     (void)dinv;                                        // (the reciprocal diagonal is recomputed from the couplings at hand: 8 B/node less)
-    const double di = pl_rcp(h.w[0] + h.w[1] + h.w[2] + h.w[3] + h.m);
-    dnext[c] = dc + (c1 != 0.0 ? c1 * (dc - dprev[c]) : 0.0) + c2 * di * (r0[c] - Ad);      // wall entries stay 0
+    dnext[c] = heat_cheb_node(h, heat_red_rdiag(h), dcur[c], dcur[c + 1], dcur[c - 1], dcur[c + p], dcur[c - p], c1 != 0.0 ? dprev[c] : 0.0, r0[c], c1, c2);      // wall entries stay 0
+}
+
+// K consecutive sweeps of k_heat_cheb in ONE launch (one rank).  The couplings, the right-hand side and the reciprocal diagonal do
+// not change between the sweeps of a round: a workgroup loads them once for a tile of 64 x 4 NPT nodes (every thread keeps those of
+// its NPT nodes in registers), sweeps the tile K times with the iterate in LDS (two buffers: one barrier per sweep), and writes the
+// last two iterates of the tile's inner (64 - 2K) x (4 NPT - 2K) nodes -- what the next launch needs as dcur / dprev.  The K nodes
+// towards each tile edge are recomputed by the neighbouring tiles (after sweep s the outermost s nodes of a tile are stale, and
+// nothing that leaves the tile depends on them).  Per K sweeps every plane is read once and two are written, instead of six reads and
+// one write per sweep.  Nodes outside the interior -- the wall nodes, whose entries are 0 in every iterate buffer, and what a tile
+// overhangs beyond them -- carry 0 and zero couplings through all sweeps.  Same arithmetic per node as k_heat_cheb (heat_cheb_node).
+struct HeatChebCoef { double c1[PL_HEAT_KMAX], c2[PL_HEAT_KMAX]; };
+template <int K, int NPT>
+__global__ __launch_bounds__(256) void k_heat_cheb_fused(PlHeatOp op, const double* __restrict__ dcur, const double* __restrict__ dprev, const double* __restrict__ r0,
+                                                         double* __restrict__ dout, double* __restrict__ dout_prev, HeatChebCoef cf) {
+    constexpr int TX = 64, TY = 4 * NPT;
+    static_assert(K >= 2 && K <= PL_HEAT_KMAX && TY > 2 * K, "tile deeper than its halo");
+    __shared__ double sh[2][TY + 2][TX + 2];           // (a border of zeros: the tile's outermost nodes read it)
+    const PlGeom& g = op.g;
+    const int tx = threadIdx.x, l0 = threadIdx.y * NPT;
+    const int j = 1 + (int)blockIdx.x * (TX - 2 * K) - K + tx, i0 = 1 + (int)blockIdx.y * (TY - 2 * K) - K + l0;
+    for (int k = threadIdx.y * 64 + tx; k < 2 * (TY + 2) * (TX + 2); k += 256) (&sh[0][0][0])[k] = 0.0;
+    __syncthreads();
+    HeatRed h[NPT];
+    double di[NPT], rr[NPT], dc[NPT], dp[NPT];
+    const bool col_in = j >= 1 && j <= g.nx - 2;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int i = i0 + k;
+        h[k].w[0] = h[k].w[1] = h[k].w[2] = h[k].w[3] = h[k].m = 0.0;
+        di[k] = rr[k] = dc[k] = dp[k] = 0.0;
+        if (col_in && i >= 1 && i <= g.nz - 2) {
+            const long long c = pl_idx(g, i, j);
+            h[k] = heat_red(op, i, j, c);
+            di[k] = heat_red_rdiag(h[k]);
+            rr[k] = r0[c]; dc[k] = dcur[c];
+            if (cf.c1[0] != 0.0) dp[k] = dprev[c];     // (the first sweep of a round has c1 = 0 and no previous iterate)
+            sh[0][l0 + k + 1][tx + 1] = dc[k];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < K; s++) {
+        const int b = s & 1;
+#pragma unroll
+        for (int k = 0; k < NPT; k++) {
+            const int l = l0 + k + 1;
+            const double dn = heat_cheb_node(h[k], di[k], dc[k], sh[b][l][tx + 2], sh[b][l][tx], sh[b][l + 1][tx + 1], sh[b][l - 1][tx + 1], dp[k], rr[k], cf.c1[s], cf.c2[s]);
+            dp[k] = dc[k]; dc[k] = dn;
+            if (s + 1 < K) sh[b ^ 1][l][tx + 1] = dn;
+        }
+        if (s + 1 < K) __syncthreads();
+    }
+    if (!col_in || tx < K || tx >= TX - K) return;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int i = i0 + k;
+        if (l0 + k < K || l0 + k >= TY - K || i < 1 || i > g.nz - 2) continue;
+        const long long c = pl_idx(g, i, j);
+        dout[c] = dc[k]; dout_prev[c] = dp[k];
+    }
+}
+
+// tiles of 64 x 32 nodes (8 per thread); the tile's inner (64 - 2 kf) x (32 - 2 kf) nodes are its output
+static_assert(PL_HEAT_KMAX == 5, "launch_heat_cheb_fused instantiates K = 2 .. 5");
+#define PL_HEAT_NPT 8        // (16, tiles of 64 x 64 at one workgroup per CU: 0.70 - 0.78 ms)
+static void launch_heat_cheb_fused(pl_ctx* ctx, int kf, const PlHeatOp& op, const double* dcur, const double* dprev, const double* r0, double* dout,
+                                   double* dout_prev, const HeatChebCoef& cf) {
+    const int ox = 64 - 2 * kf, oy = 4 * PL_HEAT_NPT - 2 * kf;
+    const dim3 gr((op.g.nx - 2 + ox - 1) / ox, (op.g.nz - 2 + oy - 1) / oy), bl(64, 4);
+    if (kf == 2) hipLaunchKernelGGL((k_heat_cheb_fused<2, PL_HEAT_NPT>), gr, bl, 0, ctx->stream, op, dcur, dprev, r0, dout, dout_prev, cf);
+    else if (kf == 3) hipLaunchKernelGGL((k_heat_cheb_fused<3, PL_HEAT_NPT>), gr, bl, 0, ctx->stream, op, dcur, dprev, r0, dout, dout_prev, cf);
+    else if (kf == 4) hipLaunchKernelGGL((k_heat_cheb_fused<4, PL_HEAT_NPT>), gr, bl, 0, ctx->stream, op, dcur, dprev, r0, dout, dout_prev, cf);
+    else hipLaunchKernelGGL((k_heat_cheb_fused<5, PL_HEAT_NPT>), gr, bl, 0, ctx->stream, op, dcur, dprev, r0, dout, dout_prev, cf);
 }
 
 // extended view of the heat operator: the block grown by e nodes into the halo (clipped at the domain walls); sh = element offset
@@ -4723,15 +4803,22 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
     hipLaunchKernelGGL(k_heat_mass_norm, gr, bl, 0, ctx->stream, hop, (const double*)x, S->hc_part);
     hipLaunchKernelGGL(k_heat_cg_scalars, dim3(1), dim3(1024), 0, ctx->stream, (int)(gr.x * gr.y), (const double*)S->hc_part, sc, 4);     // -> HC_PQ, HC_RAD
     if (multi) { PL_TRY(pl_comm_allreduce_dev(ctx, sc + HC_PQ, 1, 0)); PL_TRY(pl_comm_allreduce_dev(ctx, sc + HC_RAD, 1, 2)); }
-    PL_TRY(fetch());
-    const double xmass = hs[HC_PQ];
+    // One rank: the host does not wait for these two scalars -- the first residual launch below does not depend on them, and they
+    // are read together with its sums (one synchronisation less per solve).  Several ranks decide collectively, before the residual.
+    double xmass = 0.0, rho_g = 0.0;
+    bool cheb_ok = false;
     // Chebyshev iteration instead of CG where its sweep count is known to be small: the eigenvalues of D^-1 A_red lie in
     // [1 - rho, 1 + rho] (Gershgorin; rho = 1 / (1 + m / sum w) < 1 for a backward-Euler step), so k sweeps reduce the residual by
     // 1 / T_k(1 / rho) -- with NO reduction and ONE launch per sweep (CG: 4 launches and 2 reductions per iteration, which is what the
     // 2.2 ms of a 12-iteration solve at 2049^2 were made of).  The true residual is confirmed afterwards as before.
-    const double rho_g = hs[HC_RAD];
     const int cheb_env = getenv("PYLAMP_HEAT_CHEB") ? atoi(getenv("PYLAMP_HEAT_CHEB")) : 1;         // (read per solve: tests switch it)
-    const bool cheb_ok = cheb_env != 0 && rho_g > 0.0 && rho_g < 0.97 && std::isfinite(rho_g);
+    // PYLAMP_HEAT_FUSE=0: one sweep per launch (k_heat_cheb) on one rank too -- what k_heat_cheb_fused is checked against
+    const bool fuse = !multi && !(getenv("PYLAMP_HEAT_FUSE") && atoi(getenv("PYLAMP_HEAT_FUSE")) == 0);
+    auto read_norms = [&]() {                             // from the fetched scalars of k_heat_mass_norm
+        xmass = hs[HC_PQ]; rho_g = hs[HC_RAD];
+        cheb_ok = cheb_env != 0 && rho_g > 0.0 && rho_g < 0.97 && std::isfinite(rho_g);
+    };
+    if (multi) { PL_TRY(fetch()); read_norms(); }
     if (unsuited) *unsuited = false;
     if (multi && !cheb_ok) {                              // (rho is the same on every rank: a collective decision) -- the caller runs BiCGStab
         if (unsuited) *unsuited = true;
@@ -4758,6 +4845,7 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
         }
         S->napply++;
         PL_TRY(fetch());
+        if (pass == 0 && !multi) read_norms();            // (HC_PQ and HC_RAD: slots the residual's sums leave alone)
         if (pass == 0) ref = std::sqrt(hs[HC_REF]);
         double znorm = std::sqrt(hs[HC_ZZ]);
         if (!(ref > 0.0)) { st->converged = 1; break; }      // b = 0 on the interior: x0 with closed walls is the answer
@@ -4773,12 +4861,27 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
             ks = std::min(ks, std::max(maxit - it, 1));
             const double theta = 1.0, delta = rho_g;
             double rho_old = 1.0 / sigma;
-            double* bufs[3] = {d, pa, pbuf};                      // (cur, prev, free); d = 0 from the start kernel
+            double* bufs[4] = {d, pa, pbuf, S->hc[8]};            // (cur, prev, free, free); d = 0 from the start kernel.  The fourth
+                                                                  // plane is used by the fused launches only: they write TWO iterates
             int ext = E - 1;                                      // extension of the NEXT sweep (several ranks); r0 and d = 0 are valid that far
-            for (int k = 0; k < ks; k++) {
+            auto coef = [&](int k, double* c1, double* c2) {      // of sweep k of this round, in order
+                if (k == 0) { *c1 = 0.0; *c2 = 1.0 / theta; }
+                else { const double rr = 1.0 / (2.0 * sigma - rho_old); *c1 = rr * rho_old; *c2 = 2.0 * rr / delta; rho_old = rr; }
+            };
+            for (int k = 0; k < ks;) {
+                // one rank: PL_HEAT_KMAX sweeps per launch, then the 2 to 4 left over in a shorter one; a single sweep takes k_heat_cheb
+                const int kf = fuse ? std::min(ks - k, PL_HEAT_KMAX) : 1;
+                if (kf >= 2) {
+                    HeatChebCoef cf{};
+                    for (int q = 0; q < kf; q++) coef(k + q, &cf.c1[q], &cf.c2[q]);
+                    launch_heat_cheb_fused(ctx, kf, hop, bufs[0], bufs[1], r, bufs[2], bufs[3], cf);
+                    S->heat_fused_launches++;
+                    std::swap(bufs[0], bufs[2]); std::swap(bufs[1], bufs[3]);        // (cur, prev) <- the two planes just written
+                    k += kf; S->napply += kf;
+                    continue;
+                }
                 double c1, c2;
-                if (k == 0) { c1 = 0.0; c2 = 1.0 / theta; }
-                else { const double rr = 1.0 / (2.0 * sigma - rho_old); c1 = rr * rho_old; c2 = 2.0 * rr / delta; rho_old = rr; }
+                coef(k, &c1, &c2);
                 if (multi && ext < 0) {                           // the halo of the iterates is used up: ONE exchange of all three buffers
                     PL_TRY(pl_halo(ctx, g, S->hc3, 3, g.plane, E));
                     ext = E - 1;
@@ -4788,7 +4891,7 @@ static int heat_solve_cg(pl_ctx* ctx, PlSolver* S, const double* b_dev, double r
                                    (const double*)(r - V.sh), (const double*)(dinv - V.sh), bufs[2] - V.sh, c1, c2);
                 double* nx = bufs[2]; bufs[2] = bufs[1]; bufs[1] = bufs[0]; bufs[0] = nx;
                 ext--;
-                S->napply++;
+                k++; S->napply++;
             }
             it += ks;
             hipLaunchKernelGGL(k_add_inplace, grid1d(g.plane), dim3(256), 0, ctx->stream, (long long)g.plane, x, (const double*)bufs[0]);
@@ -4862,6 +4965,12 @@ int pl_heat_solve_device(pl_ctx* ctx, const double* b_dev, double rtol, int maxi
     PL_TRY(pl_timer_stop_ms(ctx, &ms));
     st->solve_ms = ms; st->operator_applies = S->napply; st->precond_applies = 0;
     *x_out = S->h[7];
+    return 0;
+}
+
+extern "C" int pl_heat_fused_launches(pl_ctx* ctx, long long* n) {
+    if (!n) return pl_fail(ctx, "pl_heat_fused_launches: n is NULL");
+    *n = solver_of(ctx)->heat_fused_launches;
     return 0;
 }
 

@@ -1627,7 +1627,7 @@ static int stage_heat(pl_ctx* ctx, PlStepState* S, const pl_step_config* cfg, co
     PL_TRY(pl_heat_solve_device(ctx, hb, cfg->heat_rtol > 0 ? cfg->heat_rtol : 1e-12,
                                 cfg->heat_maxit > 0 ? cfg->heat_maxit : 2000, &rep->heat, &xs, guess));
     PL_HIP(ctx, hipMemcpyAsync(P.newT, xs, pb, hipMemcpyDeviceToDevice, ctx->stream));
-    PL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->nranks > 1) PL_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (one rank: everything that follows is ordered by the stream)
     PL_TRY(pl_halo(ctx, g, P.newT, 1, g.plane));
     return 0;
 }
