@@ -221,6 +221,9 @@ int  pl_stokes_mg_precision(pl_ctx* ctx, int* nlevels, int* nlevels_fp32);
 /* fp32 = 0: all levels FP64 (default); 1: the large levels in FP32.  min_nodes > 0: smallest level, in nodes of the rank's block, that
  * runs in FP32 (default 200000: smaller levels are launch-latency bound and gain nothing). */
 int  pl_stokes_set_mg_precision(pl_ctx* ctx, int fp32, long long min_nodes);
+/* Launches of the one-workgroup V-cycle tail on this context so far: *lds those of k_mg_tail_lds (levels in LDS, rows in registers),
+ * *global those of k_mg_tail (levels in global memory: several ranks, PYLAMP_MG_FUSED=0, or a tail that does not fit the LDS pool). */
+int  pl_mg_tail_launches(pl_ctx* ctx, long long* lds, long long* global);
 
 /* ---- Heat: replaces makeDiffusionMatrix (pylamp_diff.py:85-183) + spsolve
  *      (pylamp2.py:419) --------------------------------------------------------------- */

@@ -163,6 +163,7 @@ SIGNATURES = {
     "pl_stokes_mg_precision": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "pl_stokes_set_mg_precision": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),
     "pl_stokes_sweep_bench": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "pl_mg_tail_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "pl_heat_set_coeffs": (C.c_int, [C.c_void_p] + [c_double_p] * 8 + [c_int_p, c_double_p, C.c_double]),
     "pl_heat_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),

@@ -1606,6 +1606,7 @@ struct PlSolver {
     double* hc[9] = {nullptr}; double* hc_part = nullptr; int hc_nb = 0, hc_last_its = 0;      // CG work planes (wall entries of d, r, z, p, q stay 0)
     int napply = 0, nprec = 0;
     long long heat_fused_launches = 0;        // k_heat_cheb_fused launches on this context so far (pl_heat_fused_launches)
+    long long tail_lds_launches = 0, tail_global_launches = 0;      // k_mg_tail_lds | k_mg_tail launches so far (pl_mg_tail_launches)
 };
 
 static PlSolver* solver_of(pl_ctx* ctx) {
@@ -2309,6 +2310,7 @@ template <typename T> static void vcycle(pl_ctx* ctx, PlSolver* S, size_t l, con
                                          double final_scale, int f_valid_depth, const int* first_done_anchor);
 static bool mg_fused_level_ok(pl_ctx* ctx, const PlSolver* S, size_t l);
 static bool mg_tail_lds_fits(const PlSolver* S, size_t l);
+static bool mg_tail_cheb_fits(int nlev, int nu_pre, int nu_post, int coarse_sweeps);
 __global__ void k_mg_tail_lds(TailArgs a);
 static void vcycle_fused_level(pl_ctx* ctx, PlSolver* S, size_t l, const double* f, double** out, double* final_out, double final_scale,
                                const PlStokesOp* sop, const double* rs, double* z);
@@ -2372,10 +2374,14 @@ static void vcycle(pl_ctx* ctx, PlSolver* S, size_t l, const T* f, T** out, bool
                 for (int b = 0; b < 3; b++) ta.L[q].v[b] = T_->v[b];
             }
             // one rank: the LDS-resident twin (levels kept in LDS, the tile kernels' node functions) where its pool holds the levels
-            if (S->fused && !L->dist && !L->op.szz && ta.nu_pre >= 1 && ta.nu_post >= 1 && ta.coarse_sweeps >= 1 && mg_tail_lds_fits(S, l))
+            if (S->fused && !L->dist && !L->op.szz && ta.nu_pre >= 1 && ta.nu_post >= 1 && ta.coarse_sweeps >= 1 && mg_tail_lds_fits(S, l) &&
+                mg_tail_cheb_fits(ta.nlev, ta.nu_pre, ta.nu_post, ta.coarse_sweeps)) {
                 hipLaunchKernelGGL(k_mg_tail_lds, dim3(1), dim3(1024), 0, ctx->stream, ta);
-            else
+                S->tail_lds_launches++;
+            } else {
                 hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(1024), 0, ctx->stream, ta);
+                S->tail_global_launches++;
+            }
             *out = L->v[0];
             return;
         }
@@ -2460,6 +2466,9 @@ static void vcycle(pl_ctx* ctx, PlSolver* S, size_t l, const T* f, T** out, bool
 // Row classes (wall, slaved, interior) are decided per node from the global index exactly as the one-kernel-per-stage path does,
 // and a slaved node evaluates its master's update -- so both paths compute the same numbers
 // (tests/test_hip_solve.py::test_fused_levels_match_the_staged_path).
+// The one-workgroup tail (k_mg_tail_lds, below the tile kernels) keeps its rows in registers with the same helpers -- mgt_classify,
+// mgt_coefficients, mgt_av_z / mgt_av_x, mgt_cheb -- on a region that is one whole level, so the three paths (staged, tile, tail)
+// evaluate the same expressions in the same order.
 // Requirements (vcycle_fused_ok): one rank, FP64 level, no stabilisation terms, 1 <= sweeps <= 3; otherwise the staged path runs.
 // =========================================================================================
 #define MGT_TS 16
@@ -2498,80 +2507,6 @@ __device__ inline int mgt_cls_x(const PlVvOp& op, int i, int j, int& da, double&
     if (i == op.g.nz - 2 && op.slave_zL) { da = -1; s = op.sL; return VV_SLAVE; }
     return VV_INT;
 }
-// (A_vv v)_z, (A_vv v)_x and -diagonal at region node (a, b) = LDS index c (row pitch CR): vv_row_z / vv_row_x on LDS arrays.
-// The tables are stored shifted by one: rdz[a + 1] belongs to region row a.
-template <bool NEED_A>
-__device__ inline void mgt_row_z(const MgtTab& t, const int CR, const double* vz, const double* vx, int c, int a, int b, double& Av, double& dg) {
-    const double rdz_i = t.rdz[a + 1], rdz_m = t.rdz[a], rDz_i = t.rDz[a + 1];
-    const double rdx_j = t.rdx[b + 1], rDx_j = t.rDx[b + 1], rDx_p = t.rDx[b + 2];
-    const double esC = t.es[c], esE = t.es[c + 1];
-    const double cN = 4.0 * t.en[c] * rdz_i * rDz_i, cS = 4.0 * t.en[c - CR] * rdz_m * rDz_i;
-    const double cE = 2.0 * esE * rDx_p * rdx_j, cW = 2.0 * esC * rDx_j * rdx_j;
-    dg = cN + cS + cE + cW;
-    if (NEED_A) {
-        const double xE = 2.0 * esE * rDz_i * rdx_j, xW = 2.0 * esC * rDz_i * rdx_j;
-        const double v0 = vz[c];
-        Av = cN * (vz[c + CR] - v0) - cS * (v0 - vz[c - CR]) + cE * (vz[c + 1] - v0) - cW * (v0 - vz[c - 1]) +
-             xE * (vx[c + 1] - vx[c - CR + 1]) - xW * (vx[c] - vx[c - CR]);
-    }
-}
-template <bool NEED_A>
-__device__ inline void mgt_row_x(const MgtTab& t, const int CR, const double* vz, const double* vx, int c, int a, int b, double& Av, double& dg) {
-    const double rdx_j = t.rdx[b + 1], rdx_m = t.rdx[b], rDx_j = t.rDx[b + 1];
-    const double rdz_i = t.rdz[a + 1], rDz_i = t.rDz[a + 1], rDz_p = t.rDz[a + 2];
-    const double esC = t.es[c], esN = t.es[c + CR];
-    const double cE = 4.0 * t.en[c] * rdx_j * rDx_j, cW = 4.0 * t.en[c - 1] * rdx_m * rDx_j;
-    const double cN = 2.0 * esN * rDz_p * rdz_i, cS = 2.0 * esC * rDz_i * rdz_i;
-    dg = cE + cW + cN + cS;
-    if (NEED_A) {
-        const double zN = 2.0 * esN * rDx_j * rdz_i, zS = 2.0 * esC * rDx_j * rdz_i;
-        const double v0 = vx[c];
-        Av = cE * (vx[c + 1] - v0) - cW * (v0 - vx[c - 1]) + cN * (vx[c + CR] - v0) - cS * (v0 - vx[c - CR]) +
-             zN * (vz[c + CR] - vz[c + CR - 1]) - zS * (vz[c] - vz[c - 1]);
-    }
-}
-
-// everything the stages of one tile share
-struct MgtTile {
-    int ci0, cj0;                      // global node of region element (0, 0)
-    int CR, NR;                        // row pitch (= columns) and rows of the region
-    MgtTab t;
-    // first sweep from the zero guess (cheb_first_node): v1 = -c2 f / diag, slaves copy s x their master's value
-    __device__ inline void first(const PlVvOp& op, const double* fz, const double* fx, double* oz, double* ox, double c2, int a, int b) const {
-        const int i = ci0 + a, j = cj0 + b, c = a * CR + b;
-        int d; double s, Av, dg;
-        double o = 0.0;
-        int cls = mgt_cls_z(op, i, j, d, s);
-        if (cls != VV_ZERO && b + d >= 1 && b + d <= CR - 2) { mgt_row_z<false>(t, CR, nullptr, nullptr, c + d, a, b + d, Av, dg); o = (-s * c2 * fz[c + d]) * pl_rcp(dg); }
-        oz[c] = o;
-        o = 0.0;
-        cls = mgt_cls_x(op, i, j, d, s);
-        if (cls != VV_ZERO && a + d >= 1 && a + d <= NR - 2) { mgt_row_x<false>(t, CR, nullptr, nullptr, c + d * CR, a + d, b, Av, dg); o = (-s * c2 * fx[c + d * CR]) * pl_rcp(dg); }
-        ox[c] = o;
-    }
-    // one Chebyshev sweep (cheb_node); pz == nullptr: the previous iterate is zero
-    __device__ inline void cheb(const PlVvOp& op, const double* vz, const double* vx, const double* pz, const double* px, const double* fz,
-                                const double* fx, double c1, double c2, int a, int b, double& oz, double& ox) const {
-        const int i = ci0 + a, j = cj0 + b, c = a * CR + b;
-        int d; double s, Av, dg;
-        oz = 0.0; ox = 0.0;
-        int cls = mgt_cls_z(op, i, j, d, s);
-        if (cls != VV_ZERO && b + d >= 1 && b + d <= CR - 2) {
-            const int cm = c + d;
-            mgt_row_z<true>(t, CR, vz, vx, cm, a, b + d, Av, dg);
-            const double v0 = vz[cm], mom = (c1 != 0.0) ? c1 * (v0 - (pz ? pz[cm] : 0.0)) : 0.0;
-            oz = s * (v0 + mom + (c2 * (Av - fz[cm])) * pl_rcp(dg));
-        }
-        cls = mgt_cls_x(op, i, j, d, s);
-        if (cls != VV_ZERO && a + d >= 1 && a + d <= NR - 2) {
-            const int cm = c + d * CR;
-            mgt_row_x<true>(t, CR, vz, vx, cm, a + d, b, Av, dg);
-            const double v0 = vx[cm], mom = (c1 != 0.0) ? c1 * (v0 - (px ? px[cm] : 0.0)) : 0.0;
-            ox = s * (v0 + mom + (c2 * (Av - fx[cm])) * pl_rcp(dg));
-        }
-    }
-};
-
 // the tables of the region: value of table tab (indexed by global node + PL_TOFF, defined for -PL_TOFF .. n + PL_TOFF) at region rows / columns -1 .. CR + 1
 __device__ inline void mgt_load_table(double* dst, const double* tab, int first_global, int count, int n) {
     for (int k = threadIdx.x; k < count; k += blockDim.x) {
@@ -2584,7 +2519,7 @@ __device__ inline void mgt_load_table(double* dst, const double* tab, int first_
 // it evaluates (its own, or its master's if it is a slaved node), 1 / diagonal and the right-hand side there.  The stages were
 // VALU-bound -- ~150 instructions per node and stage, two thirds of them recomputing these from the viscosity planes and spacing
 // tables in LDS (the level-1 visit took as long as the nine separate launches it replaces) -- now a sweep is 18 LDS reads and ~45 flops.
-// z: c0..c3 = cN cS cE cW, x0 x1 = xE xW;  x: c0..c3 = cE cW cN cS, x0 x1 = zN zS  (mgt_row_z / mgt_row_x: same expressions, same order).
+// z: c0..c3 = cN cS cE cW, x0 x1 = xE xW;  x: c0..c3 = cE cW cN cS, x0 x1 = zN zS  (vv_row_z / vv_row_x: same expressions, same order; the tables are stored shifted by one: rdz[a + 1] belongs to region row a).
 struct MgtC { double c0, c1, c2, c3, x0, x1, rdg, s, f; int cm, d; bool on, interior; };
 // first half (integers only, before anything is in LDS): which row the node evaluates -- so that the right-hand side there can be
 // requested together with the region's viscosities
@@ -2925,191 +2860,342 @@ __global__ __launch_bounds__(mgt_nt(mgt_post_nn(NS, TS))) void k_mg_post(MgTileA
 }
 
 // ---- LDS-resident coarse tail -----------------------------------------------------------------------------------------
-// The V-cycle of all levels <= 33^2 in ONE workgroup, like k_mg_tail -- but every level lives in LDS for the whole kernel (three
-// rotating iterates, right-hand side, viscosities, spacing tables; 147 KB for 33^2 + 17^2 + 9^2 + 5^2) and the stages are the tile
-// kernels' node functions on named __shared__ arrays.  k_mg_tail's 44 stages cost 2.3 us each whatever the level size (101 us per
-// preconditioner application, 17 % of it): generic node functions through flat pointers into global memory.  Same arithmetic, same
-// stage order: the result equals k_mg_tail's to rounding (test_fused_levels_match_the_staged_path runs both).
-#define MGT_TAIL_POOL 18600          // doubles
+// The V-cycle of all levels <= 33^2 in ONE workgroup, like k_mg_tail -- but every level lives in LDS for the whole kernel, and every
+// thread keeps in REGISTERS what the rows it evaluates need through all the stages, exactly as the tile kernels above do (MgtC:
+// couplings, 1 / diagonal, slave scale, right-hand side; the row's previous iterate for the Chebyshev momentum term).  The region is
+// one whole level: ci0 = cj0 = -1, CR = nx + 2.
+//   Thread-to-node map, fixed in the prologue (no division inside a stage): the first tail level has at most 1024 equation nodes
+//   ((nz - 1)(nx - 1) <= 32^2 follows from nz nx <= 33^2) and gets one node per thread ("rows A"); every coarser level gets a range
+//   of threads of its own that begins at a wave ("rows B"; 17^2: waves 0-3, 9^2: wave 4, 5^2: wave 5).  No thread holds rows of
+//   more than two levels: 2 x 2 x 9 doubles of coefficients + 4 carried iterates, under the 128 VGPRs that 1024 threads leave.
+//   LDS per level: two iterates (the residual goes into the free one), and the viscosity planes and spacing tables that pass
+//   through once, for mgt_coefficients.  The restriction computes the coarse right-hand side straight into its owner's register.
+// History: k_mg_tail's 44 stages cost 2.3 us each whatever the level size (101 us per preconditioner application): generic node
+// functions through flat pointers into global memory.  With the levels in LDS but the generic node functions (viscosities, tables,
+// six couplings, diagonal, reciprocal, row class and i, j from idx again for every node, component and stage: ~1700 static VALU
+// instructions, 36 v_div_scale_f64) 65.6 us.  Rows in registers 36.2 us (2049^2 benchmark, 33^2 + 17^2 + 9^2 + 5^2, V(3,3), 12
+// coarse sweeps); every global load of the prologue issued before the first wait, and a sweep's Chebyshev coefficients read from a
+// table before the barrier that precedes it, 30.9 us.  Same arithmetic, same stage order in all three: the result equals
+// k_mg_tail's to rounding (test_fused_levels_match_the_staged_path and tests/test_hip_mg_tail.py run both) and the earlier LDS
+// kernel's bit for bit.
+#define MGT_TAIL_POOL 18600          // doubles: the budget mg_tail_lds_fits decides by (ten planes per level, as the kernel once kept)
+#define MGT_TAIL_CHEB 256            // pairs of Chebyshev coefficients the kernel keeps: (levels - 1) x max(nu_pre, nu_post) + coarse sweeps
+#define MGT_TAIL_LDS 11520           // doubles the kernel itself declares: six planes per level + tables (0.6 x budget + 0.4 x tables)
 // A level's arrays are addressed as pool + offset (never through stored pointers: those would be flat accesses, not ds_read).
 struct TailLvl { int base, NR, CR, N; };
 #define TL_V(D, buf, c) (pool + (D).base + (2 * (buf) + (c)) * (D).N)
-#define TL_F(D, c) (pool + (D).base + (6 + (c)) * (D).N)
-#define TL_ES(D) (pool + (D).base + 8 * (D).N)
-#define TL_EN(D) (pool + (D).base + 9 * (D).N)
-#define TL_TAB(D, k) (pool + (D).base + 10 * (D).N + ((k) < 2 ? (k) * ((D).NR + 3) : 2 * ((D).NR + 3) + ((k) - 2) * ((D).CR + 3)))
-// nodes that carry an equation or a slave value: i <= nz - 2 and j <= nx - 2 (the last row and column are zero rows of both
-// components and stay at the pool's zero) -- 32 x 32 = one pass of the 1024 threads on the 33^2 level
-#define TL_FOR_NODES(g)                                                                                                     \
-    for (int idx = threadIdx.x, nxm_ = (g).nx - 1, pw_ = (nxm_ & (nxm_ - 1)) == 0, sh_ = 31 - __clz(nxm_), i, j;            \
-         idx < ((g).nz - 1) * nxm_ && (i = pw_ ? idx >> sh_ : idx / nxm_, j = idx - i * nxm_, true); idx += MGT_NT)
-__device__ inline MgtTile mgt_tail_tile(double* pool, const TailLvl& D) {
-    MgtTile T; T.ci0 = -1; T.cj0 = -1; T.CR = D.CR; T.NR = D.NR;
-    T.t.es = TL_ES(D); T.t.en = TL_EN(D); T.t.rdz = TL_TAB(D, 0); T.t.rDz = TL_TAB(D, 1); T.t.rdx = TL_TAB(D, 2); T.t.rDx = TL_TAB(D, 3);
-    return T;
+#define TL_ES(D) (pool + (D).base + 4 * (D).N)
+#define TL_EN(D) (pool + (D).base + 5 * (D).N)
+#define TL_TAB(D, k) (pool + (D).base + 6 * (D).N + ((k) < 2 ? (k) * ((D).NR + 3) : 2 * ((D).NR + 3) + ((k) - 2) * ((D).CR + 3)))
+__host__ __device__ inline TailLvl mgt_tail_lvl(const PlGeom& g, int base) {
+    TailLvl D; D.base = base; D.NR = g.nz + 2; D.CR = g.nx + 2; D.N = D.NR * D.CR;
+    return D;
 }
-__device__ inline void mgt_tail_smooth(double* pool, const TailLevel& L, const TailLvl& D, int& cur, int& prv, int& nxt, int nsweep, double ratio, bool zero_guess) {
-    const double lmax = L.lmax, lmin = lmax / ratio;
+__host__ __device__ inline int mgt_tail_lvl_size(const TailLvl& D) { return 6 * D.N + 2 * (D.NR + 3) + 2 * (D.CR + 3); }
+// What a thread keeps for its node of one level.  Nodes that carry an equation or a slave value: i <= nz - 2 and j <= nx - 2 (the
+// last row and column are zero rows of both components and stay at the pool's zero); node q of them is (q / (nx - 1), q % (nx - 1)).
+struct MgtTailRows {
+    MgtC kz, kx; int ij, o;                         // ij: the node, i << 16 | j (one register); o: its LDS index
+    __device__ inline int i() const { return ij >> 16; }
+    __device__ inline int j() const { return ij & 0xffff; }
+};
+// the row a node evaluates lies d nodes beside it (a slaved node: its master's): kz.cm = o + d, kx.cm = o + d CR
+__device__ inline int mgt_tail_dz(const MgtTailRows& R) { return R.kz.cm - R.o; }
+__device__ inline int mgt_tail_dx(const MgtTailRows& R) { const int t = R.kx.cm - R.o; return (t > 0) - (t < 0); }
+// a wave-uniform double, kept in scalar registers (same bits)
+__device__ inline double mgt_uniform(double x) {
+    const long long b = __double_as_longlong(x);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ inline void mgt_tail_rows(MgtTailRows& R, const PlVvOp& op, const TailLvl& D, int q) {
+    const int nxm = op.g.nx - 1;
+    const int i = q / nxm, j = q - i * nxm;
+    R.ij = i << 16 | j; R.o = (i + 1) * D.CR + (j + 1);
+    R.kz = mgt_classify<true>(op, D.CR, D.NR, -1, -1, i + 1, j + 1);
+    R.kx = mgt_classify<false>(op, D.CR, D.NR, -1, -1, i + 1, j + 1);
+    // the slave scale as mgt_cls_x sets it, but selected from the two values, not loaded from a selected address: a load per lane from
+    // the kernel's arguments would be a round trip to memory in the prologue's way
+    const double s0 = op.s0, sL = op.sL;
+    R.kx.s = R.kx.d > 0 ? s0 : (R.kx.d < 0 ? sL : 1.0);
+}
+__device__ inline void mgt_tail_coefficients(double* pool, const TailLvl& D, MgtTailRows& R) {
+    MgtTab t; t.es = TL_ES(D); t.en = TL_EN(D); t.rdz = TL_TAB(D, 0); t.rDz = TL_TAB(D, 1); t.rdx = TL_TAB(D, 2); t.rDx = TL_TAB(D, 3);
+    mgt_coefficients<true>(R.kz, t, D.CR); mgt_coefficients<false>(R.kx, t, D.CR);
+}
+// Chebyshev coefficients (c1, c2 pairs) of n sweeps on [lmax / ratio, lmax]: the recurrence of cheb_coeffs, evaluated on the device
+// as k_mg_tail does -- but once per launch by one lane per level while the loads are on their way, not by every thread in every
+// sweep (two dependent FP64 divisions per sweep, four more per sequence: a sixth of what a stage has left to do otherwise).
+__device__ inline void mgt_tail_cheb_coeffs(double* ch, double lmax, double ratio, int n) {
+    const double lmin = lmax / ratio;
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
     double rho_old = 1.0 / sigma;
-    const MgtTile T = mgt_tail_tile(pool, D);
-    for (int k = 0; k < nsweep; k++) {
+    for (int k = 0; k < n; k++) {
         double c1, c2;
         if (k == 0) { c1 = 0.0; c2 = 1.0 / theta; }
         else { const double rho = 1.0 / (2.0 * sigma - rho_old); c1 = rho * rho_old; c2 = 2.0 * rho / delta; rho_old = rho; }
-        double* const nz_ = TL_V(D, nxt, 0); double* const nx_ = TL_V(D, nxt, 1);
-        const double* const cz = TL_V(D, cur, 0); const double* const cx = TL_V(D, cur, 1);
-        const bool noprev = k == 1 && zero_guess;
-        const double* const pz = noprev ? nullptr : TL_V(D, prv, 0); const double* const px = noprev ? nullptr : TL_V(D, prv, 1);
-        TL_FOR_NODES(L.op.g) {
-            const int ra = i + 1, rb = j + 1;
-            if (k == 0 && zero_guess) T.first(L.op, TL_F(D, 0), TL_F(D, 1), nz_, nx_, c2, ra, rb);
-            else {
-                double oz, ox;
-                T.cheb(L.op, cz, cx, pz, px, TL_F(D, 0), TL_F(D, 1), c1, c2, ra, rb, oz, ox);
-                nz_[ra * D.CR + rb] = oz; nx_[ra * D.CR + rb] = ox;
-            }
-        }
-        __syncthreads();
-        const int o = prv; prv = cur; cur = nxt; nxt = o;
+        ch[2 * k] = c1; ch[2 * k + 1] = c2;
     }
+}
+// nsweep Chebyshev sweeps of one level with the coefficients ch; `mine`: this thread's R are rows of that level.
+// zero_guess: the first sweep is -c2 f / diag (cheb_first_node) and the second has no previous iterate (pvz = pvx = 0).  The rows'
+// previous iterates live only through one sequence: its first sweep never reads them (zero guess, or c1 = 0).
+__device__ inline void mgt_tail_smooth(double* pool, const double* ch, const TailLvl& D, MgtTailRows& R, bool mine, int& cur, int nsweep, bool zero_guess) {
+    double pvz = 0.0, pvx = 0.0;
+    double c1 = mgt_uniform(ch[0]), c2 = mgt_uniform(ch[1]);
+    for (int k = 0; k < nsweep; k++) {
+        if (mine) {
+            double oz, ox;
+            if (k == 0 && zero_guess) {
+                oz = R.kz.on ? (-R.kz.s * c2 * R.kz.f) * R.kz.rdg : 0.0;
+                ox = R.kx.on ? (-R.kx.s * c2 * R.kx.f) * R.kx.rdg : 0.0;
+            } else {
+                mgt_cheb(R.kz, R.kx, D.CR, TL_V(D, cur, 0), TL_V(D, cur, 1), pvz, pvx, c1, c2, oz, ox);
+            }
+            TL_V(D, cur ^ 1, 0)[R.o] = oz; TL_V(D, cur ^ 1, 1)[R.o] = ox;
+        }
+        double n1 = 0.0, n2 = 0.0;                  // the next sweep's coefficients: their read waits with the barrier, not after it
+        if (k + 1 < nsweep) { n1 = ch[2 * k + 2]; n2 = ch[2 * k + 3]; }
+        __syncthreads();
+        c1 = mgt_uniform(n1); c2 = mgt_uniform(n2);
+        cur ^= 1;
+    }
+}
+// residual on the interior rows (0 elsewhere) into the free buffer
+__device__ inline void mgt_tail_residual(double* pool, const TailLvl& D, const MgtTailRows& R, bool mine, int cur) {
+    if (mine) {
+        double v0, rz = 0.0, rx = 0.0;
+        if (R.kz.interior) rz = R.kz.f - mgt_av_z(R.kz, D.CR, TL_V(D, cur, 0), TL_V(D, cur, 1), v0);
+        if (R.kx.interior) rx = R.kx.f - mgt_av_x(R.kx, D.CR, TL_V(D, cur, 0), TL_V(D, cur, 1), v0);
+        TL_V(D, cur ^ 1, 0)[R.o] = rz; TL_V(D, cur ^ 1, 1)[R.o] = rx;
+    }
+    __syncthreads();
+}
+// prolongation + correction (prolong_node) into the free buffer: s (v[master] + P e at the master)
+__device__ inline void mgt_tail_prolong(double* pool, const TailLvl& D, const TailLvl& Dc, const PlGeom& gc, const MgtTailRows& R, bool mine, int cur,
+                                        int curc) {
+    if (mine) {
+        const double* const ez = TL_V(Dc, curc, 0); const double* const ex = TL_V(Dc, curc, 1);
+        double oz = 0.0, ox = 0.0;
+        if (R.kz.on) {
+            const int i = R.i(), jm = R.j() + mgt_tail_dz(R), I0 = i >> 1, I1 = (i + 1) >> 1;
+            int Jn = jm >> 1, Jo = (jm & 1) ? Jn + 1 : Jn - 1;
+            Jn = min(max(Jn, 0), gc.nx - 2); Jo = min(max(Jo, 0), gc.nx - 2);
+            const double pa = 0.5 * (ez[(I0 + 1) * Dc.CR + Jn + 1] + ez[(I1 + 1) * Dc.CR + Jn + 1]);
+            const double pb = 0.5 * (ez[(I0 + 1) * Dc.CR + Jo + 1] + ez[(I1 + 1) * Dc.CR + Jo + 1]);
+            oz = R.kz.s * (TL_V(D, cur, 0)[R.kz.cm] + (0.75 * pa + 0.25 * pb));
+        }
+        if (R.kx.on) {
+            const int im = R.i() + mgt_tail_dx(R), j = R.j(), J0 = j >> 1, J1 = (j + 1) >> 1;
+            int In = im >> 1, Io = (im & 1) ? In + 1 : In - 1;
+            In = min(max(In, 0), gc.nz - 2); Io = min(max(Io, 0), gc.nz - 2);
+            const double pa = 0.5 * (ex[(In + 1) * Dc.CR + J0 + 1] + ex[(In + 1) * Dc.CR + J1 + 1]);
+            const double pb = 0.5 * (ex[(Io + 1) * Dc.CR + J0 + 1] + ex[(Io + 1) * Dc.CR + J1 + 1]);
+            ox = R.kx.s * (TL_V(D, cur, 1)[R.kx.cm] + (0.75 * pa + 0.25 * pb));
+        }
+        TL_V(D, cur ^ 1, 0)[R.o] = oz; TL_V(D, cur ^ 1, 1)[R.o] = ox;
+    }
+    __syncthreads();
 }
 __global__ __launch_bounds__(MGT_NT) void k_mg_tail_lds(TailArgs a) {
-    __shared__ double pool[MGT_TAIL_POOL];
-    __shared__ TailLvl lv[PL_TAIL_MAX_LEVELS];
-    __shared__ int rot[PL_TAIL_MAX_LEVELS];          // which buffer holds a level's iterate after the way down
+    __shared__ double pool[MGT_TAIL_LDS];
+    __shared__ double chb[2 * MGT_TAIL_CHEB];       // (c1, c2) of the sweeps: level l < nlev - 1 from pair l ksm on, the coarsest after them
     const int tid = threadIdx.x;
-    for (int k = tid; k < MGT_TAIL_POOL; k += MGT_NT) pool[k] = 0.0;          // rings, last row / column and unused corners read as zero
-    if (tid == 0) {
-        int q = 0;
-        for (int l = 0; l < a.nlev; l++) {
-            const PlGeom& g = a.L[l].op.g;
-            TailLvl D; D.base = q; D.NR = g.nz + 2; D.CR = g.nx + 2; D.N = D.NR * D.CR;
-            q += 10 * D.N + 2 * (D.NR + 3) + 2 * (D.CR + 3);
-            lv[l] = D;
-        }
+    const int nlev = a.nlev, ksm = max(a.nu_pre, a.nu_post);
+    const TailLevel& L0 = a.L[0]; const PlGeom& g0 = L0.op.g; const TailLvl D0 = mgt_tail_lvl(g0, 0);
+    // ---- the thread's rows and the global loads: right-hand side of the first level, viscosities of all of them.
+    // Rows A: node tid of the first level.
+    MgtTailRows A, B = {};
+    B.kz.s = 1.0;                                   // (as mgt_classify<true> leaves it for every node: a constant, not a register)
+    const bool haveA = tid < (g0.nz - 1) * (g0.nx - 1);
+    mgt_tail_rows(A, L0.op, D0, haveA ? tid : 0);
+    if (haveA) {
+        const long long c = pl_idx(g0, A.i() - g0.gi0, A.j() - g0.gj0);
+        if (A.kz.on) A.kz.f = L0.f[c + A.kz.d];
+        if (A.kx.on) A.kx.f = L0.f[c + (long long)A.kx.d * g0.pitch + g0.plane];
     }
-    __syncthreads();
-    // ---- load: viscosities and tables of every level, right-hand side of the first
-    for (int l = 0; l < a.nlev; l++) {
-        const TailLevel& L = a.L[l]; const PlGeom& g = L.op.g; const TailLvl D = lv[l];
-        for (int idx = tid; idx < g.nz * g.nx; idx += MGT_NT) {
-            const int i = idx / g.nx, j = idx - i * g.nx;
-            const long long c = pl_idx(g, i - g.gi0, j - g.gj0);
-            const int o = (i + 1) * D.CR + (j + 1);
-            TL_ES(D)[o] = L.op.etas[c]; TL_EN(D)[o] = L.op.etan[c];
-            if (l == 0) { TL_F(D, 0)[o] = L.f[c]; TL_F(D, 1)[o] = L.f[c + g.plane]; }
-        }
-        mgt_load_table(TL_TAB(D, 0), L.op.rdz, -2, D.NR + 3, g.nz); mgt_load_table(TL_TAB(D, 1), L.op.rDz, -2, D.NR + 3, g.nz);
-        mgt_load_table(TL_TAB(D, 2), L.op.rdx, -2, D.CR + 3, g.nx); mgt_load_table(TL_TAB(D, 3), L.op.rDx, -2, D.CR + 3, g.nx);
+    double e0[2][2]; int e0o[2];                    // viscosities of the first level: nodes tid and tid + MGT_NT (nz nx <= 2 MGT_NT)
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int idx = tid + q * MGT_NT;
+        const bool ok = idx < g0.nz * g0.nx;
+        const int i = ok ? idx / g0.nx : 0, j = ok ? idx - i * g0.nx : 0;
+        const long long c = pl_idx(g0, i - g0.gi0, j - g0.gj0);
+        e0[q][0] = L0.op.etas[c]; e0[q][1] = L0.op.etan[c];
+        e0o[q] = ok ? (i + 1) * D0.CR + (j + 1) : -1;
     }
-    __syncthreads();
-    // ---- down
-    for (int l = 0; l < a.nlev; l++) {
-        const TailLevel& L = a.L[l]; const PlGeom& g = L.op.g; const TailLvl D = lv[l];
-        int cur = 0, prv = 1, nxt = 2;
-        if (l == a.nlev - 1) {
-            double ratio = 0.4 * g.nz * g.nx; if (ratio < 30.0) ratio = 30.0;
-            mgt_tail_smooth(pool, L, D, cur, prv, nxt, a.coarse_sweeps, ratio, true);
-            if (tid == 0) rot[l] = cur | (prv << 2) | (nxt << 4);
-            break;
-        }
-        mgt_tail_smooth(pool, L, D, cur, prv, nxt, a.nu_pre, a.ratio, true);
-        if (tid == 0) rot[l] = cur | (prv << 2) | (nxt << 4);
-        // residual on the interior rows (0 elsewhere) into the free buffer
-        const MgtTile T = mgt_tail_tile(pool, D);
-        double* const rz = TL_V(D, nxt, 0); double* const rx = TL_V(D, nxt, 1);
-        const double* const cz = TL_V(D, cur, 0); const double* const cx = TL_V(D, cur, 1);
-        TL_FOR_NODES(g) {
-            const int ra = i + 1, rb = j + 1, o = ra * D.CR + rb;
-            int d; double s, Av, dg, vz = 0.0, vx = 0.0;
-            if (mgt_cls_z(L.op, i, j, d, s) == VV_INT) { mgt_row_z<true>(T.t, D.CR, cz, cx, o, ra, rb, Av, dg); vz = TL_F(D, 0)[o] - Av; }
-            if (mgt_cls_x(L.op, i, j, d, s) == VV_INT) { mgt_row_x<true>(T.t, D.CR, cz, cx, o, ra, rb, Av, dg); vx = TL_F(D, 1)[o] - Av; }
-            rz[o] = vz; rx[o] = vx;
-        }
-        __syncthreads();
-        // restriction onto the next level's right-hand side (restrict_node)
-        const TailLevel& Cn = a.L[l + 1]; const TailLvl Dc = lv[l + 1];
-        double* const fz = TL_F(Dc, 0); double* const fx = TL_F(Dc, 1);
-        TL_FOR_NODES(Cn.op.g) {
-            const int b0 = (2 * i + 1) * D.CR + (2 * j + 1);
-            int d; double s, oz = 0.0, ox = 0.0;
-            if (vv_cls_z(Cn.op, i, j, d, s) == VV_INT) {
-                const double wz[3] = {0.25, 0.5, 0.25}, wx[4] = {0.125, 0.375, 0.375, 0.125};
-#pragma unroll
-                for (int u = 0; u < 3; u++)
-#pragma unroll
-                    for (int w = 0; w < 4; w++) oz += wz[u] * wx[w] * rz[b0 + (u - 1) * D.CR + (w - 1)];
-            }
-            if (vv_cls_x(Cn.op, i, j, d, s) == VV_INT) {
-                const double wz[4] = {0.125, 0.375, 0.375, 0.125}, wx[3] = {0.25, 0.5, 0.25};
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-#pragma unroll
-                    for (int w = 0; w < 3; w++) ox += wz[u] * wx[w] * rx[b0 + (u - 1) * D.CR + (w - 1)];
-            }
-            const int oc = (i + 1) * Dc.CR + (j + 1);
-            fz[oc] = oz; fx[oc] = ox;
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    // ---- up
-    for (int l = a.nlev - 2; l >= 0; l--) {
-        const TailLevel& L = a.L[l]; const PlGeom& g = L.op.g; const TailLvl D = lv[l];
-        const PlGeom& gc = a.L[l + 1].op.g; const TailLvl Dc = lv[l + 1];
-        int cur = rot[l] & 3, prv = (rot[l] >> 2) & 3, nxt = (rot[l] >> 4) & 3;
-        const int curc = rot[l + 1] & 3;
-        const double* const ez = TL_V(Dc, curc, 0); const double* const ex = TL_V(Dc, curc, 1);
-        const double* const cz = TL_V(D, cur, 0); const double* const cx = TL_V(D, cur, 1);
-        double* const wz_ = TL_V(D, nxt, 0); double* const wx_ = TL_V(D, nxt, 1);
-        TL_FOR_NODES(g) {          // prolongation + correction (prolong_node) into the free buffer
-            const int o = (i + 1) * D.CR + (j + 1);
-            int d; double s, oz = 0.0, ox = 0.0;
-            if (mgt_cls_z(L.op, i, j, d, s) != VV_ZERO) {
-                const int jm = j + d, I0 = i >> 1, I1 = (i + 1) >> 1;
-                int Jn = jm >> 1, Jo = (jm & 1) ? Jn + 1 : Jn - 1;
-                Jn = min(max(Jn, 0), gc.nx - 2); Jo = min(max(Jo, 0), gc.nx - 2);
-                const double pa = 0.5 * (ez[(I0 + 1) * Dc.CR + Jn + 1] + ez[(I1 + 1) * Dc.CR + Jn + 1]);
-                const double pb = 0.5 * (ez[(I0 + 1) * Dc.CR + Jo + 1] + ez[(I1 + 1) * Dc.CR + Jo + 1]);
-                oz = s * (cz[o + d] + (0.75 * pa + 0.25 * pb));
-            }
-            if (mgt_cls_x(L.op, i, j, d, s) != VV_ZERO) {
-                const int im = i + d, J0 = j >> 1, J1 = (j + 1) >> 1;
-                int In = im >> 1, Io = (im & 1) ? In + 1 : In - 1;
-                In = min(max(In, 0), gc.nz - 2); Io = min(max(Io, 0), gc.nz - 2);
-                const double pa = 0.5 * (ex[(In + 1) * Dc.CR + J0 + 1] + ex[(In + 1) * Dc.CR + J1 + 1]);
-                const double pb = 0.5 * (ex[(Io + 1) * Dc.CR + J0 + 1] + ex[(Io + 1) * Dc.CR + J1 + 1]);
-                ox = s * (cx[o + d * D.CR] + (0.75 * pa + 0.25 * pb));
-            }
-            wz_[o] = oz; wx_[o] = ox;
-        }
-        __syncthreads();
-        { const int o = cur; cur = nxt; nxt = o; }
-        mgt_tail_smooth(pool, L, D, cur, prv, nxt, a.nu_post, a.ratio, false);
-        if (tid == 0) rot[l] = cur | (prv << 2) | (nxt << 4);
-        __syncthreads();
-    }
-    // ---- the first tail level's iterate goes back to memory
+    // Rows B: the coarser levels one after the other over the threads, each from a wave's first lane on.  riz / rix: the node of
+    // the row is an interior row, so the restriction gives its right-hand side (else that is 0).
+    // Their viscosities: the nodes of all coarser levels in one sequence, one per thread (mg_tail_lds_fits: there are at most MGT_NT).
+    // The loops over the levels only pick addresses; every thread then has ONE load per plane, issued with all the others -- a load
+    // inside them would be waited for level by level (a dozen round trips to memory in a row, a third of what the kernel took).
+    int lb = 0, eco = -1, ecN = 0;
+    bool riz = false, rix = false;
+    const double* pes = nullptr; const double* pen = nullptr;
     {
-        const TailLevel& L = a.L[0]; const PlGeom& g = L.op.g; const TailLvl D = lv[0];
-        const int cur = rot[0] & 3;
-        const double* const cz = TL_V(D, cur, 0); const double* const cx = TL_V(D, cur, 1);
-        for (int idx = tid; idx < g.nz * g.nx; idx += MGT_NT) {
-            const int i = idx / g.nx, j = idx - i * g.nx, o = (i + 1) * D.CR + (j + 1);
-            const long long c = pl_idx(g, i - g.gi0, j - g.gj0);
-            L.v[0][c] = cz[o]; L.v[0][c + g.plane] = cx[o];
+        int base = mgt_tail_lvl_size(D0), start = 0, vstart = 0;
+        for (int l = 1; l < nlev; l++) {
+            const PlVvOp& op = a.L[l].op; const PlGeom& g = op.g; const TailLvl D = mgt_tail_lvl(g, base);
+            const int n = (g.nz - 1) * (g.nx - 1), nv = g.nz * g.nx;
+            if (tid >= start && tid < start + n) {
+                lb = l;
+                mgt_tail_rows(B, op, D, tid - start);
+                int d; double s;
+                riz = B.kz.on && mgt_cls_z(op, B.i(), B.j() + B.kz.d, d, s) == VV_INT;
+                rix = B.kx.on && mgt_cls_x(op, B.i() + B.kx.d, B.j(), d, s) == VV_INT;
+            }
+            if (tid >= vstart && tid < vstart + nv) {
+                const int q = tid - vstart, i = q / g.nx, j = q - i * g.nx;
+                const long long c = pl_idx(g, i - g.gi0, j - g.gj0);
+                pes = op.etas + c; pen = op.etan + c;
+                eco = D.base + 4 * D.N + (i + 1) * D.CR + (j + 1); ecN = D.N;
+            }
+            start = (start + n + 63) & ~63; vstart += nv; base += mgt_tail_lvl_size(D);
+        }
+    }
+    // The spacing tables of all levels (each for the region's rows / columns -1 .. n + 1, as mgt_load_table fills them: global node
+    // -2 + k at element k, 0 beyond the table's end) in one sequence as well, one element per thread.
+    int tdst = -1;
+    const double* ptab = nullptr;
+    {
+        int base = 0, tstart = 0;
+        for (int l = 0; l < nlev; l++) {
+            const PlVvOp& op = a.L[l].op; const TailLvl D = mgt_tail_lvl(op.g, base);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const double* const tab = k == 0 ? op.rdz : k == 1 ? op.rDz : k == 2 ? op.rdx : op.rDx;
+                const int n = k < 2 ? op.g.nz : op.g.nx, count = n + 5, e = tid - tstart;
+                if (e >= 0 && e < count) { tdst = (int)(TL_TAB(D, k) - pool) + e; ptab = e < n + 2 * PL_TOFF ? tab + e : nullptr; }
+                tstart += count;
+            }
+            base += mgt_tail_lvl_size(D);
+        }
+    }
+    const double ec0 = pes ? *pes : 0.0, ec1 = pen ? *pen : 0.0, tabv = ptab ? *ptab : 0.0;
+    // ---- while the loads are on their way: the Chebyshev coefficients, level l by the first lane of wave l (pre- and post-smoothing
+    //      share a level's sequence; the coarsest level has its own ratio rule) ...
+    {
+        const int l = __builtin_amdgcn_readfirstlane(tid >> 6);
+        if (l < nlev && (tid & 63) == 0) {
+            const PlGeom& g = a.L[l].op.g;
+            double ratio = 0.4 * g.nz * g.nx; if (ratio < 30.0) ratio = 30.0;
+            if (l == nlev - 1) mgt_tail_cheb_coeffs(chb + 2 * l * ksm, a.L[l].lmax, ratio, a.coarse_sweeps);
+            else mgt_tail_cheb_coeffs(chb + 2 * l * ksm, a.L[l].lmax, a.ratio, ksm);
+        }
+    }
+    // ---- ... and zeros in the iterates: their rings, last row and column are read and never written
+    {
+        int base = 0;
+        for (int l = 0; l < nlev; l++) {
+            const TailLvl D = mgt_tail_lvl(a.L[l].op.g, base);
+            for (int k = tid; k < 4 * D.N; k += MGT_NT) pool[base + k] = 0.0;
+            base += mgt_tail_lvl_size(D);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+        if (e0o[q] >= 0) { TL_ES(D0)[e0o[q]] = e0[q][0]; TL_EN(D0)[e0o[q]] = e0[q][1]; }
+    if (eco >= 0) { pool[eco] = ec0; pool[eco + ecN] = ec1; }
+    if (tdst >= 0) pool[tdst] = tabv;
+    __syncthreads();
+    // ---- the coefficients of the rows (the viscosity planes and tables are not read again)
+    if (haveA) mgt_tail_coefficients(pool, D0, A);
+    int base = mgt_tail_lvl_size(D0);
+    for (int l = 1; l < nlev; l++) {
+        const TailLvl D = mgt_tail_lvl(a.L[l].op.g, base);
+        if (lb == l) mgt_tail_coefficients(pool, D, B);
+        base += mgt_tail_lvl_size(D);
+    }
+    // After the way down a level's iterate is in buffer `sweeps & 1`, its residual in the other one.
+    const int cur_pre = a.nu_pre & 1, cur_coarse = a.coarse_sweeps & 1, cur_post = (a.nu_pre + 1 + a.nu_post) & 1;
+    int cur = 0;
+    if (nlev == 1) {
+        mgt_tail_smooth(pool, chb, D0, A, haveA, cur, a.coarse_sweeps, true);
+    } else {
+        // ---- down.  The restriction (restrict_node) onto the next level goes into the registers of that level's threads.
+        TailLvl D = D0;
+        for (int l = 0; l < nlev; l++) {
+            const bool coarsest = l == nlev - 1, mine = l == 0 ? haveA : lb == l;
+            const double* const ch = chb + 2 * l * ksm;
+            cur = 0;
+            if (l == 0) {
+                mgt_tail_smooth(pool, ch, D, A, mine, cur, a.nu_pre, true);
+                mgt_tail_residual(pool, D, A, mine, cur);
+            } else {
+                mgt_tail_smooth(pool, ch, D, B, mine, cur, coarsest ? a.coarse_sweeps : a.nu_pre, true);
+                if (coarsest) break;
+                mgt_tail_residual(pool, D, B, mine, cur);
+            }
+            if (lb == l + 1) {
+                const double* const rz = TL_V(D, cur ^ 1, 0); const double* const rx = TL_V(D, cur ^ 1, 1);
+                const int rbz = (2 * B.i() + 1) * D.CR + 2 * (B.j() + mgt_tail_dz(B)) + 1;      // the row's node in the residual of level l
+                const int rbx = (2 * (B.i() + mgt_tail_dx(B)) + 1) * D.CR + 2 * B.j() + 1;
+                double oz = 0.0, ox = 0.0;
+                if (riz) {
+                    const double wz[3] = {0.25, 0.5, 0.25}, wx[4] = {0.125, 0.375, 0.375, 0.125};
+#pragma unroll
+                    for (int u = 0; u < 3; u++)
+#pragma unroll
+                        for (int w = 0; w < 4; w++) oz += wz[u] * wx[w] * rz[rbz + (u - 1) * D.CR + (w - 1)];
+                }
+                if (rix) {
+                    const double wz[4] = {0.125, 0.375, 0.375, 0.125}, wx[3] = {0.25, 0.5, 0.25};
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+#pragma unroll
+                        for (int w = 0; w < 3; w++) ox += wz[u] * wx[w] * rx[rbx + (u - 1) * D.CR + (w - 1)];
+                }
+                B.kz.f = oz; B.kx.f = ox;
+            }
+            __syncthreads();
+            D = mgt_tail_lvl(a.L[l + 1].op.g, D.base + mgt_tail_lvl_size(D));
+        }
+        // ---- up (D: the coarsest level)
+        for (int l = nlev - 2; l >= 0; l--) {
+            const TailLvl Dc = D;
+            D = mgt_tail_lvl(a.L[l].op.g, 0); D.base = Dc.base - mgt_tail_lvl_size(D);
+            const double* const ch = chb + 2 * l * ksm;
+            const int curc = l + 1 == nlev - 1 ? cur_coarse : cur_post;
+            cur = cur_pre;
+            if (l == 0) {
+                mgt_tail_prolong(pool, D, Dc, a.L[l + 1].op.g, A, haveA, cur, curc);
+                cur ^= 1;
+                mgt_tail_smooth(pool, ch, D, A, haveA, cur, a.nu_post, false);
+            } else {
+                mgt_tail_prolong(pool, D, Dc, a.L[l + 1].op.g, B, lb == l, cur, curc);
+                cur ^= 1;
+                mgt_tail_smooth(pool, ch, D, B, lb == l, cur, a.nu_post, false);
+            }
+        }
+    }
+    // ---- the first tail level's iterate goes back to memory (last row and column: the pool's zero)
+    {
+        const double* const cz = TL_V(D0, cur, 0); const double* const cx = TL_V(D0, cur, 1);
+        for (int idx = tid; idx < g0.nz * g0.nx; idx += MGT_NT) {
+            const int i = idx / g0.nx, j = idx - i * g0.nx, o = (i + 1) * D0.CR + (j + 1);
+            const long long c = pl_idx(g0, i - g0.gi0, j - g0.gj0);
+            L0.v[0][c] = cz[o]; L0.v[0][c + g0.plane] = cx[o];
         }
     }
 }
-// does the tail starting at level l fit into k_mg_tail_lds' pool?
+// (sweep counts far beyond any in use -- 3 + 3 and 12 by default, at most 150 on the coarsest level -- leave the tail to k_mg_tail)
+static bool mg_tail_cheb_fits(int nlev, int nu_pre, int nu_post, int coarse_sweeps) {
+    return (long long)(nlev - 1) * std::max(nu_pre, nu_post) + coarse_sweeps <= MGT_TAIL_CHEB;
+}
+// Does the tail starting at level l run in k_mg_tail_lds?  The pool rule (ten planes per level + tables within MGT_TAIL_POOL doubles)
+// decides; the conditions after it are what the kernel's thread-to-node map takes for granted -- they hold for every tail
+// the rule lets through at the default tail size (nz nx <= 33^2) and only guard a PYLAMP_MG_TAIL_NODES beyond it.
 static bool mg_tail_lds_fits(const PlSolver* S, size_t l) {
-    long long need = 0;
+    long long need = 0, lds = 0, coarse_threads = 0, coarse_nodes = 0, table_entries = 0;
     for (size_t q = l; q < S->levels.size(); q++) {
         const PlGeom& g = S->levels[q]->gh.d;
         need += 10LL * (g.nz + 2) * (g.nx + 2) + 2LL * (g.nz + 5) + 2LL * (g.nx + 5);
+        lds += mgt_tail_lvl_size(mgt_tail_lvl(g, 0)); table_entries += 2LL * (g.nz + 5) + 2LL * (g.nx + 5);
+        if (q > l) { coarse_threads = (coarse_threads + 63) / 64 * 64 + (long long)(g.nz - 1) * (g.nx - 1); coarse_nodes += (long long)g.nz * g.nx; }
     }
-    return need <= MGT_TAIL_POOL;
+    const PlGeom& g0 = S->levels[l]->gh.d;
+    return need <= MGT_TAIL_POOL && lds <= MGT_TAIL_LDS && (long long)(g0.nz - 1) * (g0.nx - 1) <= MGT_NT && (long long)g0.nz * g0.nx <= 2 * MGT_NT &&
+           coarse_threads <= MGT_NT && coarse_nodes <= MGT_NT && table_entries <= MGT_NT;
 }
 
 // Chebyshev coefficients of a sequence of n sweeps on [lmax / ratio, lmax], as smooth() computes them
@@ -4971,6 +5057,12 @@ int pl_heat_solve_device(pl_ctx* ctx, const double* b_dev, double rtol, int maxi
 extern "C" int pl_heat_fused_launches(pl_ctx* ctx, long long* n) {
     if (!n) return pl_fail(ctx, "pl_heat_fused_launches: n is NULL");
     *n = solver_of(ctx)->heat_fused_launches;
+    return 0;
+}
+
+extern "C" int pl_mg_tail_launches(pl_ctx* ctx, long long* lds, long long* global) {
+    if (!lds || !global) return pl_fail(ctx, "pl_mg_tail_launches: lds or global is NULL");
+    *lds = solver_of(ctx)->tail_lds_launches; *global = solver_of(ctx)->tail_global_launches;
     return 0;
 }
 

@@ -138,6 +138,12 @@ class StokesOperator:
         self._ctx.check(self._ctx.lib.pl_stokes_mg_info(self._ctx.handle(), C.byref(n), lm, 32))
         return n.value, [lm[k] for k in range(n.value)]
 
+    def mg_tail_launches(self):
+        """(LDS tail, global-memory tail): launches of k_mg_tail_lds and of k_mg_tail on this operator's context so far."""
+        lds = C.c_longlong(); glob = C.c_longlong()
+        self._ctx.check(self._ctx.lib.pl_mg_tail_launches(self._ctx.handle(), C.byref(lds), C.byref(glob)))
+        return lds.value, glob.value
+
     def mg_plan(self):
         """What the last preconditioner build chose: dict(smoother=[-1 point | 0 z-lines | 1 x-lines per level], nu=(pre, post),
         nu0=(pre, post) of level 0, ratio=Chebyshev ratio, wall=wall stencils of the pressure block on)."""
