@@ -474,6 +474,22 @@ int  pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int gnx, int 
  * Changing the switch while tracers are resident re-sorts them by the new rule. */
 int  pl3_mic_set_search(pl3_ctx* ctx, int on);
 int  pl3_mic_get_search(pl3_ctx* ctx, int* on);
+/* Deletion of the tracers that leave the box (pylamp2.py:563-581), opt-in per context, default off = every kernel, message and
+ * result as without it.  With deletion on, a resident tracer is OUTSIDE when, for any axis d, x_d <= 0 or x_d >= L_d, L_d = the last
+ * node coordinate of the context's grid (the comparison of the 2-D sort key; a NaN coordinate compares false and the tracer is
+ * kept).  An outside tracer is removed by the next sort of the resident tracers: pl3_tracers_upload, pl3_resident_refill,
+ * pl3_resident_rk4 / pl3_resident_advect, the re-sort of pl3_mic_set_search, the sort of pl3_resident_step, and switching deletion
+ * on (which re-sorts when tracers are resident; switching it off changes nothing).  Removal takes the position, the 13 fields and
+ * the stored velocity; the survivors keep the order the plain sort would give them alone (cell by cell, stable within a cell).
+ * The census counts survivors only and the refill of the same sort sees the counts after the removal: a cell the removal emptied
+ * counts in out[2] and its new tracers carry NaN fields.  The largest ID the refill numbers from is the largest among the
+ * survivors, reduced again in every refilling sort (-1 when no survivor has a finite ID).  All tracers may leave: count 0 is a valid
+ * state of every call.  `fence` of pl3_resident_rk4 / pl3_resident_advect keeps its meaning; with deletion on, fence == 0 may
+ * inject, and pl3_resident_step runs fence off exactly when deletion is on.  One rank only.
+ * pl3_tracers_removed: out = { tracers removed by the last sort, removed since the last pl3_tracers_upload (its own included) }. */
+int  pl3_mic_set_deletion(pl3_ctx* ctx, int on);
+int  pl3_mic_get_deletion(pl3_ctx* ctx, int* on);
+int  pl3_tracers_removed(pl3_ctx* ctx, int64_t out[2]);
 int  pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f);
 int  pl3_tracers_download(pl3_ctx* ctx, int64_t n, double* tr_x, double* tr_f);
 int  pl3_tracers_count(pl3_ctx* ctx, int64_t* n);
@@ -504,8 +520,8 @@ int  pl3_get_tracer_velocity(pl3_ctx* ctx, int64_t n, double* out);
  * what the plain sort leaves.  The arrays grow inside the sort when the new total exceeds their capacity.
  * refill: sort + refill without advection (top up a sparse initial set).  advect: pl3_resident_rk4 with the refill in its sort.
  * out = { tracers injected, cells refilled, cells that were empty, smallest count of a cell before the refill }.
- * Errors: tracdens < tracdens_min; tracdens_min > 0 with fence == 0 (a tracer outside the box would be counted in the nearest
- * cell, and the deletion the reference does instead is not built in 3-D); a context with pl3_set_comm attached. */
+ * Errors: tracdens < tracdens_min; tracdens_min > 0 with fence == 0 on a context without pl3_mic_set_deletion (a tracer outside
+ * the box would be counted in the nearest cell); a context with pl3_set_comm attached. */
 int  pl3_resident_refill(pl3_ctx* ctx, int tracdens, int tracdens_min, uint64_t seed, int it, int unique_ids, int64_t out[4]);
 int  pl3_resident_advect(pl3_ctx* ctx, const double* gz, const double* gx, const double* gy, const double* vz, const double* vx,
                          const double* vy, double tstep, int fence, int tracdens, int tracdens_min, uint64_t seed, int it,
@@ -553,6 +569,7 @@ typedef struct pl3_step_report {
     int64_t nan_rho, nan_etas; /* nodes of the scattered rho / etas that hold NaN */
     double ms_scatter, ms_stokes, ms_heat, ms_gather, ms_rk4, ms_sort;      /* device time of the stages */
     double ms_total;           /* host wall time of the call */
+    int64_t nremoved;          /* tracers the step's sort removed (pl3_mic_set_deletion; 0 without it) */
 } pl3_step_report;
 int  pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* report);
 /* A grid field of the last resident step, downloaded on demand into out (nz, nx, ny): rho, etas, etan, cp, T, H, mat, kz, kx, ky,

@@ -62,7 +62,7 @@ class Step3Report(C.Structure):
                 ("ninjected", C.c_int64), ("nrefilled", C.c_int64), ("nempty", C.c_int64), ("mincount", C.c_int64),
                 ("ntrac", C.c_int64), ("nan_rho", C.c_int64), ("nan_etas", C.c_int64),
                 ("ms_scatter", C.c_double), ("ms_stokes", C.c_double), ("ms_heat", C.c_double), ("ms_gather", C.c_double),
-                ("ms_rk4", C.c_double), ("ms_sort", C.c_double), ("ms_total", C.c_double)]
+                ("ms_rk4", C.c_double), ("ms_sort", C.c_double), ("ms_total", C.c_double), ("nremoved", C.c_int64)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/pylamp_hip.h
@@ -104,6 +104,9 @@ SIGNATURES = {
                 [C.c_double, c_double_p, c_double_p]),
     "pl3_mic_set_search": (C.c_int, [C.c_void_p, C.c_int]),
     "pl3_mic_get_search": (C.c_int, [C.c_void_p, c_int_p]),
+    "pl3_mic_set_deletion": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl3_mic_get_deletion": (C.c_int, [C.c_void_p, c_int_p]),
+    "pl3_tracers_removed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "pl3_tracers_upload": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
     "pl3_tracers_download": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
     "pl3_tracers_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -71,10 +71,25 @@ __device__ inline int m3_sort_cell_of(const M3Axis& a, double p) {
 // position of tracer t along axis a is x[a][t * xs]: xs = 1 for the resident SoA columns, 3 for a host (n,3) array
 struct M3Pos { const double* x[3]; long long xs; };
 
-template <bool SEARCH>
+// DEL (pl3_mic_set_deletion): a tracer with x_d <= 0 or x_d >= the last coordinate on any axis (NaN compares false and stays) gets
+// the key m = the number of cells, a trash bucket behind the last cell.  The bucket is counted with ONE add per wave (ballot and
+// popcount of the leaving lanes): when a whole layer leaves, tens of thousands of lanes would otherwise queue on one address.
+template <bool SEARCH, bool DEL>
 __global__ __launch_bounds__(256) void k_m3_key(long long n, M3Pos p, M3Grid s, int* __restrict__ key, int* __restrict__ count) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
+    if constexpr (DEL) {
+        bool out = false;
+#pragma unroll
+        for (int d = 0; d < 3; d++) { const double x = p.x[d][t * p.xs]; out = out || x <= 0.0 || x >= s.a[d].cl; }
+        const unsigned long long leaving = __ballot(out);
+        if (out) {
+            const int m = (s.a[0].n - 1) * (s.a[1].n - 1) * (s.a[2].n - 1);
+            key[t] = m;
+            if ((int)(threadIdx.x & 63) == __ffsll((long long)leaving) - 1) atomicAdd(&count[m], __popcll(leaving));
+            return;
+        }
+    }
     const int ci = m3_sort_cell_of<SEARCH>(s.a[0], p.x[0][t * p.xs]), cj = m3_sort_cell_of<SEARCH>(s.a[1], p.x[1][t * p.xs]),
               ck = m3_sort_cell_of<SEARCH>(s.a[2], p.x[2][t * p.xs]);
     const int c = (ci * (s.a[1].n - 1) + cj) * (s.a[2].n - 1) + ck;
@@ -215,7 +230,7 @@ __global__ __launch_bounds__(1024) void k_m3_scan_sums(int nb, int* __restrict__
 template <int NS>
 __global__ __launch_bounds__(256) void k_m3_scan_tiles(int m, const int* __restrict__ cnt, M3Need r, int nb, const int* __restrict__ bsum,
                                                        const M3Totals* __restrict__ tot, int* __restrict__ start, int* __restrict__ cursor,
-                                                       int* __restrict__ list, int* __restrict__ loff) {
+                                                       int* __restrict__ list, int* __restrict__ loff, int trash) {
     const long long base = (long long)blockIdx.x * M3_TILE + threadIdx.x * 8;
     int v[8], s[NS], o[8];
     m3_load8(m, cnt, base, v);
@@ -236,12 +251,30 @@ __global__ __launch_bounds__(256) void k_m3_scan_tiles(int m, const int* __restr
         *(int4*)(cursor + base) = a; *(int4*)(cursor + base + 4) = b;
     } else
         for (int k = 0; k < 8; k++) if (base + k < (long long)m) { start[base + k] = o[k]; cursor[base + k] = o[k]; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) start[m] = tot->v[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) { start[m] = tot->v[0]; if (trash) cursor[m] = tot->v[0]; }      // the trash bucket's slice starts behind the last cell
 }
 __global__ __launch_bounds__(256) void k_m3_place(long long n, const int* __restrict__ key, int* __restrict__ cursor, int* __restrict__ perm) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
     perm[atomicAdd(&cursor[key[t]], 1)] = (int)t;
+}
+// k_m3_place of a deleting sort: the leavers (key == trash) go behind the last cell.  They all want the same cursor, so a wave takes
+// its slots with one add and hands them out by lane rank
+__global__ __launch_bounds__(256) void k_m3_place_del(long long n, const int* __restrict__ key, int* __restrict__ cursor, int* __restrict__ perm, int trash) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int c = key[t];
+    const bool out = c == trash;
+    const unsigned long long leaving = __ballot(out);
+    if (out) {
+        const int lane = threadIdx.x & 63, lead = __ffsll((long long)leaving) - 1;
+        int base = 0;
+        if (lane == lead) base = atomicAdd(&cursor[trash], __popcll(leaving));
+        base = __shfl(base, lead, 64);
+        perm[base + __popcll(leaving & ((1ull << lane) - 1ull))] = (int)t;
+        return;
+    }
+    perm[atomicAdd(&cursor[c], 1)] = (int)t;
 }
 // the slots inside a cell were handed out in order of arrival: order every cell's slice by the previous index, which makes the
 // sort stable and its result independent of the scheduling.  cnt: the residents of every cell when its slice holds room for new tracers
@@ -297,11 +330,12 @@ __global__ __launch_bounds__(256) void k_m3_census(int m, const int* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------
 // refill of depleted cells (the extension of pylamp2.py:588-633 by one axis), fused into the sort
 // ---------------------------------------------------------------------------------------------------------------------
-// block partials of the largest tracer ID (NaN ignored)
-__global__ __launch_bounds__(256) void k_m3_max(long long n, const double* __restrict__ x, double* __restrict__ part) {
+// block partials of the largest tracer ID (NaN ignored); with key, over the survivors of this sort only (key == trash: the tracer leaves)
+__global__ __launch_bounds__(256) void k_m3_max(long long n, const double* __restrict__ x, const int* __restrict__ key, int trash, double* __restrict__ part) {
     __shared__ double sh[4];
     double m = -INFINITY;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) m = fmax(m, x[t]);
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256)
+        if (!key || key[t] != trash) m = fmax(m, x[t]);
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -600,8 +634,11 @@ struct Mic3 {
     double *x = nullptr, *f = nullptr, *v = nullptr;
     double ms[4] = {0, 0, 0, 0};         // device time of the last resident scatter / temperature gather / RK4 / sort
     // largest TR__ID of the resident tracers: reduced on the device when a refill first needs it after an upload, then kept up to
-    // date by the refill (nothing deletes tracers in 3-D; whatever does one day sets have_maxid = false)
+    // date by the refill.  With deletion on, a sort can remove the holder: a refilling sort then reduces the IDs of its survivors
+    // itself, every time, and any other sort that removed something sets have_maxid = false
     bool have_maxid = false; double maxid = 0.0;
+    bool deletion = false;                           // pl3_mic_set_deletion: every sort of the resident tracers drops those outside the box
+    long long removed_last = 0, removed_total = 0;   // by the last sort / since the last upload (pl3_tracers_removed)
     bool have_vgrid = false; M3Grid vgrid;           // the padded centre grid of the resident step: uploaded once per context
     bool search = false;                             // pl3_mic_set_search: cells by per-axis search in every marker kernel of this context
 };
@@ -717,41 +754,58 @@ static void m3_scan_sums(Pl3HostView& v, int m, const int* cnt, M3Need r, int nb
 // counting sort by cell of the node set s: perm (sorted slot -> previous index) and start (ncell + 1).  With rf the cells that hold
 // fewer than rf->dmin tracers get room for rf->dens - count more behind their residents: start describes the slices WITH the room,
 // perm has n + rf->ninj slots (-1 in those of the new tracers) and rf carries the counters and the list of the deficient cells.
+// With trash (the resident tracers of a context with deletion on) the tracers outside the box go to a bucket behind the last cell:
+// the scans, the census and the refill see the m cells alone, start[m] is the number of tracers that stay (with the room for the new
+// ones), the leavers sit in perm[start[m] .. start[m] + *trash) in no particular order and nothing reads them.
 static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long long n, const M3Pos& p, const M3Grid& s, int** perm_out, int** start_out,
-                   M3Refill* rf = nullptr) {
+                   M3Refill* rf = nullptr, long long* trash = nullptr) {
     const long long m = m3_ncells(s);
     if (m >= (1ll << 31) - 1 || n >= (1ll << 31) - 1) return pl3_fail(ctx, "3-D marker-in-cell: more than 2^31 cells or tracers");
     int *key, *perm, *cnt, *start, *cur, *bsum; M3Totals* tot;
     const std::string t(tag);
-    const int nb = (int)((m + M3_TILE - 1) / M3_TILE);
+    const int nb = (int)((m + M3_TILE - 1) / M3_TILE), del = trash ? 1 : 0;
     M3_TRY(m3_buf(ctx, v, M, (t + "_key").c_str(), (size_t)n, &key));
-    M3_TRY(m3_buf(ctx, v, M, (t + "_cnt").c_str(), (size_t)m, &cnt));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_cnt").c_str(), (size_t)m + 1, &cnt));
     M3_TRY(m3_buf(ctx, v, M, (t + "_start").c_str(), (size_t)m + 1, &start));
-    M3_TRY(m3_buf(ctx, v, M, (t + "_cur").c_str(), (size_t)m, &cur));
+    M3_TRY(m3_buf(ctx, v, M, (t + "_cur").c_str(), (size_t)m + 1, &cur));
     M3_TRY(m3_buf(ctx, v, M, (t + "_bsum").c_str(), (size_t)nb * 5, &bsum));
     M3_TRY(m3_buf(ctx, v, M, (t + "_tot").c_str(), (size_t)1, &tot));
-    M3_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(int), v.stream));
-    if (n > 0 && M->search) hipLaunchKernelGGL(k_m3_key<true>, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
-    else if (n > 0) hipLaunchKernelGGL(k_m3_key<false>, m3_blocks(n), dim3(256), 0, v.stream, n, p, s, key, cnt);
+    M3_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)(m + del) * sizeof(int), v.stream));
+    if (n > 0) {
+        const dim3 g = m3_blocks(n), b(256);
+        if (M->search && del) hipLaunchKernelGGL((k_m3_key<true, true>), g, b, 0, v.stream, n, p, s, key, cnt);
+        else if (M->search) hipLaunchKernelGGL((k_m3_key<true, false>), g, b, 0, v.stream, n, p, s, key, cnt);
+        else if (del) hipLaunchKernelGGL((k_m3_key<false, true>), g, b, 0, v.stream, n, p, s, key, cnt);
+        else hipLaunchKernelGGL((k_m3_key<false, false>), g, b, 0, v.stream, n, p, s, key, cnt);
+    }
+    int hcnt = 0;                                     // the trash count: a small read-back that only a context with deletion on makes
     long long slots = n;
     if (!rf) {
         const M3Need none{0, 0};
         M3_TRY(m3_buf(ctx, v, M, (t + "_perm").c_str(), (size_t)n, &perm));
         m3_scan_sums<1>(v, (int)m, cnt, none, nb, bsum, tot, nullptr, 0);
         hipLaunchKernelGGL(k_m3_scan_tiles<1>, dim3(nb), dim3(256), 0, v.stream, (int)m, (const int*)cnt, none, nb, (const int*)bsum, (const M3Totals*)tot,
-                           start, cur, (int*)nullptr, (int*)nullptr);
+                           start, cur, (int*)nullptr, (int*)nullptr, del);
+        if (del && n > 0) {
+            M3_HIP(ctx, hipGetLastError());
+            M3_HIP(ctx, m3_copy(ctx, &hcnt, cnt + m, sizeof(int), hipMemcpyDeviceToHost, v.stream));
+            M3_HIP(ctx, hipStreamSynchronize(v.stream));
+        }
     } else {
         const M3Need need{rf->dens, rf->dmin};
         double* idpart = nullptr; int nid = 0;
-        if (!M->have_maxid && rf->dmin > 0) {
+        // with deletion on the largest ID is that of THIS sort's survivors: reduced here every time, the cached value is not trusted
+        if ((!M->have_maxid || del) && rf->dmin > 0) {
             nid = (int)std::min<long long>(1024, (std::max<long long>(n, 1) + 255) / 256);
             M3_TRY(m3_buf(ctx, v, M, (t + "_idpart").c_str(), (size_t)nid, &idpart));
-            hipLaunchKernelGGL(k_m3_max, dim3(nid), dim3(256), 0, v.stream, n, (const double*)(M->f + (long long)M3_ID * M->cap), idpart);
+            hipLaunchKernelGGL(k_m3_max, dim3(nid), dim3(256), 0, v.stream, n, (const double*)(M->f + (long long)M3_ID * M->cap),
+                               (const int*)(del ? key : nullptr), (int)m, idpart);
         }
         m3_scan_sums<3>(v, (int)m, cnt, need, nb, bsum, tot, idpart, nid);
         M3_HIP(ctx, hipGetLastError());
         M3Totals h;                                   // the one read-back of a refill: how many tracers the arrays must hold
         M3_HIP(ctx, m3_copy(ctx, &h, tot, sizeof(h), hipMemcpyDeviceToHost, v.stream));
+        if (del && n > 0) M3_HIP(ctx, m3_copy(ctx, &hcnt, cnt + m, sizeof(int), hipMemcpyDeviceToHost, v.stream));
         M3_HIP(ctx, hipStreamSynchronize(v.stream));
         rf->ninj = h.v[1]; rf->nref = h.v[2]; rf->nempty = h.v[3]; rf->mincnt = m > 0 ? h.v[4] : 0;
         if (idpart) { M->maxid = std::isfinite(h.maxid) ? h.maxid : -1.0; M->have_maxid = true; }     // no finite ID: numbering starts at 0
@@ -763,11 +817,13 @@ static int m3_sort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const char* tag, long 
         M3_TRY(m3_buf(ctx, v, M, (t + "_loff").c_str(), (size_t)rf->nref, &loff));
         if (rf->ninj > 0) M3_HIP(ctx, hipMemsetAsync(perm, 0xff, (size_t)slots * sizeof(int), v.stream));
         hipLaunchKernelGGL(k_m3_scan_tiles<3>, dim3(nb), dim3(256), 0, v.stream, (int)m, (const int*)cnt, need, nb, (const int*)bsum, (const M3Totals*)tot,
-                           start, cur, list, loff);
+                           start, cur, list, loff, del);
         rf->list = list; rf->loff = loff; rf->cnt = cnt;
     }
+    if (trash) *trash = hcnt;
     if (n > 0) {
-        hipLaunchKernelGGL(k_m3_place, m3_blocks(n), dim3(256), 0, v.stream, n, (const int*)key, cur, perm);
+        if (del) hipLaunchKernelGGL(k_m3_place_del, m3_blocks(n), dim3(256), 0, v.stream, n, (const int*)key, cur, perm, (int)m);
+        else hipLaunchKernelGGL(k_m3_place, m3_blocks(n), dim3(256), 0, v.stream, n, (const int*)key, cur, perm);
         hipLaunchKernelGGL(k_m3_cell_order, m3_blocks(m), dim3(256), 0, v.stream, (int)m, (const int*)start, (const int*)(slots > n ? cnt : nullptr), perm);
     }
     M3_HIP(ctx, hipGetLastError());
@@ -973,8 +1029,11 @@ static int m3_resort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Refill* rf = nullp
     M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
     M3Pos p{{M->x, M->x + cap, M->x + 2 * cap}, 1};
     int *perm, *start;
-    M3_TRY(m3_sort(ctx, v, M, "r", n, p, sg, &perm, &start, rf));
-    const long long nn = n + (rf ? rf->ninj : 0);
+    long long removed = 0;
+    M3_TRY(m3_sort(ctx, v, M, "r", n, p, sg, &perm, &start, rf, M->deletion ? &removed : nullptr));
+    M->removed_last = removed; M->removed_total += removed;
+    if (removed > 0 && !(rf && rf->dmin > 0)) M->have_maxid = false;      // the holder of the cached largest ID may be among them
+    const long long nn = n - removed + (rf ? rf->ninj : 0);               // = start[ncell]: the take below leaves the trash bucket behind
     const long long ncap = nn <= cap ? cap : ((nn + nn / 8 + 63) / 64) * 64;
     double* alt;
     M3_TRY(m3_buf(ctx, v, M, M->x == (double*)M->bufs["r_a"] ? "r_b" : "r_a", (size_t)ncap * (6 + M3_NFTRAC), &alt));
@@ -1017,6 +1076,31 @@ extern "C" int pl3_mic_get_search(pl3_ctx* ctx, int* on) {
     return 0;
 }
 
+// Deletion is context state like the search: every sort of the resident tracers of this context then drops the tracers outside the
+// box.  Switching it on re-sorts resident tracers, which removes those that are outside already; switching it off changes no state.
+extern "C" int pl3_mic_set_deletion(pl3_ctx* ctx, int on) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_set_deletion", v, &M));
+    const bool d = on != 0;
+    if (d == M->deletion) return 0;
+    M->deletion = d;
+    return d && M->have ? m3_resort(ctx, v, M) : 0;
+}
+extern "C" int pl3_mic_get_deletion(pl3_ctx* ctx, int* on) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_get_deletion", v, &M));
+    if (!on) return pl3_fail(ctx, "pl3_mic_get_deletion: NULL argument");
+    *on = M->deletion ? 1 : 0;
+    return 0;
+}
+extern "C" int pl3_tracers_removed(pl3_ctx* ctx, int64_t out[2]) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_tracers_removed", v, &M));
+    if (!out) return pl3_fail(ctx, "pl3_tracers_removed: NULL argument");
+    out[0] = M->removed_last; out[1] = M->removed_total;
+    return 0;
+}
+
 extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f) {
     Pl3HostView v; Mic3* M;
     M3_TRY(m3_open(ctx, "pl3_tracers_upload", v, &M));
@@ -1026,6 +1110,7 @@ extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, c
     M3_TRY(m3_buf(ctx, v, M, "h_aos", (size_t)cap * (3 + M3_NFTRAC), &aos));
     M3_TRY(m3_buf(ctx, v, M, "r_a", (size_t)cap * (6 + M3_NFTRAC), &a));
     M->n = n; M->cap = cap; M->x = a; M->f = a + 3 * cap; M->v = a + (3 + M3_NFTRAC) * cap; M->have = true; M->have_maxid = false;
+    M->removed_last = 0; M->removed_total = 0;
     M3_HIP(ctx, hipMemsetAsync(a, 0, (size_t)cap * (6 + M3_NFTRAC) * sizeof(double), v.stream));
     if (n > 0) {
         M3_HIP(ctx, m3_copy(ctx, aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
@@ -1234,14 +1319,14 @@ int pl3i_mic_temp_to_tracers(pl3_ctx* ctx, int absolute, const double* dfield, i
 }
 
 // what a refill may be asked for; out = the four counters of the header
-static int m3_refill_args(pl3_ctx* ctx, const char* who, int tracdens, int tracdens_min, int fence, const int64_t* out) {
+static int m3_refill_args(pl3_ctx* ctx, const Mic3* M, const char* who, int tracdens, int tracdens_min, int fence, const int64_t* out) {
     const std::string w(who);
     if (!out) return pl3_fail(ctx, w + ": NULL out");
     if (tracdens < 0 || tracdens_min < 0) return pl3_fail(ctx, w + ": tracdens and tracdens_min must not be negative");
     if (tracdens_min > 0 && tracdens < tracdens_min) return pl3_fail(ctx, w + ": tracdens < tracdens_min (a refilled cell would still be deficient)");
-    if (tracdens_min > 0 && !fence)
+    if (tracdens_min > 0 && !fence && !M->deletion)
         return pl3_fail(ctx, w + ": tracer injection needs the fence: without it a tracer outside the box would be counted in the nearest "
-                                 "cell, and the deletion that pylamp2.py:574-581 does instead is not built in 3-D");
+                                 "cell, and the deletion that pylamp2.py:574-581 does instead needs pl3_mic_set_deletion on this context");
     return 0;
 }
 static void m3_refill_out(const M3Refill& rf, int64_t out[4]) { out[0] = rf.ninj; out[1] = rf.nref; out[2] = rf.nempty; out[3] = rf.mincnt; }
@@ -1280,7 +1365,7 @@ int pl3i_mic_advect(pl3_ctx* ctx, const double* dV, double tstep, int tracdens, 
     Pl3HostView v; Mic3* M;
     M3_TRY(m3_open(ctx, "pl3_resident_step", v, &M));
     M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_step"));
-    M3_TRY(m3_refill_args(ctx, "pl3_resident_step", tracdens, tracdens_min, 1, out));
+    M3_TRY(m3_refill_args(ctx, M, "pl3_resident_step", tracdens, tracdens_min, M->deletion ? 0 : 1, out));
     const int gn[3] = {v.gn[0] + 1, v.gn[1] + 1, v.gn[2] + 1};
     if (!M->have_vgrid) {
         std::vector<double> c[3];
@@ -1296,7 +1381,7 @@ int pl3i_mic_advect(pl3_ctx* ctx, const double* dV, double tstep, int tracdens, 
         M->have_vgrid = true;
     }
     M3Refill rf{tracdens, tracdens_min, seed, it, unique_ids ? 1 : 0};
-    M3_TRY(m3_advect_dev(ctx, v, M, M->vgrid, dV, tstep, 1, &rf));
+    M3_TRY(m3_advect_dev(ctx, v, M, M->vgrid, dV, tstep, M->deletion ? 0 : 1, &rf));       // the fence is off exactly when the sort deletes
     m3_refill_out(rf, out);
     return 0;
 }
@@ -1313,7 +1398,7 @@ extern "C" int pl3_resident_advect(pl3_ctx* ctx, const double* gz, const double*
     Pl3HostView v; Mic3* M;
     M3_TRY(m3_open(ctx, "pl3_resident_advect", v, &M));
     M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_advect"));
-    M3_TRY(m3_refill_args(ctx, "pl3_resident_advect", tracdens, tracdens_min, fence, out));
+    M3_TRY(m3_refill_args(ctx, M, "pl3_resident_advect", tracdens, tracdens_min, fence, out));
     M3Refill rf{tracdens, tracdens_min, seed, it, unique_ids ? 1 : 0};
     M3_TRY(m3_advect(ctx, v, M, "pl3_resident_advect", gz, gx, gy, vz, vx, vy, tstep, fence, &rf));
     m3_refill_out(rf, out);
@@ -1323,7 +1408,7 @@ extern "C" int pl3_resident_refill(pl3_ctx* ctx, int tracdens, int tracdens_min,
     Pl3HostView v; Mic3* M;
     M3_TRY(m3_open(ctx, "pl3_resident_refill", v, &M));
     M3_TRY(m3_need_tracers(ctx, M, "pl3_resident_refill"));
-    M3_TRY(m3_refill_args(ctx, "pl3_resident_refill", tracdens, tracdens_min, 1, out));
+    M3_TRY(m3_refill_args(ctx, M, "pl3_resident_refill", tracdens, tracdens_min, 1, out));
     M3Refill rf{tracdens, tracdens_min, seed, it, unique_ids ? 1 : 0};
     M3_TRY(m3_resort(ctx, v, M, &rf));
     m3_refill_out(rf, out);

@@ -336,13 +336,16 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
         else S3_TRY(pl3i_mic_temp_to_tracers(ctx, 0, dT, cfg->do_subgrid_heatdiff ? 1 : 0, tstep));
     }
 
-    // 8. + 9. advection velocity on the padded centre grid; RK4 + fence + sort + refill
+    // 8. + 9. advection velocity on the padded centre grid; RK4 + fence (or, with pl3_mic_set_deletion, deletion in the sort) + sort + refill
     s3_advvel(o, o.d.X, adv);
     S3_HIP(ctx, hipGetLastError());
     int64_t cnt[4] = {0, 0, 0, 0};
     S3_TRY(pl3i_mic_advect(ctx, adv, tstep, cfg->tracdens, cfg->tracdens_min, cfg->inject_seed, it, cfg->inject_unique_ids, cnt));
     rep->ninjected = cnt[0]; rep->nrefilled = cnt[1]; rep->nempty = cnt[2]; rep->mincount = cnt[3];
     S3_TRY(pl3_tracers_count(ctx, &rep->ntrac));
+    int64_t gone[2];
+    S3_TRY(pl3_tracers_removed(ctx, gone));
+    rep->nremoved = gone[0];
     rep->ms_scatter = ms[0]; rep->ms_gather = heat ? ms[1] : 0.0; rep->ms_rk4 = ms[2]; rep->ms_sort = ms[3];
     rep->ms_stokes = rep->stokes.solve_ms; rep->ms_heat = rep->heat.solve_ms;
     rep->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();

@@ -142,6 +142,23 @@ class Context3:
         self.check(self.lib.pl3_mic_get_search(self.handle(), C.byref(on)))
         return bool(on.value)
 
+    def set_marker_deletion(self, on):
+        """Deletion of the resident tracers that leave the box (default off): with it on, every sort of the resident tracers drops
+        those with x_d <= 0 or x_d >= L_d on any axis (the rule is in include/pylamp_hip.h at pl3_mic_set_deletion).  Switching it on
+        re-sorts resident tracers, which removes those already outside."""
+        self.check(self.lib.pl3_mic_set_deletion(self.handle(), 1 if on else 0))
+
+    def marker_deletion(self):
+        on = C.c_int()
+        self.check(self.lib.pl3_mic_get_deletion(self.handle(), C.byref(on)))
+        return bool(on.value)
+
+    def tracers_removed(self):
+        """(removed by the last sort of the resident tracers, removed since the last upload)."""
+        v = (C.c_int64 * 2)()
+        self.check(self.lib.pl3_tracers_removed(self.handle(), v))
+        return int(v[0]), int(v[1])
+
     def set_stokes_walls(self, bc):
         """The kinds of the six Stokes walls [z0, x0, y0, zL, xL, yL] of this context (None: all free-slip); kept until set again."""
         self.check(self.lib.pl3_stokes_set_walls(self.handle(), (C.c_int * 6)(*stokes_walls(bc))))
@@ -609,6 +626,10 @@ class Options3:
         self.resident = False
         # beyond the reference: cells of the markers by per-axis search, which lets Simulation3 take a rectilinear grid=
         self.marker_search = False
+        # the fence-off path of pylamp2.py:563-581: tracs_fence_enabled = False AND marker_deletion = True.  Two switches because the
+        # plain rejection of tracs_fence_enabled = False is pinned behaviour: the deletion is opted into by name, and
+        # marker_deletion = True with the fence on is rejected too, so that one combination has one meaning
+        self.marker_deletion = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
@@ -624,7 +645,11 @@ class Simulation3:
     Stokes walls free-slip or no-slip per wall (Options3.bcstokes = [z0, x0, y0, zL, xL, yL]), a no-slip wall may move in its own plane (Options3.bcstokesvel, set_wall_velocity); a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
     axis strictly increasing from 0 to L[d]): the marker kernels then find cells by search in the coordinates (the rule is in
     include/pylamp_hip.h at pl3_mic_set_search), while the time-step rules and the subgrid time scale keep the mean spacing.  Options3.resident = True runs the same sequence inside the library with every grid field
-    kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Not built: the fence-off deletion path, surface stabilisation, several ranks -- each is rejected with an error that names it."""
+    kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Options3.tracs_fence_enabled = False together with
+    Options3.marker_deletion = True runs without the fence: a tracer that leaves the box (x_d <= 0 or x_d >= L_d) is removed by the
+    next sort, the census and the refill of that sort see the survivors, step() / advect() / refill() report nremoved and
+    Context3.tracers_removed() counts them.  Not built: wall-normal (through-flow) velocities, surface stabilisation, several
+    ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
         self.nx = [int(v) for v in nx]
@@ -653,8 +678,12 @@ class Simulation3:
         if int(o.tracdens) < 0 or int(o.tracdens_min) < 0 or int(o.tracdens_min) > int(o.tracdens):
             raise Exception("Simulation3: tracer injection needs tracdens >= tracdens_min >= 0 (got tracdens = %s, tracdens_min = %s)"
                             % (o.tracdens, o.tracdens_min))
-        if not o.tracs_fence_enabled:
-            raise Exception("Simulation3: the fence-off deletion path (tracs_fence_enabled = False) is not supported in 3-D")
+        if not o.tracs_fence_enabled and not o.marker_deletion:
+            raise Exception("Simulation3: the fence-off deletion path (tracs_fence_enabled = False) is not supported in 3-D "
+                            "unless Options3.marker_deletion = True")
+        if o.marker_deletion and o.tracs_fence_enabled:
+            raise Exception("Simulation3: Options3.marker_deletion = True needs tracs_fence_enabled = False (with the fence on no "
+                            "tracer leaves the box and there is nothing to delete)")
         if o.surface_stabilization:
             raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
@@ -664,6 +693,8 @@ class Simulation3:
         self.ctx.set_wall_velocity(self.bcstokesvel)
         if o.marker_search:
             self.ctx.set_marker_search(True)
+        if o.marker_deletion:
+            self.ctx.set_marker_deletion(True)
         self.it = 0
         self.totaltime = 0.0
         self.last = None
@@ -691,8 +722,8 @@ class Simulation3:
         tr_x = _x3(tr_x); tr_f = _lib.f64(tr_f)
         if tr_f.shape != (tr_x.shape[0], NFTRAC):
             raise Exception("tracer arrays must be (n, 3) and (n, %d)" % NFTRAC)
-        self.ntrac = tr_x.shape[0]
-        self._lib_call("pl3_tracers_upload", self.ntrac, _lib.dptr(tr_x), _lib.dptr(tr_f))
+        self._lib_call("pl3_tracers_upload", tr_x.shape[0], _lib.dptr(tr_x), _lib.dptr(tr_f))
+        self.ntrac = tr_x.shape[0] - self.ctx.tracers_removed()[0]
 
     def count(self):
         n = C.c_int64()
@@ -786,26 +817,33 @@ class Simulation3:
         return out, (int(o.tracdens), int(o.tracdens_min), int(o.inject_seed) & (2 ** 64 - 1), int(self.it if it is None else it),
                      1 if o.inject_unique_ids else 0, out)
 
-    @staticmethod
-    def _counters(out):
-        return dict(ninjected=int(out[0]), nrefilled=int(out[1]), nempty=int(out[2]), mincount=int(out[3]))
+    def _counters(self, out):
+        """The four counters of a sort with refill; with Options3.marker_deletion also nremoved (without it the dict keeps its four
+        keys: callers compare it whole).  ntrac follows both."""
+        c = dict(ninjected=int(out[0]), nrefilled=int(out[1]), nempty=int(out[2]), mincount=int(out[3]))
+        gone = self.ctx.tracers_removed()[0]
+        if self.opt.marker_deletion:
+            c["nremoved"] = gone
+        self.ntrac += c["ninjected"] - gone
+        return c
 
     def refill(self, it=None):
         """Sort + census + refill of the cells below opt.tracdens_min to opt.tracdens, without advection (a sparse initial set is
         topped up with it).  `it` selects the random stream (default: the step counter).  Returns ninjected, nrefilled (cells),
-        nempty (cells without any tracer before the call) and mincount (smallest count before the call)."""
+        nempty (cells without any tracer before the call) and mincount (smallest count before the call); with Options3.marker_deletion
+        also nremoved, the tracers the sort removed (the counts are those after the removal)."""
         out, args = self._refill_args(it)
         self._lib_call("pl3_resident_refill", *args)
-        self.ntrac += int(out[0])
         return self._counters(out)
 
     def advect(self, grids, vels, tstep, it=None):
-        """RK4 + fence + the sort by cell with the refill in the same pass; returns the counters of refill()."""
+        """RK4 + fence (with Options3.marker_deletion: no fence, the sort removes the tracers outside the box) + the sort by cell with
+        the refill in the same pass; returns the counters of refill()."""
         shp = tuple(v + 1 for v in self.nx)
         g = [_lib.f64(c) for c in grids]; V = [_f3(a, shp) for a in vels]
         out, args = self._refill_args(it)
-        self._lib_call("pl3_resident_advect", *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V], float(tstep), 1, *args)
-        self.ntrac += int(out[0])
+        self._lib_call("pl3_resident_advect", *[_lib.dptr(c) for c in g], *[_lib.dptr(a) for a in V], float(tstep),
+                       0 if self.opt.marker_deletion else 1, *args)
         return self._counters(out)
 
     # -- one time step -----------------------------------------------------------------------------------------------
@@ -846,7 +884,7 @@ class Simulation3:
         self.totaltime += r.tstep
         rep = dict(it=self.it, tstep=r.tstep, limiter="H" if r.limiter else "S", stokes=r.stokes.as_dict(),
                    heat=r.heat.as_dict() if o.do_heatdiff else None, ninjected=int(r.ninjected), nrefilled=int(r.nrefilled),
-                   nempty=int(r.nempty), mincount=int(r.mincount), time=self.totaltime, ntrac=self.ntrac)
+                   nempty=int(r.nempty), mincount=int(r.mincount), nremoved=int(r.nremoved), time=self.totaltime, ntrac=self.ntrac)
         self.fields = {}
         self._stepped = True
         self.last = rep
@@ -900,6 +938,7 @@ class Simulation3:
             f["temp"] = newtemp
         grids, vels = advection_velocity(newvel, self.gridmp, self.nx, self.bcstokes, self.bcstokesvel)
         rep.update(self.advect(grids, vels, tstep, self.it))
+        rep.setdefault("nremoved", 0)
         self.totaltime += tstep
         rep["time"] = self.totaltime; rep["ntrac"] = self.count()
         self.fields = f

@@ -16,6 +16,16 @@ then carries "search" and "graded".
 --parent FILE [FILE ...] embeds the sort_off figures that the same script wrote for another tree (the parent commit's), run in
 separate processes alternating with this one, and reports the run-to-run spread of both next to the medians.
 
+--delete runs with the fence off and the marker deletion on (Options3.tracs_fence_enabled = False, marker_deletion = True): the
+stages and --step as they are (nothing leaves the box: what the switch itself costs), and --sort-only as two states written to
+profiles/mic3_129_delete.json:
+  sort_none_leaving   RK4 + deleting sort of a set that stays where it is,
+  sort_layer_leaving  the same under a uniform velocity along +z that carries the outermost cell layer out of the box (uploaded
+                      afresh for every repetition, --refill-reps repetitions),
+  sort_layer_fenced   that motion with the fence on and deletion off: every tracer changes its cell, none leaves.
+--off FILE [FILE ...] / --parent FILE [FILE ...] embed, per stage, the figures the plain script wrote for this tree with deletion off
+and for the parent commit's tree (separate processes, alternating), with the ratio of the medians and both run-to-run spreads.
+
 --step [--resident] times whole steps of Simulation3 -- the falling sphere with heat on, --n nodes per axis, 8 tracers per cell:
 host wall time per step (device synchronisation, then perf_counter, on either side of step()), median and min-max over --reps
 steps after --warmup, and the medians of the stage times (device events); writes profiles/mic3_step_129.json unless --out says
@@ -44,6 +54,57 @@ BYTES = dict(scatter=lambda tpc: 24 + 56 + 80.0 / tpc, gather=lambda tpc: 24 + 1
 def _stat(v, n):
     ms = float(np.median(v))
     return dict(ms=round(ms, 4), ms_min=round(float(np.min(v)), 4), ms_max=round(float(np.max(v)), 4), ps_per_tracer=round(ms * 1e9 / n, 2), reps=len(v))
+
+
+def _delete_kw(a):
+    return dict(tracs_fence_enabled=False, marker_deletion=True) if a.delete else {}
+
+
+def _spread(files, pick):
+    """Median and min-max over the medians that separate processes wrote."""
+    v = [pick(json.loads(open(f).read())) for f in files]
+    return dict(ms=round(float(np.median(v)), 4), ms_min=round(float(np.min(v)), 4), ms_max=round(float(np.max(v)), 4), runs=len(v))
+
+
+def sort_delete(a):
+    """The deleting sort: nothing leaving, and one cell layer leaving."""
+    nx = [a.n] * 3; L = [100e3] * 3
+    rng = np.random.default_rng(0)
+    tr_x, tr_f = P3.falling_sphere_tracers(nx, L, rng, per_axis=a.per_axis)
+    n = tr_x.shape[0]
+    sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**_delete_kw(a)))
+    h = L[0] / (a.n - 1); dt = 1e12
+    vel = [rng.standard_normal(nx) * (1e-3 * h / dt) for _ in range(3)]
+    grids, V = P3.advection_velocity(vel, sim.gridmp, nx)
+    t = []
+    for rep in range(a.warmup + a.reps):
+        c = sim.advect(grids, V, dt)
+        assert c["nremoved"] == 0, c
+        if rep >= a.warmup:
+            t.append(sim.stage_times()["sort"])
+    out = dict(config="mic3_%d_delete" % a.n, nodes=a.n ** 3, tracers=n, reps=a.reps, warmup=a.warmup, states=dict(sort_none_leaving=_stat(t, n)))
+    W = [np.zeros_like(V[0]) for _ in range(3)]
+    W[0][...] = 1.5 * h / dt                     # the reference's weights (1,1,1,1)/6 carry a tracer 2/3 w dt: one cell
+    t, gone = [], 0
+    for rep in range(1 + a.refill_reps):
+        sim.upload(tr_x, tr_f)
+        c = sim.advect(grids, W, dt)
+        gone = c["nremoved"]
+        if rep >= 1:
+            t.append(sim.stage_times()["sort"])
+    out["states"]["sort_layer_leaving"] = dict(_stat(t, n), removed=int(gone), tracers_after=int(sim.count()))
+    sim.close()
+    # the same motion with the fence on and deletion off: what moving every tracer by one cell costs the sort by itself
+    sim = P3.Simulation3(nx, L, tr_x, tr_f)
+    t = []
+    for rep in range(1 + a.refill_reps):
+        sim.upload(tr_x, tr_f)
+        sim.advect(grids, W, dt)
+        if rep >= 1:
+            t.append(sim.stage_times()["sort"])
+    out["states"]["sort_layer_fenced"] = _stat(t, n)
+    sim.close()
+    return out
 
 
 def sort_only(a):
@@ -106,7 +167,7 @@ def step_bench(a):
     n = tr_x.shape[0]
     tr_f[:, 3] = 273 + 1350 * tr_x[:, 0] / L[0]; tr_f[:, 4] = 4.0; tr_f[:, 5] = 1250; tr_f[:, 7] = 3.5e-5; tr_f[:, 11] = 1e-9
     kw = dict(resident=True) if a.resident else {}
-    sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**kw))
+    sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**kw, **_delete_kw(a)))
     del tr_x, tr_f
     wall, stages, its = [], {}, []
     for rep in range(a.warmup + a.reps):
@@ -121,7 +182,7 @@ def step_bench(a):
             st = dict(sim.stage_times(), stokes=r["stokes"]["solve_ms"], heat=r["heat"]["solve_ms"])
             for k, v in st.items():
                 stages.setdefault(k, []).append(v)
-    out = dict(config="mic3_%d_step" % a.n, mode="resident" if a.resident else "staged", tree=a.tree or ".", nodes=a.n ** 3, tracers=n,
+    out = dict(config="mic3_%d_step" % a.n, mode="resident" if a.resident else "staged", delete=bool(a.delete), tree=a.tree or ".", nodes=a.n ** 3, tracers=n,
                reps=a.reps, warmup=a.warmup, step_ms=round(float(np.median(wall)), 2), step_ms_min=round(float(np.min(wall)), 2),
                step_ms_max=round(float(np.max(wall)), 2), stokes_iterations=its,
                stage_ms={k: round(float(np.median(v)), 3) for k, v in stages.items()})
@@ -143,11 +204,13 @@ def main():
     ap.add_argument("--parent", nargs="*", default=[])
     ap.add_argument("--step", action="store_true"); ap.add_argument("--resident", action="store_true"); ap.add_argument("--tree", default=None)
     ap.add_argument("--search", action="store_true"); ap.add_argument("--graded", type=float, default=0.0)
+    ap.add_argument("--delete", action="store_true"); ap.add_argument("--off", nargs="*", default=[])
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join("profiles", "mic3_step_129.json" if a.step else ("mic3_129_refill.json" if a.sort_only else "mic3_129.json"))
+        a.out = os.path.join("profiles", "mic3_step_129.json" if a.step else ("mic3_129_delete.json" if a.sort_only and a.delete else
+                                                                              ("mic3_129_refill.json" if a.sort_only else "mic3_129.json")))
     if a.sort_only or a.step:
-        line = json.dumps(step_bench(a) if a.step else sort_only(a))
+        line = json.dumps(step_bench(a) if a.step else (sort_delete(a) if a.delete else sort_only(a)))
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(line + "\n")
@@ -170,7 +233,7 @@ def main():
     elif a.search:
         sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(marker_search=True))
     else:
-        sim = P3.Simulation3(nx, L, tr_x, tr_f)
+        sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**_delete_kw(a)))
     del tr_x, tr_f
     h = L[0] / (a.n - 1)
     dT = rng.standard_normal(nx)
@@ -199,10 +262,19 @@ def main():
         out["search"] = True; out["graded"] = a.graded
     if a.tree:
         out["tree"] = a.tree
+    if a.delete:
+        out["delete"] = True
     for k, v in t.items():
         ms = float(np.median(v)); b = BYTES[k](tpc)
         out["stages"][k] = dict(ms=round(ms, 4), ms_min=round(float(np.min(v)), 4), ms_max=round(float(np.max(v)), 4),
                                 ps_per_tracer=round(ms * 1e9 / n, 2), bytes_per_tracer=round(b, 1), fraction_of_8TBs_roof=round(b * n / (ms * 1e-3) / ROOF, 4))
+    for name, files in (("off", a.off), ("parent", a.parent)):
+        if files:
+            out[name] = {k: _spread(files, lambda r, k=k: r["stages"][k]["ms"]) for k in t}
+    if a.off and a.parent:
+        out["off_over_parent"] = {k: round(out["off"][k]["ms"] / out["parent"][k]["ms"], 4) for k in t}
+    if a.off:
+        out["on_over_off"] = {k: round(out["stages"][k]["ms"] / out["off"][k]["ms"], 4) for k in t}
     sim.close()
     line = json.dumps(out)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
