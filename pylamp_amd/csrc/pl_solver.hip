@@ -1592,7 +1592,7 @@ struct PlSolver {
     double schur_scale = 1.0;    // S^ = schur_scale * Kc^2 / eta_n (PYLAMP_SCHUR_SCALE)
     double ref_cached = 0.0, ref_kc = 0.0; int ref_age = 0;      // dynamic-load reference norm of the last solve that computed it (pl_stokes_solve_device)
     long long fused_max_nodes = 1100000;      // PYLAMP_MG_FUSED_MAX: largest level (nodes) that takes the tile kernels
-    long long tile32_min_nodes = 1000000;            // PYLAMP_MG_TS32: levels from this many nodes use 32 x 32 tiles (2049^2: level 1; 36.6 against 37.4 ms per step)
+    long long tile32_min_nodes = 250000;             // PYLAMP_MG_TS32: levels from this many nodes use 32 x 32 tiles (2049^2: levels 1 and 2; 513^2 nodes are 256 tiles, one per CU: 27 against 37 us per visit)
     bool fused = true;           // PYLAMP_MG_FUSED=0: every multigrid stage as a kernel of its own (the path the tile kernels are checked against)
     bool fuse_first = true;      // false: the first sweep of level 0 as a pass of its own
     bool l0_mixed = true;        // PYLAMP_L0_MIXED=0: every vector of a staged level 0 in FP64 (stokes_precond_t)
@@ -2461,8 +2461,8 @@ static void vcycle(pl_ctx* ctx, PlSolver* S, size_t l, const T* f, T** out, bool
 // rectilinear grids work.  Measured on the way (2049^2, level 1 = 1025^2, pre kernel): with viscosities, tables, right-hand side
 // and three iterates in LDS and the coefficients recomputed in every stage 73 us; coefficients in registers 64; right-hand side
 // requested with the first loads instead of after the first barrier 52 (32 x 32 tiles) -- of which the loads are 22, coefficients
-// and first sweep 8, a sweep 6, residual + restriction 10.  Tile edge 32 from 10^6 nodes (halo recomputation 1.7x instead of
-// 2.6x at three sweeps), 16 below (more workgroups than CUs down to 257^2).
+// and first sweep 8, a sweep 6, residual + restriction 10.  Tile edge 32 from 250 000 nodes (halo recomputation 1.7x instead of
+// 2.6x at three sweeps; 513^2 nodes are 256 tiles, one per CU), 16 below (more workgroups than CUs down to 257^2).
 // Row classes (wall, slaved, interior) are decided per node from the global index exactly as the one-kernel-per-stage path does,
 // and a slaved node evaluates its master's update -- so both paths compute the same numbers
 // (tests/test_hip_solve.py::test_fused_levels_match_the_staged_path).
@@ -2500,21 +2500,17 @@ __device__ inline int mgt_cls_z(const PlVvOp& op, int i, int j, int& db, double&
     }
     return VV_INT;
 }
+// (the slave scale is selected from the two values, both read first: read inside the branches it becomes ONE load per lane from a
+// selected address of the kernel's arguments -- a round trip to memory in a branch, behind which every wait is a wait for all loads)
 __device__ inline int mgt_cls_x(const PlVvOp& op, int i, int j, int& da, double& s) {
+    const double s0 = op.s0, sL = op.sL;
     da = 0; s = 1.0;
     if (j <= 0 || j >= op.g.nx - 1 || i < 0 || i >= op.g.nz - 1) return VV_ZERO;
-    if (i == 0 && op.slave_z0) { da = 1; s = op.s0; return VV_SLAVE; }
-    if (i == op.g.nz - 2 && op.slave_zL) { da = -1; s = op.sL; return VV_SLAVE; }
-    return VV_INT;
+    if (i == 0 && op.slave_z0) da = 1;
+    else if (i == op.g.nz - 2 && op.slave_zL) da = -1;
+    s = da > 0 ? s0 : (da < 0 ? sL : 1.0);
+    return da ? VV_SLAVE : VV_INT;
 }
-// the tables of the region: value of table tab (indexed by global node + PL_TOFF, defined for -PL_TOFF .. n + PL_TOFF) at region rows / columns -1 .. CR + 1
-__device__ inline void mgt_load_table(double* dst, const double* tab, int first_global, int count, int n) {
-    for (int k = threadIdx.x; k < count; k += blockDim.x) {
-        const int gk = first_global + k;
-        dst[k] = (gk >= -PL_TOFF && gk < n + PL_TOFF) ? TB(tab, gk) : 0.0;
-    }
-}
-
 // What a thread keeps in REGISTERS for one component of one node of its tile through all the stages: the coefficients of the row
 // it evaluates (its own, or its master's if it is a slaved node), 1 / diagonal and the right-hand side there.  The stages were
 // VALU-bound -- ~150 instructions per node and stage, two thirds of them recomputing these from the viscosity planes and spacing
@@ -2599,6 +2595,111 @@ __host__ __device__ constexpr int mgt_nt(int nn) { return ((nn + mgt_npt(nn) - 1
 __host__ __device__ constexpr int mgt_pre_nn(int NS, int TS) { return (TS + 2 * (NS + 2)) * (TS + 2 * (NS + 2)); }
 __host__ __device__ constexpr int mgt_post_nn(int NS, int TS) { return (TS + 2 * (NS + 1)) * (TS + 2 * (NS + 1)); }
 
+// What a thread requests from memory for its tile before anything of it is in LDS ("raw" inputs, one set per thread):
+//   MgtRawE: the viscosities of the thread's node slots and one entry of the region's spacing tables
+//   MgtRawF: the right-hand side of the rows it evaluates (its own, a slaved node its master's)
+//   MgtRawV, MgtRawC: (k_mg_post) the pre-smoothed iterate of the node slots; one node of the coarse correction's window
+// Every load is issued by every thread, from a clamped address where the value does not exist (node 0, 0; the table's first entry);
+// whether it counts is decided where it is put to use (0 otherwise).  Loads inside a branch make the number of loads in flight
+// depend on the path, and the wait for an older load then has to be a wait for all of them.
+// Integers and addresses only (mgt_classify): nothing here depends on LDS.
+template <int NPT> struct MgtRawE { double es[NPT], en[NPT], tab; };
+template <int NPT> struct MgtRawF { double fz[NPT], fx[NPT]; };
+template <int NPT> struct MgtRawV { double vz[NPT], vx[NPT]; };
+struct MgtRawC { double ez, ex; };
+// slot q of thread tid: node idx of the region, whether its planes' entry c exists (inmem: the node lies within the planes' ring)
+#define MGT_SLOT(q) const int idx = tid + (q) * NT; const bool have = idx < CR * CR; \
+    const int ra = have ? idx / CR : 0, rb = have ? idx % CR : 0, i = ci0 + ra, j = cj0 + rb; \
+    const bool inmem = have && i - g.gi0 >= -PL_RING && i - g.gi0 < g.lnz + PL_RING && j - g.gj0 >= -PL_RING && j - g.gj0 < g.lnx + PL_RING; \
+    const long long c = inmem ? pl_idx(g, i - g.gi0, j - g.gj0) : pl_idx(g, 0, 0);
+// the table entry of thread tid: wave w holds table w (rdz, rDz, rdx, rDx) at region rows / columns -1 .. CR + 1 (tables are indexed
+// by global node + PL_TOFF and defined for -PL_TOFF .. n + PL_TOFF)
+#define MGT_TAB_SLOT const int w = __builtin_amdgcn_readfirstlane(tid >> 6), k = tid & 63; \
+    const int gk = (w < 2 ? ci0 : cj0) - 1 + k, n = w < 2 ? g.nz : g.nx; \
+    const bool intab = w < 4 && k < CR + 3 && gk >= -PL_TOFF && gk < n + PL_TOFF;
+template <int NPT, int NT, int CR, int HC, int TS>
+__device__ inline void mgt_fetch_visc(MgtRawE<NPT>& r, const MgTileArgs& a, int tile, int tid) {
+    static_assert(CR + 3 <= 64 && NT >= 256, "one table per wave");
+    const PlGeom& g = a.op.g;
+    const int ci0 = g.gi0 + tile / a.tiles_x * TS - HC, cj0 = g.gj0 + tile % a.tiles_x * TS - HC;
+    MGT_TAB_SLOT
+    const double* const tab = w == 0 ? a.op.rdz : w == 1 ? a.op.rDz : w == 2 ? a.op.rdx : a.op.rDx;
+    r.tab = TB(tab, intab ? gk : -PL_TOFF);
+#pragma unroll
+    for (int q = 0; q < NPT; q++) {
+        MGT_SLOT(q)
+        r.es[q] = a.op.etas[c]; r.en[q] = a.op.etan[c];
+    }
+}
+template <int NPT, int NT, int CR, int HC, int TS>
+__device__ inline void mgt_store_visc(const MgtRawE<NPT>& r, const MgTileArgs& a, int tile, double* es, double* en, double* tab, int tid) {      // tab: TAB[4][CR + 4]
+    const PlGeom& g = a.op.g;
+    const int ci0 = g.gi0 + tile / a.tiles_x * TS - HC, cj0 = g.gj0 + tile % a.tiles_x * TS - HC;
+#pragma unroll
+    for (int q = 0; q < NPT; q++) {
+        MGT_SLOT(q)
+        (void)c;
+        if (have) { es[idx] = inmem ? r.es[q] : 0.0; en[idx] = inmem ? r.en[q] : 0.0; }
+    }
+    MGT_TAB_SLOT
+    if (w < 4 && k < CR + 3) tab[w * (CR + 4) + k] = intab ? r.tab : 0.0;
+}
+template <int NPT, int NT, int CR, int HC, int TS>
+__device__ inline void mgt_fetch_rhs(MgtRawF<NPT>& r, const MgTileArgs& a, const double* fsrc, int tile, int tid) {      // (counts where the row is on)
+    const PlGeom& g = a.op.g;
+    const int ci0 = g.gi0 + tile / a.tiles_x * TS - HC, cj0 = g.gj0 + tile % a.tiles_x * TS - HC;
+#pragma unroll
+    for (int q = 0; q < NPT; q++) {
+        MGT_SLOT(q)
+        const MgtC kz = mgt_classify<true>(a.op, CR, CR, ci0, cj0, ra, rb), kx = mgt_classify<false>(a.op, CR, CR, ci0, cj0, ra, rb);
+        const long long c0 = pl_idx(g, 0, 0), cn = pl_idx(g, i - g.gi0, j - g.gj0);
+        (void)c;
+        r.fz[q] = fsrc[kz.on ? cn + kz.d : c0];
+        r.fx[q] = fsrc[(kx.on ? cn + (long long)kx.d * g.pitch : c0) + g.plane];
+    }
+}
+template <int NPT, int NT, int CR, int HC, int TS>
+__device__ inline void mgt_fetch_v(MgtRawV<NPT>& r, const MgTileArgs& a, int tile, int tid) {
+    const PlGeom& g = a.op.g;
+    const int ci0 = g.gi0 + tile / a.tiles_x * TS - HC, cj0 = g.gj0 + tile % a.tiles_x * TS - HC;
+#pragma unroll
+    for (int q = 0; q < NPT; q++) {
+        MGT_SLOT(q)
+        r.vz[q] = a.v[c]; r.vx[q] = a.v[c + g.plane];
+    }
+}
+template <int NPT, int NT, int CR, int HC, int TS>
+__device__ inline void mgt_store_v(const MgtRawV<NPT>& r, const MgTileArgs& a, int tile, double* pvz, double* pvx, int tid) {
+    const PlGeom& g = a.op.g;
+    const int ci0 = g.gi0 + tile / a.tiles_x * TS - HC, cj0 = g.gj0 + tile % a.tiles_x * TS - HC;
+#pragma unroll
+    for (int q = 0; q < NPT; q++) {
+        MGT_SLOT(q)
+        (void)c;
+        if (have) { pvz[idx] = inmem ? r.vz[q] : 0.0; pvx[idx] = inmem ? r.vx[q] : 0.0; }
+    }
+}
+// node e of the coarse window (ECR x ECR coarse nodes from (eI0, eJ0) on): its planes' entry, or node 0, 0 where it has none
+#define MGT_EC_SLOT const PlGeom& gc = a.opc.g; \
+    const int e = min(tid, ECR * ECR - 1), I = ((a.op.g.gi0 + tile / a.tiles_x * TS - H) >> 1) - 2 + e / ECR, J = ((a.op.g.gj0 + tile % a.tiles_x * TS - H) >> 1) - 2 + e % ECR; \
+    const bool inmem = I - gc.gi0 >= -PL_RING && I - gc.gi0 < gc.lnz + PL_RING && J - gc.gj0 >= -PL_RING && J - gc.gj0 < gc.lnx + PL_RING; \
+    const long long cc = inmem ? pl_idx(gc, I - gc.gi0, J - gc.gj0) : pl_idx(gc, 0, 0);
+template <int NT, int TS, int H, int ECR>
+__device__ inline void mgt_fetch_ec(MgtRawC& r, const MgTileArgs& a, int tile, int tid) {
+    static_assert(ECR * ECR <= NT, "one node of the coarse window per thread");
+    MGT_EC_SLOT
+    r.ez = a.ec[cc]; r.ex = a.ec[cc + gc.plane];
+}
+template <int NT, int TS, int H, int ECR>
+__device__ inline void mgt_store_ec(const MgtRawC& r, const MgTileArgs& a, int tile, double* ecz, double* ecx, int tid) {
+    MGT_EC_SLOT
+    (void)cc;
+    if (tid < ECR * ECR) { ecz[tid] = inmem ? r.ez : 0.0; ecx[tid] = inmem ? r.ex : 0.0; }
+}
+#undef MGT_EC_SLOT
+#undef MGT_SLOT
+#undef MGT_TAB_SLOT
+
 // NS: sweeps of the pre-smoothing sequence, the first from the zero guess included (1..3).  L0: level 0 of the Stokes
 // preconditioner -- the right-hand side is computed from the scaled residual rs (stage1_node) instead of read.
 // EXT = 1 (a level DISTRIBUTED over several ranks): the region is one node wider, so that the pre-smoothed iterate comes out valid NS
@@ -2613,15 +2714,19 @@ __global__ __launch_bounds__(mgt_nt(mgt_pre_nn(NS + EXT, TS))) void k_mg_pre(MgT
     double* const ES = V[1][0]; double* const EN = V[1][1];
     const PlGeom& g = a.op.g;
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x % a.tiles_x;
-    const int ti0 = g.gi0 + ty * TS, tj0 = g.gj0 + tx * TS;          // tiles cover this rank's block (global node indices)
-    const int ci0 = ti0 - HC, cj0 = tj0 - HC;
     MgtTab t; t.es = ES; t.en = EN; t.rdz = TAB[0]; t.rDz = TAB[1]; t.rdx = TAB[2]; t.rDx = TAB[3];
-    mgt_load_table(TAB[0], a.op.rdz, ci0 - 1, CR + 3, g.nz); mgt_load_table(TAB[1], a.op.rDz, ci0 - 1, CR + 3, g.nz);
-    mgt_load_table(TAB[2], a.op.rdx, cj0 - 1, CR + 3, g.nx); mgt_load_table(TAB[3], a.op.rDx, cj0 - 1, CR + 3, g.nx);
     const long long P = g.plane;
+    const double* const fsrc = L0 ? a.rs : a.f;
     // ---- load: viscosities (level 0: and S^-1 r_p) of the whole region, 0 beyond the planes' ring -- and in the same breath the
     //      right-hand side (level 0: the scaled residual) of the row each node evaluates: its own, a slaved node its master's
+    MgtRawE<NPT> rawe;
+    MgtRawF<NPT> rawf;
+    mgt_fetch_visc<NPT, NT, CR, HC, TS>(rawe, a, blockIdx.x, tid);
+    mgt_fetch_rhs<NPT, NT, CR, HC, TS>(rawf, a, fsrc, blockIdx.x, tid);
+    mgt_store_visc<NPT, NT, CR, HC, TS>(rawe, a, blockIdx.x, ES, EN, TAB[0], tid);
+    const int tile = blockIdx.x, ty = tile / a.tiles_x, tx = tile % a.tiles_x;
+    const int ti0 = g.gi0 + ty * TS, tj0 = g.gj0 + tx * TS;          // tiles cover this rank's block (global node indices)
+    const int ci0 = ti0 - HC, cj0 = tj0 - HC;
     MgtC kz[NPT], kx[NPT];
     int depth[NPT];                                 // distance of the node from the border of the region; -1: no node
 #pragma unroll
@@ -2632,17 +2737,12 @@ __global__ __launch_bounds__(mgt_nt(mgt_pre_nn(NS + EXT, TS))) void k_mg_pre(MgT
         depth[q] = have ? min(min(ra, CR - 1 - ra), min(rb, CR - 1 - rb)) : -1;
         kz[q] = mgt_classify<true>(a.op, CR, CR, ci0, cj0, ra, rb);
         kx[q] = mgt_classify<false>(a.op, CR, CR, ci0, cj0, ra, rb);
-        const bool inmem = i - g.gi0 >= -PL_RING && i - g.gi0 < g.lnz + PL_RING && j - g.gj0 >= -PL_RING && j - g.gj0 < g.lnx + PL_RING;
-        const long long c = pl_idx(g, i - g.gi0, j - g.gj0);
-        const double* const fsrc = L0 ? a.rs : a.f;
-        if (kz[q].on) kz[q].f = fsrc[c + kz[q].d];
-        if (kx[q].on) kx[q].f = fsrc[c + (long long)kx[q].d * g.pitch + P];
-        if (have) {
-            ES[idx] = inmem ? a.op.etas[c] : 0.0; EN[idx] = inmem ? a.op.etan[c] : 0.0;
-            if (L0) {
-                const bool indom = i >= 0 && i < g.nz && j >= 0 && j < g.nx;
-                ZP[idx] = indom ? prec_p_value(a.sop, a.rs + 2 * P, i, j, c) : 0.0;
-            }
+        if (kz[q].on) kz[q].f = rawf.fz[q];
+        if (kx[q].on) kx[q].f = rawf.fx[q];
+        if (L0 && have) {
+            const long long c = pl_idx(g, i - g.gi0, j - g.gj0);
+            const bool indom = i >= 0 && i < g.nz && j >= 0 && j < g.nx;
+            ZP[idx] = indom ? prec_p_value(a.sop, a.rs + 2 * P, i, j, c) : 0.0;
         }
     }
     __syncthreads();
@@ -2753,15 +2853,24 @@ __global__ __launch_bounds__(mgt_nt(mgt_post_nn(NS, TS))) void k_mg_post(MgTileA
     __shared__ double EC[2][ENN];
     __shared__ double TAB[4][CR + 4];
     double* const ES = V[0][0]; double* const EN = V[0][1];
+    double* const PVz = V[1][0]; double* const PVx = V[1][1];
     const PlGeom& g = a.op.g; const PlGeom& gc = a.opc.g;
     const int tid = threadIdx.x;
-    const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x % a.tiles_x;
+    MgtTab t; t.es = ES; t.en = EN; t.rdz = TAB[0]; t.rDz = TAB[1]; t.rdx = TAB[2]; t.rDx = TAB[3];
+    MgtRawV<NPT> rawv;
+    MgtRawC rawc;
+    MgtRawE<NPT> rawe;
+    MgtRawF<NPT> rawf;
+    mgt_fetch_v<NPT, NT, CR, HC, TS>(rawv, a, blockIdx.x, tid);
+    mgt_fetch_ec<NT, TS, H, ECR>(rawc, a, blockIdx.x, tid);
+    mgt_fetch_visc<NPT, NT, CR, HC, TS>(rawe, a, blockIdx.x, tid);
+    mgt_fetch_rhs<NPT, NT, CR, HC, TS>(rawf, a, a.f, blockIdx.x, tid);
+    mgt_store_v<NPT, NT, CR, HC, TS>(rawv, a, blockIdx.x, PVz, PVx, tid);
+    mgt_store_ec<NT, TS, H, ECR>(rawc, a, blockIdx.x, EC[0], EC[1], tid);
+    mgt_store_visc<NPT, NT, CR, HC, TS>(rawe, a, blockIdx.x, ES, EN, TAB[0], tid);
+    const int tile = blockIdx.x, ty = tile / a.tiles_x, tx = tile % a.tiles_x;
     const int ti0 = g.gi0 + ty * TS, tj0 = g.gj0 + tx * TS;
     const int ci0 = ti0 - HC, cj0 = tj0 - HC;
-    MgtTab t; t.es = ES; t.en = EN; t.rdz = TAB[0]; t.rDz = TAB[1]; t.rdx = TAB[2]; t.rDx = TAB[3];
-    mgt_load_table(TAB[0], a.op.rdz, ci0 - 1, CR + 3, g.nz); mgt_load_table(TAB[1], a.op.rDz, ci0 - 1, CR + 3, g.nz);
-    mgt_load_table(TAB[2], a.op.rdx, cj0 - 1, CR + 3, g.nx); mgt_load_table(TAB[3], a.op.rDx, cj0 - 1, CR + 3, g.nx);
-    const long long P = g.plane;
     const int eI0 = ((ti0 - H) >> 1) - 2, eJ0 = ((tj0 - H) >> 1) - 2;      // coarse node of EC element (0, 0)
     MgtC kz[NPT], kx[NPT];
     int depth[NPT];
@@ -2769,24 +2878,12 @@ __global__ __launch_bounds__(mgt_nt(mgt_post_nn(NS, TS))) void k_mg_post(MgTileA
     for (int q = 0; q < NPT; q++) {
         const int idx = tid + q * NT;
         const bool have = idx < NN;
-        const int ra = have ? idx / CR : 0, rb = have ? idx % CR : 0, i = ci0 + ra, j = cj0 + rb;
+        const int ra = have ? idx / CR : 0, rb = have ? idx % CR : 0;
         depth[q] = have ? min(min(ra, CR - 1 - ra), min(rb, CR - 1 - rb)) : -1;
         kz[q] = mgt_classify<true>(a.op, CR, CR, ci0, cj0, ra, rb);
         kx[q] = mgt_classify<false>(a.op, CR, CR, ci0, cj0, ra, rb);
-        const bool inmem = i - g.gi0 >= -PL_RING && i - g.gi0 < g.lnz + PL_RING && j - g.gj0 >= -PL_RING && j - g.gj0 < g.lnx + PL_RING;
-        const long long c = pl_idx(g, i - g.gi0, j - g.gj0);
-        if (kz[q].on) kz[q].f = a.f[c + kz[q].d];
-        if (kx[q].on) kx[q].f = a.f[c + (long long)kx[q].d * g.pitch + P];
-        if (have) {
-            ES[idx] = inmem ? a.op.etas[c] : 0.0; EN[idx] = inmem ? a.op.etan[c] : 0.0;
-            V[1][0][idx] = inmem ? a.v[c] : 0.0; V[1][1][idx] = inmem ? a.v[c + P] : 0.0;     // the pre-smoothed iterate
-        }
-    }
-    for (int idx = tid; idx < ENN; idx += NT) {
-        const int I = eI0 + idx / ECR, J = eJ0 + idx % ECR;
-        const bool inmem = I - gc.gi0 >= -PL_RING && I - gc.gi0 < gc.lnz + PL_RING && J - gc.gj0 >= -PL_RING && J - gc.gj0 < gc.lnx + PL_RING;
-        const long long cc = pl_idx(gc, I - gc.gi0, J - gc.gj0);
-        EC[0][idx] = inmem ? a.ec[cc] : 0.0; EC[1][idx] = inmem ? a.ec[cc + gc.plane] : 0.0;
+        if (kz[q].on) kz[q].f = rawf.fz[q];
+        if (kx[q].on) kx[q].f = rawf.fx[q];
     }
     __syncthreads();
 #pragma unroll
@@ -2808,7 +2905,7 @@ __global__ __launch_bounds__(mgt_nt(mgt_post_nn(NS, TS))) void k_mg_post(MgTileA
                 int Jn = jm >> 1, Jo = (jm & 1) ? Jn + 1 : Jn - 1;
                 Jn = min(max(Jn, 0), gc.nx - 2); Jo = min(max(Jo, 0), gc.nx - 2);
                 const double pa = 0.5 * (ecz(I0, Jn) + ecz(I1, Jn)), pb = 0.5 * (ecz(I0, Jo) + ecz(I1, Jo));
-                oz = s * (V[1][0][idx + d] + (0.75 * pa + 0.25 * pb));
+                oz = s * (PVz[idx + d] + (0.75 * pa + 0.25 * pb));
             }
             if (mgt_cls_x(a.op, i, j, d, s) != VV_ZERO) {
                 const int im = i + d;
@@ -2816,7 +2913,7 @@ __global__ __launch_bounds__(mgt_nt(mgt_post_nn(NS, TS))) void k_mg_post(MgTileA
                 int In = im >> 1, Io = (im & 1) ? In + 1 : In - 1;
                 In = min(max(In, 0), gc.nz - 2); Io = min(max(Io, 0), gc.nz - 2);
                 const double pa = 0.5 * (ecx(In, J0) + ecx(In, J1)), pb = 0.5 * (ecx(Io, J0) + ecx(Io, J1));
-                ox = s * (V[1][1][idx + d * CR] + (0.75 * pa + 0.25 * pb));
+                ox = s * (PVx[idx + d * CR] + (0.75 * pa + 0.25 * pb));
             }
             V[0][0][idx] = oz; V[0][1][idx] = ox;
         }
@@ -3253,19 +3350,16 @@ static void vcycle_fused_level(pl_ctx* ctx, PlSolver* S, size_t l, const double*
     const dim3 grid((unsigned)(a.tiles_x * ((own_z + TS - 1) / TS)));
     cheb_coeffs(L->lmax, S->cheb_ratio, npre, a.c1, a.c2);
     if (rs) { a.sop = *sop; a.rs = rs; a.z = z; }
-#define MGT_PRE(NS, L0) do { if (TS == 32) hipLaunchKernelGGL((k_mg_pre<NS, L0, 32>), grid, dim3(mgt_nt(mgt_pre_nn(NS, 32))), 0, ctx->stream, a); \
-                             else hipLaunchKernelGGL((k_mg_pre<NS, L0, MGT_TS>), grid, dim3(mgt_nt(mgt_pre_nn(NS, MGT_TS))), 0, ctx->stream, a); } while (0)
-#define MGT_PRE_X(NS) do { if (TS == 32) hipLaunchKernelGGL((k_mg_pre<NS, false, 32, 1>), grid, dim3(mgt_nt(mgt_pre_nn(NS + 1, 32))), 0, ctx->stream, a); \
-                           else hipLaunchKernelGGL((k_mg_pre<NS, false, MGT_TS, 1>), grid, dim3(mgt_nt(mgt_pre_nn(NS + 1, MGT_TS))), 0, ctx->stream, a); } while (0)
+#define MGT_PRE(NS, L0, EXT) do { if (TS == 32) hipLaunchKernelGGL((k_mg_pre<NS, L0, 32, EXT>), grid, dim3(mgt_nt(mgt_pre_nn(NS + EXT, 32))), 0, ctx->stream, a); \
+                                  else hipLaunchKernelGGL((k_mg_pre<NS, L0, MGT_TS, EXT>), grid, dim3(mgt_nt(mgt_pre_nn(NS + EXT, MGT_TS))), 0, ctx->stream, a); } while (0)
     if (L->dist) {
         (void)pl_halo(ctx, g, (double*)a.f, 2, g.plane, npre + 2);          // ONE exchange on the way down: the right-hand side
-        if (npre == 1) MGT_PRE_X(1); else if (npre == 2) MGT_PRE_X(2); else MGT_PRE_X(3);
+        if (npre == 1) MGT_PRE(1, false, 1); else if (npre == 2) MGT_PRE(2, false, 1); else MGT_PRE(3, false, 1);
         if (!C->dist) (void)pl_gather_blocks(ctx, C->gh.d, C->f, 2, C->gh.d.plane);      // replicated coarse level: everybody's restricted residual
     }
-    else if (rs) { if (npre == 1) MGT_PRE(1, true); else if (npre == 2) MGT_PRE(2, true); else MGT_PRE(3, true); }
-    else { if (npre == 1) MGT_PRE(1, false); else if (npre == 2) MGT_PRE(2, false); else MGT_PRE(3, false); }
+    else if (rs) { if (npre == 1) MGT_PRE(1, true, 0); else if (npre == 2) MGT_PRE(2, true, 0); else MGT_PRE(3, true, 0); }
+    else { if (npre == 1) MGT_PRE(1, false, 0); else if (npre == 2) MGT_PRE(2, false, 0); else MGT_PRE(3, false, 0); }
 #undef MGT_PRE
-#undef MGT_PRE_X
     double* ec = nullptr;
     bool wf = false;
     vcycle<double>(ctx, S, l + 1, C->f, &ec, &wf, nullptr, 1.0, 0, nullptr);      // (takes the tile kernels itself where it can)
