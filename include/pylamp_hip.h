@@ -424,6 +424,16 @@ int  pl3_stokes_rhs_scaled(pl3_ctx* ctx, double* rhs);
 int  pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int use_x0, double rtol, int maxit, pl_solve_stats* stats);
 int  pl3_stokes_apply_bench(pl3_ctx* ctx, int scaled, int reps, double* avg_ms);     /* 80 B/node algorithmic */
 int  pl3_stokes_mg_info(pl3_ctx* ctx, int* nlevels, double* lmax, int max_levels);
+/* Diagnostics for component tests of the 3-D solver (the counterparts of pl_stokes_precond_apply / pl_stokes_mg_plan).
+ * pl3_stokes_precond_apply: z = M^-1 r on host vectors (nz, nx, ny, 4); r is the ROW-SCALED residual exactly as the Krylov iteration
+ * hands it to the preconditioner (rows without an equation are ignored).  Builds or refreshes the multigrid hierarchy as a solve does
+ * (lmax is re-estimated), applies the solve's own preconditioner once without the deflation correction.  Collective on a context with
+ * pl3_set_comm attached; every rank receives the global z.
+ * pl3_stokes_mg_plan (read-only; any pointer may be NULL; valid once the hierarchy is built): nu[2] = Chebyshev sweeps before and after
+ * the coarse correction on the finest level and on the other levels (the >= 10^6-node rule, PYLAMP_MG_NU3 / PYLAMP_MG_NU3_FINE), the
+ * ratio lmax / lmin of their window, sweeps and ratio of the coarsest level, and lds[l] != 0 where the marching LDS kernels take level l. */
+int  pl3_stokes_precond_apply(pl3_ctx* ctx, const double* r, double* z);
+int  pl3_stokes_mg_plan(pl3_ctx* ctx, int* nu, double* ratio, int* coarse_sweeps, double* coarse_ratio, int* lds, int max_levels);
 int  pl3_heat_set_coeffs(pl3_ctx* ctx, const double* zmp, const double* xmp, const double* ymp, const double* T, const double* kz,
                          const double* kx, const double* ky, const double* cp, const double* rho, const double* H, const int bc[6],
                          const double bcvalue[6], double tstep);

@@ -90,6 +90,8 @@ SIGNATURES = {
     "pl3_stokes_solve": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.POINTER(SolveStats)]),
     "pl3_stokes_apply_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),
     "pl3_stokes_mg_info": (C.c_int, [C.c_void_p, c_int_p, c_double_p, C.c_int]),
+    "pl3_stokes_precond_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "pl3_stokes_mg_plan": (C.c_int, [C.c_void_p, c_int_p, c_double_p, c_int_p, c_double_p, c_int_p, C.c_int]),
     "pl3_heat_set_coeffs": (C.c_int, [C.c_void_p] + [c_double_p] * 10 + [c_int_p, c_double_p, C.c_double]),
     "pl3_heat_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),

@@ -1714,14 +1714,25 @@ static int smooth3(pl3_ctx* ctx, Lev3* L, double* const* f, int nsweep, double r
     }
     return 0;
 }
+// the coarsest level's smoothing: ratio by its size (floor 30), sweeps sqrt(ratio) within coarse_sweeps .. 150
+static void coarsest_plan3(const pl3_ctx* ctx, const G3& g, int& n, double& ratio) {
+    ratio = 0.4 * std::pow((double)g.gn[0] * g.gn[1] * g.gn[2], 2.0 / 3.0); if (ratio < 30.0) ratio = 30.0;
+    n = std::max((int)std::sqrt(ratio), ctx->coarse_sweeps); if (n > 150) n = 150;
+}
+// sweeps on the finest level and on the others
+static void level_nu3(const pl3_ctx* ctx, int& nu_fine, int& nu_rest) {
+    const bool big = (long long)ctx->gn[0] * ctx->gn[1] * ctx->gn[2] >= 1000000;
+    nu_fine = ctx->nu_fine > 0 ? ctx->nu_fine : (big && !ctx->nu_set ? 1 : ctx->nu);
+    nu_rest = (big && !ctx->nu_set) ? 3 : ctx->nu;
+}
 // one V-cycle of level l for the right-hand side f; the result is in buffer out_buf of the level (or in final_out)
 static int vcycle3(pl3_ctx* ctx, size_t l, double* const* f, int& out_buf, const W3* final_out = nullptr) {
     Lev3* L = ctx->levels[l];
     const G3& g = L->gh.d;
     int cur = 0;
     if (l + 1 == ctx->levels.size()) {
-        double ratio = 0.4 * std::pow((double)g.gn[0] * g.gn[1] * g.gn[2], 2.0 / 3.0); if (ratio < 30.0) ratio = 30.0;
-        int n = std::max((int)std::sqrt(ratio), ctx->coarse_sweeps); if (n > 150) n = 150;
+        double ratio; int n;
+        coarsest_plan3(ctx, g, n, ratio);
         P3_TRY(smooth3(ctx, L, f, n, ratio, true, cur));
         out_buf = cur;
         return 0;
@@ -1729,9 +1740,8 @@ static int vcycle3(pl3_ctx* ctx, size_t l, double* const* f, int& out_buf, const
     // From 10^6 nodes up: V(1,1) on the finest level, V(3,3) below (the 2-D solver's choice, pl_solver.hip) -- 257^3: 494 ms per solve
     // pair with 24 iterations against 539 ms with 23 for V(2,2) throughout (1/4: 492, 2/3: 499, 1/2: 504; tools/run_nu3.sh).
     // PYLAMP_MG_NU3 / PYLAMP_MG_NU3_FINE override the two counts.
-    const bool big = (long long)ctx->gn[0] * ctx->gn[1] * ctx->gn[2] >= 1000000;
-    const int nu_fine = ctx->nu_fine > 0 ? ctx->nu_fine : (big && !ctx->nu_set ? 1 : ctx->nu);
-    const int nu_rest = (big && !ctx->nu_set) ? 3 : ctx->nu;
+    int nu_fine, nu_rest;
+    level_nu3(ctx, nu_fine, nu_rest);
     const int nu = l == 0 ? nu_fine : nu_rest;
     P3_TRY(smooth3(ctx, L, f, nu, ctx->cheb_ratio, true, cur));
     P3_TRY(halo3(ctx, g, L->v[cur], 3));
@@ -2139,6 +2149,34 @@ extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int 
 extern "C" int pl3_stokes_mg_info(pl3_ctx* ctx, int* nlevels, double* lmax, int max_levels) {
     if (nlevels) *nlevels = (int)ctx->levels.size();
     for (int l = 0; lmax && l < max_levels && l < (int)ctx->levels.size(); l++) lmax[l] = ctx->levels[l]->lmax;
+    return 0;
+}
+// What vcycle3 does on a hierarchy of this context (read-only; any pointer may be NULL): nu[2] = sweeps on the finest level and on the
+// others, the Chebyshev ratio of their window, sweeps and ratio of the coarsest level, and per level whether the marching LDS kernels
+// take it.  Valid once the hierarchy is built (a solve or pl3_stokes_precond_apply).
+extern "C" int pl3_stokes_mg_plan(pl3_ctx* ctx, int* nu, double* ratio, int* coarse_sweeps, double* coarse_ratio, int* lds, int max_levels) {
+    if (nu) level_nu3(ctx, nu[0], nu[1]);
+    if (ratio) *ratio = ctx->cheb_ratio;
+    int cn = 0; double cr = 0.0;
+    if (!ctx->levels.empty()) coarsest_plan3(ctx, ctx->levels.back()->gh.d, cn, cr);
+    if (coarse_sweeps) *coarse_sweeps = cn;
+    if (coarse_ratio) *coarse_ratio = cr;
+    for (int l = 0; lds && l < max_levels && l < (int)ctx->levels.size(); l++) lds[l] = k3_use_lds(ctx->levels[l]->gh.d) ? 1 : 0;
+    return 0;
+}
+// z = M^-1 r by stokes_M3 itself, without the deflation correction: r is the row-scaled residual as bicgstab3 hands it over
+extern "C" int pl3_stokes_precond_apply(pl3_ctx* ctx, const double* r, double* z) {
+    if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
+    if (!r || !z) return p3_fail(ctx, "pl3_stokes_precond_apply: NULL argument");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    P3_TRY(build_levels3(ctx));
+    const Vec3 R = svec(ctx, 0), Z = svec(ctx, 1);
+    P3_TRY(upload3(ctx, r, 4, wv4(R).p));
+    ctx->dfl_active = false;
+    P3_TRY(stokes_M3(ctx, R, Z));
+    P3_HIP(ctx, hipGetLastError());
+    P3_TRY(download3(ctx, wv4(Z).p, 4, z));
     return 0;
 }
 

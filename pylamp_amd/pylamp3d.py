@@ -229,6 +229,25 @@ class StokesOperator3:
         self._ctx.check(self._ctx.lib.pl3_stokes_mg_info(self._ctx.handle(), C.byref(n), lm, 32))
         return n.value, [lm[k] for k in range(n.value)]
 
+    def precond(self, r):
+        """z = M^-1 r by the solve's own preconditioner (no deflation correction); r: the row-scaled residual, (nz, nx, ny, 4).
+        Builds or refreshes the hierarchy first, as a solve does.  Collective on an attached context; returns the global z."""
+        r = _lib.f64(r).reshape(-1)
+        if r.size != self.shape[0]:
+            raise Exception("dimension mismatch")
+        z = np.empty_like(r)
+        self._ctx.check(self._ctx.lib.pl3_stokes_precond_apply(self._ctx.handle(), _lib.dptr(r), _lib.dptr(z)))
+        return z
+
+    def mg_plan(self):
+        """What the V-cycle does on the built hierarchy: sweeps on the finest level and on the others, the Chebyshev ratio, the
+        coarsest level's sweeps and ratio, and per level whether the marching LDS kernels take it."""
+        nu = (C.c_int * 2)(); ratio = C.c_double(); cn = C.c_int(); cr = C.c_double(); lds = (C.c_int * 32)()
+        n = self.mg_info()[0]
+        self._ctx.check(self._ctx.lib.pl3_stokes_mg_plan(self._ctx.handle(), nu, C.byref(ratio), C.byref(cn), C.byref(cr), lds, 32))
+        return dict(nu_fine=nu[0], nu=nu[1], ratio=ratio.value, coarse_sweeps=cn.value, coarse_ratio=cr.value,
+                    lds=[bool(lds[k]) for k in range(n)])
+
 
 def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True, wallvel=None):
     """3-D counterpart of pylamp_stokes.makeStokesMatrix: f_etas at the NODES (averaged onto the edges by the kernels),

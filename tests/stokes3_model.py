@@ -8,6 +8,8 @@ Arrays are (nz, nx, ny); vz lives at (z_i, x_j+1/2, y_k+1/2), vx at (z_i+1/2, x_
 P and etan at the cell centres, etas and rho at the nodes; the last index of an axis along which a quantity sits at
 midpoints is a ghost.  Vectors are C-order (nz, nx, ny, 4) with the components vz, vx, vy, P (pylamp3d.gidx).
 """
+import contextlib
+
 import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
@@ -20,6 +22,18 @@ FIXTEMP, FIXFLOW = 0, 1
 
 def _ld(a):
     return np.asarray(a, dtype=LD)
+
+
+@contextlib.contextmanager
+def working_precision(dtype):
+    """Inside the block every function of this module (and of stokes3_walls_model) works in `dtype` instead of np.longdouble: the
+    same expressions evaluated in float64 (tests/stokes3_mg_model.py: its float64 evaluation and its eigenvalue estimates)."""
+    global LD
+    old, LD = LD, dtype
+    try:
+        yield
+    finally:
+        LD = old
 
 
 def _out(y, rounded):

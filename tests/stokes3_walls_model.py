@@ -11,7 +11,6 @@ import numpy as np
 
 import stokes3_model as M
 
-LD = np.longdouble
 NOSLIP, FREESLIP = 0, 1
 WALLS = ("z0", "x0", "y0", "zL", "xL", "yL")
 _ld = M._ld
@@ -33,8 +32,8 @@ def stokes_apply(nx, grid, etas, etan, x, bc=None, strict=True, rounded=True):
     """The unscaled operator, as pl3_stokes_apply after pl3_stokes_set_walls(bc)."""
     n = [int(v) for v in nx]
     kinds = walls(bc)
-    Y = np.array(M.stokes_apply(n, grid, etas, etan, x, strict=strict, rounded=False), dtype=LD).reshape(n + [4])
-    Kc = LD(M.scaling(grid, etas, etan)[0])
+    Y = np.array(M.stokes_apply(n, grid, etas, etan, x, strict=strict, rounded=False), dtype=M.LD).reshape(n + [4])
+    Kc = M.LD(M.scaling(grid, etas, etan)[0])
     X = _ld(x).reshape(n + [4])
     es = _ld(etas)
     ix = M._index(n)
