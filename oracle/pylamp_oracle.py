@@ -560,8 +560,10 @@ def trac2grid(tr_x, tr_f, grid, nx, avgscheme=None):
     # NOTE the accumulator shape in the reference is mesh[0].shape, i.e. the *extended*
     # shape when the grid was modified and the caller's mesh shape otherwise.
     ie, je = _cell_lookup(tr_x, g, n)
-    if RECT_SEARCH:      # a marker exactly on the last coordinate belongs to the last cell (a = 1)
-        ie = np.minimum(ie, n[0] - 2); je = np.minimum(je, n[1] - 2)
+    if RECT_SEARCH:      # a marker exactly on the last coordinate of the caller's node set belongs to its last cell (a = 1),
+        for d, idx in ((IZ, ie), (IX, je)):     # whether or not other markers lie beyond it (include/pylamp_hip.h, mic_axis_locate)
+            last = addl[d] + len(grid[d]) - 1
+            idx[tr_x[:, d] == g[d][last]] = last - 1
     a = (tr_x[:, IZ] - g[IZ][ie]) / (g[IZ][ie + 1] - g[IZ][ie])
     b = (tr_x[:, IX] - g[IX][je]) / (g[IX][je + 1] - g[IX][je])
     w = [(1 - b) * (1 - a), (1 - b) * a, b * (1 - a), b * a]

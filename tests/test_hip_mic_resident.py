@@ -43,10 +43,10 @@ def _targets(oracle, nx, L):
     return {"nodes": grid, "centres": gmp, "zmid": [gmp[0], grid[1]], "xmid": [grid[0], gmp[1]]}
 
 
-def _sim(nx, L, tr_x, tr_f, **kw):
+def _sim(nx, L, tr_x, tr_f, grid=None, **kw):
     from pylamp_amd import driver
     opt = driver.Options(tdep_rho=False, tdep_eta=False, **kw)          # rho = RH0, eta = ET0: the fixture's columns as they are
-    return driver.Simulation(nx, L, tr_x, tr_f, opt)
+    return driver.Simulation(nx, L, tr_x, tr_f, opt, grid=grid)
 
 
 @pytest.mark.parametrize("case", ["dense", "sparse", "outside"])
