@@ -413,6 +413,34 @@ int  pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]);
  *  - identity rows, pressure rows and all coarse levels are unchanged: corrections are homogeneous. */
 int  pl3_stokes_set_wall_velocity(pl3_ctx* ctx, const double vel[18]);
 int  pl3_stokes_get_wall_velocity(pl3_ctx* ctx, double vel[18]);
+/* Flow through walls.  For wall w of [z0, x0, y0, zL, xL, yL] with axis a, let p < q be the two other axes in z, x, y order.  flow[w]
+ * is an array Un_w of (n_p - 1) x (n_q - 1) doubles, entry i (n_q - 1) + j the wall-normal velocity on the wall face between the nodes
+ * i, i + 1 along p and j, j + 1 along q -- where v_a lives on that wall plane -- as the component along +a (the convention of
+ * pl3_stokes_set_wall_velocity): positive is inflow on z0, x0, y0 and outflow on zL, xL, yL.  flow[w] == NULL: no flow through wall w;
+ * all NULL (or flow == NULL) clears the setting, the state at creation.  A wall of either kind may carry a flow; a NOSLIP wall keeps
+ * its tangential velocity, possibly zero.  The indices are GLOBAL: every rank of a pl3_set_comm decomposition is given the same six
+ * planes.  The state belongs to the context, survives pl3_stokes_set_coeffs and pl3_stokes_set_walls, and is read by
+ * pl3_stokes_rhs[_scaled], the solves of the operator's own right-hand side, pl3_resident_step and pl3_advection_velocity.
+ *  - Matrix: unchanged.  So on the edge of a FREESLIP wall whose Un varies along the wall the rows keep their dv_a/dx half of the shear
+ *    stress (the wall is free of the OTHER half only), and with slaved rows the cube-edge cells keep their pressure-symmetry rows in
+ *    place of continuity.
+ *  - Right-hand side: the identity rows of the wall-normal velocities -- component a at global index 0 or n_a - 1 along a and at most
+ *    n_p - 2, n_q - 2 along p, q -- gain Kcont Un_w[i, j] (row-scaled: Un_w[i, j]); the ghost entries beyond stay 0 and no other row
+ *    changes.  A right-hand side handed to pl3_stokes_solve stays as given.
+ *  - Net flux: Phi = sum_w s_w sum_ij Un_w[i, j] dp_i dq_j with s = +1 on z0, x0, y0 and -1 on zL, xL, yL, summed in long double on
+ *    the host.  |Phi| > 1e-10 sum |Un| dp dq is an error that gives Phi and the six wall fluxes: the pressure anchor cell would absorb
+ *    Phi as a divergence (1e-10 is a thousand times below the solve's rtol of 1e-7 and far above the rounding of the sum).  Hence all
+ *    six walls in one call.
+ *  - Advection ghosts (pl3_advection_velocity, pl3_resident_step): the pass of a wall with a flow runs in its slot of the order z0 ..
+ *    yL, even for a NOSLIP wall at rest.  From the neighbouring plane as it is at that moment it writes 2 Un_w[ci, cj] - V for the
+ *    normal component (ci, cj: the padded tangential indices minus 1, clamped to [0, n - 2]), so that the velocity interpolated onto
+ *    the wall is Un; tangential components are copied on a FREESLIP wall and follow 2 U_c - V on a NOSLIP wall.  Walls without a flow
+ *    keep their arithmetic bit for bit.
+ * Errors, a rejected call changing nothing: a NULL context; a non-finite entry (names the wall and the index); the net flux. */
+int  pl3_stokes_set_wall_flow(pl3_ctx* ctx, const double* const flow[6]);
+/* *mask: bit w set = wall w carries a flow; flow[w] != NULL receives the plane of such a wall, downloaded from the device (either
+ * argument may be NULL) */
+int  pl3_stokes_get_wall_flow(pl3_ctx* ctx, int* mask, double* const flow[6]);
 int  pl3_stokes_get_scaling(pl3_ctx* ctx, double* kcont, double* kbond);
 int  pl3_stokes_apply(pl3_ctx* ctx, const double* x, double* y);
 int  pl3_stokes_rhs(pl3_ctx* ctx, double* rhs);
@@ -499,6 +527,12 @@ int  pl3_mic_get_search(pl3_ctx* ctx, int* on);
  * pl3_tracers_removed: out = { tracers removed by the last sort, removed since the last pl3_tracers_upload (its own included) }. */
 int  pl3_mic_set_deletion(pl3_ctx* ctx, int on);
 int  pl3_mic_get_deletion(pl3_ctx* ctx, int* on);
+/* RK4 weights of the 3-D marker advection of this context (pl3_rk4, pl3_resident_rk4, pl3_resident_advect, pl3_resident_step).  Off,
+ * the default: the reference's x + dt (k1 + k2 + k3 + k4) / 6 (pylamp_trac.py:385), whose weights sum to 4/6, so that a uniform field U
+ * moves a tracer by 2/3 U dt; every result is what it was.  On: the classical x + dt (k1 + 2 k2 + 2 k3 + k4) / 6, which moves it by U dt.
+ * A flow through the walls (pl3_stokes_set_wall_flow) wants it on: the markers then carry the volume that the wall flux brings in. */
+int  pl3_mic_set_rk4_classic(pl3_ctx* ctx, int on);
+int  pl3_mic_get_rk4_classic(pl3_ctx* ctx, int* on);
 int  pl3_tracers_removed(pl3_ctx* ctx, int64_t out[2]);
 int  pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f);
 int  pl3_tracers_download(pl3_ctx* ctx, int64_t n, double* tr_x, double* tr_f);

@@ -83,6 +83,8 @@ SIGNATURES = {
     "pl3_stokes_set_walls": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pl3_stokes_set_wall_velocity": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_stokes_get_wall_velocity": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_stokes_set_wall_flow": (C.c_int, [C.c_void_p, C.POINTER(c_double_p)]),
+    "pl3_stokes_get_wall_flow": (C.c_int, [C.c_void_p, c_int_p, C.POINTER(c_double_p)]),
     "pl3_stokes_get_scaling": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_rhs": (C.c_int, [C.c_void_p, c_double_p]),
@@ -108,6 +110,8 @@ SIGNATURES = {
     "pl3_mic_get_search": (C.c_int, [C.c_void_p, c_int_p]),
     "pl3_mic_set_deletion": (C.c_int, [C.c_void_p, C.c_int]),
     "pl3_mic_get_deletion": (C.c_int, [C.c_void_p, c_int_p]),
+    "pl3_mic_set_rk4_classic": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl3_mic_get_rk4_classic": (C.c_int, [C.c_void_p, c_int_p]),
     "pl3_tracers_removed": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "pl3_tracers_upload": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),
     "pl3_tracers_download": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p]),

@@ -282,11 +282,25 @@ template <int A, int D> __device__ inline double wall_rhs3(const Op3& op, const 
     if ((ia != 0 && ia != op.g.gn[A] - 2) || !((mv.moving >> (A + 3 * hi)) & 1)) return 0.0;
     return wall_coef3<A>(op, ia, em, ep) * wall_vel3<A, D>(mv, hi);
 }
-template <int D> __device__ inline double rhs_vel3(const Op3& op, const Pl3WallVel& mv, long long c, const int* idx, bool scaled) {
+// ---- flow through walls (pl3_stokes_set_wall_flow; include/pylamp_hip.h).  Affine as well: the identity row of a wall-normal
+// velocity v_D on the wall plane of D (global index 0 or n_D - 1, and at most n - 2 along the two other axes) gains Un -- unscaled Kc Un --
+// read from the wall's plane by the global face indices, so that every block of a decomposition reads the same six planes.  The planes
+// travel as an argument of k3_rhs alone; mask == 0 skips all of it.  The test on idx[D] is wave-uniform for D = z, x.
+template <int D> __device__ inline double flow_rhs3(const Op3& op, const Pl3WallFlow& fl, const int* idx, bool scaled) {
+    constexpr int E = (D + 1) % 3, F = (D + 2) % 3, P = E < F ? E : F, Q = E < F ? F : E;
+    const int* n = op.g.gn;
+    const int hi = idx[D] == 0 ? 0 : 1;
+    if ((idx[D] != 0 && idx[D] != n[D] - 1) || !((fl.mask >> (D + 3 * hi)) & 1)) return 0.0;
+    if (idx[P] > n[P] - 2 || idx[Q] > n[Q] - 2) return 0.0;                   // the ghost entries beyond stay 0
+    const double un = fl.un[D + 3 * hi][(long long)idx[P] * (n[Q] - 1) + idx[Q]];
+    return scaled ? un : op.Kc * un;
+}
+template <int D> __device__ inline double rhs_vel3(const Op3& op, const Pl3WallVel& mv, const Pl3WallFlow& fl, long long c, const int* idx, bool scaled) {
     constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
     long long moff;
     const int cl = cls3<D>(op, idx, moff);
-    if (mv.moving != 0 && cl == C3_SLAVE) {                  // the wall of the first boundary axis (E before F) supplies U
+    if (fl.mask != 0 && cl == C3_ZERO) return flow_rhs3<D>(op, fl, idx, scaled);
+    if (mv.moving != 0 && cl == C3_SLAVE) {                 // the wall of the first boundary axis (E before F) supplies U
         const int* n = op.g.gn;
         if (idx[E] == 0) return slave_rhs3<E, D>(op, mv, 0, scaled);
         if (idx[E] == n[E] - 2) return slave_rhs3<E, D>(op, mv, 1, scaled);
@@ -308,11 +322,11 @@ template <int D> __device__ inline double rhs_vel3(const Op3& op, const Pl3WallV
     }
     return scaled ? b / diag3<D>(op, c, idx) : b;
 }
-__global__ __launch_bounds__(256) void k3_rhs(Op3 op, W4 b, int scaled, Pl3WallVel mv) {
+__global__ __launch_bounds__(256) void k3_rhs(Op3 op, W4 b, int scaled, Pl3WallVel mv, Pl3WallFlow fl) {
     K3_PROLOGUE(op.g)
-    b.p[0][c] = rhs_vel3<0>(op, mv, c, idx, scaled);
-    b.p[1][c] = rhs_vel3<1>(op, mv, c, idx, scaled);
-    b.p[2][c] = rhs_vel3<2>(op, mv, c, idx, scaled);
+    b.p[0][c] = rhs_vel3<0>(op, mv, fl, c, idx, scaled);
+    b.p[1][c] = rhs_vel3<1>(op, mv, fl, c, idx, scaled);
+    b.p[2][c] = rhs_vel3<2>(op, mv, fl, c, idx, scaled);
     b.p[3][c] = 0.0;
 }
 // b *= D_r (a user-supplied right-hand side)
@@ -1174,6 +1188,9 @@ struct pl3_ctx {
     double *es = nullptr, *en = nullptr, *rho = nullptr; Op3 op{}; bool op_ready = false;
     int noslip = 0;                 // pl3_stokes_set_walls: bit w of [z0, x0, y0, zL, xL, yL] set = no-slip; kept across pl3_stokes_set_coeffs
     Pl3WallVel wallvel{};           // pl3_stokes_set_wall_velocity: U_w = (Uz, Ux, Uy) per wall and the mask of the moving ones; kept likewise
+    // pl3_stokes_set_wall_flow: the six wall planes of the through-flow, one device buffer (flow_dev) that wallflow.un points into, and
+    // their host copies; kept likewise
+    Pl3WallFlow wallflow{}; double* flow_dev = nullptr; std::vector<double> flow_host[6];
     std::vector<Lev3*> levels;
     double* vec[14] = {nullptr};                // BiCGStab work vectors: 4 consecutive arrays each (svec)
     double* part = nullptr; double* hpart = nullptr;
@@ -1297,7 +1314,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     pl3_step_free(&ctx->step3);
     pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
-    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf}) if (q) (void)hipFree(q);
+    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow_dev}) if (q) (void)hipFree(q);
     for (double* q : ctx->vec) if (q) (void)hipFree(q);
     for (double* q : ctx->hk) if (q) (void)hipFree(q);
     for (double* q : ctx->hvec) if (q) (void)hipFree(q);
@@ -1535,6 +1552,79 @@ extern "C" int pl3_stokes_get_wall_velocity(pl3_ctx* ctx, double vel[18]) {
     for (int e = 0; e < 18; e++) vel[e] = ctx->wallvel.u[e];
     return 0;
 }
+// Flow through the walls: flow[w] is the plane of wall w of [z0, x0, y0, zL, xL, yL], (n_p - 1, n_q - 1) wall-normal velocities along +a on
+// the faces of the wall (p < q the two other axes in z, x, y order), or NULL for no flow; all NULL clears the setting.  All six walls are
+// set in one call because the net flux must vanish: the anchor cell would absorb it as a divergence.  Kept on the context like the kinds
+// and the velocities; a rejected call changes nothing.
+static void flow_axes3(int w, int& p, int& q) { const int a = w % 3; p = a == 0 ? 1 : 0; q = a == 2 ? 1 : 2; }
+extern "C" int pl3_stokes_set_wall_flow(pl3_ctx* ctx, const double* const flow[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_wall_flow: NULL context");
+    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
+    size_t off[7] = {0};
+    long double flux[6] = {0, 0, 0, 0, 0, 0}, phi = 0.0L, tot = 0.0L;
+    int mask = 0;
+    for (int w = 0; w < 6; w++) {
+        int p, q;
+        flow_axes3(w, p, q);
+        const int np = ctx->gn[p] - 1, nq = ctx->gn[q] - 1;
+        off[w + 1] = off[w] + (size_t)np * nq;
+        if (!flow || !flow[w]) continue;
+        mask |= 1 << w;
+        const std::vector<double>&cp = ctx->gcoord[p], &cq = ctx->gcoord[q];
+        long double f = 0.0L;
+        for (int i = 0; i < np; i++)
+            for (int j = 0; j < nq; j++) {
+                const double u = flow[w][(size_t)i * nq + j];
+                if (!std::isfinite(u))
+                    return p3_fail(ctx, std::string("pl3_stokes_set_wall_flow: wall ") + names[w] + " has a non-finite flow entry [" + std::to_string(i) +
+                                            ", " + std::to_string(j) + "] = " + num_str3(u));
+                const long double area = ((long double)cp[i + 1] - (long double)cp[i]) * ((long double)cq[j + 1] - (long double)cq[j]);
+                f += (long double)u * area;
+                tot += std::fabs((long double)u) * area;
+            }
+        flux[w] = w < 3 ? f : -f;                             // inflow positive
+        phi += flux[w];
+    }
+    if (std::fabs(phi) > 1e-10L * tot) {
+        std::string six;
+        for (int w = 0; w < 6; w++) six += std::string(w ? ", " : "") + names[w] + " " + num_str3((double)flux[w]);
+        return p3_fail(ctx, "pl3_stokes_set_wall_flow: the net flux through the walls is " + num_str3((double)phi) + " (inflow positive), more than 1e-10 of the sum " +
+                                num_str3((double)tot) + " of |Un| over the wall faces: the walls must balance, or the pressure anchor cell absorbs the rest as a "
+                                "divergence; fluxes into the box: " + six);
+    }
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    if (mask && !ctx->flow_dev) P3_HIP(ctx, hipMalloc((void**)&ctx->flow_dev, off[6] * sizeof(double)));
+    if (mask) {
+        std::vector<double> all(off[6], 0.0);
+        for (int w = 0; w < 6; w++) if ((mask >> w) & 1) std::copy(flow[w], flow[w] + (off[w + 1] - off[w]), all.begin() + off[w]);
+        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (kernels in flight may still read the planes)
+        pl3_count_copy(ctx, off[6] * sizeof(double));
+        P3_HIP(ctx, hipMemcpy(ctx->flow_dev, all.data(), off[6] * sizeof(double), hipMemcpyHostToDevice));
+    }
+    Pl3WallFlow fl{};
+    fl.mask = mask;
+    for (int w = 0; w < 6; w++) {
+        if ((mask >> w) & 1) { fl.un[w] = ctx->flow_dev + off[w]; ctx->flow_host[w].assign(flow[w], flow[w] + (off[w + 1] - off[w])); }
+        else ctx->flow_host[w].clear();
+    }
+    ctx->wallflow = fl;
+    return 0;
+}
+// mask: bit w set = wall w carries a flow; flow[w] (NULL: not wanted) receives that wall's plane as the device holds it
+extern "C" int pl3_stokes_get_wall_flow(pl3_ctx* ctx, int* mask, double* const flow[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_get_wall_flow: NULL context");
+    if (mask) *mask = ctx->wallflow.mask;
+    if (!flow || !ctx->wallflow.mask) return 0;
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int w = 0; w < 6; w++) {
+        if (!flow[w] || !((ctx->wallflow.mask >> w) & 1)) continue;
+        const size_t bytes = ctx->flow_host[w].size() * sizeof(double);
+        pl3_count_copy(ctx, bytes);
+        P3_HIP(ctx, hipMemcpy(flow[w], ctx->wallflow.un[w], bytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
 extern "C" int pl3_stokes_get_scaling(pl3_ctx* ctx, double* kc, double* kb) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     if (kc) *kc = ctx->op.Kc; if (kb) *kb = ctx->op.Kb;
@@ -1560,7 +1650,7 @@ static int stokes_rhs3(pl3_ctx* ctx, double* rhs, int scaled) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 2));
-    launch3(ctx, ctx->op.g, k3_rhs, ctx->op, wv4(svec(ctx, 1)), scaled, ctx->wallvel);
+    launch3(ctx, ctx->op.g, k3_rhs, ctx->op, wv4(svec(ctx, 1)), scaled, ctx->wallvel, ctx->wallflow);
     P3_HIP(ctx, hipGetLastError());
     return download3(ctx, wv4(svec(ctx, 1)).p, 4, rhs);
 }
@@ -2122,7 +2212,7 @@ extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int 
     for (int q = 0; q < K_NW; q++) w[q] = svec(ctx, q);
     const Vec3 B = svec(ctx, 10), X = svec(ctx, 11), XH = svec(ctx, 12);
     if (rhs) { P3_TRY(upload3(ctx, rhs, 4, wv4(B).p)); launch3(ctx, g, k3_scale_rows, ctx->op, wv4(B)); }
-    else launch3(ctx, g, k3_rhs, ctx->op, wv4(B), 1, ctx->wallvel);
+    else launch3(ctx, g, k3_rhs, ctx->op, wv4(B), 1, ctx->wallvel, ctx->wallflow);
     ctx->napply = ctx->nprec = 0;
     ctx->dfl_active = false; ctx->dfl_yAw = 1.0; ctx->dfl_wvel2 = 0.0;
     double ref = 0.0;
@@ -2297,6 +2387,7 @@ int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     v->s0 = g.s[0]; v->s1 = g.s[1]; v->pad = P3_PAD; v->stream = ctx->stream; v->slot = &ctx->step3;
     for (int q = 0; q < 4; q++) { v->X[q] = svec(ctx, 11)[q]; v->scratch[q] = svec(ctx, 0)[q]; }
     v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T; v->noslip = ctx->noslip; v->wallvel = ctx->wallvel;
+    v->wallflow = ctx->wallflow;
     return 0;
 }
 // counts and bytes of the host <-> device copies of this context's pl3_* calls since the last reset: out = { copies of at least one

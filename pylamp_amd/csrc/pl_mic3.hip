@@ -564,11 +564,14 @@ __global__ __launch_bounds__(256) void k_m3_gather(M3Gather a) {
 }
 
 // RK4 with the reference's weights (1,1,1,1)/6 (pylamp_trac.py:385) and v = (x_new - x)/dt; the four stages of a tracer run in
-// registers.  72 B/tracer: read the position, write the new one and the velocity; the velocity grid is read through the caches.
+// registers.  Those weights sum to 4/6, so a uniform field U moves a tracer by 2/3 U dt.  classic != 0 (pl3_mic_set_rk4_classic, opt-in)
+// takes the classical weights (1,2,2,1)/6 instead, with which it moves by U dt -- what a flow through the walls needs, where the markers
+// must carry the volume that the wall flux brings in.  The default arithmetic is untouched.  72 B/tracer: read the position, write the new one and the velocity; the velocity grid is read through the caches.
 struct M3Rk4 {
     long long n; M3Pos p; M3Grid g; const double* V[3]; double dt;
     double* xo[3]; double* vo[3]; long long os;
     int fence; double eps, L[3];                   // pylamp2.py:558-572 per axis
+    int classic;
 };
 template <bool SEARCH>
 __global__ __launch_bounds__(256) void k_m3_rk4(M3Rk4 a) {
@@ -585,7 +588,9 @@ __global__ __launch_bounds__(256) void k_m3_rk4(M3Rk4 a) {
     for (int d = 0; d < 3; d++) q[d] = x[d] + dt * k3[d];
     m3_veldiv<SEARCH>(a.g, a.V[0], a.V[1], a.V[2], q, 0.0, k4, bad);
     for (int d = 0; d < 3; d++) {
-        const double xn = x[d] + (1.0 / 6.0) * dt * (k1[d] + k2[d] + k3[d] + k4[d]);
+        double xn;
+        if (a.classic) xn = x[d] + (1.0 / 6.0) * dt * (k1[d] + 2.0 * k2[d] + 2.0 * k3[d] + k4[d]);
+        else xn = x[d] + (1.0 / 6.0) * dt * (k1[d] + k2[d] + k3[d] + k4[d]);
         a.vo[d][t * a.os] = (xn - x[d]) / dt;
         double xf = xn;
         if (a.fence) { if (xf <= 0.0) xf = a.eps; if (xf >= a.L[d]) xf = a.L[d] - a.eps; }
@@ -637,6 +642,7 @@ struct Mic3 {
     // date by the refill.  With deletion on, a sort can remove the holder: a refilling sort then reduces the IDs of its survivors
     // itself, every time, and any other sort that removed something sets have_maxid = false
     bool have_maxid = false; double maxid = 0.0;
+    bool rk4_classic = false;                        // pl3_mic_set_rk4_classic: RK4 weights (1,2,2,1)/6 instead of the reference's (1,1,1,1)/6
     bool deletion = false;                           // pl3_mic_set_deletion: every sort of the resident tracers drops those outside the box
     long long removed_last = 0, removed_total = 0;   // by the last sort / since the last upload (pl3_tracers_removed)
     bool have_vgrid = false; M3Grid vgrid;           // the padded centre grid of the resident step: uploaded once per context
@@ -1001,7 +1007,7 @@ extern "C" int pl3_rk4(pl3_ctx* ctx, int64_t n, const double* tr_x, int gnz, int
     M3_TRY(m3_grid(ctx, v, M, "h_ggrid", gc, gn, a.g));
     M3_TRY(m3_fields_up(ctx, v, M, "h_gfields", 3, vel, GN, &df));
     if (n > 0) M3_HIP(ctx, m3_copy(ctx, dx, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));
-    a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.dt = tstep; a.os = 3; a.fence = 0;
+    a.n = n; a.p = M3Pos{{dx, dx + 1, dx + 2}, 3}; a.dt = tstep; a.os = 3; a.fence = 0; a.classic = M->rk4_classic ? 1 : 0;
     for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = dx + 3 * nn + d; a.vo[d] = dx + 6 * nn + d; }
     if (n > 0) {
         m3_launch_rk4(v, M, a);
@@ -1091,6 +1097,20 @@ extern "C" int pl3_mic_get_deletion(pl3_ctx* ctx, int* on) {
     M3_TRY(m3_open(ctx, "pl3_mic_get_deletion", v, &M));
     if (!on) return pl3_fail(ctx, "pl3_mic_get_deletion: NULL argument");
     *on = M->deletion ? 1 : 0;
+    return 0;
+}
+// The RK4 weights are context state like the search and the deletion: read by pl3_rk4, pl3_resident_rk4 / _advect and pl3_resident_step.
+extern "C" int pl3_mic_set_rk4_classic(pl3_ctx* ctx, int on) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_set_rk4_classic", v, &M));
+    M->rk4_classic = on != 0;
+    return 0;
+}
+extern "C" int pl3_mic_get_rk4_classic(pl3_ctx* ctx, int* on) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_get_rk4_classic", v, &M));
+    if (!on) return pl3_fail(ctx, "pl3_mic_get_rk4_classic: NULL argument");
+    *on = M->rk4_classic ? 1 : 0;
     return 0;
 }
 extern "C" int pl3_tracers_removed(pl3_ctx* ctx, int64_t out[2]) {
@@ -1339,6 +1359,7 @@ static int m3_advect_dev(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, const M3Grid& g,
     M3Rk4 a{};
     a.g = g;
     a.n = n; a.p = M3Pos{{M->x, M->x + cap, M->x + 2 * cap}, 1}; a.dt = tstep; a.os = 1; a.fence = fence ? 1 : 0; a.eps = 1.0 / 1024.0;   // EPS of pylamp_const.py
+    a.classic = M->rk4_classic ? 1 : 0;
     for (int d = 0; d < 3; d++) { a.V[d] = df + d * GN; a.xo[d] = M->x + d * cap; a.vo[d] = M->v + d * cap; a.L[d] = v.coord[d][v.gn[d] - 1]; }
     M3_HIP(ctx, hipEventRecord(M->ev0, v.stream));
     if (n > 0) m3_launch_rk4(v, M, a);       // in place: a tracer reads its position before it writes

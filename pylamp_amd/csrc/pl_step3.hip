@@ -104,14 +104,21 @@ __global__ __launch_bounds__(256) void k_s3_velmax(S3Dims d, S3Vel x, S3Ops ops,
 // as it is at that moment it writes -V for the normal component and 2 U_c - V for a tangential component c, so that the velocity
 // interpolated onto the wall is U.  These steps round, so a chain that holds one is replayed forwards, first wall first, as the passes
 // ran; without a moving wall in the chain the walk is the one above.
+// The pass of a wall with a FLOW through it (bit w of fl.mask; pl3_stokes_set_wall_flow) runs in its slot as well, even for a no-slip wall
+// at rest: the normal component becomes 2 Un[ci, cj] - V, with ci, cj the padded tangential indices minus 1 clamped to the wall's faces
+// (a ghost point and its source share them, so they follow from the thread's own point), and the velocity interpolated onto the wall is
+// Un; the tangential components are copied on a free-slip wall and follow 2 U_c - V on a no-slip wall (U_c possibly 0).  Such a chain
+// is replayed forwards too.  A wall without a flow keeps the arithmetic above (-V, not 2 0 - V: the sign of zero differs).
 struct S3Adv { double* V[3]; };
-__global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, int noslip, Pl3WallVel mv) {
+__global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, int noslip, Pl3WallVel mv, Pl3WallFlow fl) {
     const int pn[3] = {d.n[0] + 1, d.n[1] + 1, d.n[2] + 1};
     const long long GN = (long long)pn[0] * pn[1] * pn[2];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= GN) return;
     const int p0[3] = {(int)(t / ((long long)pn[2] * pn[1])), (int)((t / pn[2]) % pn[1]), (int)(t % pn[2])};
-    const int skip = noslip & ~mv.moving;                    // the walls whose pass does not run
+    const int skip = noslip & ~mv.moving & ~fl.mask;         // the walls whose pass does not run
+    const int replay = mv.moving | fl.mask;                  // the walls whose pass rounds
+    const int shear = mv.moving | (fl.mask & noslip);        // the walls whose tangential components follow 2 U_c - V
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         int p[3] = {p0[0], p0[1], p0[2]};
@@ -123,7 +130,7 @@ __global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, i
             p[a] = w < 3 ? 1 : pn[a] - 2;
             if (a == q) sign = -sign;
             chain = (chain << 3) | (w + 1);
-            moved |= (mv.moving >> w) & 1;
+            moved |= (replay >> w) & 1;
         }
         const bool inner = p[0] >= 1 && p[0] <= pn[0] - 2 && p[1] >= 1 && p[1] <= pn[1] - 2 && p[2] >= 1 && p[2] <= pn[2] - 2;
         double r = 0.0;
@@ -137,8 +144,14 @@ __global__ __launch_bounds__(256) void k_s3_advvel(S3Dims d, S3Vel x, S3Adv o, i
         if (moved) {
             for (; chain; chain >>= 3) {
                 const int w = (chain & 7) - 1;
-                if (w % 3 == q) r = -r;
-                else if ((mv.moving >> w) & 1) r = 2.0 * mv.u[3 * w + q] - r;
+                if (w % 3 == q) {
+                    if ((fl.mask >> w) & 1) {                // (the two other axes P < Q in z, x, y order)
+                        const int P = q == 0 ? 1 : 0, Q = q == 2 ? 1 : 2;
+                        const int ci = min(max(p0[P] - 1, 0), d.n[P] - 2), cj = min(max(p0[Q] - 1, 0), d.n[Q] - 2);
+                        r = 2.0 * fl.un[w][(long long)ci * (d.n[Q] - 1) + cj] - r;
+                    } else r = -r;
+                }
+                else if ((shear >> w) & 1) r = 2.0 * mv.u[3 * w + q] - r;
             }
         }
         o.V[q][t] = r;
@@ -216,7 +229,7 @@ static int s3_finish(pl3_ctx* ctx, S3Open& o, int nb, const S3Ops& ops, const do
 static void s3_advvel(S3Open& o, double* const X[3], double* adv) {
     const size_t GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
     S3Vel x{{X[0], X[1], X[2]}}; S3Adv a{{adv, adv + GNp, adv + 2 * GNp}};
-    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip, o.d.wallvel);
+    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip, o.d.wallvel, o.d.wallflow);
 }
 
 extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* rep) {

@@ -86,6 +86,66 @@ def wall_velocities(wallvel, bc=None, who="3-D Stokes"):
     return v
 
 
+FLOW_AXES = ((1, 2), (0, 2), (0, 1))        # the two axes p < q of a wall plane of axis a, in z, x, y order
+_AXIS_N = ("nz", "nx", "ny")
+
+
+def wall_flows(flow, nx, who="3-D Stokes"):
+    """flow: the wall-normal velocities through the six walls [z0, x0, y0, zL, xL, yL] -- a list of six entries (or a dict by wall
+    name), each None (no flow), a scalar (the constant profile) or an array Un of shape (n_p - 1, n_q - 1) over the wall's faces, p < q
+    the two other axes in z, x, y order; the value is the component along +a, so positive is inflow on z0, x0, y0 and outflow on zL,
+    xL, yL.  None: no flow anywhere.  Returns six entries, None or a contiguous float64 array; shapes and non-finite entries are
+    rejected by name (the rule is in include/pylamp_hip.h at pl3_stokes_set_wall_flow)."""
+    if flow is None:
+        return [None] * 6
+    if isinstance(flow, dict):
+        for k in flow:
+            if k not in WALL_NAMES:
+                raise Exception("%s: the wall flow names a wall '%s' (the walls are %s)" % (who, k, ", ".join(WALL_NAMES)))
+        flow = [flow.get(k) for k in WALL_NAMES]
+    flow = list(flow)
+    if len(flow) != 6:
+        raise Exception("%s: the wall flow needs six entries [z0, x0, y0, zL, xL, yL] (got %d)" % (who, len(flow)))
+    out = []
+    for w, f in enumerate(flow):
+        if f is None:
+            out.append(None)
+            continue
+        p, q = FLOW_AXES[w % 3]
+        shp = (int(nx[p]) - 1, int(nx[q]) - 1)
+        try:
+            a = np.array(f, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = None
+        if a is not None and a.ndim == 0:
+            a = np.full(shp, float(a))
+        if a is None or a.shape != shp:
+            raise Exception("%s: the flow of wall %s needs the shape (%s - 1, %s - 1) = %r or a scalar (got %s)"
+                            % (who, WALL_NAMES[w], _AXIS_N[p], _AXIS_N[q], shp, "an object that is no array" if a is None else a.shape))
+        bad = np.argwhere(~np.isfinite(a))
+        if bad.size:
+            i, j = (int(v) for v in bad[0])
+            raise Exception("%s: wall %s has a non-finite flow entry [%d, %d] = %r" % (who, WALL_NAMES[w], i, j, float(a[i, j])))
+        out.append(np.ascontiguousarray(a))
+    return out
+
+
+def wall_fluxes(grid, flow):
+    """(fluxes, Phi) of a wall flow on the grid [z, x, y]: fluxes[w] = s_w sum_ij Un_w[i, j] dp_i dq_j, the volume per second that
+    enters the box through wall w (s = +1 on z0, x0, y0, -1 on zL, xL, yL; 0 for a wall without flow), and their sum Phi, which
+    Context3.set_wall_flow requires to vanish to 1e-10 of sum |Un| dp dq.  Summed in np.longdouble."""
+    g = [np.asarray(c, dtype=np.float64).reshape(-1) for c in grid]
+    fl = wall_flows(flow, [c.size for c in g], "wall_fluxes")
+    out = np.zeros(6, dtype=np.longdouble)
+    for w, a in enumerate(fl):
+        if a is None:
+            continue
+        p, q = FLOW_AXES[w % 3]
+        dp, dq = np.diff(g[p].astype(np.longdouble)), np.diff(g[q].astype(np.longdouble))
+        out[w] = (1 if w < 3 else -1) * np.sum(a.astype(np.longdouble) * dp[:, None] * dq[None, :])
+    return out.astype(np.float64), float(out.sum())
+
+
 class Context3:
     def __init__(self, nx, grid, device=0):
         lib = _lib.load()
@@ -153,6 +213,17 @@ class Context3:
         self.check(self.lib.pl3_mic_get_deletion(self.handle(), C.byref(on)))
         return bool(on.value)
 
+    def set_rk4_classic(self, on):
+        """RK4 weights of the marker advection of this context: off (default) the reference's (1, 1, 1, 1) / 6, which sum to 4 / 6 and
+        move a tracer by 2/3 U dt in a uniform field U; on the classical (1, 2, 2, 1) / 6, which move it by U dt (the rule is in
+        include/pylamp_hip.h at pl3_mic_set_rk4_classic)."""
+        self.check(self.lib.pl3_mic_set_rk4_classic(self.handle(), 1 if on else 0))
+
+    def rk4_classic(self):
+        on = C.c_int()
+        self.check(self.lib.pl3_mic_get_rk4_classic(self.handle(), C.byref(on)))
+        return bool(on.value)
+
     def tracers_removed(self):
         """(removed by the last sort of the resident tracers, removed since the last upload)."""
         v = (C.c_int64 * 2)()
@@ -174,6 +245,24 @@ class Context3:
         v = np.zeros((6, 3))
         self.check(self.lib.pl3_stokes_get_wall_velocity(self.handle(), _lib.dptr(v)))
         return v
+
+    def set_wall_flow(self, flow):
+        """The flow through the six Stokes walls of this context (wall_flows: six entries, each None, a scalar or the plane Un of
+        the wall; None clears it); kept until set again.  All six are set at once because their net flux must vanish
+        (include/pylamp_hip.h at pl3_stokes_set_wall_flow; wall_fluxes gives the figures)."""
+        fl = wall_flows(flow, self.nx)
+        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in fl])
+        self.check(self.lib.pl3_stokes_set_wall_flow(self.handle(), ptr))
+
+    def wall_flow(self):
+        """Six entries, None or the plane of the wall as the device holds it."""
+        mask = C.c_int()
+        self.check(self.lib.pl3_stokes_get_wall_flow(self.handle(), C.byref(mask), None))
+        out = [np.zeros((self.nx[FLOW_AXES[w % 3][0]] - 1, self.nx[FLOW_AXES[w % 3][1]] - 1)) if (mask.value >> w) & 1 else None
+               for w in range(6)]
+        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in out])
+        self.check(self.lib.pl3_stokes_get_wall_flow(self.handle(), None, ptr))
+        return out
 
     def close(self):
         if self.h is not None:
@@ -249,7 +338,8 @@ class StokesOperator3:
                     lds=[bool(lds[k]) for k in range(n)])
 
 
-def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True, wallvel=None):
+def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True, wallvel=None,
+                     wallflow=None):
     """3-D counterpart of pylamp_stokes.makeStokesMatrix: f_etas at the NODES (averaged onto the edges by the kernels),
     f_etan at the cell centres, f_rho at the nodes; bc = [z0, x0, y0, zL, xL, yL], each BC_TYPE_FREESLIP or BC_TYPE_NOSLIP.
     bc=None leaves the walls of the context as they are: all free-slip on a new context, or what Context3.set_stokes_walls /
@@ -261,10 +351,16 @@ def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device
     pl3_stokes_set_walls.
     wallvel: the velocities (Uz, Ux, Uy) of the six walls, (6, 3); only the tangential components of a NOSLIP wall may be
     non-zero.  They enter the returned right-hand side (and solve(A) without rhs=) and nothing else; None leaves the velocities
-    of the context as they are (at rest on a new context).  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_velocity."""
+    of the context as they are (at rest on a new context).  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_velocity.
+    wallflow: the flow through the six walls (wall_flows: six entries, each None, a scalar or the plane Un of the wall-normal
+    velocity); it enters the returned right-hand side likewise, and its net flux must vanish.  None leaves the flow of the context as
+    it is (none on a new context); six None clear it.  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_flow."""
     walls = None if bc is None else stokes_walls(bc)
     vel = None if wallvel is None else wall_velocities(wallvel, walls)
+    flows = None if wallflow is None else wall_flows(wallflow, nx)
     ctx = ctx or Context3(nx, grid, device)
+    if flows is not None:
+        ctx.set_wall_flow(flows)
     if vel is not None and walls is not None:
         ctx.set_wall_velocity(None)                 # (the new kinds are checked against the new velocities, not the old ones)
     if walls is not None:
@@ -528,7 +624,8 @@ def grid2trac(tr_x, tr_f, grid, gridfield, nx, defval=np.nan, method=INTERP_METH
 
 def RK(tr_x, grids, vels, nx, tstep, order=4, ctx=None, search=False):
     """Runge-Kutta advection; returns (vel_final, tr_x_final), both (n, 3).  grids / vels live on the padded
-    (nz+1, nx+1, ny+1) cell-centre grid (advection_velocity); the reference's weights (1,1,1,1)/6 are kept.
+    (nz+1, nx+1, ny+1) cell-centre grid (advection_velocity); the reference's weights (1,1,1,1)/6 are kept unless the context has
+    Context3.set_rk4_classic(True).
     search=True: cells by per-axis search (rectilinear grids)."""
     if order != 4:
         raise Exception("RK: only order=4 is functional (as in 2-D)")
@@ -578,7 +675,7 @@ def refined_grid(n, L, centre=0.5, ratio=3.0, width=0.2):
     return c
 
 
-def advection_velocity(newvel, gridmp, nx, bc=None, wallvel=None):
+def advection_velocity(newvel, gridmp, nx, bc=None, wallvel=None, wallflow=None):
     """Cell-centred velocities on the padded (nz+1, nx+1, ny+1) grid (pylamp2.py:491-545 extended by one axis): every
     component is averaged along its own axis; ghosts wall by wall in the order z0, x0, y0, zL, xL, yL -- a free-slip wall
     mirrors the normal component with a sign flip and copies the tangential ones, the pass of a no-slip wall
@@ -586,9 +683,13 @@ def advection_velocity(newvel, gridmp, nx, bc=None, wallvel=None):
     The pass of a no-slip wall with a non-zero velocity wallvel[w] = (Uz, Ux, Uy) runs in its slot: -V for the normal component
     and 2 U_c - V for a tangential component c, so that the velocity interpolated onto the wall is U (deliberately
     discontinuous at U = 0, where walls at rest keep the reference's behaviour).
+    The pass of a wall with a flow (wallflow[w] not None; wall_flows) runs in its slot too, even for a no-slip wall at rest: the
+    normal component becomes 2 Un - V with Un continued constantly into the ghost rim, so that the velocity interpolated onto the
+    wall is Un; the tangential components are copied on a free-slip wall and follow 2 U_c - V on a no-slip wall.
     Returns ([gz, gx, gy], [Vz, Vx, Vy])."""
     walls = stokes_walls(bc, "advection_velocity")
     U = wall_velocities(wallvel, walls, "advection_velocity")
+    Un = wall_flows(wallflow, nx, "advection_velocity")
     shp = tuple(int(v) + 1 for v in nx)
     vz, vx, vy = newvel
     V = [np.zeros(shp) for _ in range(3)]
@@ -599,13 +700,15 @@ def advection_velocity(newvel, gridmp, nx, bc=None, wallvel=None):
     for ghost, inner in ((0, 1), (-1, -2)):
         for axis in range(3):
             w = axis + (0 if ghost == 0 else 3)
-            moving = walls[w] == BC_TYPE_NOSLIP and U[w].any()
+            moving = walls[w] == BC_TYPE_NOSLIP and (U[w].any() or Un[w] is not None)
             if walls[w] == BC_TYPE_NOSLIP and not moving:
                 continue
             for comp in range(3):
                 dst = [slice(None)] * 3; src = [slice(None)] * 3
                 dst[axis] = ghost; src[axis] = inner
-                if comp == axis:
+                if comp == axis and Un[w] is not None:
+                    V[comp][tuple(dst)] = 2 * np.pad(Un[w], 1, mode="edge") - V[comp][tuple(src)]
+                elif comp == axis:
                     V[comp][tuple(dst)] = -V[comp][tuple(src)]
                 elif moving:
                     V[comp][tuple(dst)] = 2 * U[w, comp] - V[comp][tuple(src)]
@@ -629,6 +732,9 @@ class Options3:
         self.bcstokes = [BC_TYPE_FREESLIP] * 6
         # beyond the reference: velocities (Uz, Ux, Uy) of the six walls, (6, 3); tangential components of NOSLIP walls only (None: at rest)
         self.bcstokesvel = None
+        # beyond the reference: flow through the six walls (wall_flows: per wall None, a scalar or the plane Un of the wall-normal
+        # velocity along +axis); needs tracs_fence_enabled = False with marker_deletion = True, and tracdens_min > 0 (None: no flow)
+        self.bcstokesflow = None
         self.bcheat = [BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW, BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW]
         self.bcheatvals = [273.0, 0.0, 0.0, 1623.0, 0.0, 0.0]
         self.stokes_rtol, self.stokes_maxit = DEFAULT_RTOL, DEFAULT_MAXIT
@@ -649,6 +755,9 @@ class Options3:
         # plain rejection of tracs_fence_enabled = False is pinned behaviour: the deletion is opted into by name, and
         # marker_deletion = True with the fence on is rejected too, so that one combination has one meaning
         self.marker_deletion = False
+        # beyond the reference: the classical RK4 weights (1, 2, 2, 1) / 6 instead of the reference's (1, 1, 1, 1) / 6, which move a tracer
+        # by 2/3 U tstep in a uniform field U.  A flow through the walls wants True: the markers then carry the volume the walls bring in
+        self.rk4_classic = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
@@ -667,8 +776,11 @@ class Simulation3:
     kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Options3.tracs_fence_enabled = False together with
     Options3.marker_deletion = True runs without the fence: a tracer that leaves the box (x_d <= 0 or x_d >= L_d) is removed by the
     next sort, the census and the refill of that sort see the survivors, step() / advect() / refill() report nremoved and
-    Context3.tracers_removed() counts them.  Not built: wall-normal (through-flow) velocities, surface stabilisation, several
-    ranks -- each is rejected with an error that names it."""
+    Context3.tracers_removed() counts them.  On that path material may flow through the walls (Options3.bcstokesflow,
+    set_wall_flow; wall_flows states the format): the outflow is deleted, the cells along an inflow wall are kept filled by the refill
+    (tracdens_min > 0 is required), whose new tracers carry the mean of their cell's residents -- a zero-gradient inflow; the net flux
+    must vanish (wall_fluxes); Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default,
+    move them by 2/3 of that).  Not built: surface stabilisation, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
         self.nx = [int(v) for v in nx]
@@ -706,14 +818,19 @@ class Simulation3:
         if o.surface_stabilization:
             raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
+        self.bcstokesflow = self._checked_flow(o.bcstokesflow, "Simulation3: Options3.bcstokesflow")
         self.ctx = Context3(self.nx, self.grid, device)
         self.bcstokesvel = wall_velocities(o.bcstokesvel, self.bcstokes, "Simulation3: Options3.bcstokesvel")
         self.ctx.set_stokes_walls(self.bcstokes)        # the resident step and the device advection velocity read them from the context
         self.ctx.set_wall_velocity(self.bcstokesvel)
+        if any(a is not None for a in self.bcstokesflow):
+            self.ctx.set_wall_flow(self.bcstokesflow)
         if o.marker_search:
             self.ctx.set_marker_search(True)
         if o.marker_deletion:
             self.ctx.set_marker_deletion(True)
+        if o.rk4_classic:
+            self.ctx.set_rk4_classic(True)
         self.it = 0
         self.totaltime = 0.0
         self.last = None
@@ -730,6 +847,27 @@ class Simulation3:
         v = wall_velocities(wallvel, self.bcstokes, "Simulation3.set_wall_velocity")
         self.ctx.set_wall_velocity(v)
         self.bcstokesvel = v
+
+    def _checked_flow(self, flow, who):
+        """wall_flows plus what a flow needs of the markers: the fence would stop the outflow, and the cells along an inflow wall are
+        kept filled by the census refill alone."""
+        o = self.opt
+        fl = wall_flows(flow, self.nx, who)
+        if any(a is not None for a in fl):
+            if o.tracs_fence_enabled or not o.marker_deletion:
+                raise Exception("%s: a flow through the walls needs tracs_fence_enabled = False together with marker_deletion = True "
+                                "(the fence would hold the outflowing tracers at the wall)" % who)
+            if int(o.tracdens_min) == 0:
+                raise Exception("%s: a flow through the walls needs the refill of depleted cells, tracdens >= tracdens_min > 0 (got "
+                                "tracdens_min = 0): the cells along an inflow wall would run empty" % who)
+        return fl
+
+    def set_wall_flow(self, flow):
+        """A new flow through the six walls (wall_flows; None: none) from the next step on.  New tracers of the refilled cells along an
+        inflow wall carry the mean of the cell's residents: a zero-gradient inflow."""
+        fl = self._checked_flow(flow, "Simulation3.set_wall_flow")
+        self.ctx.set_wall_flow(fl)
+        self.bcstokesflow = fl
 
     # -- tracer state ------------------------------------------------------------------------------------------------
     def _lib_call(self, name, *args):
@@ -955,7 +1093,7 @@ class Simulation3:
                 self.temp_to_tracers(newtemp - f["T"], False, tstep)
             self._newtemp = newtemp
             f["temp"] = newtemp
-        grids, vels = advection_velocity(newvel, self.gridmp, self.nx, self.bcstokes, self.bcstokesvel)
+        grids, vels = advection_velocity(newvel, self.gridmp, self.nx, self.bcstokes, self.bcstokesvel, self.bcstokesflow)
         rep.update(self.advect(grids, vels, tstep, self.it))
         rep.setdefault("nremoved", 0)
         self.totaltime += tstep

@@ -2,10 +2,11 @@
 and a cold device-resident solve on the problem of `bench.py --config 3d257`, at the given sizes, with free-slip walls or with
 no-slip z-walls.  Prints one JSON line.  Run it in alternating processes for the two builds that are compared:
 
-    python tools/stokes3_walls_probe.py [--root CHECKOUT] [--noslip z] [--sizes 129,257] [--tag NAME]
+    python tools/stokes3_walls_probe.py [--root CHECKOUT] [--noslip z] [--plug U] [--sizes 129,257] [--tag NAME]
 
 --root: import pylamp_amd from that checkout (a build of another commit) instead of this one; without --noslip no wall call is made,
 so the script also runs on a commit that has none.
+--plug U: a uniform flow of U m/s in through z0 and out through zL (makeStokesMatrix(wallflow=...)); without it no flow call is made.
 """
 import argparse
 import json
@@ -18,13 +19,14 @@ import numpy as np
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 ap.add_argument("--noslip", default="", choices=["", "z", "zx", "zxy"])
+ap.add_argument("--plug", type=float, default=0.0)
 ap.add_argument("--sizes", default="129,257")
 ap.add_argument("--tag", default="")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 from pylamp_amd import pylamp3d as P3                                             # noqa: E402
 
-out = {"tag": args.tag, "noslip": args.noslip, "sizes": {}}
+out = {"tag": args.tag, "noslip": args.noslip, "plug": args.plug, "sizes": {}}
 for nb in [int(v) for v in args.sizes.split(",")]:
     n = [nb] * 3; L = [660e3] * 3
     grid = [np.linspace(0, L[d], n[d]) for d in range(3)]
@@ -40,6 +42,8 @@ for nb in [int(v) for v in args.sizes.split(",")]:
     kw = {}
     if args.noslip:
         kw["bc"] = [0 if "zxy"[w % 3] in args.noslip else 1 for w in range(6)]
+    if args.plug:
+        kw["wallflow"] = [args.plug, None, None, args.plug, None, None]
     A, _ = P3.makeStokesMatrix(n, grid, es, en, rho, ctx=ctx, **kw)
     A.apply_bench(20, True)                                                        # warm-up
     apply_ms = [A.apply_bench(50, True) for _ in range(5)]
