@@ -571,6 +571,38 @@ int  pl3_resident_advect(pl3_ctx* ctx, const double* gz, const double* gx, const
                          const double* vy, double tstep, int fence, int tracdens, int tracdens_min, uint64_t seed, int it,
                          int unique_ids, int64_t out[4]);
 int  pl3_resident_times(pl3_ctx* ctx, double ms[4]);
+/* Inflow material: what the refill's new tracers carry where a wall flow (pl3_stokes_set_wall_flow) brings material into the box.
+ * Opt-in per wall, default none = every kernel and result as without it.  An overlay on the refill above: positions, IDs, stored
+ * velocities, counts, the sort, the census and the deletion are bit for bit what they are without a material; only field values of
+ * new tracers change.  Per wall w of [z0, x0, y0, zL, xL, yL] (axis a = w mod 3, p < q the two other axes in z, x, y order) a context
+ * may hold a set of tracer columns -- bits 0 ... 11 of `columns`; TR__ID, column 12, is never allowed -- and one plane per column,
+ * (n_p - 1) x (n_q - 1) doubles over the wall's faces, entry i (n_q - 1) + j: the layout and the indices of the planes of
+ * pl3_stokes_set_wall_flow.  `values` holds popcount(columns) planes in ascending column order.
+ * In every sort that refills (pl3_resident_refill, pl3_resident_advect, pl3_resident_step) a refilled cell c = (i_z, i_x, i_y) is an
+ * INFLOW CELL of wall w when (a) w has a material, (b) the cell touches w: its index along a is 0 for z0, x0, y0 and n_a - 2 for zL,
+ * xL, yL, and (c) the context's wall flow at the time of the sort is non-zero and inward at the cell's own face (i_p, i_q) of w:
+ * Un_w > 0 on z0, x0, y0, Un_w < 0 on zL, xL, yL; no flow on w, or Un_w == 0, means no.  If several walls qualify (edge and corner
+ * cells) the first in the order z0, x0, y0, zL, xL, yL decides alone.
+ * For an inflow cell of wall w let s(x) be the distance of a position from the wall, x_a - c_a[0] for a low wall and c_a[n_a - 1] - x_a
+ * for a high one, and dmin the minimum of s over the cell's residents after the deletion (the residents the refill averages; a NaN
+ * coordinate is ignored; +inf when the cell has none).  New tracer q of the cell is an INFLOW TRACER exactly when s(x_q) < dmin,
+ * strictly: it lies between the wall and every resident, in the gap the wall flux opened.  It takes mat_w[col][i_p (n_q - 1) + i_q] in
+ * every column of the wall's set and the residents' mean (possibly NaN) in the others; a new tracer that is no inflow tracer keeps the
+ * mean in every column.  In an inflow cell the removal emptied every new tracer is an inflow tracer, so the prescribed columns are
+ * finite there (a column the material leaves out is still 0/0 = NaN).  The rule needs no time step and no random numbers of its own:
+ * a function of the sorted state and the two wall settings, so two runs agree bitwise.  A prescribed TR_TMP is a tracer temperature
+ * like any other: with heat diffusion on it enters the next step's temperature scatter.
+ * set: columns == 0 clears the wall (values may then be NULL); a new context has none.  The state belongs to the context like the
+ * search, the deletion and the RK4 weights: it survives uploads, pl3_stokes_set_wall_flow and pl3_stokes_set_walls, a wall without a
+ * flow may hold a material (the rule never fires there), and setting it changes no resident tracer.
+ * get: either pointer may be NULL; values receives the wall's planes, downloaded from the device.
+ * pl3_mic_inflow_count: out = { inflow tracers of the last sort, since the last pl3_tracers_upload }.
+ * Errors, a rejected call changing nothing: a NULL context; wall outside 0 ... 5; a bit >= 12 in columns (bit 12 is named as TR__ID);
+ * columns != 0 with values == NULL; a non-finite value (names the wall, the column and the index); a context with pl3_set_comm
+ * attached. */
+int  pl3_mic_set_inflow(pl3_ctx* ctx, int wall, unsigned columns, const double* values);
+int  pl3_mic_get_inflow(pl3_ctx* ctx, int wall, unsigned* columns, double* values);
+int  pl3_mic_inflow_count(pl3_ctx* ctx, int64_t out[2]);
 
 /* ---- device-resident 3-D time step (one rank) ------------------------------------------------------------------------
  * pl3_resident_step is one step of the loop of pylamp2.py:290-581 with a third axis on the resident tracers, with every grid field

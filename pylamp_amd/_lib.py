@@ -127,6 +127,9 @@ SIGNATURES = {
     "pl3_resident_advect": (C.c_int, [C.c_void_p] + [c_double_p] * 6 + [C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                       C.POINTER(C.c_int64)]),
     "pl3_resident_times": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_mic_set_inflow": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, c_double_p]),
+    "pl3_mic_get_inflow": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint), c_double_p]),
+    "pl3_mic_inflow_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "pl3_resident_step": (C.c_int, [C.c_void_p, C.POINTER(Step3Config), C.c_int, C.POINTER(Step3Report)]),
     "pl3_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p]),
     "pl3_advection_velocity": (C.c_int, [C.c_void_p] + [c_double_p] * 6),

@@ -1273,7 +1273,7 @@ extern "C" const char* pl3_last_error(const pl3_ctx* ctx) { return ctx ? ctx->er
 int pl3_fail(pl3_ctx* ctx, const std::string& m) { return p3_fail(ctx, m); }
 int pl3_host_view(pl3_ctx* ctx, Pl3HostView* v) {
     if (!ctx) return p3_fail(nullptr, "3-D marker-in-cell: NULL context");
-    v->device = ctx->device; v->stream = ctx->stream; v->nranks = ctx->nranks; v->slot = &ctx->mic3;
+    v->device = ctx->device; v->stream = ctx->stream; v->nranks = ctx->nranks; v->slot = &ctx->mic3; v->wallflow = ctx->wallflow;
     for (int a = 0; a < 3; a++) { v->gn[a] = ctx->gn[a]; v->coord[a] = ctx->gcoord[a].data(); }
     return 0;
 }

@@ -346,11 +346,21 @@ __global__ __launch_bounds__(256) void k_m3_max(long long n, const double* __res
 // idle 63 lanes of 64 and touch 64 cache lines with every load).  Lane j < 13 sums column j of the residents one after the other in
 // resident order -- a fixed order, no atomics, so two runs agree bitwise; then lane q writes the q-th new tracer, column by column
 // (neighbouring lanes, neighbouring addresses).  0 residents: 0/0 = NaN in every field, as in the reference.
+//
+// INFLOW (pl3_mic_set_inflow: some wall of the context has a material; the rule is in include/pylamp_hip.h): a cell on a wall with
+// a material whose own face carries an inward flow hands the wall's plane values, in the wall's columns, to those of its new tracers
+// that lie nearer the wall than every resident.  The wall test depends on the cell alone, so it is the same in all 64 lanes; dmin is
+// an fmin over the residents (strided: a cell can hold more than 64) with a butterfly; every lane then works on its own tracers q,
+// q + 64, ...: the position once, from it the inflow flag, and the value of a column is a select between the mean and the plane's
+// entry.  The inflow tracers are counted with ONE add per wave (ballot and popcount), like the trash bucket of k_m3_key.
+struct M3Inflow { unsigned mask[6]; const double* mat[6]; Pl3WallFlow fl; int* count; };
 struct M3Inject {
     int nref; const int* list; const int* loff; const int* start; const int* cnt; int dens;
     M3Grid g; double* x; double* f; double* v; long long cap;
     unsigned long long seed; unsigned it3; double id0; int unique;
+    M3Inflow in;                                                      // read by k_m3_inject<true> only
 };
+template <bool INFLOW>
 __global__ __launch_bounds__(256) void k_m3_inject(M3Inject a) {
     const int w = (int)(((long long)blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (w >= a.nref) return;                                          // the whole wave leaves
@@ -363,6 +373,64 @@ __global__ __launch_bounds__(256) void k_m3_inject(M3Inject a) {
         double s = 0.0;
         for (int t = t0; t < t1; t++) s += col[t];
         mean = s / (double)k;
+    }
+    if constexpr (INFLOW) {
+        // the first wall in the order z0, x0, y0, zL, xL, yL that has a material, touches the cell and flows inward at the cell's face
+        int ws = -1, face = 0;
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            const int ax = q % 3, p = ax == 0 ? 1 : 0, r = ax == 2 ? 1 : 2;
+            const bool here = a.in.mask[q] != 0u && ((a.in.fl.mask >> q) & 1) && ic[ax] == (q < 3 ? 0 : a.g.a[ax].n - 2);
+            if (ws < 0 && here) {
+                const int fi = ic[p] * (a.g.a[r].n - 1) + ic[r];
+                const double un = a.in.fl.un[q][fi];
+                if (q < 3 ? un > 0.0 : un < 0.0) { ws = q; face = fi; }
+            }
+        }
+        const int wa = ws < 0 ? 0 : ws % 3;
+        const bool low = ws < 3;
+        const double wc = low ? a.g.a[wa].c0 : a.g.a[wa].cl;          // the wall's coordinate: c[0] or c[n - 1]
+        double dmin = INFINITY;                                       // distance of the nearest resident from the wall (fmin drops a NaN)
+        if (ws >= 0) {
+            const double* xa = a.x + (long long)wa * a.cap;
+            for (int t = t0 + lane; t < t1; t += 64) dmin = fmin(dmin, low ? xa[t] - wc : wc - xa[t]);
+            for (int o = 32; o > 0; o >>= 1) dmin = fmin(dmin, __shfl_xor(dmin, o, 64));
+        }
+        const unsigned cols = ws < 0 ? 0u : a.in.mask[ws];
+        const long long nface = ws < 0 ? 0 : (long long)(a.g.a[wa == 0 ? 1 : 0].n - 1) * (a.g.a[wa == 2 ? 1 : 2].n - 1);
+        double mj[M3_NFTRAC], pj[M3_NFTRAC];                          // per column: the mean, and what an inflow tracer takes instead
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < M3_NFTRAC; j++) {
+            mj[j] = __shfl(mean, j, 64);
+            pj[j] = mj[j];
+            if (j != M3_ID && ((cols >> j) & 1u)) { pj[j] = a.in.mat[ws][(long long)rank * nface + face]; rank++; }
+        }
+        int ninflow = 0;
+        for (int q0 = 0; q0 < m; q0 += 64) {                          // every lane enters every round: the ballot sees the whole wave
+            const int q = q0 + lane;
+            bool infl = false;
+            if (q < m) {
+                const long long ord = a.unique ? (long long)off + q + 1 : (long long)off + q - w;
+                double xq[3];
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    const double g0 = a.g.a[d].c[ic[d]], h = a.g.a[d].c[ic[d] + 1] - g0;
+                    const double u = inj_uniform(a.seed, (unsigned)c, (unsigned)q, a.it3 + d);
+                    xq[d] = __dadd_rn(g0, __dmul_rn(u, h));           // the expression of the plain kernel: the same bits
+                    a.x[(long long)d * a.cap + t1 + q] = xq[d];
+                    a.v[(long long)d * a.cap + t1 + q] = 0.0;
+                }
+                const double xw = wa == 0 ? xq[0] : (wa == 1 ? xq[1] : xq[2]);
+                infl = ws >= 0 && (low ? xw - wc : wc - xw) < dmin;
+#pragma unroll
+                for (int j = 0; j < M3_NFTRAC; j++)
+                    a.f[(long long)j * a.cap + t1 + q] = j == M3_ID ? a.id0 + (double)ord : (infl ? pj[j] : mj[j]);
+            }
+            ninflow += __popcll(__ballot(infl));
+        }
+        if (lane == 0 && ninflow > 0) atomicAdd(a.in.count, ninflow);
+        return;
     }
     for (int j = 0; j < M3_NFTRAC; j++) {
         const double mj = __shfl(mean, j, 64);
@@ -647,7 +715,12 @@ struct Mic3 {
     long long removed_last = 0, removed_total = 0;   // by the last sort / since the last upload (pl3_tracers_removed)
     bool have_vgrid = false; M3Grid vgrid;           // the padded centre grid of the resident step: uploaded once per context
     bool search = false;                             // pl3_mic_set_search: cells by per-axis search in every marker kernel of this context
+    // pl3_mic_set_inflow: per wall of [z0, x0, y0, zL, xL, yL] the columns an inflow tracer takes from the wall (0: no material) and
+    // their planes on the device, in ascending column order (buffers "inflow_w" of bufs)
+    unsigned inflow_mask[6] = {0, 0, 0, 0, 0, 0}; double* inflow_dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    long long inflow_last = 0, inflow_total = 0;     // tracers given a wall's material by the last sort / since the last upload
 };
+static bool m3_has_inflow(const Mic3* M) { unsigned any = 0; for (int w = 0; w < 6; w++) any |= M->inflow_mask[w]; return any != 0u; }
 // a refill riding on a sort: what to do, and what the sort found
 struct M3Refill {
     int dens, dmin; unsigned long long seed; int it, unique;
@@ -1049,17 +1122,31 @@ static int m3_resort(pl3_ctx* ctx, Pl3HostView& v, Mic3* M, M3Refill* rf = nullp
         hipLaunchKernelGGL(k_m3_take, m3_blocks(nn), dim3(256), 0, v.stream, nn, (const double*)M->v, 1ll, cap, 3, (const int*)perm, alt + (3 + M3_NFTRAC) * ncap, ncap, 0u);
     }
     M->x = alt; M->f = alt + 3 * ncap; M->v = alt + (3 + M3_NFTRAC) * ncap; M->n = nn; M->cap = ncap;
+    M->inflow_last = 0;
+    int hinflow = 0; const int* counted = nullptr;    // the inflow count: a small read-back that only a context with a material makes
     if (rf && rf->nref > 0) {
         M3Inject a{};
         a.nref = (int)rf->nref; a.list = rf->list; a.loff = rf->loff; a.start = start; a.cnt = rf->cnt; a.dens = rf->dens;
         a.g = sg; a.x = M->x; a.f = M->f; a.v = M->v; a.cap = ncap;
         a.seed = rf->seed; a.it3 = 3u * (unsigned)rf->it; a.id0 = M->maxid; a.unique = rf->unique;
-        hipLaunchKernelGGL(k_m3_inject, m3_blocks(rf->nref * 64), dim3(256), 0, v.stream, a);
+        if (m3_has_inflow(M)) {
+            // the flow planes are those of the context at this moment (pl3_stokes_set_wall_flow may have replaced them since the last sort)
+            int* dcount;
+            M3_TRY(m3_buf(ctx, v, M, "inflow_count", (size_t)1, &dcount));
+            M3_HIP(ctx, hipMemsetAsync(dcount, 0, sizeof(int), v.stream));
+            for (int w = 0; w < 6; w++) { a.in.mask[w] = M->inflow_mask[w]; a.in.mat[w] = M->inflow_dev[w]; }
+            a.in.fl = v.wallflow; a.in.count = dcount;
+            hipLaunchKernelGGL(k_m3_inject<true>, m3_blocks(rf->nref * 64), dim3(256), 0, v.stream, a);
+            counted = dcount;
+        } else
+            hipLaunchKernelGGL(k_m3_inject<false>, m3_blocks(rf->nref * 64), dim3(256), 0, v.stream, a);
         M->maxid += (double)(rf->unique ? rf->ninj : rf->ninj - rf->nref);
     }
     M3_HIP(ctx, hipGetLastError());
     M3_HIP(ctx, hipEventRecord(M->ev1, v.stream));
+    if (counted) M3_HIP(ctx, m3_copy(ctx, &hinflow, counted, sizeof(int), hipMemcpyDeviceToHost, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    M->inflow_last = hinflow; M->inflow_total += hinflow;
     float ms = 0; (void)hipEventElapsedTime(&ms, M->ev0, M->ev1); M->ms[3] = ms;
     return 0;
 }
@@ -1121,6 +1208,65 @@ extern "C" int pl3_tracers_removed(pl3_ctx* ctx, int64_t out[2]) {
     return 0;
 }
 
+// The inflow material is context state like the search, the deletion and the RK4 weights: read by every refilling sort, which takes the
+// flow planes from the context at that moment.  Setting it touches no resident tracer.
+static const char* const m3_wall_names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
+static size_t m3_wall_faces(const Pl3HostView& v, int wall) {
+    const int a = wall % 3;
+    return (size_t)(v.gn[a == 0 ? 1 : 0] - 1) * (size_t)(v.gn[a == 2 ? 1 : 2] - 1);
+}
+extern "C" int pl3_mic_set_inflow(pl3_ctx* ctx, int wall, unsigned columns, const double* values) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_set_inflow", v, &M));
+    if (wall < 0 || wall > 5) return pl3_fail(ctx, "pl3_mic_set_inflow: wall " + std::to_string(wall) + " is not one of 0 ... 5 (z0, x0, y0, zL, xL, yL)");
+    const std::string wn = m3_wall_names[wall];
+    if (columns >> M3_ID) {
+        int bit = M3_ID;
+        while (!((columns >> bit) & 1u)) bit++;
+        if (bit == M3_ID) return pl3_fail(ctx, "pl3_mic_set_inflow: the column mask of wall " + wn + " has bit 12 set: TR__ID is handed out by the refill and cannot be prescribed");
+        return pl3_fail(ctx, "pl3_mic_set_inflow: the column mask of wall " + wn + " has bit " + std::to_string(bit) + " set: the tracer columns are 0 ... 11");
+    }
+    if (columns == 0u) { M->inflow_mask[wall] = 0u; return 0; }
+    if (!values) return pl3_fail(ctx, "pl3_mic_set_inflow: wall " + wn + " names columns but values is NULL");
+    const size_t nface = m3_wall_faces(v, wall);
+    const int ncol = __builtin_popcount(columns);
+    for (int j = 0, r = 0; j < M3_ID; j++) {
+        if (!((columns >> j) & 1u)) continue;
+        for (size_t i = 0; i < nface; i++)
+            if (!std::isfinite(values[(size_t)r * nface + i])) {
+                char num[40];
+                snprintf(num, sizeof(num), "%g", values[(size_t)r * nface + i]);
+                return pl3_fail(ctx, "pl3_mic_set_inflow: wall " + wn + ", column " + std::to_string(j) + " has a non-finite value at index " + std::to_string(i) + " = " + num);
+            }
+        r++;
+    }
+    double* d;
+    M3_TRY(m3_buf(ctx, v, M, (std::string("inflow_w") + std::to_string(wall)).c_str(), (size_t)ncol * nface, &d));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));          // (nothing of this context is in flight between calls; the copy below is blocking anyway)
+    M3_HIP(ctx, m3_copy(ctx, d, values, (size_t)ncol * nface * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));          // the host array may be a temporary of the caller
+    M->inflow_dev[wall] = d; M->inflow_mask[wall] = columns;
+    return 0;
+}
+extern "C" int pl3_mic_get_inflow(pl3_ctx* ctx, int wall, unsigned* columns, double* values) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_get_inflow", v, &M));
+    if (wall < 0 || wall > 5) return pl3_fail(ctx, "pl3_mic_get_inflow: wall " + std::to_string(wall) + " is not one of 0 ... 5 (z0, x0, y0, zL, xL, yL)");
+    if (columns) *columns = M->inflow_mask[wall];
+    if (!values || !M->inflow_mask[wall]) return 0;
+    const size_t count = (size_t)__builtin_popcount(M->inflow_mask[wall]) * m3_wall_faces(v, wall);
+    M3_HIP(ctx, m3_copy(ctx, values, M->inflow_dev[wall], count * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    M3_HIP(ctx, hipStreamSynchronize(v.stream));
+    return 0;
+}
+extern "C" int pl3_mic_inflow_count(pl3_ctx* ctx, int64_t out[2]) {
+    Pl3HostView v; Mic3* M;
+    M3_TRY(m3_open(ctx, "pl3_mic_inflow_count", v, &M));
+    if (!out) return pl3_fail(ctx, "pl3_mic_inflow_count: NULL argument");
+    out[0] = M->inflow_last; out[1] = M->inflow_total;
+    return 0;
+}
+
 extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, const double* tr_f) {
     Pl3HostView v; Mic3* M;
     M3_TRY(m3_open(ctx, "pl3_tracers_upload", v, &M));
@@ -1130,7 +1276,7 @@ extern "C" int pl3_tracers_upload(pl3_ctx* ctx, int64_t n, const double* tr_x, c
     M3_TRY(m3_buf(ctx, v, M, "h_aos", (size_t)cap * (3 + M3_NFTRAC), &aos));
     M3_TRY(m3_buf(ctx, v, M, "r_a", (size_t)cap * (6 + M3_NFTRAC), &a));
     M->n = n; M->cap = cap; M->x = a; M->f = a + 3 * cap; M->v = a + (3 + M3_NFTRAC) * cap; M->have = true; M->have_maxid = false;
-    M->removed_last = 0; M->removed_total = 0;
+    M->removed_last = 0; M->removed_total = 0; M->inflow_last = 0; M->inflow_total = 0;
     M3_HIP(ctx, hipMemsetAsync(a, 0, (size_t)cap * (6 + M3_NFTRAC) * sizeof(double), v.stream));
     if (n > 0) {
         M3_HIP(ctx, m3_copy(ctx, aos, tr_x, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, v.stream));

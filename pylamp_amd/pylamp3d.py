@@ -130,6 +130,58 @@ def wall_flows(flow, nx, who="3-D Stokes"):
     return out
 
 
+def wall_materials(material, nx, who="3-D markers"):
+    """material: what the new tracers of the refill carry where a wall flow brings material into the box (the rule is in
+    include/pylamp_hip.h at pl3_mic_set_inflow) -- None, or six entries [z0, x0, y0, zL, xL, yL], each None or a dict {column: value}
+    with the TR_* constants as keys and a scalar or an array of shape (n_p - 1, n_q - 1) over the wall's faces as value (the planes of
+    wall_flows).  Scalars are broadcast to planes.  Returns six entries, None or (mask, float64 array (ncol, n_p - 1, n_q - 1)) with
+    the planes in ascending column order; a wrong length, a wrong plane shape, TR__ID, an unknown column and a non-finite value are
+    rejected by name."""
+    if material is None:
+        return [None] * 6
+    if isinstance(material, dict) or not hasattr(material, "__len__"):
+        raise Exception("%s: the inflow material needs six entries [z0, x0, y0, zL, xL, yL], each None or a dict (got %s)" % (who, type(material).__name__))
+    material = list(material)
+    if len(material) != 6:
+        raise Exception("%s: the inflow material needs six entries [z0, x0, y0, zL, xL, yL] (got %d)" % (who, len(material)))
+    out = []
+    for w, m in enumerate(material):
+        if m is None or (isinstance(m, dict) and not m):
+            out.append(None)
+            continue
+        if not isinstance(m, dict):
+            raise Exception("%s: the inflow material of wall %s needs a dict {column: value} or None (got %s)" % (who, WALL_NAMES[w], type(m).__name__))
+        p, q = FLOW_AXES[w % 3]
+        shp = (int(nx[p]) - 1, int(nx[q]) - 1)
+        cols = {}
+        for key, val in m.items():
+            col = int(key) if isinstance(key, (int, np.integer)) and not isinstance(key, bool) else None
+            if col == TR__ID:
+                raise Exception("%s: the inflow material of wall %s names TR__ID: the IDs are handed out by the refill and cannot be prescribed"
+                                % (who, WALL_NAMES[w]))
+            if col is None or not 0 <= col < TR__ID:
+                raise Exception("%s: the inflow material of wall %s names an unknown column %r (the tracer columns are the TR_* constants 0 ... %d)"
+                                % (who, WALL_NAMES[w], key, TR__ID - 1))
+            try:
+                a = np.array(val, dtype=np.float64)
+            except (TypeError, ValueError):
+                a = None
+            if a is not None and a.ndim == 0:
+                a = np.full(shp, float(a))
+            if a is None or a.shape != shp:
+                raise Exception("%s: column %d of the inflow material of wall %s needs the shape (%s - 1, %s - 1) = %r or a scalar (got %s)"
+                                % (who, col, WALL_NAMES[w], _AXIS_N[p], _AXIS_N[q], shp, "an object that is no array" if a is None else a.shape))
+            bad = np.argwhere(~np.isfinite(a))
+            if bad.size:
+                i, j = (int(v) for v in bad[0])
+                raise Exception("%s: column %d of the inflow material of wall %s has a non-finite value [%d, %d] = %r"
+                                % (who, col, WALL_NAMES[w], i, j, float(a[i, j])))
+            cols[col] = a
+        order = sorted(cols)
+        out.append((sum(1 << c for c in order), np.ascontiguousarray(np.stack([cols[c] for c in order]))))
+    return out
+
+
 def wall_fluxes(grid, flow):
     """(fluxes, Phi) of a wall flow on the grid [z, x, y]: fluxes[w] = s_w sum_ij Un_w[i, j] dp_i dq_j, the volume per second that
     enters the box through wall w (s = +1 on z0, x0, y0, -1 on zL, xL, yL; 0 for a wall without flow), and their sum Phi, which
@@ -228,6 +280,41 @@ class Context3:
         """(removed by the last sort of the resident tracers, removed since the last upload)."""
         v = (C.c_int64 * 2)()
         self.check(self.lib.pl3_tracers_removed(self.handle(), v))
+        return int(v[0]), int(v[1])
+
+    def set_inflow_material(self, material):
+        """What the refill's new tracers carry where a wall flow brings material in (wall_materials: six entries, each None or a dict
+        {TR_* column: scalar or plane}; None clears all six); kept until set again, like the search and the deletion.  All six are
+        checked before the first is set, so a rejected call changes nothing.  A material on a wall without a flow is accepted: the
+        rule (include/pylamp_hip.h at pl3_mic_set_inflow) fires only where the wall flow is inward at the time of a sort."""
+        ms = wall_materials(material, self.nx, "Context3.set_inflow_material")
+        h = self.handle()
+        for w, m in enumerate(ms):
+            if m is None:
+                self.check(self.lib.pl3_mic_set_inflow(h, w, 0, None))
+            else:
+                self.check(self.lib.pl3_mic_set_inflow(h, w, m[0], _lib.dptr(m[1])))
+
+    def inflow_material(self):
+        """Six entries, None or the dict {column: plane} of the wall as the device holds it."""
+        out = []
+        for w in range(6):
+            mask = C.c_uint()
+            self.check(self.lib.pl3_mic_get_inflow(self.handle(), w, C.byref(mask), None))
+            if not mask.value:
+                out.append(None)
+                continue
+            cols = [c for c in range(NFTRAC) if (mask.value >> c) & 1]
+            p, q = FLOW_AXES[w % 3]
+            planes = np.zeros((len(cols), self.nx[p] - 1, self.nx[q] - 1))
+            self.check(self.lib.pl3_mic_get_inflow(self.handle(), w, None, _lib.dptr(planes)))
+            out.append({c: planes[r] for r, c in enumerate(cols)})
+        return out
+
+    def inflow_count(self):
+        """(tracers given a wall's material by the last sort of the resident tracers, since the last upload)."""
+        v = (C.c_int64 * 2)()
+        self.check(self.lib.pl3_mic_inflow_count(self.handle(), v))
         return int(v[0]), int(v[1])
 
     def set_stokes_walls(self, bc):
@@ -507,7 +594,7 @@ class VirtualCluster3:
 # =====================================================================================================================
 # The reference's marker code is 2-D (pylamp_trac.py); these are its functions extended by one axis.  tr_x is (n, 3) in
 # [z, x, y] order, tr_f has the 2-D columns of pylamp_const.py, grid arrays are C-order (nz, nx, ny).
-from .pylamp_const import (NFTRAC, EPS, TR_RHO, TR_ETA, TR_TMP, TR_HCD, TR_HCP, TR_MAT, TR_IHT, TR__ID)  # noqa: E402,F401
+from .pylamp_const import (NFTRAC, EPS, TR_RHO, TR_ETA, TR_MRK, TR_TMP, TR_HCD, TR_HCP, TR_RH0, TR_MAT, TR_IHT, TR__ID)  # noqa: E402,F401
 
 INTERP_AVG_ARITHMETIC = 1
 INTERP_AVG_GEOMETRIC = 2
@@ -735,6 +822,10 @@ class Options3:
         # beyond the reference: flow through the six walls (wall_flows: per wall None, a scalar or the plane Un of the wall-normal
         # velocity along +axis); needs tracs_fence_enabled = False with marker_deletion = True, and tracdens_min > 0 (None: no flow)
         self.bcstokesflow = None
+        # beyond the reference: what enters through an inflow wall (wall_materials: per wall None or {TR_* column: scalar or plane}); the
+        # refill's new tracers between the wall and the cell's residents take these values where the wall flow is inward (None: the
+        # zero-gradient inflow, every new tracer the mean of its cell)
+        self.bcinflow = None
         self.bcheat = [BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW, BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW]
         self.bcheatvals = [273.0, 0.0, 0.0, 1623.0, 0.0, 0.0]
         self.stokes_rtol, self.stokes_maxit = DEFAULT_RTOL, DEFAULT_MAXIT
@@ -778,8 +869,13 @@ class Simulation3:
     next sort, the census and the refill of that sort see the survivors, step() / advect() / refill() report nremoved and
     Context3.tracers_removed() counts them.  On that path material may flow through the walls (Options3.bcstokesflow,
     set_wall_flow; wall_flows states the format): the outflow is deleted, the cells along an inflow wall are kept filled by the refill
-    (tracdens_min > 0 is required), whose new tracers carry the mean of their cell's residents -- a zero-gradient inflow; the net flux
-    must vanish (wall_fluxes); Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default,
+    (tracdens_min > 0 is required), whose new tracers carry the mean of their cell's residents -- a zero-gradient inflow -- unless the
+    wall has an inflow material (Options3.bcinflow, set_inflow_material; wall_materials states the format): then the new tracers that
+    lie between the wall and every resident of their cell take the wall's values in the columns it names, step() / advect() / refill()
+    report them as ninflow, and an inflow cell that ran empty gets finite values in those columns (a scattered column the material
+    leaves out is still NaN there and step() raises its NaN error); a prescribed TR_TMP is a tracer temperature like any other, so
+    with heat diffusion on it enters the next step's temperature scatter, while the heat solve keeps its one boundary value per wall;
+    the net flux must vanish (wall_fluxes); Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default,
     move them by 2/3 of that).  Not built: surface stabilisation, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
@@ -819,6 +915,7 @@ class Simulation3:
             raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
         self.bcstokesflow = self._checked_flow(o.bcstokesflow, "Simulation3: Options3.bcstokesflow")
+        wall_materials(o.bcinflow, self.nx, "Simulation3: Options3.bcinflow")
         self.ctx = Context3(self.nx, self.grid, device)
         self.bcstokesvel = wall_velocities(o.bcstokesvel, self.bcstokes, "Simulation3: Options3.bcstokesvel")
         self.ctx.set_stokes_walls(self.bcstokes)        # the resident step and the device advection velocity read them from the context
@@ -831,6 +928,9 @@ class Simulation3:
             self.ctx.set_marker_deletion(True)
         if o.rk4_classic:
             self.ctx.set_rk4_classic(True)
+        self._inflow = False
+        if o.bcinflow is not None:
+            self.set_inflow_material(o.bcinflow)
         self.it = 0
         self.totaltime = 0.0
         self.last = None
@@ -864,10 +964,17 @@ class Simulation3:
 
     def set_wall_flow(self, flow):
         """A new flow through the six walls (wall_flows; None: none) from the next step on.  New tracers of the refilled cells along an
-        inflow wall carry the mean of the cell's residents: a zero-gradient inflow."""
+        inflow wall carry the mean of the cell's residents, a zero-gradient inflow, or the wall's material (set_inflow_material)."""
         fl = self._checked_flow(flow, "Simulation3.set_wall_flow")
         self.ctx.set_wall_flow(fl)
         self.bcstokesflow = fl
+
+    def set_inflow_material(self, material):
+        """The material of the six walls (wall_materials; None: none) for the refills from now on: new tracers between an inflow wall
+        and the residents of their cell take it.  A wall that carries no flow right now may hold one; it waits for set_wall_flow."""
+        ms = wall_materials(material, self.nx, "Simulation3.set_inflow_material")
+        self.ctx.set_inflow_material(material)
+        self._inflow = any(m is not None for m in ms)
 
     # -- tracer state ------------------------------------------------------------------------------------------------
     def _lib_call(self, name, *args):
@@ -975,12 +1082,15 @@ class Simulation3:
                      1 if o.inject_unique_ids else 0, out)
 
     def _counters(self, out):
-        """The four counters of a sort with refill; with Options3.marker_deletion also nremoved (without it the dict keeps its four
-        keys: callers compare it whole).  ntrac follows both."""
+        """The four counters of a sort with refill; with Options3.marker_deletion also nremoved, and with an inflow material set also
+        ninflow, the new tracers that took a wall's material (without them the dict keeps its four keys: callers compare it whole).
+        ntrac follows the first two."""
         c = dict(ninjected=int(out[0]), nrefilled=int(out[1]), nempty=int(out[2]), mincount=int(out[3]))
         gone = self.ctx.tracers_removed()[0]
         if self.opt.marker_deletion:
             c["nremoved"] = gone
+        if self._inflow:
+            c["ninflow"] = self.ctx.inflow_count()[0]
         self.ntrac += c["ninjected"] - gone
         return c
 
@@ -988,7 +1098,8 @@ class Simulation3:
         """Sort + census + refill of the cells below opt.tracdens_min to opt.tracdens, without advection (a sparse initial set is
         topped up with it).  `it` selects the random stream (default: the step counter).  Returns ninjected, nrefilled (cells),
         nempty (cells without any tracer before the call) and mincount (smallest count before the call); with Options3.marker_deletion
-        also nremoved, the tracers the sort removed (the counts are those after the removal)."""
+        also nremoved, the tracers the sort removed (the counts are those after the removal); with an inflow material set also ninflow,
+        the new tracers that took a wall's material."""
         out, args = self._refill_args(it)
         self._lib_call("pl3_resident_refill", *args)
         return self._counters(out)
@@ -1042,6 +1153,8 @@ class Simulation3:
         rep = dict(it=self.it, tstep=r.tstep, limiter="H" if r.limiter else "S", stokes=r.stokes.as_dict(),
                    heat=r.heat.as_dict() if o.do_heatdiff else None, ninjected=int(r.ninjected), nrefilled=int(r.nrefilled),
                    nempty=int(r.nempty), mincount=int(r.mincount), nremoved=int(r.nremoved), time=self.totaltime, ntrac=self.ntrac)
+        if self._inflow:
+            rep["ninflow"] = self.ctx.inflow_count()[0]
         self.fields = {}
         self._stepped = True
         self.last = rep

@@ -26,6 +26,15 @@ profiles/mic3_129_delete.json:
 --off FILE [FILE ...] / --parent FILE [FILE ...] embed, per stage, the figures the plain script wrote for this tree with deletion off
 and for the parent commit's tree (separate processes, alternating), with the ratio of the medians and both run-to-run spreads.
 
+--inflow times the refilling sort along an inflow wall and writes profiles/mic3_129_inflow.json: a plug flow z0 -> zL is set (fence
+off, deletion on), the cell layer along z0 is thinned to 2 of its 8 tracers per cell and uploaded afresh for every repetition
+(--refill-reps), and pl3_resident_refill tops the layer up -- one wave of k_m3_inject per cell of the layer:
+  sort_layer_refill   no inflow material: k_m3_inject<false>, every new tracer the mean of its cell,
+  sort_layer_inflow   a material {TR_MAT, TR_TMP, TR_RH0} on z0: k_m3_inject<true>, the new tracers below the lowest resident take it
+(the two alternate inside one loop).  --parent-sort / --this-sort FILE ... and --parent-step / --this-step FILE ... embed what
+--sort-only and --step --resident wrote for the parent commit's tree and for this one without a material (separate processes,
+alternating): the sort with refill (sort_on_1pct) and the resident step, ratio of the medians next to the parent's own spread.
+
 --step [--resident] times whole steps of Simulation3 -- the falling sphere with heat on, --n nodes per axis, 8 tracers per cell:
 host wall time per step (device synchronisation, then perf_counter, on either side of step()), median and min-max over --reps
 steps after --warmup, and the medians of the stage times (device events); writes profiles/mic3_step_129.json unless --out says
@@ -159,6 +168,50 @@ def sort_only(a):
     return out
 
 
+def sort_inflow(a):
+    """The refill of the cell layer along an inflow wall, without and with a material on that wall."""
+    nx = [a.n] * 3; L = [100e3] * 3
+    rng = np.random.default_rng(0)
+    tr_x, tr_f = P3.falling_sphere_tracers(nx, L, rng, per_axis=a.per_axis)
+    h = L[0] / (a.n - 1)
+    layer = tr_x[:, 0] < h
+    cell = np.clip(np.floor(tr_x[:, 1] / h).astype(np.int64), 0, a.n - 2) * (a.n - 1) + np.clip(np.floor(tr_x[:, 2] / h).astype(np.int64), 0, a.n - 2)
+    order = np.argsort(np.where(layer, cell, -1), kind="stable")
+    key = np.where(layer, cell, -1)[order]
+    rank = np.empty(tr_x.shape[0], dtype=np.int64)
+    rank[order] = np.arange(key.size) - np.searchsorted(key, key, side="left")
+    keep = ~layer | (rank < 2)
+    sx, sf = np.ascontiguousarray(tr_x[keep]), np.ascontiguousarray(tr_f[keep])
+    del tr_x, tr_f, cell, order, key, rank
+    n = sx.shape[0]
+    U = 1e-9
+    sim = P3.Simulation3(nx, L, options=P3.Options3(tracs_fence_enabled=False, marker_deletion=True, tracdens=8, tracdens_min=4,
+                                                    bcstokesflow=[U, None, None, U, None, None]))
+    mat = [{P3.TR_MAT: 3, P3.TR_TMP: 1500.0, P3.TR_RH0: 3200.0}, None, None, None, None, None]
+    t = dict(sort_layer_refill=[], sort_layer_inflow=[])
+    last = {}
+    for rep in range(1 + a.refill_reps):
+        for key, m in (("sort_layer_refill", None), ("sort_layer_inflow", mat)):
+            sim.set_inflow_material(m)
+            sim.upload(sx, sf)
+            last[key] = sim.refill(it=1)
+            if rep >= 1:
+                t[key].append(sim.stage_times()["sort"])
+    sim.close()
+    out = dict(config="mic3_%d_inflow" % a.n, nodes=a.n ** 3, tracers_before=n, refill_reps=a.refill_reps, states={})
+    for key in t:
+        out["states"][key] = dict(_stat(t[key], n), cells_refilled=int(last[key]["nrefilled"]), injected=int(last[key]["ninjected"]),
+                                  inflow=int(last[key].get("ninflow", 0)))
+    out["inflow_over_refill"] = round(out["states"]["sort_layer_inflow"]["ms"] / out["states"]["sort_layer_refill"]["ms"], 4)
+    for name, mine, theirs, pick in (("sort_on_1pct", a.this_sort, a.parent_sort, lambda r: r["states"]["sort_on_1pct"]["ms"]),
+                                     ("resident_step", a.this_step, a.parent_step, lambda r: r["step_ms"])):
+        if mine and theirs:
+            me, pa = _spread(mine, pick), _spread(theirs, pick)
+            out["no_material_" + name] = dict(this=me, parent=pa, ratio=round(me["ms"] / pa["ms"], 4),
+                                              parent_spread=round((pa["ms_max"] - pa["ms_min"]) / pa["ms"], 4))
+    return out
+
+
 def step_bench(a):
     import time
     import torch
@@ -205,12 +258,17 @@ def main():
     ap.add_argument("--step", action="store_true"); ap.add_argument("--resident", action="store_true"); ap.add_argument("--tree", default=None)
     ap.add_argument("--search", action="store_true"); ap.add_argument("--graded", type=float, default=0.0)
     ap.add_argument("--delete", action="store_true"); ap.add_argument("--off", nargs="*", default=[])
+    ap.add_argument("--inflow", action="store_true")
+    for name in ("--parent-sort", "--this-sort", "--parent-step", "--this-step"):
+        ap.add_argument(name, nargs="*", default=[])
     a = ap.parse_args()
-    if a.out is None:
+    if a.out is None and not a.inflow:
         a.out = os.path.join("profiles", "mic3_step_129.json" if a.step else ("mic3_129_delete.json" if a.sort_only and a.delete else
                                                                               ("mic3_129_refill.json" if a.sort_only else "mic3_129.json")))
-    if a.sort_only or a.step:
-        line = json.dumps(step_bench(a) if a.step else (sort_delete(a) if a.delete else sort_only(a)))
+    if a.inflow and a.out is None:
+        a.out = os.path.join("profiles", "mic3_129_inflow.json")
+    if a.inflow or a.sort_only or a.step:
+        line = json.dumps(sort_inflow(a) if a.inflow else (step_bench(a) if a.step else (sort_delete(a) if a.delete else sort_only(a))))
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(line + "\n")
