@@ -462,6 +462,42 @@ int  pl3_stokes_mg_info(pl3_ctx* ctx, int* nlevels, double* lmax, int max_levels
  * ratio lmax / lmin of their window, sweeps and ratio of the coarsest level, and lds[l] != 0 where the marching LDS kernels take level l. */
 int  pl3_stokes_precond_apply(pl3_ctx* ctx, const double* r, double* z);
 int  pl3_stokes_mg_plan(pl3_ctx* ctx, int* nu, double* ratio, int* coarse_sweeps, double* coarse_ratio, int* lds, int max_levels);
+/* Diagnostics for component tests of the 3-D Krylov loop (tests/test_hip_3d_krylov.py).  Each runs the solve's own
+ * kernels and host epilogues; none changes what pl3_stokes_solve computes.  Host vectors are (nz, nx, ny, 4), global on every rank.
+ * pl3_stokes_precond_apply_deflated: as pl3_stokes_precond_apply, with the deflation correction of the last solve of this context (an
+ *   error if that solve did not deflate).
+ * pl3_krylov_probe: ONE launch of one Krylov kernel.  in[q], q < 10 (NULL: none), is uploaded into Stokes work vector q -- equal
+ *   pointers share the work vector of the first -- and out[q] != NULL (out itself may be NULL) receives work vector q afterwards:
+ *     PL3_PROBE_DOTS    scal[0] = nd products (1 .. 5) in[q] . in[5 + q] -> sums[0 .. nd - 1]; on a context with pl3_set_comm attached
+ *                       the owned-nodes kernel and the all-reduce, as the solve chooses (collective)
+ *     PL3_PROBE_DOTS11  the fused reduction (one rank): t, s, rt = in[0 .. 2]; x = in[3] or NULL; dx = in[4], NULL or in[3] itself; yw the
+ *                       (nz, nx, ny) array or NULL -> sums[0 .. 10] = t.s, t.t, rt.s, rt.t, s.s | t.s, t.t, s.s of the pressure array |
+ *                       |(x + dx)_vel|^2 | yw.s_p, yw.t_p
+ *     PL3_PROBE_AXPBY   work 2 = scal[0] in[0] + scal[1] in[1]
+ *     PL3_PROBE_P       p, r, v = in[0 .. 2], beta, omega = scal[0 .. 1]:  p = r + beta (p - omega v) in work 0
+ *     PL3_PROBE_XR      x, y, z, r, s, t = in[0 .. 5], alpha, omega:  x += alpha y + omega z (work 0), r = s - omega t (work 3)
+ *     PL3_PROBE_XRP     ... and p, v = in[6 .. 7], beta = scal[2]:  also p = r + beta (p - omega v) (work 6)
+ *     PL3_PROBE_RANDOM  the shadow residual with seed scal[0] (the solve's is 1234) in work 0
+ * pl3_stokes_hydrostatic: the scaled right-hand side and the hydrostatic start exactly as pl3_stokes_solve(rhs = NULL) runs them:
+ *   xh = the start vector, *ref = the reference norm |b - A x_h| (0: not usable).  Collective on an attached context.
+ * pl3_stokes_work_vector: Stokes work vector `index` as the last solve left it -- 0 the recurrence residual r, 1 the shadow residual,
+ *   4 the last true residual, 8 the correction dx, 10 the scaled right-hand side, 13 the deflation vector w.
+ * pl3_stokes_defl_info (about the last solve): out[0] a deflation vector is kept, [1] the deflation was on during the solve, [2] the
+ *   quality |u - A w| / |u| measured on the kept vector (-1: none was), [3] iterations of the inner solve for w (0: reused as it is),
+ *   [4] its final |u - A w| / |u| (-1: no inner solve), [5] yw.(A w), [6] |w_vel|^2, [7] the true-residual checks the solve took,
+ *   [8] the iteration at which the estimate between the checks was last evaluated (0: never), [9] its value, [10 .. 14] what went into
+ *   it: |r|^2 and |r_cont|^2 of the recurrence residual, |x_vel|^2, the anchor part, a_mom.
+ *   u, yw (either may be NULL): the (nz, nx, ny) pressure plane of u and the weights yw of the deflation set-up.
+ * pl3_stokes_ring_sum: sum |entry| over the ring and padding entries of the 14 Stokes work vectors of this rank's block.  On one rank
+ *   the flat reductions rely on it being zero; on blocks the rings hold the neighbours' values (the sum is per rank, not reduced). */
+enum { PL3_PROBE_DOTS = 0, PL3_PROBE_DOTS11 = 1, PL3_PROBE_AXPBY = 2, PL3_PROBE_P = 3, PL3_PROBE_XR = 4, PL3_PROBE_XRP = 5, PL3_PROBE_RANDOM = 6 };
+int  pl3_stokes_precond_apply_deflated(pl3_ctx* ctx, const double* r, double* z);
+int  pl3_krylov_probe(pl3_ctx* ctx, int what, const double* const in[10], const double* yw, const double scal[3], double* const out[10],
+                      double* sums);
+int  pl3_stokes_hydrostatic(pl3_ctx* ctx, double* xh, double* ref);
+int  pl3_stokes_work_vector(pl3_ctx* ctx, int index, double* out);
+int  pl3_stokes_defl_info(pl3_ctx* ctx, double out[15], double* u, double* yw);
+int  pl3_stokes_ring_sum(pl3_ctx* ctx, double* out);
 int  pl3_heat_set_coeffs(pl3_ctx* ctx, const double* zmp, const double* xmp, const double* ymp, const double* T, const double* kz,
                          const double* kx, const double* ky, const double* cp, const double* rho, const double* H, const int bc[6],
                          const double bcvalue[6], double tstep);

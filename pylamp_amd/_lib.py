@@ -94,6 +94,12 @@ SIGNATURES = {
     "pl3_stokes_mg_info": (C.c_int, [C.c_void_p, c_int_p, c_double_p, C.c_int]),
     "pl3_stokes_precond_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_stokes_mg_plan": (C.c_int, [C.c_void_p, c_int_p, c_double_p, c_int_p, c_double_p, c_int_p, C.c_int]),
+    "pl3_stokes_precond_apply_deflated": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "pl3_krylov_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(c_double_p), c_double_p, c_double_p, C.POINTER(c_double_p), c_double_p]),
+    "pl3_stokes_hydrostatic": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "pl3_stokes_work_vector": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "pl3_stokes_defl_info": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "pl3_stokes_ring_sum": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_heat_set_coeffs": (C.c_int, [C.c_void_p] + [c_double_p] * 10 + [c_int_p, c_double_p, C.c_double]),
     "pl3_heat_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),

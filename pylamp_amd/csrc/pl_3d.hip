@@ -1146,6 +1146,17 @@ __global__ __launch_bounds__(256) void k3_dots_own(G3 g, int na, Dot5 d, double*
     }
     block_sums3<5>(acc, part);
 }
+// sum |v| over the entries of na consecutive arrays that lie OUTSIDE the owned block (the ring of nodes in z and x, the padding of the
+// y-lines): part[5 b] -- what the flat kernels above rely on being zero on one rank (pl3_stokes_ring_sum)
+__global__ __launch_bounds__(256) void k3_ring_abs(G3 g, int na, const double* __restrict__ v, double* __restrict__ part) {
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < g.vol; e += (long long)gridDim.x * 256) {
+        const long long li = e / g.s[0] - 1, lj = (e % g.s[0]) / g.s[1] - 1, lk = e % g.s[1] - P3_PAD;
+        if (li >= 0 && li < g.n[0] && lj >= 0 && lj < g.n[1] && lk >= 0 && lk < g.n[2]) continue;
+        for (int q = 0; q < na; q++) acc[0] += fabs(v[q * g.vol + e]);
+    }
+    block_sums3<5>(acc, part);
+}
 
 // =====================================================================================================================
 // host side
@@ -1202,6 +1213,9 @@ struct pl3_ctx {
     // deflation of the pressure-anchor mode (see pl_solver.hip): the vector w = A^-1 u lives in vec[13], kept between solves
     double *dfl_y = nullptr, *dfl_t = nullptr; bool dfl_valid = false;
     bool dfl_active = false; double dfl_yAw = 0.0, dfl_wvel2 = 0.0;      // of the running solve: the anchor-mode term of the error estimate
+    // what the last pl3_stokes_solve did about it (pl3_stokes_defl_info): the deflation was on, the quality of the kept vector as measured
+    // (-1: none), iterations and final residual of the inner solve (0 / -1: the vector was reused as it is), true-residual checks
+    struct { int active = 0, inner_its = 0, checks = 0, rec_it = 0; double q = -1.0, inner_res = -1.0, rec[6] = {0, 0, 0, 0, 0, 0}; } dfl_last;
     double etol = 3e-8;                     // bound on the velocity-error estimate of a converged Stokes solve (PYLAMP_STOKES_ETOL)
     void* mic3 = nullptr;                   // pl_mic3.hip: resident tracers and the work buffers of the 3-D marker kernels
     void* step3 = nullptr;                  // pl_step3.hip: state of the device-resident time step
@@ -1881,12 +1895,25 @@ __global__ __launch_bounds__(256) void k3_cont_rows(Op3 op, V3 v, double* __rest
 
 // ---- right-preconditioned BiCGStab on Krylov vectors (correction form, true-residual stopping) ----------------------------------
 typedef int (*Op3Fn)(pl3_ctx*, const Vec3& in, const Vec3& out);
-struct Stats3 { int iterations, converged; double rel_residual; double error_estimate; };
-enum { K_R, K_RT, K_P, K_V, K_S, K_T, K_Y, K_Z, K_DX, K_R0, K_NW };      // the work vectors of bicgstab3
+// rec_it > 0: the iteration at which the estimate between the checks was last evaluated, with its value and what went into est_rec3
+struct Stats3 { int iterations, converged; double rel_residual; double error_estimate; int checks; int rec_it; double rec[6]; };enum { K_R, K_RT, K_P, K_V, K_S, K_T, K_Y, K_Z, K_DX, K_R0, K_NW };      // the work vectors of bicgstab3
 static void axpby3(pl3_ctx* ctx, const Vec3& y, double a, const Vec3& x, double b, const Vec3& z) {
     hipLaunchKernelGGL(k3_axpby, g1(y.n()), dim3(256), 0, ctx->stream, y.n(), y.p, a, (const double*)x.p, b, (const double*)z.p);
 }
 static int zero3(pl3_ctx* ctx, const Vec3& y) { P3_HIP(ctx, hipMemsetAsync(y.p, 0, (size_t)y.n() * sizeof(double), ctx->stream)); return 0; }
+// the shadow residual of bicgstab3: array c of rt from the hash of the global node index, seed + c
+static void random3(pl3_ctx* ctx, const Vec3& rt, unsigned seed) {
+    for (int c = 0; c < rt.na; c++) launch3(ctx, *rt.g, k3_random, *rt.g, rt[c], seed + c);
+}
+// the fused reduction of bicgstab3 (one rank, Stokes vectors): the 11 sums of k3_dots11; x / dx / yw as the iteration has them (x NULL:
+// no |x_vel|^2; dx the vector x itself: x alone; yw NULL: no anchor sums)
+static int dots11_3(pl3_ctx* ctx, const Vec3& t, const Vec3& s, const Vec3& rt, const Vec3* x, const Vec3* dx, const double* yw, double* f11) {
+    Fuse11 fa{}; fa.t = t.p; fa.s = s.p; fa.rt = rt.p; fa.vol = t.g->vol;
+    if (x) { fa.x = x->p; fa.dx = (dx && dx->p != x->p) ? dx->p : nullptr; }
+    fa.yw = yw;
+    hipLaunchKernelGGL(k3_dots11, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, fa, ctx->part);
+    return sum_partials3(ctx, 11, 11, f11);
+}
 static bool trace3() { static const bool on = getenv("PYLAMP_SOLVER_TRACE") != nullptr; return on; }
 
 // The velocity-error estimate (n |r_cont| + |(M^-1 r)_vel|) / |x_vel| of a Stokes solve, as in pl_solver.hip.  anchor: the component of
@@ -1895,6 +1922,9 @@ static bool trace3() { static const bool on = getenv("PYLAMP_SOLVER_TRACE") != n
 // tol, bnorm: the residual test of the iteration (tol tightens while the estimate is above etol); rec: the estimate between the checks;
 // est: that of the last check; resume: the check sends the iteration on.
 struct Est3 { bool on, anchor, resume; double etol, n_amp, a_mom, rec, est, tol, bnorm; int checks; };
+static void note_rec3(Stats3* st, int it, const Est3& e, double rr, double rc, double xx, double ap) {
+    st->rec_it = it; st->rec[0] = e.rec; st->rec[1] = rr; st->rec[2] = rc; st->rec[3] = xx; st->rec[4] = ap; st->rec[5] = e.a_mom;
+}
 static double anchor_amp3(const pl3_ctx* ctx, double yr, double xx) { return std::fabs(yr / ctx->dfl_yAw) * std::sqrt(ctx->dfl_wvel2 / xx); }
 static int anchor_part3(pl3_ctx* ctx, const Est3& e, const Vec3& res, double xx, double* out) {
     *out = 0.0;
@@ -1947,13 +1977,13 @@ static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& 
     P3_TRY(dot3(ctx, b, b, d));
     double bnorm = std::sqrt(d[0]);
     if (ref_norm > 0.0 && bnorm > 0.0) bnorm = ref_norm;
-    st->iterations = 0; st->converged = 0; st->rel_residual = 0.0; st->error_estimate = 0.0;
+    st->iterations = 0; st->converged = 0; st->rel_residual = 0.0; st->error_estimate = 0.0; st->rec_it = 0;
     if (!(bnorm > 0.0)) { P3_TRY(zero3(ctx, x)); st->converged = 1; return 0; }
     Vec3 dx = x, r0 = b;
     if (use_x0) { dx = w[K_DX]; P3_TRY(A(ctx, x, v)); r0 = w[K_R0]; axpby3(ctx, r0, 1.0, b, -1.0, v); }
     P3_TRY(zero3(ctx, dx));
     axpby3(ctx, r, 1.0, r0, 0.0, r0);
-    for (int c = 0; c < na; c++) launch3(ctx, g, k3_random, g, rt[c], 1234u + c);
+    random3(ctx, rt, 1234u);
     int it = 0, restarts = 0; double true_norm = -1.0, last_true = -1.0;
     Est3 e{};
     e.on = etol > 0.0 && na == 4 && M; e.anchor = e.on && ctx->dfl_active && ctx->dfl_yAw != 0.0;
@@ -1992,10 +2022,7 @@ static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& 
             double f11[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             const bool late = e.on && rnorm <= 1e3 * e.tol * bnorm;
             if (fused) {       // ... and, near the end, everything the error estimate of the updated iterate needs, in the same pass
-                Fuse11 fa{}; fa.t = t.p; fa.s = s.p; fa.rt = rt.p; fa.vol = g.vol;
-                if (late) { fa.x = x.p; fa.dx = (dx.p != x.p) ? dx.p : nullptr; fa.yw = e.anchor ? ctx->dfl_y : nullptr; }
-                hipLaunchKernelGGL(k3_dots11, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, fa, ctx->part);
-                P3_TRY(sum_partials3(ctx, 11, 11, f11));
+                P3_TRY(dots11_3(ctx, t, s, rt, late ? &x : nullptr, &dx, (late && e.anchor) ? ctx->dfl_y : nullptr, f11));
                 for (int q = 0; q < 5; q++) d[q] = f11[q];
             } else { const Vec3 aa[5] = {t, t, rt, rt, s}, bb[5] = {s, t, s, t, s}; P3_TRY(dots3(ctx, 5, aa, bb, d)); }
             omega = (d[1] > 0.0) ? d[0] / d[1] : 0.0;
@@ -2019,12 +2046,14 @@ static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& 
                 const double rc = f11[7] - 2.0 * omega * f11[5] + omega * omega * f11[6], xx = f11[8];
                 const double ap = (e.anchor && xx > 0.0) ? anchor_amp3(ctx, f11[9] - omega * f11[10], xx) : 0.0;
                 e.rec = est_rec3(e, rr, rc > 0.0 ? rc : 0.0, xx, ap);
+                note_rec3(st, it, e, rr, rc, xx, ap);
             } else if (e.on && rnorm <= 1e3 * e.tol * bnorm) {    // near the end: the estimate from the recurrence residual
                 double rc, xx = 0.0, ap = 0.0;
                 P3_TRY(dot3(ctx, r.prs(), r.prs(), &rc));
                 P3_TRY(vel_norm2_3(ctx, x, dx, t, &xx));
                 P3_TRY(anchor_part3(ctx, e, r, xx, &ap));
                 e.rec = est_rec3(e, rr, rc, xx, ap);
+                note_rec3(st, it, e, rr, rc, xx, ap);
             }
             if (it - best_it > 80 || rnorm > 1e8 * best) { broke = true; break; }
         }
@@ -2043,7 +2072,7 @@ static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& 
         axpby3(ctx, r, 1.0, s, 0.0, s);
     }
     if (dx.p != x.p) axpby3(ctx, x, 1.0, x, 1.0, dx);
-    st->iterations = it; st->rel_residual = true_norm / bnorm;
+    st->iterations = it; st->rel_residual = true_norm / bnorm; st->checks = e.checks;
     st->converged = (st->rel_residual <= rtol && !(e.on && st->error_estimate > 1.5 * etol)) ? 1 : 0;
     return 0;
 }
@@ -2182,6 +2211,7 @@ static int deflation_setup3(pl3_ctx* ctx, const Vec3& U, const Vec3* w) {
         const Vec3 aa[2] = {res, U};
         P3_TRY(dots3(ctx, 2, aa, aa, dq));
         q = (dq[1] > 0.0 && std::isfinite(dq[0])) ? std::sqrt(dq[0] / dq[1]) : 1.0;
+        ctx->dfl_last.q = q;
     }
     const bool reuse = ctx->dfl_valid && q < 0.5;
     if (reuse) P3_TRY(activate());
@@ -2190,6 +2220,7 @@ static int deflation_setup3(pl3_ctx* ctx, const Vec3& U, const Vec3* w) {
         Stats3 st{};
         P3_TRY(bicgstab3(ctx, stokes_A3, stokes_M3, U, W, reuse, 1e-3, 80, w, &st, 0.0));
         ctx->dfl_valid = st.rel_residual < 0.05 && std::isfinite(st.rel_residual);
+        ctx->dfl_last.inner_its = st.iterations; ctx->dfl_last.inner_res = st.rel_residual;
         ctx->dfl_active = false;
         if (ctx->dfl_valid) P3_TRY(activate());
     }
@@ -2223,9 +2254,13 @@ extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int 
     launch3(ctx, g, k3_close, ctx->op, wv3(X), cv3(B));
     static const bool defl_on = !(getenv("PYLAMP_DEFLATE") && atoi(getenv("PYLAMP_DEFLATE")) == 0);
     if (const char* e = getenv("PYLAMP_STOKES_ETOL")) { const double v = atof(e); if (v >= 0.0) ctx->etol = v; }
+    ctx->dfl_last = {};
     if (defl_on && ctx->levels.size() > 1) P3_TRY(deflation_setup3(ctx, XH, w));        // (the hydrostatic vector is not needed any more)
+    ctx->dfl_last.active = ctx->dfl_active ? 1 : 0;
     Stats3 st{};
     P3_TRY(bicgstab3(ctx, stokes_A3, stokes_M3, B, X, true, rtol, maxit, w, &st, ref, ctx->etol));
+    ctx->dfl_last.checks = st.checks; ctx->dfl_last.rec_it = st.rec_it;
+    for (int q = 0; q < 6; q++) ctx->dfl_last.rec[q] = st.rec_it ? st.rec[q] : 0.0;
     ctx->dfl_active = false;
     P3_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     P3_HIP(ctx, hipEventSynchronize(ctx->ev1));
@@ -2255,18 +2290,147 @@ extern "C" int pl3_stokes_mg_plan(pl3_ctx* ctx, int* nu, double* ratio, int* coa
     return 0;
 }
 // z = M^-1 r by stokes_M3 itself, without the deflation correction: r is the row-scaled residual as bicgstab3 hands it over
-extern "C" int pl3_stokes_precond_apply(pl3_ctx* ctx, const double* r, double* z) {
+static int precond_apply3(pl3_ctx* ctx, const double* r, double* z, bool deflated) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     if (!r || !z) return p3_fail(ctx, "pl3_stokes_precond_apply: NULL argument");
+    if (deflated && !(ctx->dfl_valid && ctx->dfl_last.active)) return p3_fail(ctx, "pl3_stokes_precond_apply_deflated: the last solve of this context did not deflate");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_vecs(ctx, 14));
     P3_TRY(build_levels3(ctx));
     const Vec3 R = svec(ctx, 0), Z = svec(ctx, 1);
     P3_TRY(upload3(ctx, r, 4, wv4(R).p));
+    ctx->dfl_active = deflated;
+    const int rc = stokes_M3(ctx, R, Z);
     ctx->dfl_active = false;
-    P3_TRY(stokes_M3(ctx, R, Z));
+    P3_TRY(rc);
     P3_HIP(ctx, hipGetLastError());
     P3_TRY(download3(ctx, wv4(Z).p, 4, z));
+    return 0;
+}
+extern "C" int pl3_stokes_precond_apply(pl3_ctx* ctx, const double* r, double* z) { return precond_apply3(ctx, r, z, false); }
+// ... and with the deflation correction of the last solve: its w (work vector 13), yw and yw.(A w)
+extern "C" int pl3_stokes_precond_apply_deflated(pl3_ctx* ctx, const double* r, double* z) { return precond_apply3(ctx, r, z, true); }
+
+// ---- component tests of the Krylov loop (tests/test_hip_3d_krylov.py): the solve's own kernels and host epilogues on given vectors ----
+// One launch of one Krylov kernel.  in[q] (q < 10; (nz, nx, ny, 4) host vectors, NULL: none) goes into Stokes work vector q -- equal
+// pointers share the work vector of the first -- and out[q] != NULL receives work vector q afterwards.  Slots per kernel:
+//   PL3_PROBE_DOTS     scal[0] = nd products (1 .. 5) a_q . b_q, a_q = in[q], b_q = in[5 + q]; sums[0 .. nd - 1] (dots3: k3_dots on one
+//                      rank, k3_dots_own and the all-reduce on an attached context)
+//   PL3_PROBE_DOTS11   t, s, rt = in[0 .. 2], x = in[3] or NULL, dx = in[4] or NULL or in[3] itself, yw: the (nz, nx, ny) array or NULL;
+//                      sums[0 .. 10]
+//   PL3_PROBE_AXPBY    work 2 = scal[0] in[0] + scal[1] in[1]
+//   PL3_PROBE_P        p, r, v = in[0 .. 2]; beta, omega = scal[0 .. 1]; p in work 0
+//   PL3_PROBE_XR       x, y, z, r, s, t = in[0 .. 5]; alpha, omega; x in work 0, r in work 3
+//   PL3_PROBE_XRP      x, y, z, r, s, t, p, v = in[0 .. 7]; alpha, omega, beta; x, r, p in work 0, 3, 6
+//   PL3_PROBE_RANDOM   scal[0] = seed; the shadow residual in work 0
+extern "C" int pl3_krylov_probe(pl3_ctx* ctx, int what, const double* const in[10], const double* yw, const double scal[3], double* const out[10],
+                                double* sums) {
+    if (!ctx) return p3_fail(ctx, "pl3_krylov_probe: NULL context");
+    if (!in || !scal) return p3_fail(ctx, "pl3_krylov_probe: NULL argument");
+    static const int nin[7] = {0, 3, 2, 3, 6, 8, 0};
+    if (what < 0 || what > PL3_PROBE_RANDOM) return p3_fail(ctx, "pl3_krylov_probe: unknown kernel");
+    const int nd = what == PL3_PROBE_DOTS ? (int)scal[0] : 0;
+    if (what == PL3_PROBE_DOTS && (nd < 1 || nd > 5)) return p3_fail(ctx, "pl3_krylov_probe: 1 .. 5 products");
+    if (what == PL3_PROBE_DOTS11 && ctx->nranks > 1) return p3_fail(ctx, "pl3_krylov_probe: the fused reduction runs on one rank");
+    if ((what == PL3_PROBE_DOTS || what == PL3_PROBE_DOTS11) && !sums) return p3_fail(ctx, "pl3_krylov_probe: NULL sums");
+    for (int q = 0; q < nin[what]; q++) if (!in[q]) return p3_fail(ctx, "pl3_krylov_probe: an operand is missing");
+    for (int q = 0; q < nd; q++) if (!in[q] || !in[5 + q]) return p3_fail(ctx, "pl3_krylov_probe: an operand is missing");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    Vec3 v[10];
+    for (int q = 0; q < 10; q++) {
+        v[q] = svec(ctx, q);
+        if (!in[q]) continue;
+        int first = q;
+        for (int p = 0; p < q; p++) if (in[p] == in[q]) { first = p; break; }
+        if (first != q) v[q] = v[first];
+        else P3_TRY(upload3(ctx, in[q], 4, wv4(v[q]).p));
+    }
+    const long long n = v[0].n();
+    const double* ywd = nullptr;
+    if (what == PL3_PROBE_DOTS11 && yw) {          // (an array of its own: the solve's yw stays as the last solve left it)
+        double* a = svec(ctx, 10).p;
+        P3_TRY(upload3(ctx, yw, 1, &a));
+        ywd = a;
+    }
+    switch (what) {
+    case PL3_PROBE_DOTS: P3_TRY(dots3(ctx, nd, v, v + 5, sums)); break;
+    case PL3_PROBE_DOTS11: P3_TRY(dots11_3(ctx, v[0], v[1], v[2], in[3] ? &v[3] : nullptr, in[4] ? &v[4] : nullptr, ywd, sums)); break;
+    case PL3_PROBE_AXPBY: axpby3(ctx, v[2], scal[0], v[0], scal[1], v[1]); break;
+    case PL3_PROBE_P:
+        hipLaunchKernelGGL(k3_p_update, g1(n), dim3(256), 0, ctx->stream, n, v[0].p, (const double*)v[1].p, (const double*)v[2].p, scal[0], scal[1]);
+        break;
+    case PL3_PROBE_XR:
+        hipLaunchKernelGGL(k3_xr_update, g1(n), dim3(256), 0, ctx->stream, n, v[0].p, (const double*)v[1].p, (const double*)v[2].p, v[3].p,
+                           (const double*)v[4].p, (const double*)v[5].p, scal[0], scal[1]);
+        break;
+    case PL3_PROBE_XRP:
+        hipLaunchKernelGGL(k3_xrp_update, g1(n), dim3(256), 0, ctx->stream, n, v[0].p, (const double*)v[1].p, (const double*)v[2].p, v[3].p,
+                           (const double*)v[4].p, (const double*)v[5].p, v[6].p, (const double*)v[7].p, scal[0], scal[1], scal[2]);
+        break;
+    default: random3(ctx, v[0], (unsigned)scal[0]); break;
+    }
+    P3_HIP(ctx, hipGetLastError());
+    for (int q = 0; out && q < 10; q++) if (out[q]) P3_TRY(download3(ctx, wv4(svec(ctx, q)).p, 4, out[q]));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+// The hydrostatic start of pl3_stokes_solve(rhs = NULL): the scaled right-hand side, then hydrostatic_start3, exactly as the solve calls
+// them.  xh (nz, nx, ny, 4) receives x_h, *ref the reference norm |b - A x_h| (0: not usable).  Collective on an attached context.
+extern "C" int pl3_stokes_hydrostatic(pl3_ctx* ctx, double* xh, double* ref) {
+    if (!ctx || !ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
+    if (!xh || !ref) return p3_fail(ctx, "pl3_stokes_hydrostatic: NULL argument");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    const G3& g = ctx->geom.d;
+    const Vec3 B = svec(ctx, 10), XH = svec(ctx, 12);
+    launch3(ctx, g, k3_rhs, ctx->op, wv4(B), 1, ctx->wallvel, ctx->wallflow);
+    P3_TRY(hydrostatic_start3(ctx, B, XH, ref));
+    P3_HIP(ctx, hipGetLastError());
+    return download3(ctx, wv4(XH).p, 4, xh);
+}
+// Stokes work vector `index` (0 .. 13) as the last solve left it: K_R 0, K_RT 1, K_S 4 (the last true residual), K_DX 8, 10 the scaled
+// right-hand side, 13 the deflation vector w
+extern "C" int pl3_stokes_work_vector(pl3_ctx* ctx, int index, double* out) {
+    if (!ctx || !out) return p3_fail(ctx, "pl3_stokes_work_vector: NULL argument");
+    if (index < 0 || index >= 14 || !ctx->vec[index]) return p3_fail(ctx, "pl3_stokes_work_vector: no such work vector (0 .. 13, after a solve)");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    return download3(ctx, wv4(svec(ctx, index)).p, 4, out);
+}
+// What the last pl3_stokes_solve did about the deflation: out[0] dfl_valid, [1] the deflation was on during the solve, [2] the quality
+// |u - A w| / |u| of the kept vector as measured (-1: none was), [3] iterations of the inner solve (0: w reused as it is), [4] its final
+// |u - A w| / |u| (-1: no inner solve), [5] yw.(A w), [6] |w_vel|^2, [7] true-residual checks of the solve (Est3::checks).
+// [8] the iteration at which the estimate between the checks was last evaluated (0: never), [9] its value, [10 .. 14] what went into it:
+// |r|^2, |r_cont|^2, |x_vel|^2, the anchor part, a_mom.
+// u, yw (either may be NULL): the (nz, nx, ny) pressure plane of u and yw of k3_defl_setup, meaningful when out[1] or out[2] >= 0.
+extern "C" int pl3_stokes_defl_info(pl3_ctx* ctx, double out[15], double* u, double* yw) {
+    if (!ctx) return p3_fail(ctx, "pl3_stokes_defl_info: NULL context");
+    if (out) {
+        out[0] = ctx->dfl_valid ? 1.0 : 0.0; out[1] = ctx->dfl_last.active; out[2] = ctx->dfl_last.q; out[3] = ctx->dfl_last.inner_its;
+        out[4] = ctx->dfl_last.inner_res; out[5] = ctx->dfl_yAw; out[6] = ctx->dfl_wvel2; out[7] = ctx->dfl_last.checks;
+        out[8] = ctx->dfl_last.rec_it;
+        for (int q = 0; q < 6; q++) out[9 + q] = ctx->dfl_last.rec[q];
+    }
+    if ((u || yw) && !(ctx->dfl_y && ctx->vec[12])) return p3_fail(ctx, "pl3_stokes_defl_info: no deflation set-up has run on this context");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    if (u) { double* a = svec(ctx, 12)[3]; P3_TRY(download3(ctx, &a, 1, u)); }
+    if (yw) { double* a = ctx->dfl_y; P3_TRY(download3(ctx, &a, 1, yw)); }
+    return 0;
+}
+// sum |entry| over the ring and padding entries of the 14 Stokes work vectors of THIS rank's block (one rank: they are zero and stay
+// zero; on blocks the rings hold the neighbours' values, and the sum is not reduced over the ranks)
+extern "C" int pl3_stokes_ring_sum(pl3_ctx* ctx, double* out) {
+    if (!ctx || !out) return p3_fail(ctx, "pl3_stokes_ring_sum: NULL argument");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    double tot = 0.0;
+    for (int q = 0; q < 14; q++) {
+        double s;
+        hipLaunchKernelGGL(k3_ring_abs, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, ctx->geom.d, 4, (const double*)ctx->vec[q], ctx->part);
+        P3_TRY(sum_partials3(ctx, 5, 1, &s));
+        tot += s;
+    }
+    *out = tot;
     return 0;
 }
 

@@ -23,6 +23,9 @@ BC_TYPE_FIXTEMP = 0
 BC_TYPE_FIXFLOW = 1
 DEFAULT_RTOL = 1e-7        # residual bound; the solve also has to meet the velocity-error estimate 3e-8 (as pylamp_stokes.solve)
 DEFAULT_MAXIT = 600
+# StokesOperator3.krylov_probe / work_vector (include/pylamp_hip.h at pl3_krylov_probe, pl3_stokes_work_vector)
+PROBE_DOTS, PROBE_DOTS11, PROBE_AXPBY, PROBE_P, PROBE_XR, PROBE_XRP, PROBE_RANDOM = range(7)
+WORK_R, WORK_RT, WORK_S, WORK_DX, WORK_B, WORK_W = 0, 1, 4, 8, 10, 13
 
 
 def gidx(idxs, nx):
@@ -423,6 +426,69 @@ class StokesOperator3:
         self._ctx.check(self._ctx.lib.pl3_stokes_mg_plan(self._ctx.handle(), nu, C.byref(ratio), C.byref(cn), C.byref(cr), lds, 32))
         return dict(nu_fine=nu[0], nu=nu[1], ratio=ratio.value, coarse_sweeps=cn.value, coarse_ratio=cr.value,
                     lds=[bool(lds[k]) for k in range(n)])
+
+    # ---- diagnostics for component tests of the Krylov loop (include/pylamp_hip.h at pl3_krylov_probe) ----
+    def precond_deflated(self, r):
+        """precond(r) with the deflation correction of the last solve of this context."""
+        r = _lib.f64(r).reshape(-1)
+        if r.size != self.shape[0]:
+            raise Exception("dimension mismatch")
+        z = np.empty_like(r)
+        self._ctx.check(self._ctx.lib.pl3_stokes_precond_apply_deflated(self._ctx.handle(), _lib.dptr(r), _lib.dptr(z)))
+        return z
+
+    def krylov_probe(self, what, vectors, scalars=(), yw=None, fetch=()):
+        """One launch of Krylov kernel `what` (PROBE_*): vectors[q] (None: none; the same array object twice shares one work vector)
+        goes into Stokes work vector q, `fetch` lists the work vectors to return.  Returns (the 11 sums, {q: vector})."""
+        vec = list(vectors) + [None] * (10 - len(vectors))
+        held = {}
+        for q, a in enumerate(vec):
+            if a is not None:
+                same = [p for p in range(q) if vec[p] is a]
+                held[q] = held[same[0]] if same else _lib.f64(a).reshape(-1)
+                if held[q].size != self.shape[0]:
+                    raise Exception("dimension mismatch")
+        ins = (_lib.c_double_p * 10)(*[_lib.dptr(held[q]) if q in held else None for q in range(10)])
+        outs = {q: np.empty(self.shape[0]) for q in fetch}
+        outp = (_lib.c_double_p * 10)(*[_lib.dptr(outs[q]) if q in outs else None for q in range(10)])
+        sc = np.zeros(3); sc[:len(scalars)] = scalars
+        sums = np.full(11, np.nan)
+        y = None if yw is None else _f3(yw, self._ctx.nx)
+        self._ctx.check(self._ctx.lib.pl3_krylov_probe(self._ctx.handle(), int(what), ins, None if y is None else _lib.dptr(y), _lib.dptr(sc),
+                                                       outp, _lib.dptr(sums)))
+        return sums, outs
+
+    def hydrostatic(self):
+        """(x_h, ref): the hydrostatic start vector and the reference norm |b - A x_h| of solve(A), 0 where it is not usable."""
+        xh = np.empty(self.shape[0]); ref = C.c_double()
+        self._ctx.check(self._ctx.lib.pl3_stokes_hydrostatic(self._ctx.handle(), _lib.dptr(xh), C.byref(ref)))
+        return xh, ref.value
+
+    def work_vector(self, index):
+        """Stokes work vector `index` (WORK_*) as the last solve left it."""
+        v = np.empty(self.shape[0])
+        self._ctx.check(self._ctx.lib.pl3_stokes_work_vector(self._ctx.handle(), int(index), _lib.dptr(v)))
+        return v
+
+    def defl_info(self, vectors=False):
+        """What the last solve did about the deflation of the pressure-anchor mode; vectors=True adds u (pressure plane) and yw."""
+        o = np.zeros(15)
+        u, yw = (np.empty(self._ctx.nx), np.empty(self._ctx.nx)) if vectors else (None, None)
+        self._ctx.check(self._ctx.lib.pl3_stokes_defl_info(self._ctx.handle(), _lib.dptr(o), None if u is None else _lib.dptr(u),
+                                                           None if yw is None else _lib.dptr(yw)))
+        d = dict(valid=bool(o[0]), active=bool(o[1]), q=o[2], inner_iterations=int(o[3]), inner_residual=o[4], yAw=o[5], wvel2=o[6],
+                 checks=int(o[7]), rec_iteration=int(o[8]), rec=o[9], rec_rr=o[10], rec_rc=o[11], rec_xx=o[12], rec_anchor=o[13],
+                 rec_a_mom=o[14])
+        if vectors:
+            d.update(u=u, yw=yw)
+        return d
+
+    def ring_sum(self):
+        """Sum |entry| over the ring and padding entries of the Stokes work vectors of this rank's block: on one rank 0.0 unless a kernel
+        wrote there; on blocks the rings hold the neighbours' values."""
+        s = C.c_double()
+        self._ctx.check(self._ctx.lib.pl3_stokes_ring_sum(self._ctx.handle(), C.byref(s)))
+        return s.value
 
 
 def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True, wallvel=None,
