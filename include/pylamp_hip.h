@@ -498,6 +498,33 @@ int  pl3_stokes_hydrostatic(pl3_ctx* ctx, double* xh, double* ref);
 int  pl3_stokes_work_vector(pl3_ctx* ctx, int index, double* out);
 int  pl3_stokes_defl_info(pl3_ctx* ctx, double out[15], double* u, double* yw);
 int  pl3_stokes_ring_sum(pl3_ctx* ctx, double* out);
+/* Warm start of pl3_stokes_solve from its solution history (opt-in, off at creation, one rank).  The context keeps the last `points`
+ * committed solutions on the device (points x 32 B per padded node) and the model time steps between them.  A solve of the operator's
+ * own right-hand side (rhs == NULL) with use_x0 == 0 then starts from the polynomial of degree `order` through (least squares: more
+ * than order + 1 levels) those solutions, evaluated at the time of the solve, with the weights of the 2-D step (a time step that more
+ * than doubled, or one older level only, falls back to the linear formula with its weight capped at 2).  The right-hand side, the
+ * hydrostatic start and its reference norm `ref` are computed as in a cold solve, so the stopping test is the cold solve's.  Guard: if
+ * ref is unusable or the scaled residual |r0| of the closed extrapolated start is not below ref, the solve falls back to the hydrostatic
+ * start and is the cold solve bit for bit, counters included.  An accepted start hands its residual on to the iteration, so the guard
+ * costs one reduction (and one operator application when the deflation vector had to be solved for anew in between).  With the warm
+ * start off every solve launches what it launched before.  Explicit right-hand sides and use_x0 != 0 ignore it.
+ * pl3_stokes_set_warm_start: points = 0 (off; frees the history) or 2 .. 6, order = 1 .. 3 with points >= order + 1; a change clears
+ *   the history.  Errors name the argument; a context with pl3_set_comm attached is refused.
+ * pl3_stokes_history_commit: the device solution of the last pl3_stokes_solve becomes the newest level; dt > 0 is the model time from
+ *   it to the next solve.  Error: no solution yet, dt not positive.  Returns 0 and does nothing with the warm start off.
+ *   pl3_resident_step commits with its time step.
+ * pl3_stokes_history_clear: forgets the levels (the storage stays).  pl3_stokes_set_walls does it when a wall's kind changes;
+ *   pl3_stokes_set_wall_velocity, pl3_stokes_set_wall_flow and pl3_stokes_set_coeffs keep the history.
+ * pl3_stokes_history_info: out[0] levels held, [1] start of the last solve (0 cold: off or no history, 1 warm, 2 warm rejected by the
+ *   guard), [2] levels it used, [3] |r0| of the warm candidate, [4] ref, [5 .. 7] the first three weights, newest level first.
+ * pl3_stokes_start_vector: the linear combination as the next solve would form it, before the closure of the identity rows, as
+ *   (nz, nx, ny, 4).  Error: warm start off or no level held. */
+int  pl3_stokes_set_warm_start(pl3_ctx* ctx, int points, int order);
+int  pl3_stokes_get_warm_start(pl3_ctx* ctx, int* points, int* order);
+int  pl3_stokes_history_commit(pl3_ctx* ctx, double dt);
+int  pl3_stokes_history_clear(pl3_ctx* ctx);
+int  pl3_stokes_history_info(pl3_ctx* ctx, double out[8]);
+int  pl3_stokes_start_vector(pl3_ctx* ctx, double* out);
 int  pl3_heat_set_coeffs(pl3_ctx* ctx, const double* zmp, const double* xmp, const double* ymp, const double* T, const double* kz,
                          const double* kx, const double* ky, const double* cp, const double* rho, const double* H, const int bc[6],
                          const double bcvalue[6], double tstep);

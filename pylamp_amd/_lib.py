@@ -100,6 +100,12 @@ SIGNATURES = {
     "pl3_stokes_work_vector": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     "pl3_stokes_defl_info": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     "pl3_stokes_ring_sum": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_stokes_set_warm_start": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pl3_stokes_get_warm_start": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
+    "pl3_stokes_history_commit": (C.c_int, [C.c_void_p, C.c_double]),
+    "pl3_stokes_history_clear": (C.c_int, [C.c_void_p]),
+    "pl3_stokes_history_info": (C.c_int, [C.c_void_p, c_double_p]),
+    "pl3_stokes_start_vector": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_heat_set_coeffs": (C.c_int, [C.c_void_p] + [c_double_p] * 10 + [c_int_p, c_double_p, C.c_double]),
     "pl3_heat_apply": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),

@@ -16,6 +16,7 @@
 #include "pl_internal.h"
 #include "pl_mic3.h"
 #include "pl_step3.h"
+#include "pl_x0.h"
 #include <algorithm>
 #include <cmath>
 
@@ -983,6 +984,16 @@ __global__ void k3_xr_update(long long n, double* __restrict__ x, const double* 
         x[t] += alpha * y[t] + omega * z[t]; r[t] = s[t] - omega * t_[t];
     }
 }
+// The extrapolated start of a warm Stokes solve: x = sum_k l[k] h[k] over the n kept solutions, newest first and summed in that order.
+// (Every h[k] is zero on the rings and the padding, so x is.)
+struct X0Start3 { const double* h[X0_HIST + 1]; double l[X0_HIST + 1]; int n; };
+__global__ void k3_x0_start(long long n, X0Start3 a, double* __restrict__ x) {
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        double acc = a.l[0] * a.h[0][t];
+        for (int k = 1; k < a.n; k++) acc += a.l[k] * a.h[k][t];
+        x[t] = acc;
+    }
+}
 #define D3_BLOCKS 1024
 // the end of every reduction kernel (256 threads): part[NQ b + q] = the sum of acc[q] over workgroup b -- a shuffle tree per wave, then
 // the four wave sums in order
@@ -1216,6 +1227,11 @@ struct pl3_ctx {
     // what the last pl3_stokes_solve did about it (pl3_stokes_defl_info): the deflation was on, the quality of the kept vector as measured
     // (-1: none), iterations and final residual of the inner solve (0 / -1: the vector was reused as it is), true-residual checks
     struct { int active = 0, inner_its = 0, checks = 0, rec_it = 0; double q = -1.0, inner_res = -1.0, rec[6] = {0, 0, 0, 0, 0, 0}; } dfl_last;
+    // warm start (pl3_stokes_set_warm_start; off at creation): the last warm_held <= warm_points solutions, newest first, rotated by
+    // pointer, and the model time steps between them as pl_x0_weights takes them (dt_hist[0] leads to the solution sought)
+    int warm_points = 0, warm_order = 0, warm_held = 0;
+    double* hist[X0_HIST + 1] = {nullptr}; double dt_hist[X0_HIST + 1] = {0};
+    struct { int start = 0, used = 0; double r0 = 0.0, ref = 0.0, l[3] = {0, 0, 0}; } warm_last;      // of the last solve (pl3_stokes_history_info)
     double etol = 3e-8;                     // bound on the velocity-error estimate of a converged Stokes solve (PYLAMP_STOKES_ETOL)
     void* mic3 = nullptr;                   // pl_mic3.hip: resident tracers and the work buffers of the 3-D marker kernels
     void* step3 = nullptr;                  // pl_step3.hip: state of the device-resident time step
@@ -1330,6 +1346,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     free_levels3(ctx);
     for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow_dev}) if (q) (void)hipFree(q);
     for (double* q : ctx->vec) if (q) (void)hipFree(q);
+    for (double* q : ctx->hist) if (q) (void)hipFree(q);
     for (double* q : ctx->hk) if (q) (void)hipFree(q);
     for (double* q : ctx->hvec) if (q) (void)hipFree(q);
     if (ctx->hpart) (void)hipHostFree(ctx->hpart);
@@ -1429,6 +1446,7 @@ extern "C" int pl3_set_comm(pl3_ctx* ctx, pl_ctx* comm, int Pz, int Px, int Py) 
     if (!ctx || !comm) return p3_fail(ctx, "pl3_set_comm: NULL argument");
     if (Pz < 1 || Px < 1 || Py < 1 || Pz * Px * Py != comm->nranks) return p3_fail(ctx, "pl3_set_comm: Pz * Px * Py must equal the number of ranks of the communicator");
     if (ctx->op_ready || ctx->hop_ready || !ctx->levels.empty()) return p3_fail(ctx, "pl3_set_comm: call it right after pl3_create");
+    if (ctx->warm_points) return p3_fail(ctx, "pl3_set_comm: the warm start of the Stokes solve (pl3_stokes_set_warm_start) runs on one rank; switch it off first");
     if (comm->device != ctx->device) return p3_fail(ctx, "pl3_set_comm: the communicator context lives on another device");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1505,7 +1523,8 @@ extern "C" int pl3_stokes_set_wall_rows(pl3_ctx* ctx, int slaved) {
     ctx->op.slave = slaved ? 1 : 0;
     return 0;
 }
-// bc = [z0, x0, y0, zL, xL, yL], each PL_BC_FREESLIP or PL_BC_NOSLIP.  Kept on the context (which starts all free-slip) across
+static void history_clear3(pl3_ctx* ctx) { ctx->warm_held = 0; for (double& d : ctx->dt_hist) d = 0.0; }
+// bc = [z0, x0, y0, zL, xL, yL], each PL_BC_FREESLIP or PL_BC_NOSLIP.  A change of a wall's kind clears the warm-start history.  Kept on the context (which starts all free-slip) across
 // pl3_stokes_set_coeffs; read by the solves, pl3_resident_step and pl3_advection_velocity.
 static std::string num_str3(double v) {          // the shortest decimal that reads back as v
     char b[40];
@@ -1530,6 +1549,7 @@ extern "C" int pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]) {
             return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + names[w] + " moves with velocity " + wallvel_str3(u) +
                                     " and cannot become FREESLIP: only a NOSLIP wall carries a velocity (set it to zero first)");
         }
+    if (m != ctx->noslip) history_clear3(ctx);          // solutions of other wall kinds are no start for these
     ctx->noslip = m;
     if (ctx->op_ready) ctx->op.noslip = m;
     return 0;
@@ -1967,9 +1987,9 @@ static int true_check3(pl3_ctx* ctx, Op3Fn M, Est3& e, const Vec3* w, const Vec3
 }
 
 // Solves A x = b (from x if use_x0, else from zero); w: K_NW work vectors of b's shape.  ref_norm > 0 replaces |b| in the stopping test;
-// etol > 0 (Stokes vectors with M): also bound the velocity-error estimate.
+// etol > 0 (Stokes vectors with M): also bound the velocity-error estimate.  r0_ready (with use_x0): w[K_R0] holds b - A x already.
 static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& x, bool use_x0, double rtol, int maxit, const Vec3* w,
-                     Stats3* st, double ref_norm, double etol = 0.0) {
+                     Stats3* st, double ref_norm, double etol = 0.0, bool r0_ready = false) {
     const Vec3 &r = w[K_R], &rt = w[K_RT], &p = w[K_P], &v = w[K_V], &s = w[K_S], &t = w[K_T], &y = w[K_Y], &z = w[K_Z];
     const G3& g = *b.g;
     const int na = b.na; const long long n = b.n();
@@ -1980,7 +2000,7 @@ static int bicgstab3(pl3_ctx* ctx, Op3Fn A, Op3Fn M, const Vec3& b, const Vec3& 
     st->iterations = 0; st->converged = 0; st->rel_residual = 0.0; st->error_estimate = 0.0; st->rec_it = 0;
     if (!(bnorm > 0.0)) { P3_TRY(zero3(ctx, x)); st->converged = 1; return 0; }
     Vec3 dx = x, r0 = b;
-    if (use_x0) { dx = w[K_DX]; P3_TRY(A(ctx, x, v)); r0 = w[K_R0]; axpby3(ctx, r0, 1.0, b, -1.0, v); }
+    if (use_x0) { dx = w[K_DX]; r0 = w[K_R0]; if (!r0_ready) { P3_TRY(A(ctx, x, v)); axpby3(ctx, r0, 1.0, b, -1.0, v); } }
     P3_TRY(zero3(ctx, dx));
     axpby3(ctx, r, 1.0, r0, 0.0, r0);
     random3(ctx, rt, 1234u);
@@ -2227,6 +2247,111 @@ static int deflation_setup3(pl3_ctx* ctx, const Vec3& U, const Vec3* w) {
     if (ctx->dfl_active) P3_TRY(dot3(ctx, W.vel(), W.vel(), &ctx->dfl_wvel2));
     return 0;
 }
+// ---- warm start of the Stokes solve from its solution history (opt-in, one rank) -----------------------------------------------
+static void history_free3(pl3_ctx* ctx) {
+    for (double*& q : ctx->hist) { if (q) (void)hipFree(q); q = nullptr; }
+    history_clear3(ctx);
+}
+// points: solutions kept, 0 (off, frees the history) or 2 .. X0_HIST + 1; order: degree of the extrapolating polynomial, 1 .. 3, with
+// points >= order + 1.  A change of either clears the history.
+extern "C" int pl3_stokes_set_warm_start(pl3_ctx* ctx, int points, int order) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_warm_start: NULL context");
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_stokes_set_warm_start: a context with pl3_set_comm attached has no warm start (one rank)");
+    if (points != 0) {
+        if (points < 2 || points > X0_HIST + 1)
+            return p3_fail(ctx, "pl3_stokes_set_warm_start: points = " + std::to_string(points) + " must be 0 (off) or 2 .. " + std::to_string(X0_HIST + 1));
+        if (order < 1 || order > 3) return p3_fail(ctx, "pl3_stokes_set_warm_start: order = " + std::to_string(order) + " must be 1 .. 3");
+        if (points < order + 1)
+            return p3_fail(ctx, "pl3_stokes_set_warm_start: order = " + std::to_string(order) + " needs points >= " + std::to_string(order + 1) +
+                                    ", got points = " + std::to_string(points));
+    }
+    if (points == ctx->warm_points && (points == 0 || order == ctx->warm_order)) return 0;
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    history_free3(ctx);
+    ctx->warm_points = 0; ctx->warm_order = 0; ctx->warm_last = {};
+    for (int k = 0; k < points; k++)
+        if (dmal(ctx, &ctx->hist[k], 4 * ctx->geom.d.vol)) { const std::string m = ctx->err; history_free3(ctx); return p3_fail(ctx, "pl3_stokes_set_warm_start: " + m); }
+    ctx->warm_points = points; ctx->warm_order = points ? order : 0;
+    return 0;
+}
+extern "C" int pl3_stokes_get_warm_start(pl3_ctx* ctx, int* points, int* order) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_get_warm_start: NULL context");
+    if (points) *points = ctx->warm_points;
+    if (order) *order = ctx->warm_order;
+    return 0;
+}
+// The device solution of the last pl3_stokes_solve becomes the newest time level; dt > 0: the model time from it to the next solve.
+// Warm start off: nothing happens.
+extern "C" int pl3_stokes_history_commit(pl3_ctx* ctx, double dt) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_history_commit: NULL context");
+    if (!ctx->warm_points) return 0;
+    if (!(dt > 0.0) || !std::isfinite(dt)) return p3_fail(ctx, "pl3_stokes_history_commit: dt = " + num_str3(dt) + " must be positive and finite");
+    if (!ctx->have_x) return p3_fail(ctx, "pl3_stokes_history_commit: no Stokes solution to commit (pl3_stokes_solve has not run on this context)");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    const int np = ctx->warm_points;
+    double* newest = ctx->hist[np - 1];                 // the oldest level's storage takes the new one
+    for (int k = np - 1; k > 0; k--) ctx->hist[k] = ctx->hist[k - 1];
+    ctx->hist[0] = newest;
+    P3_HIP(ctx, hipMemcpyAsync(newest, ctx->vec[11], (size_t)4 * ctx->geom.d.vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    for (int k = X0_HIST; k > 0; k--) ctx->dt_hist[k] = ctx->dt_hist[k - 1];
+    ctx->dt_hist[0] = dt;
+    ctx->warm_held = std::min(ctx->warm_held + 1, np);
+    return 0;
+}
+extern "C" int pl3_stokes_history_clear(pl3_ctx* ctx) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_history_clear: NULL context");
+    history_clear3(ctx);
+    return 0;
+}
+// X = sum_k L_k h_k with the weights of pl_x0.h (the header of the 2-D step: its fall-backs for a doubled time step and a short
+// history come with it); what it used goes into ctx->warm_last
+static int x0_start3(pl3_ctx* ctx, const Vec3& X) {
+    const X0Weights wt = pl_x0_weights(ctx->dt_hist, ctx->warm_held - 1, ctx->warm_points - 1, ctx->warm_order, 1.0);
+    X0Start3 a{};
+    a.n = wt.nh + 1;
+    for (int k = 0; k < a.n; k++) { a.h[k] = ctx->hist[k]; a.l[k] = k ? wt.l[k - 1] : wt.l0; }
+    if (wt.nh >= 2 && wt.nh <= ctx->warm_order) {
+        // The fit interpolates: its weights are the Lagrange basis values at the time of the solve.  The normal equations of the
+        // header leave some 30 eps in them, more than the kernel's own rounding, so they are evaluated directly, in long double,
+        // on the header's choice of levels (times 0, -d[1], -d[1] - d[2], ...; the solve at +d[0]).
+        long double t[X0_HIST + 1] = {0.0L};
+        for (int k = 1; k < a.n; k++) t[k] = t[k - 1] - (long double)ctx->dt_hist[k];
+        for (int i = 0; i < a.n; i++) {
+            long double l = 1.0L;
+            for (int j = 0; j < a.n; j++) if (j != i) l *= ((long double)ctx->dt_hist[0] - t[j]) / (t[i] - t[j]);
+            a.l[i] = (double)l;
+        }
+    }
+    ctx->warm_last.used = a.n;
+    for (int k = 0; k < 3; k++) ctx->warm_last.l[k] = k < a.n ? a.l[k] : 0.0;
+    hipLaunchKernelGGL(k3_x0_start, g1(X.n()), dim3(256), 0, ctx->stream, X.n(), a, X.p);
+    P3_HIP(ctx, hipGetLastError());
+    return 0;
+}
+// out: levels held; start of the last solve (0 cold: off or no history, 1 warm, 2 warm rejected by the guard); levels it used; |r0| of
+// the warm candidate; ref; its first three weights (newest first)
+extern "C" int pl3_stokes_history_info(pl3_ctx* ctx, double out[8]) {
+    if (!ctx || !out) return p3_fail(ctx, "pl3_stokes_history_info: NULL argument");
+    out[0] = ctx->warm_held; out[1] = ctx->warm_last.start; out[2] = ctx->warm_last.used; out[3] = ctx->warm_last.r0; out[4] = ctx->warm_last.ref;
+    for (int k = 0; k < 3; k++) out[5 + k] = ctx->warm_last.l[k];
+    return 0;
+}
+// The linear combination as the next solve would form it, before halo3 and k3_close: out (nz, nx, ny, 4).  Leaves the record of the last
+// solve (pl3_stokes_history_info) alone.
+extern "C" int pl3_stokes_start_vector(pl3_ctx* ctx, double* out) {
+    if (!ctx || !out) return p3_fail(ctx, "pl3_stokes_start_vector: NULL argument");
+    if (!ctx->warm_points) return p3_fail(ctx, "pl3_stokes_start_vector: warm start is off (pl3_stokes_set_warm_start)");
+    if (ctx->warm_held < 1) return p3_fail(ctx, "pl3_stokes_start_vector: the history is empty (pl3_stokes_history_commit)");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    const auto keep = ctx->warm_last;
+    const Vec3 S = svec(ctx, K_T);
+    const int rc = x0_start3(ctx, S);
+    ctx->warm_last = keep;
+    if (rc) return rc;
+    return download3(ctx, wv4(S).p, 4, out);
+}
 extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int use_x0, double rtol, int maxit, pl_solve_stats* stats) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
     // x == NULL: device-resident solve -- the solution stays in the context (pl3_get_solution fetches it), use_x0 starts from the
@@ -2248,17 +2373,40 @@ extern "C" int pl3_stokes_solve(pl3_ctx* ctx, const double* rhs, double* x, int 
     ctx->dfl_active = false; ctx->dfl_yAw = 1.0; ctx->dfl_wvel2 = 0.0;
     double ref = 0.0;
     P3_TRY(hydrostatic_start3(ctx, B, XH, &ref));
+    // warm start: the operator's own right-hand side, no start given, and at least one committed solution
+    const bool warm = !rhs && !use_x0 && ctx->warm_points > 0 && ctx->warm_held > 0;
+    ctx->warm_last = {};
+    ctx->warm_last.ref = ref;
     if (use_x0) { if (x) P3_TRY(upload3(ctx, x, 4, wv4(X).p)); }
+    else if (warm) P3_TRY(x0_start3(ctx, X));
     else P3_HIP(ctx, hipMemcpyAsync(X.p, XH.p, (size_t)X.n() * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     P3_TRY(halo3(ctx, X.vel()));
     launch3(ctx, g, k3_close, ctx->op, wv3(X), cv3(B));
+    bool r0_kept = false;          // w[K_R0] holds the residual of the start (the guard's), for bicgstab3 to take over
+    if (warm) {
+        // the guard: the extrapolated start is kept only if its residual is below the hydrostatic start's, the reference of the stopping
+        // test; otherwise the solve is the cold one from here on (w[K_V], w[K_R0]: written before they are read by what follows)
+        const int napply0 = ctx->napply; double rr = 0.0;
+        P3_TRY(stokes_A3(ctx, X, w[K_V]));
+        axpby3(ctx, w[K_R0], 1.0, B, -1.0, w[K_V]);
+        P3_TRY(dot3(ctx, w[K_R0], w[K_R0], &rr));
+        ctx->warm_last.r0 = std::sqrt(rr);
+        ctx->warm_last.start = 1; r0_kept = true;
+        if (!(ref > 0.0) || !(ctx->warm_last.r0 < ref)) {          // (a NaN fails)
+            ctx->warm_last.start = 2; ctx->napply = napply0; r0_kept = false;
+            P3_HIP(ctx, hipMemcpyAsync(X.p, XH.p, (size_t)X.n() * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+            P3_TRY(halo3(ctx, X.vel()));
+            launch3(ctx, g, k3_close, ctx->op, wv3(X), cv3(B));
+        }
+    }
     static const bool defl_on = !(getenv("PYLAMP_DEFLATE") && atoi(getenv("PYLAMP_DEFLATE")) == 0);
     if (const char* e = getenv("PYLAMP_STOKES_ETOL")) { const double v = atof(e); if (v >= 0.0) ctx->etol = v; }
     ctx->dfl_last = {};
     if (defl_on && ctx->levels.size() > 1) P3_TRY(deflation_setup3(ctx, XH, w));        // (the hydrostatic vector is not needed any more)
     ctx->dfl_last.active = ctx->dfl_active ? 1 : 0;
+    if (!(ctx->dfl_last.inner_res < 0.0)) r0_kept = false;         // the inner solve for the deflation vector ran on the same work vectors
     Stats3 st{};
-    P3_TRY(bicgstab3(ctx, stokes_A3, stokes_M3, B, X, true, rtol, maxit, w, &st, ref, ctx->etol));
+    P3_TRY(bicgstab3(ctx, stokes_A3, stokes_M3, B, X, true, rtol, maxit, w, &st, ref, ctx->etol, r0_kept));
     ctx->dfl_last.checks = st.checks; ctx->dfl_last.rec_it = st.rec_it;
     for (int q = 0; q < 6; q++) ctx->dfl_last.rec[q] = st.rec_it ? st.rec[q] : 0.0;
     ctx->dfl_active = false;

@@ -318,7 +318,7 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
         tstep_temp = py_max(py_min(tstep_temp, cfg->tstep_dif_max), cfg->tstep_dif_min);
     }
 
-    // 4. Stokes: coefficients from the device fields, cold resident solve
+    // 4. Stokes: coefficients from the device fields, resident solve (cold, or warm with pl3_stokes_set_warm_start)
     S3_TRY(pl3i_stokes_set_coeffs_dev(ctx, F + S3_ETAS * N, F + S3_ETAN * N, F + S3_RHO * N, cfg->use_grav ? cfg->grav : nullptr, mineta));
     S3_TRY(pl3_stokes_solve(ctx, nullptr, nullptr, 0, cfg->stokes_rtol, cfg->stokes_maxit, &rep->stokes));
     o.S->have_vel = true;
@@ -335,6 +335,7 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     double tstep = tstep_stokes; int limiter = 0;
     if (heat) { limiter = tstep_temp < tstep_stokes ? 1 : 0; tstep = py_min(tstep_temp, tstep_stokes); }
     rep->tstep = tstep; rep->limiter = limiter; rep->tstep_heat = tstep_temp; rep->tstep_stokes = tstep_stokes;
+    S3_TRY(pl3_stokes_history_commit(ctx, tstep));          // (nothing unless the warm start is on: the next solve is tstep of model time away)
 
     // 6. + 7. heat: coefficients from the device fields, resident solve, temperature to the tracers
     if (heat) {

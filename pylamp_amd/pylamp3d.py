@@ -247,6 +247,43 @@ class Context3:
             msg = self.lib.pl3_last_error(self.h)
             raise Exception(msg.decode() if msg else "libpylamp_hip error %d" % rc)
 
+    def set_warm_start(self, points, order=2):
+        """Warm start of the Stokes solves of this context from the extrapolated history of their solutions (off at creation): points =
+        solutions kept, 0 (off) or 2 .. 6; order = degree of the extrapolation, 1 .. 3, points >= order + 1.  The rule and the guard
+        are in include/pylamp_hip.h at pl3_stokes_set_warm_start."""
+        self.check(self.lib.pl3_stokes_set_warm_start(self.handle(), int(points), int(order)))
+
+    def warm_start(self):
+        """(points, order) of set_warm_start; (0, 0): off."""
+        p, o = C.c_int(), C.c_int()
+        self.check(self.lib.pl3_stokes_get_warm_start(self.handle(), C.byref(p), C.byref(o)))
+        return p.value, o.value
+
+    def commit_solution(self, dt):
+        """The device solution of the last Stokes solve becomes the newest level of the history; dt > 0 is the model time to the next
+        solve.  Does nothing with the warm start off."""
+        self.check(self.lib.pl3_stokes_history_commit(self.handle(), float(dt)))
+
+    def clear_history(self):
+        self.check(self.lib.pl3_stokes_history_clear(self.handle()))
+
+    _START_NAMES = ("cold", "warm", "rejected")
+
+    def history_info(self):
+        """Levels held, and of the last Stokes solve: its start ("cold": warm start off or no history; "warm"; "rejected": the guard
+        fell back to the hydrostatic start), the levels it used, |r0| of the extrapolated start, the reference norm and the first
+        three weights (newest level first)."""
+        o = np.zeros(8)
+        self.check(self.lib.pl3_stokes_history_info(self.handle(), _lib.dptr(o)))
+        return dict(held=int(o[0]), start=self._START_NAMES[int(o[1])], used=int(o[2]), r0=float(o[3]), ref=float(o[4]),
+                    weights=[float(v) for v in o[5:8]])
+
+    def start_vector(self):
+        """The extrapolated start as the next Stokes solve would form it, before the closure of the identity rows: (nz nx ny 4,)."""
+        x = np.zeros(int(np.prod(self.nx)) * 4)
+        self.check(self.lib.pl3_stokes_start_vector(self.handle(), _lib.dptr(x)))
+        return x
+
     def set_marker_search(self, on):
         """Per-axis cell search for the 3-D marker kernels of this context (rectilinear grids; default off = the regular-grid
         formula).  Resident tracers are re-sorted by the new rule."""
@@ -870,6 +907,34 @@ def advection_velocity(newvel, gridmp, nx, bc=None, wallvel=None, wallflow=None)
     return g, V
 
 
+WARM_START_DEFAULT = (3, 2)          # (points, order) of Options3.stokes_warm_start = True: the 2-D step's default
+WARM_START_MAX_POINTS = 6            # X0_HIST + 1 of csrc/pl_x0.h
+
+
+def warm_start_setting(value, who="Options3.stokes_warm_start"):
+    """(points, order) of a stokes_warm_start value: False / None -> (0, 0), off; True -> WARM_START_DEFAULT; a (points, order) pair
+    is checked by the library's rule (pl3_stokes_set_warm_start): points 2 .. 6, order 1 .. 3, points >= order + 1."""
+    if value is None or value is False:
+        return (0, 0)
+    if value is True:
+        return WARM_START_DEFAULT
+    try:
+        points, order = value
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in (points, order))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise Exception("%s: expected False, True or a (points, order) pair of integers, got %r" % (who, value))
+    points, order = int(points), int(order)
+    if points < 2 or points > WARM_START_MAX_POINTS:
+        raise Exception("%s: points = %d must be 2 .. %d" % (who, points, WARM_START_MAX_POINTS))
+    if order < 1 or order > 3:
+        raise Exception("%s: order = %d must be 1 .. 3" % (who, order))
+    if points < order + 1:
+        raise Exception("%s: order = %d needs points >= %d, got points = %d" % (who, order, order + 1, points))
+    return (points, order)
+
+
 class Options3:
     """Options of pylamp2.py:37-77 that Simulation3 honours (the 2-D driver's names)."""
 
@@ -915,10 +980,14 @@ class Options3:
         # beyond the reference: the classical RK4 weights (1, 2, 2, 1) / 6 instead of the reference's (1, 1, 1, 1) / 6, which move a tracer
         # by 2/3 U tstep in a uniform field U.  A flow through the walls wants True: the markers then carry the volume the walls bring in
         self.rk4_classic = False
+        # beyond the reference: the Stokes solve starts from the extrapolated history of its solutions (Context3.set_warm_start) instead
+        # of the hydrostatic state.  False: off; True: (points, order) = WARM_START_DEFAULT; or a (points, order) pair
+        self.stokes_warm_start = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
             setattr(self, k, v)
+        warm_start_setting(self.stokes_warm_start)
 
 
 class Simulation3:
@@ -994,6 +1063,9 @@ class Simulation3:
             self.ctx.set_marker_deletion(True)
         if o.rk4_classic:
             self.ctx.set_rk4_classic(True)
+        self.warm_start = warm_start_setting(o.stokes_warm_start, "Simulation3: Options3.stokes_warm_start")
+        if self.warm_start[0]:
+            self.ctx.set_warm_start(*self.warm_start)
         self._inflow = False
         if o.bcinflow is not None:
             self.set_inflow_material(o.bcinflow)
@@ -1054,6 +1126,11 @@ class Simulation3:
             raise Exception("tracer arrays must be (n, 3) and (n, %d)" % NFTRAC)
         self._lib_call("pl3_tracers_upload", tr_x.shape[0], _lib.dptr(tr_x), _lib.dptr(tr_f))
         self.ntrac = tr_x.shape[0] - self.ctx.tracers_removed()[0]
+        self.reset_stokes_history()              # other tracers, another flow: its solutions are no start for the next solve
+
+    def reset_stokes_history(self):
+        """Forget the Stokes solutions kept for the warm start (Options3.stokes_warm_start): the next solve starts cold."""
+        self.ctx.clear_history()
 
     def count(self):
         n = C.c_int64()
@@ -1221,6 +1298,8 @@ class Simulation3:
                    nempty=int(r.nempty), mincount=int(r.mincount), nremoved=int(r.nremoved), time=self.totaltime, ntrac=self.ntrac)
         if self._inflow:
             rep["ninflow"] = self.ctx.inflow_count()[0]
+        if self.warm_start[0]:
+            rep["stokes_start"] = self.ctx.history_info()["start"]
         self.fields = {}
         self._stepped = True
         self.last = rep
@@ -1260,6 +1339,8 @@ class Simulation3:
         else:
             tstep, limiter = tstep_stokes, "S"
         rep = dict(it=self.it, tstep=tstep, limiter=limiter, stokes=A.last_stats, heat=None)
+        if self.warm_start[0]:
+            self.ctx.commit_solution(tstep)      # (as pl3_resident_step does: both paths keep the same history)
         f.update(velz=newvel[0], velx=newvel[1], vely=newvel[2], pres=pres)
         if o.do_heatdiff:
             H, _ = makeDiffusionMatrix(self.nx, self.grid, self.gridmp, f["T"], [f["kz"], f["kx"], f["ky"]], f["cp"], f["rho"], f["H"],
@@ -1277,6 +1358,8 @@ class Simulation3:
         rep.setdefault("nremoved", 0)
         self.totaltime += tstep
         rep["time"] = self.totaltime; rep["ntrac"] = self.count()
+        if self.warm_start[0]:
+            rep["stokes_start"] = self.ctx.history_info()["start"]
         self.fields = f
         self.last = rep
         return rep

@@ -39,6 +39,9 @@ alternating): the sort with refill (sort_on_1pct) and the resident step, ratio o
 host wall time per step (device synchronisation, then perf_counter, on either side of step()), median and min-max over --reps
 steps after --warmup, and the medians of the stage times (device events); writes profiles/mic3_step_129.json unless --out says
 otherwise.  --resident selects Options3.resident (one pl3_resident_step call per step, the grid fields stay on the device).
+--warm switches Options3.stokes_warm_start on (three solutions kept, quadratic extrapolation) and adds how the timed solves started
+and the guard's residuals; writes profiles/mic3_step_129_warm.json unless --out says otherwise (profiles/stokes3_warm.json holds the
+medians of three such processes alternating with three without --warm).
 --tree DIR imports pylamp_amd from another checkout: the host-staged yardstick is run on the parent commit's library, in
 separate processes alternating with the resident runs of this one.
 """
@@ -220,9 +223,11 @@ def step_bench(a):
     n = tr_x.shape[0]
     tr_f[:, 3] = 273 + 1350 * tr_x[:, 0] / L[0]; tr_f[:, 4] = 4.0; tr_f[:, 5] = 1250; tr_f[:, 7] = 3.5e-5; tr_f[:, 11] = 1e-9
     kw = dict(resident=True) if a.resident else {}
+    if a.warm:
+        kw["stokes_warm_start"] = True
     sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**kw, **_delete_kw(a)))
     del tr_x, tr_f
-    wall, stages, its = [], {}, []
+    wall, stages, its, starts, guard = [], {}, [], [], []
     for rep in range(a.warmup + a.reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -232,6 +237,9 @@ def step_bench(a):
         assert r["stokes"]["converged"] == 1 and r["heat"]["converged"] == 1, r
         if rep >= a.warmup:
             wall.append(ms); its.append(r["stokes"]["iterations"])
+            if a.warm:
+                h = sim.ctx.history_info()
+                starts.append(r["stokes_start"]); guard.append(h["r0"] / h["ref"] if h["ref"] > 0 else None)
             st = dict(sim.stage_times(), stokes=r["stokes"]["solve_ms"], heat=r["heat"]["solve_ms"])
             for k, v in st.items():
                 stages.setdefault(k, []).append(v)
@@ -239,6 +247,8 @@ def step_bench(a):
                reps=a.reps, warmup=a.warmup, step_ms=round(float(np.median(wall)), 2), step_ms_min=round(float(np.min(wall)), 2),
                step_ms_max=round(float(np.max(wall)), 2), stokes_iterations=its,
                stage_ms={k: round(float(np.median(v)), 3) for k, v in stages.items()})
+    if a.warm:          # r0_over_ref: the guard's |r0| / ref of every timed solve (below 1: the extrapolated start was taken)
+        out.update(warm_start=list(sim.warm_start), stokes_start=starts, r0_over_ref=[None if g is None else float("%.3e" % g) for g in guard])
     # what the stage times do not cover: host work and copies (staged: "scatter" is the LAST of the step's five scatters alone)
     out["other_ms"] = round(out["step_ms"] - sum(out["stage_ms"].values()), 2)
     if hasattr(sim, "transfer_stats"):
@@ -256,6 +266,7 @@ def main():
     ap.add_argument("--sort-only", action="store_true"); ap.add_argument("--refill-reps", type=int, default=7)
     ap.add_argument("--parent", nargs="*", default=[])
     ap.add_argument("--step", action="store_true"); ap.add_argument("--resident", action="store_true"); ap.add_argument("--tree", default=None)
+    ap.add_argument("--warm", action="store_true")
     ap.add_argument("--search", action="store_true"); ap.add_argument("--graded", type=float, default=0.0)
     ap.add_argument("--delete", action="store_true"); ap.add_argument("--off", nargs="*", default=[])
     ap.add_argument("--inflow", action="store_true")
@@ -263,7 +274,7 @@ def main():
         ap.add_argument(name, nargs="*", default=[])
     a = ap.parse_args()
     if a.out is None and not a.inflow:
-        a.out = os.path.join("profiles", "mic3_step_129.json" if a.step else ("mic3_129_delete.json" if a.sort_only and a.delete else
+        a.out = os.path.join("profiles", ("mic3_step_129_warm.json" if a.warm else "mic3_step_129.json") if a.step else ("mic3_129_delete.json" if a.sort_only and a.delete else
                                                                               ("mic3_129_refill.json" if a.sort_only else "mic3_129.json")))
     if a.inflow and a.out is None:
         a.out = os.path.join("profiles", "mic3_129_inflow.json")
