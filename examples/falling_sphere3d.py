@@ -2,7 +2,7 @@
 griddata.NNNNNN.npz / tracs.NNNNNN.npz in the style of the 2-D example, with a third axis (gridy, vely, tr_x (n, 3)).
 Cells that run below tracdens_min markers are refilled to tracdens inside the end-of-step sort (0 0 switches that off).
 
-    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R] [--noslip=z] [--fence-off] [--warm]
+    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R] [--noslip=z] [--fence-off] [--warm] [--strain]
 
 --resident runs the device-resident step (Options3.resident): the grid fields stay on the GPU and are downloaded for the snapshots only.
 --refine=R (e.g. 3) makes the cells R times finer around the sphere's path than far from it (pylamp3d.refined_grid) and switches
@@ -16,6 +16,8 @@ the velocity interpolated onto a no-slip wall at rest is half the last centre va
 census and refill inside the same sort restore the density behind them.  Every step prints the markers removed and injected.
 --warm starts every Stokes solve from the extrapolated history of the last three solutions instead of the hydrostatic state
 (Options3.stokes_warm_start); every step then prints how its solve started (cold, warm, or rejected by the guard).
+--strain keeps the second invariants of the strain rate and of the stress and the viscous dissipation of every step
+(Options3.strain_fields): the snapshots gain strainrate, stress and dissipation, and every step prints the total dissipation.
 """
 import os
 import sys
@@ -30,6 +32,7 @@ refine = [float(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--ref
 refine = refine[0] if refine else 0.0
 fence_off = "--fence-off" in sys.argv[1:]
 warm = "--warm" in sys.argv[1:]
+strain = "--strain" in sys.argv[1:]
 noslip = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--noslip=")]
 noslip = noslip[0] if noslip else ""
 if noslip not in ("", "z", "zx", "zxy"):
@@ -51,7 +54,7 @@ if refine > 1.0:                                                                
 tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1), per_axis=per_axis)
 opt = P3.Options3(do_heatdiff=False, tdep_rho=False, tdep_eta=False,             # isothermal, constant properties
                   tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident, marker_search=grid is not None,
-                  bcstokes=bcstokes, tracs_fence_enabled=not fence_off, marker_deletion=fence_off, stokes_warm_start=warm)
+                  bcstokes=bcstokes, tracs_fence_enabled=not fence_off, marker_deletion=fence_off, stokes_warm_start=warm, strain_fields=strain)
 sim = P3.Simulation3(nx, L, tr_x, tr_f, opt, grid=grid)
 sphere = None
 for it in range(1, steps + 1):
@@ -61,6 +64,8 @@ for it in range(1, steps + 1):
           (it, sim.totaltime / 3.15576e13, rep["tstep"], rep["limiter"], rep["stokes"]["iterations"],
            "ok" if rep["stokes"]["converged"] else "NOT CONVERGED", " (%s start)" % rep["stokes_start"] if warm else "", x[f[:, 8] == 2, 0].mean() / 1e3, rep["ntrac"], rep["nremoved"], rep["ninjected"],
            rep["nrefilled"]), flush=True)
+    if strain:
+        print("          dissipation %.4e W, largest strain rate %.3e 1/s" % (rep["dissipation_total"], sim.field("strainrate").max()), flush=True)
     if it % 10 == 0 or it == steps:
         sim.write_snapshot(outdir)
 sim.close()

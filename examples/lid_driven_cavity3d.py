@@ -2,11 +2,14 @@
 as well) at a fixed speed -- the moving walls of pylamp3d.Simulation3 (Options3.bcstokesvel, Simulation3.set_wall_velocity).  Writes
 griddata.NNNNNN.npz / tracs.NNNNNN.npz through Simulation3.write_snapshot, like examples/falling_sphere3d.py.
 
-    python examples/lid_driven_cavity3d.py [n=33] [steps=20] [outdir=out] [--u=1e-9] [--uy=0] [--resident] [--reverse=K]
+    python examples/lid_driven_cavity3d.py [n=33] [steps=20] [outdir=out] [--u=1e-9] [--uy=0] [--resident] [--reverse=K] [--shear-heating]
 
 --u, --uy: the lid's velocity components along x and y in m/s (1e-9 m/s is about 3 cm/yr).
 --resident runs the device-resident step (Options3.resident).
 --reverse=K turns the lid round after K steps (set_wall_velocity between two steps).
+--shear-heating switches the heat solve on (the fluid starts at 1000 K between z walls held at 1000 K, insulated side walls) and lets the
+viscous dissipation of the flow heat it (Options3.shear_heating): every step prints the total dissipation and the warmest node, and the
+snapshots gain strainrate, stress and dissipation.
 The advective time-step rule is the reference's: 0.67 dx over the largest SIGNED velocity component.  Under a lid that moves along -x
 that is the return flow, not the lid, so the step is capped here by the lid's speed (Options3.tstep_adv_max): a marker next to the lid
 crosses at most two thirds of a cell per step in either direction.
@@ -26,6 +29,7 @@ def flag(name, default):
 
 
 resident = "--resident" in sys.argv[1:]
+shear = "--shear-heating" in sys.argv[1:]
 ux, uy, reverse = flag("u", 1e-9), flag("uy", 0.0), int(flag("reverse", 0))
 argv = [a for a in sys.argv if not a.startswith("--")]
 n = int(argv[1]) if len(argv) > 1 else 33
@@ -37,8 +41,11 @@ tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1))         
 tr_f[:, P3.TR_RHO] = 3300.0; tr_f[:, P3.TR_ETA] = 1e21                           # ... of one uniform fluid (TR_MAT still marks the sphere)
 lid = np.zeros((6, 3))                                                           # (Uz, Ux, Uy) of [z0, x0, y0, zL, xL, yL]
 lid[0] = (0.0, ux, uy)
-opt = P3.Options3(do_heatdiff=False, tdep_rho=False, tdep_eta=False, grav=(0.0, 0.0, 0.0), resident=resident,
-                  bcstokes=[P3.BC_TYPE_NOSLIP] * 6, bcstokesvel=lid)
+opt = P3.Options3(do_heatdiff=shear, tdep_rho=False, tdep_eta=False, grav=(0.0, 0.0, 0.0), resident=resident,
+                  bcstokes=[P3.BC_TYPE_NOSLIP] * 6, bcstokesvel=lid, shear_heating=shear)
+if shear:
+    tr_f[:, P3.TR_TMP] = 1000.0; tr_f[:, P3.TR_HCD] = 4.0; tr_f[:, P3.TR_HCP] = 1250.0
+    opt.bcheatvals = [1000.0, 0.0, 0.0, 1000.0, 0.0, 0.0]
 if ux or uy:
     opt.tstep_adv_max = min(opt.tstep_adv_max, opt.tstep_modifier * (L[0] / (n - 1)) / max(abs(ux), abs(uy)))
 sim = P3.Simulation3(nx, L, tr_x, tr_f, opt)
@@ -50,6 +57,8 @@ for it in range(1, steps + 1):
     print("step %3d  t = %8.3f Myr  dt = %.3e s  Stokes %3d its %s  vx in [%.3e, %.3e]  max |vz| %.3e m/s" %
           (it, sim.totaltime / 3.15576e13, rep["tstep"], rep["stokes"]["iterations"], "ok" if rep["stokes"]["converged"] else "NOT CONVERGED",
            vx.min(), vx.max(), np.abs(vz).max()), flush=True)
+    if shear:
+        print("          dissipation %.4e W, warmest node %.4f K" % (rep["dissipation_total"], sim.field("temp").max()), flush=True)
     if it % 10 == 0 or it == steps:
         sim.write_snapshot(outdir)
 sim.close()

@@ -534,6 +534,33 @@ int  pl3_heat_rhs(pl3_ctx* ctx, double* rhs);
 int  pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double rtol, int maxit, pl_solve_stats* stats);
 /* solution of the last solve of this context: which = 0 Stokes (nz, nx, ny, 4), 1 heat (nz, nx, ny) */
 int  pl3_get_solution(pl3_ctx* ctx, int which, double* out);
+/* Strain rate, deviatoric stress and viscous dissipation of a velocity field, as the operator's own rows define them (one rank).
+ * vz, vx, vy: host (nz, nx, ny) arrays on the staggered positions of the solution vector; all three NULL: the solution of the last
+ * pl3_stokes_solve of this context, still on the device.  strainrate, stress, dissipation: host (nz, nx, ny) node fields, total: the
+ * integral of the dissipation over the box; any of them may be NULL.  The coefficients (pl3_stokes_set_coeffs), wall kinds, wall
+ * velocities and wall flow currently set on the context are used.
+ * The strain rates are those of the momentum rows, div(2 eta eps) written out; (D, E, F) is a cyclic permutation of (z, x, y), rd_A[i] =
+ * 1 / (c_A[i+1] - c_A[i]), rD_A[i] = 1 / (c_A[i+1] - c_A[i-1]) inside and 0 on the two walls:
+ *  - normal components at the cell centres, viscosity eta_n:  eps_DD = (v_D[i_D + 1] - v_D[i_D]) rd_D[i_D];
+ *  - shear components on the edges: the edge of the pair (D, E) lies at node i_D, node i_E, cell i_F, its viscosity is the mean of the two
+ *    nodal eta_s at its ends along F, and  eps_DE = 1/2 (g_DE + g_ED)  with  g_DE = dv_D/dx_E = 2 rD_E[i_E] (v_D[i_E] - v_D[i_E - 1])
+ *    inside (v_D at the cells i_E, i_E - 1 of axis E).  On a wall of E: FREESLIP, g_DE = 0 (the zero-padded table, as in the rows);
+ *    NOSLIP, the one-sided value against the wall's tangential velocity U_D (pl3_stokes_set_wall_velocity) that the natural rows use,
+ *    2 rd_E[0] (v_D[0] - U_D) on the low wall and 2 rd_E[n_E - 2] (U_D - v_D[n_E - 2]) on the high one.  The same rule holds in strict mode
+ *    (pl3_stokes_set_wall_rows) and on the cube edges, where v_D is a wall-normal velocity of the solution vector (0, or the through-flow).
+ *  - no trace is removed: the flow is incompressible to the solver's tolerance.
+ * A node field is the control-volume weighted mean around the node: the node's control volume reaches half a cell to either side (half
+ * widths on the walls); a cell holds 1/8 of its volume in each corner's control volume, an edge's control volume (half a cell to either
+ * side of its two nodes, its own length along F) is halved between its end nodes.  With < > that mean,
+ *    dissipation = < 2 eta_n sum_D eps_DD^2 >_cells + < 4 eta_edge eps_DE^2 >_edges summed over the three pairs     [W/m^3]
+ *    strainrate  = sqrt(1/2 (< sum_D eps_DD^2 >_cells + 2 sum_pairs < eps_DE^2 >_edges))                              [1/s]
+ *    stress      = sqrt(1/2 (< (2 eta_n)^2 sum_D eps_DD^2 >_cells + 2 sum_pairs < (2 eta_edge eps_DE)^2 >_edges))     [Pa]
+ * so that total = sum_nodes dissipation x V_node = the sum of the cell and edge dissipations times their volumes.  The sums run in a
+ * fixed order without atomics: a call repeats bit for bit.  Work: two per-node kernels on Stokes work vectors 0 .. 2.
+ * Errors (each names the entry): a context with pl3_set_comm attached; no coefficients set; NULL velocities before any solve; only some of
+ * vz, vx, vy given. */
+int  pl3_stokes_strain_fields(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* strainrate, double* stress,
+                              double* dissipation, double* total);
 
 /* ---- 3-D marker-in-cell (one rank; every entry point fails on a context that has pl3_set_comm attached) -------------
  * The dimension-by-dimension extension of pylamp_trac.py:30-388.  tr_x is (n, 3) in [z, x, y] order, tr_f is (n, ld_f) with the
@@ -712,9 +739,20 @@ typedef struct pl3_step_report {
 } pl3_step_report;
 int  pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* report);
 /* A grid field of the last resident step, downloaded on demand into out (nz, nx, ny): rho, etas, etan, cp, T, H, mat, kz, kx, ky,
- * velz, velx, vely, pres (Kcont-scaled, ghosts retained), temp.  An unknown or not-yet-computed name is an error that lists the
- * available ones. */
+ * velz, velx, vely, pres (Kcont-scaled, ghosts retained), temp; after a step with pl3_step_set_shear_heating or
+ * pl3_step_set_strain_fields on also strainrate, stress, dissipation (they live in a Stokes work vector: until the next call that uses
+ * the work vectors).  An unknown or not-yet-computed name is an error that lists the available ones. */
 int  pl3_get_field(pl3_ctx* ctx, const char* name, double* out);
+/* Opt-in switches of pl3_resident_step, context state, both off at creation; with both off the step is bit for bit what it is without
+ * them.  Shear heating: after the Stokes solve the dissipation of the solution (pl3_stokes_strain_fields) is added to the scattered H,
+ * one IEEE addition per node, and the heat solve takes the sum (pl3_get_field("H") returns it); wall nodes keep their boundary rows, the
+ * dissipation there is diagnostic only; a step with do_heatdiff == 0 fails by name.  Strain fields: the step computes the three fields
+ * without touching H.  Either switch makes strainrate, stress and dissipation available to pl3_get_field and the integral of the
+ * dissipation to pl3_step_dissipation_total (an error before the first such step).  The time-step rules are unchanged. */
+int  pl3_step_set_shear_heating(pl3_ctx* ctx, int on);
+int  pl3_step_shear_heating(pl3_ctx* ctx, int* on);
+int  pl3_step_set_strain_fields(pl3_ctx* ctx, int on);
+int  pl3_step_dissipation_total(pl3_ctx* ctx, double* total);
 /* The step's advection-velocity kernel on host arrays: vz, vx, vy (nz, nx, ny) -> Vz, Vx, Vy on the padded (nz+1, nx+1, ny+1)
  * centre grid: every component averaged along its own axis, then the ghosts wall by wall in the order z0, x0, y0, zL, xL, yL: a
  * FREESLIP wall mirrors the normal component with a sign flip and copies the tangential ones, the pass of a NOSLIP wall

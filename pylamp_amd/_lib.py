@@ -144,6 +144,11 @@ SIGNATURES = {
     "pl3_mic_inflow_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "pl3_resident_step": (C.c_int, [C.c_void_p, C.POINTER(Step3Config), C.c_int, C.POINTER(Step3Report)]),
     "pl3_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p]),
+    "pl3_stokes_strain_fields": (C.c_int, [C.c_void_p] + [c_double_p] * 7),
+    "pl3_step_set_shear_heating": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl3_step_shear_heating": (C.c_int, [C.c_void_p, c_int_p]),
+    "pl3_step_set_strain_fields": (C.c_int, [C.c_void_p, C.c_int]),
+    "pl3_step_dissipation_total": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_advection_velocity": (C.c_int, [C.c_void_p] + [c_double_p] * 6),
     "pl3_transfer_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "pl3_abi_layout": (C.c_int, [C.POINTER(C.c_size_t)]),

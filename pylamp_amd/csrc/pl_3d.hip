@@ -1235,6 +1235,7 @@ struct pl3_ctx {
     double etol = 3e-8;                     // bound on the velocity-error estimate of a converged Stokes solve (PYLAMP_STOKES_ETOL)
     void* mic3 = nullptr;                   // pl_mic3.hip: resident tracers and the work buffers of the 3-D marker kernels
     void* step3 = nullptr;                  // pl_step3.hip: state of the device-resident time step
+    bool strain_kept = false;               // Stokes work vector 2 still holds the fields of the last pl3_stokes_strain_fields / resident step
     int64_t xfer[4] = {0, 0, 0, 0};         // host <-> device copies (pl3_transfer_stats): count and bytes of those of at least one node field, of the smaller ones
 };
 static thread_local std::string p3_tls_error;
@@ -1429,6 +1430,7 @@ static int allreduce3(pl3_ctx* ctx, double* v, int n, int op) {
 }
 static int need_vecs(pl3_ctx* ctx, int nvec) {
     const long long vol = ctx->geom.d.vol;
+    ctx->strain_kept = false;                   // whoever asks for work vectors may write them
     // the four arrays of a work vector are ONE allocation (array q at vec[v] + q vol): the flat vector kernels and the reductions
     // of BiCGStab take a whole vector per launch (and per host synchronisation)
     for (int v = 0; v < nvec; v++) if (!ctx->vec[v]) P3_TRY(dmal(ctx, &ctx->vec[v], 4 * vol));
@@ -2690,10 +2692,166 @@ extern "C" int pl3_get_solution(pl3_ctx* ctx, int which, double* out) {
     return download3(ctx, &ctx->hvec[11], 1, out);
 }
 
+// ---- strain rate, deviatoric stress and viscous dissipation (pl3_stokes_strain_fields; include/pylamp_hip.h) ------------
+// Two per-node passes over the K3_PROLOGUE grid.  k3_strain_ce writes, at the element of node (i, j, k), the sum of the squared normal
+// strain rates of the CELL whose lowest corner the node is and the squared shear strain rate of the three EDGES that start at the node
+// (pair (D, E): along F); k3_strain_node gathers the eight cells and six edges around a node with their shares of the node's control
+// volume, in a fixed order.  No atomics: a node's sum is one thread's.  The four intermediate arrays and the three results live in Stokes
+// work vectors 1 and 2, which are free outside a solve (the velocities given by the host go to work vector 0).
+//
+// dv_D/dx_A on the edge of v_D at node idx[A] of axis A (element c): between the two midpoints inside; on a no-slip wall one-sided
+// against the wall's velocity component U_D, 2 rd (v - U), as wall_coef3 / wall_rhs3 have it; dropped on a free-slip wall (what the
+// zero-padded rD table does in row3)
+template <int D, int A> __device__ inline double shear_half3(const Op3& op, const Pl3WallVel& mv, const double* __restrict__ u, long long c, const int* idx) {
+    const G3& g = op.g;
+    const int ia = idx[A], na = g.gn[A];
+    if (ia == 0) return nos3<A>(op, 0) ? 2.0 * TB(g.rd[A], 0) * (u[c] - wall_vel3<A, D>(mv, 0)) : 0.0;
+    if (ia == na - 1) return nos3<A>(op, 1) ? 2.0 * TB(g.rd[A], na - 2) * (wall_vel3<A, D>(mv, 1) - u[c - g.s[A]]) : 0.0;
+    return 2.0 * TB(g.rD[A], ia) * (u[c] - u[c - g.s[A]]);
+}
+// eps_DE^2 on the edge of the pair (D, E = D + 1) at node idx[D], node idx[E], cell idx[F]; 0 where there is no such edge
+template <int D> __device__ inline double edge_sq3(const Op3& op, const Pl3WallVel& mv, const double* const* v, long long c, const int* idx) {
+    constexpr int E = (D + 1) % 3, F = (D + 2) % 3;
+    if (idx[F] >= op.g.gn[F] - 1) return 0.0;
+    const double e = 0.5 * (shear_half3<D, E>(op, mv, v[D], c, idx) + shear_half3<E, D>(op, mv, v[E], c, idx));
+    return e * e;
+}
+__global__ __launch_bounds__(256) void k3_strain_ce(Op3 op, V3 x, Pl3WallVel mv, W4 o) {
+    K3_PROLOGUE(op.g)
+    const G3& g = op.g;
+    const double* v[3] = {x.p[0], x.p[1], x.p[2]};
+    double s = 0.0;
+    if (i < g.gn[0] - 1 && j < g.gn[1] - 1 && k < g.gn[2] - 1) {
+        const double ez = (v[0][c + g.s[0]] - v[0][c]) * TB(g.rd[0], i), ex = (v[1][c + g.s[1]] - v[1][c]) * TB(g.rd[1], j),
+                     ey = (v[2][c + g.s[2]] - v[2][c]) * TB(g.rd[2], k);
+        s = ez * ez + ex * ex + ey * ey;
+    }
+    o.p[0][c] = s;
+    o.p[1][c] = edge_sq3<0>(op, mv, v, c, idx);
+    o.p[2][c] = edge_sq3<1>(op, mv, v, c, idx);
+    o.p[3][c] = edge_sq3<2>(op, mv, v, c, idx);
+}
+// along axis A at node ia: the shares wl, wh of the node's width that the cell below / above holds (0 and 1 on a wall) and the width h itself
+// (half a cell on a wall)
+template <int A> __device__ inline void node_w3(const G3& g, int ia, double& wl, double& wh, double& h) {
+    const int n = g.gn[A];
+    if (ia == 0) { wl = 0.0; wh = 1.0; h = 0.5 / TB(g.rd[A], 0); }
+    else if (ia == n - 1) { wl = 1.0; wh = 0.0; h = 0.5 / TB(g.rd[A], n - 2); }
+    else { const double rD = TB(g.rD[A], ia); wl = rD / TB(g.rd[A], ia - 1); wh = rD / TB(g.rd[A], ia); h = 0.5 / rD; }
+}
+// the two edges of the pair (D, D + 1) that meet at the node, the lower one first: t = 2 eta_edge
+template <int D> __device__ inline void edges_node3(const Op3& op, const double* __restrict__ q, long long c, const double* wl, const double* wh,
+                                                    double& Y, double& T, double& P) {
+    constexpr int F = (D + 2) % 3;
+    const long long sf = op.g.s[F];
+    for (int d = 0; d < 2; d++) {
+        const double w = d ? wh[F] : wl[F];
+        if (w == 0.0) continue;
+        const long long cc = d ? c : c - sf;
+        const double e2 = q[cc], t = op.es[cc] + op.es[cc + sf];
+        Y += w * (2.0 * e2); T += w * (2.0 * (t * t) * e2); P += w * (2.0 * t * e2);
+    }
+}
+// e2 / t2 / phi: ringed arrays (NULL: not wanted); H: a plain (nz, nx, ny) array that gains phi, one IEEE addition per node (NULL: none)
+struct Strain3Out { double* e2; double* t2; double* phi; double* H; };
+__global__ __launch_bounds__(256) void k3_strain_node(Op3 op, V4 ce, Strain3Out o) {
+    K3_PROLOGUE(op.g)
+    const G3& g = op.g;
+    double wl[3], wh[3], h[3];
+    node_w3<0>(g, i, wl[0], wh[0], h[0]); node_w3<1>(g, j, wl[1], wh[1], h[1]); node_w3<2>(g, k, wl[2], wh[2], h[2]);
+    double Y = 0.0, T = 0.0, P = 0.0;              // the weighted means of eps_ij eps_ij, tau_ij tau_ij and 2 eta eps_ij eps_ij
+    for (int dz = 0; dz < 2; dz++) {               // the eight cells: z outermost, the lower one first; t = 2 eta_n
+        const double wz = dz ? wh[0] : wl[0];
+        if (wz == 0.0) continue;
+        for (int dx = 0; dx < 2; dx++) {
+            const double wx = dx ? wh[1] : wl[1];
+            if (wx == 0.0) continue;
+            for (int dy = 0; dy < 2; dy++) {
+                const double wy = dy ? wh[2] : wl[2];
+                if (wy == 0.0) continue;
+                const long long cc = c - (dz ? 0 : g.s[0]) - (dx ? 0 : g.s[1]) - (dy ? 0 : g.s[2]);
+                const double w = wz * wx * wy, s = ce.p[0][cc], t = 2.0 * op.en[cc];
+                Y += w * s; T += w * ((t * t) * s); P += w * (t * s);
+            }
+        }
+    }
+    edges_node3<0>(op, ce.p[1], c, wl, wh, Y, T, P);
+    edges_node3<1>(op, ce.p[2], c, wl, wh, Y, T, P);
+    edges_node3<2>(op, ce.p[3], c, wl, wh, Y, T, P);
+    if (o.e2) o.e2[c] = sqrt(0.5 * Y);
+    if (o.t2) o.t2[c] = sqrt(0.5 * T);
+    o.phi[c] = P;
+    if (o.H) { const long long t = ((long long)li * g.n[1] + lj) * g.n[2] + lk; o.H[t] = __dadd_rn(o.H[t], P); }
+}
+// part[b] = the sum over workgroup b's nodes of phi x the node's control volume
+__global__ __launch_bounds__(256) void k3_strain_total(G3 g, const double* __restrict__ phi, double* __restrict__ part) {
+    const long long N = (long long)g.n[0] * g.n[1] * g.n[2];
+    double acc[1] = {0.0};
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < N; t += (long long)gridDim.x * 256) {
+        const int k = (int)(t % g.n[2]), j = (int)((t / g.n[2]) % g.n[1]), i = (int)(t / ((long long)g.n[2] * g.n[1]));
+        double wl, wh, hz, hx, hy;
+        node_w3<0>(g, i, wl, wh, hz); node_w3<1>(g, j, wl, wh, hx); node_w3<2>(g, k, wl, wh, hy);
+        acc[0] += phi[i3(g, i, j, k)] * (hz * hx * hy);
+    }
+    block_sums3<1>(acc, part);
+}
+static Vec3 strain_out3(pl3_ctx* ctx) { return svec(ctx, 2); }      // strainrate, stress, dissipation (ringed)
+// the three node fields of the velocities vel (three ringed arrays; not work vector 1 or 2) into strain_out3; Hplain (NULL: none) gains the
+// dissipation; total (NULL: not wanted): its integral over the box
+static int strain_run3(pl3_ctx* ctx, const Vec3& vel, double* Hplain, double* total) {
+    const G3& g = ctx->geom.d;
+    const Vec3 ce = svec(ctx, 1), out = strain_out3(ctx);
+    launch3(ctx, g, k3_strain_ce, ctx->op, cv3(vel), ctx->wallvel, wv4(ce));
+    launch3(ctx, g, k3_strain_node, ctx->op, cv4(ce), Strain3Out{out[0], out[1], out[2], Hplain});
+    P3_HIP(ctx, hipGetLastError());
+    ctx->strain_kept = true;
+    if (total) {
+        hipLaunchKernelGGL(k3_strain_total, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, g, (const double*)out[2], ctx->part);
+        P3_TRY(sum_partials3(ctx, 1, 1, total));
+    }
+    return 0;
+}
+static int strain_check3(pl3_ctx* ctx, const char* who, bool resident) {
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, std::string(who) + ": the strain-rate, stress and dissipation fields run on one rank (this context has pl3_set_comm attached)");
+    if (!ctx->op_ready) return p3_fail(ctx, std::string(who) + ": no Stokes coefficients set (pl3_stokes_set_coeffs)");
+    if (resident && !ctx->have_x) return p3_fail(ctx, std::string(who) + ": NULL velocities mean the solution of the last Stokes solve, and no solve has run on this context");
+    return 0;
+}
+extern "C" int pl3_stokes_strain_fields(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* strainrate, double* stress,
+                                        double* dissipation, double* total) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_strain_fields: NULL context");
+    const bool given = vz || vx || vy;
+    if (given && !(vz && vx && vy)) return p3_fail(ctx, "pl3_stokes_strain_fields: vz, vx, vy must be given all three or all NULL");
+    P3_TRY(strain_check3(ctx, "pl3_stokes_strain_fields", !given));
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, given ? 3 : 14));
+    Vec3 vel = svec(ctx, 11).vel();
+    if (given) {
+        vel = svec(ctx, 0).vel();
+        const double* in[3] = {vz, vx, vy};
+        for (int q = 0; q < 3; q++) { double* d = vel[q]; P3_TRY(upload3(ctx, in[q], 1, &d)); }
+    }
+    P3_TRY(strain_run3(ctx, vel, nullptr, total));
+    double* host[3] = {strainrate, stress, dissipation};
+    for (int q = 0; q < 3; q++) if (host[q]) { double* d = strain_out3(ctx)[q]; P3_TRY(download3(ctx, &d, 1, host[q])); }
+    return 0;
+}
+// the same for the resident solution, for pl_step3.hip: nothing but the total crosses the bus
+int pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total) {
+    P3_TRY(strain_check3(ctx, "pl3_resident_step", true));
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    return strain_run3(ctx, svec(ctx, 11).vel(), Hplain, total);
+}
+
 // ---- what the device-resident step (pl_step3.hip) needs of a context ----------------------------------------------------------
 int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     P3_HIP(ctx, hipSetDevice(ctx->device));
+    const bool kept = ctx->strain_kept;                 // (looking at the context does not touch the work vectors)
     P3_TRY(need_vecs(ctx, 14));
+    ctx->strain_kept = kept;
+    for (int q = 0; q < 3; q++) v->strain[q] = strain_out3(ctx)[q];
+    v->have_strain = kept;
     P3_TRY(need_hvecs(ctx));
     const G3& g = ctx->geom.d;
     v->s0 = g.s[0]; v->s1 = g.s[1]; v->pad = P3_PAD; v->stream = ctx->stream; v->slot = &ctx->step3;

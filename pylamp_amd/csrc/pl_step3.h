@@ -21,12 +21,15 @@ struct Pl3DevView {
     int noslip;                             // Stokes walls (pl3_stokes_set_walls): bit w of [z0, x0, y0, zL, xL, yL] set = no-slip
     Pl3WallVel wallvel;                     // ... and their velocities
     Pl3WallFlow wallflow;                   // ... and the flow through them
+    double* strain[3];                      // strainrate, stress, dissipation of the last pl3i_strain_fields_dev (Stokes work vector 2) ...
+    bool have_strain;                       // ... and whether nothing has asked for the work vectors since
     void** slot;                            // opaque state owned by pl_step3.hip, released by pl3_step_free
 };
 // pl_3d.hip
 int  pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v);
 int  pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3], double mineta);
 int  pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const double* const src[7], const int bc[6], const double bcvalue[6], double tstep);
+int  pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total);     // the fields of the resident solution; Hplain (NULL: none) += dissipation
 void pl3_count_copy(pl3_ctx* ctx, size_t bytes);          // every host <-> device copy of a pl3_* entry point reports here
 // pl_mic3.hip (plain (nz, nx, ny) device arrays in and out)
 int  pl3i_mic_scatter(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* const tc[3], const int tn[3], double* dout);

@@ -191,12 +191,17 @@ __global__ __launch_bounds__(256) void k_s3_layout(S3Dims d, double* __restrict_
 // =====================================================================================================================
 struct Step3 {
     bool have_scattered = false, have_heat_fields = false, have_vel = false, have_temp = false;
+    // pl3_step_set_shear_heating / pl3_step_set_strain_fields (both off at creation), and the integral of the dissipation of the last step
+    // that ran with one of them on
+    bool shear_heating = false, strain_fields = false, have_strain = false;
+    double dissipation_total = 0.0;
 };
 void pl3_step_free(void** slot) {
     delete (Step3*)*slot;
     *slot = nullptr;
 }
-static const char* const S3_NAMES[15] = {"rho", "etas", "cp", "T", "H", "mat", "etan", "kz", "kx", "ky", "velz", "velx", "vely", "pres", "temp"};
+static const char* const S3_NAMES[18] = {"rho", "etas", "cp", "T", "H", "mat", "etan", "kz", "kx", "ky", "velz", "velx", "vely", "pres", "temp",
+                                         "strainrate", "stress", "dissipation"};
 
 struct S3Open { Pl3HostView h; Pl3DevView d; Step3* S; S3Dims dims; size_t N; };
 static int s3_open(pl3_ctx* ctx, const char* who, S3Open& o) {
@@ -252,7 +257,8 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     S3_TRY(pl3i_mic_buf(ctx, "s_part", (size_t)S3_MAXPART * 8, &part));
     S3_TRY(pl3i_mic_buf(ctx, "s_red", 8, &red));
     double* ms = pl3i_mic_ms(ctx);
-    o.S->have_scattered = false; o.S->have_vel = false;       // the fields of the previous step go as this one overwrites them
+    o.S->have_scattered = false; o.S->have_vel = false; o.S->have_strain = false;       // the fields of the previous step go as this one overwrites them
+    if (o.S->shear_heating && !heat) return pl3_fail(ctx, "pl3_resident_step: shear heating (pl3_step_set_shear_heating) needs the heat solve, do_heatdiff = 1");
 
     // 1. properties and the field list of scatter_fields(): node grid, cell centres, the three mixed sets of the conductivity
     // (the two columns the properties overwrite are kept, so that a step that fails its NaN check leaves the tracers as they were)
@@ -322,6 +328,12 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     S3_TRY(pl3i_stokes_set_coeffs_dev(ctx, F + S3_ETAS * N, F + S3_ETAN * N, F + S3_RHO * N, cfg->use_grav ? cfg->grav : nullptr, mineta));
     S3_TRY(pl3_stokes_solve(ctx, nullptr, nullptr, 0, cfg->stokes_rtol, cfg->stokes_maxit, &rep->stokes));
     o.S->have_vel = true;
+    // 4b. strain rate, stress and dissipation of that solution (opt-in); with shear heating H += dissipation, one addition per node,
+    // before the heat coefficients are taken from it
+    if (o.S->shear_heating || o.S->strain_fields) {
+        S3_TRY(pl3i_strain_fields_dev(ctx, o.S->shear_heating ? F + S3_H * N : nullptr, &o.S->dissipation_total));
+        o.S->have_strain = true;
+    }
 
     // 5. the Stokes time-step rule, the limiter and the clamps
     const S3Ops vops{{S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX}};
@@ -367,7 +379,8 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
 }
 
 // A grid field of the last resident step, (nz, nx, ny): rho, etas, etan, cp, T, H, mat, kz, kx, ky (cp .. ky but etan only with heat
-// on), velz, velx, vely, pres (Kcont-scaled), temp.  One node-sized copy.
+// on), velz, velx, vely, pres (Kcont-scaled), temp; strainrate, stress, dissipation after a step with pl3_step_set_shear_heating or
+// pl3_step_set_strain_fields on, until the Stokes work vectors are used again.  One node-sized copy.
 extern "C" int pl3_get_field(pl3_ctx* ctx, const char* name, double* out) {
     if (!ctx) return pl3_fail(nullptr, "pl3_get_field: NULL context");
     if (!name || !out) return pl3_fail(ctx, "pl3_get_field: NULL argument");
@@ -376,8 +389,9 @@ extern "C" int pl3_get_field(pl3_ctx* ctx, const char* name, double* out) {
     const Step3& S = *o.S;
     int id = -1;
     std::string have;
-    for (int q = 0; q < 15; q++) {
-        const bool ok = q < 10 ? S.have_scattered && (S.have_heat_fields || q == S3_RHO || q == S3_ETAS || q == S3_ETAN) : (q < 14 ? S.have_vel : S.have_temp);
+    for (int q = 0; q < 18; q++) {
+        const bool ok = q < 10 ? S.have_scattered && (S.have_heat_fields || q == S3_RHO || q == S3_ETAS || q == S3_ETAN)
+                               : (q < 14 ? S.have_vel : (q == 14 ? S.have_temp : S.have_strain && o.d.have_strain));
         if (ok) have += std::string(have.empty() ? "" : ", ") + S3_NAMES[q];
         if (ok && !std::strcmp(name, S3_NAMES[q])) id = q;
     }
@@ -388,12 +402,48 @@ extern "C" int pl3_get_field(pl3_ctx* ctx, const char* name, double* out) {
     else if (id == 14) S3_TRY(pl3i_mic_buf(ctx, "s_temp", N, &src));
     else {
         S3_TRY(pl3i_mic_buf(ctx, "s_stage", 3 * N, &src));
-        hipLaunchKernelGGL(k_s3_layout, s3_blocks((long long)N), dim3(256), 0, o.d.stream, o.dims, o.d.X[id - 10], src, 0);
+        hipLaunchKernelGGL(k_s3_layout, s3_blocks((long long)N), dim3(256), 0, o.d.stream, o.dims, id < 14 ? o.d.X[id - 10] : o.d.strain[id - 15], src, 0);
         S3_HIP(ctx, hipGetLastError());
     }
     pl3_count_copy(ctx, N * sizeof(double));
     S3_HIP(ctx, hipMemcpyAsync(out, src, N * sizeof(double), hipMemcpyDeviceToHost, o.d.stream));
     S3_HIP(ctx, hipStreamSynchronize(o.d.stream));
+    return 0;
+}
+
+// Opt-in switches of the resident step, both off at creation (with both off the step is bit for bit what it is without them).  Shear
+// heating: after the Stokes solve the dissipation of the solution (pl3_stokes_strain_fields) is added to the scattered H, and the heat solve
+// takes that sum; it needs do_heatdiff.  Strain fields: the step keeps strainrate, stress and dissipation for pl3_get_field; either
+// switch makes them available.  pl3_step_dissipation_total: the integral of the dissipation of the last such step.
+extern "C" int pl3_step_set_shear_heating(pl3_ctx* ctx, int on) {
+    if (!ctx) return pl3_fail(nullptr, "pl3_step_set_shear_heating: NULL context");
+    S3Open o;
+    S3_TRY(s3_open(ctx, "pl3_step_set_shear_heating", o));
+    o.S->shear_heating = on != 0;
+    return 0;
+}
+extern "C" int pl3_step_shear_heating(pl3_ctx* ctx, int* on) {
+    if (!ctx) return pl3_fail(nullptr, "pl3_step_shear_heating: NULL context");
+    if (!on) return pl3_fail(ctx, "pl3_step_shear_heating: NULL argument");
+    S3Open o;
+    S3_TRY(s3_open(ctx, "pl3_step_shear_heating", o));
+    *on = o.S->shear_heating ? 1 : 0;
+    return 0;
+}
+extern "C" int pl3_step_set_strain_fields(pl3_ctx* ctx, int on) {
+    if (!ctx) return pl3_fail(nullptr, "pl3_step_set_strain_fields: NULL context");
+    S3Open o;
+    S3_TRY(s3_open(ctx, "pl3_step_set_strain_fields", o));
+    o.S->strain_fields = on != 0;
+    return 0;
+}
+extern "C" int pl3_step_dissipation_total(pl3_ctx* ctx, double* total) {
+    if (!ctx) return pl3_fail(nullptr, "pl3_step_dissipation_total: NULL context");
+    if (!total) return pl3_fail(ctx, "pl3_step_dissipation_total: NULL argument");
+    S3Open o;
+    S3_TRY(s3_open(ctx, "pl3_step_dissipation_total", o));
+    if (!o.S->have_strain) return pl3_fail(ctx, "pl3_step_dissipation_total: no resident step has run with shear heating or the strain fields on (pl3_step_set_shear_heating, pl3_step_set_strain_fields)");
+    *total = o.S->dissipation_total;
     return 0;
 }
 

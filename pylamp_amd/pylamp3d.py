@@ -284,6 +284,26 @@ class Context3:
         self.check(self.lib.pl3_stokes_start_vector(self.handle(), _lib.dptr(x)))
         return x
 
+    def set_shear_heating(self, on):
+        """Shear heating in the resident step of this context (default off): the viscous dissipation of the Stokes solution is added to
+        the scattered H before the heat solve.  The rule is in include/pylamp_hip.h at pl3_step_set_shear_heating."""
+        self.check(self.lib.pl3_step_set_shear_heating(self.handle(), 1 if on else 0))
+
+    def shear_heating(self):
+        on = C.c_int()
+        self.check(self.lib.pl3_step_shear_heating(self.handle(), C.byref(on)))
+        return bool(on.value)
+
+    def set_strain_fields(self, on):
+        """The resident step of this context keeps strainrate, stress and dissipation for pl3_get_field (default off)."""
+        self.check(self.lib.pl3_step_set_strain_fields(self.handle(), 1 if on else 0))
+
+    def dissipation_total(self):
+        """The integral of the dissipation over the box, of the last resident step that ran with one of the two switches on."""
+        t = C.c_double()
+        self.check(self.lib.pl3_step_dissipation_total(self.handle(), C.byref(t)))
+        return t.value
+
     def set_marker_search(self, on):
         """Per-axis cell search for the 3-D marker kernels of this context (rectilinear grids; default off = the regular-grid
         formula).  Resident tracers are re-sorted by the new rule."""
@@ -584,6 +604,29 @@ def solve(A, rhs=None, x0=None, rtol=DEFAULT_RTOL, maxit=DEFAULT_MAXIT, resident
     ctx.check(ctx.lib.pl3_stokes_solve(ctx.handle(), r, _lib.dptr(x), 0 if x0 is None else 1, float(rtol), int(maxit), C.byref(st)))
     A.last_stats = st.as_dict()
     return x
+
+
+STRAIN_FIELDS = ("strainrate", "stress", "dissipation")
+
+
+def strain_fields(A, x=None):
+    """Second invariants of the strain rate [1/s] and of the deviatoric stress [Pa] and the viscous dissipation [W/m^3] at the nodes,
+    (nz, nx, ny) each, and dissipation_total [W], the integral of the dissipation over the box, for the velocities of the solution
+    vector x (nz nx ny 4) with the coefficients, walls, wall velocities and wall flow of A's context; x=None: the solution of the last
+    solve(A), still on the device.  The definition is in include/pylamp_hip.h at pl3_stokes_strain_fields.  One rank."""
+    ctx = A._ctx
+    out = {k: np.empty(ctx.nx) for k in STRAIN_FIELDS}
+    tot = C.c_double()
+    if x is None:
+        v = [None, None, None]
+    else:
+        x = _lib.f64(x).reshape(-1)
+        if x.size != A.shape[0]:
+            raise Exception("dimension mismatch")
+        v = [_lib.dptr(np.ascontiguousarray(c)) for c in x2vp(x, ctx.nx)[0]]
+    ctx.check(ctx.lib.pl3_stokes_strain_fields(ctx.handle(), v[0], v[1], v[2], *[_lib.dptr(out[k]) for k in STRAIN_FIELDS], C.byref(tot)))
+    out["dissipation_total"] = tot.value
+    return out
 
 
 class HeatOperator3:
@@ -983,6 +1026,11 @@ class Options3:
         # beyond the reference: the Stokes solve starts from the extrapolated history of its solutions (Context3.set_warm_start) instead
         # of the hydrostatic state.  False: off; True: (points, order) = WARM_START_DEFAULT; or a (points, order) pair
         self.stokes_warm_start = False
+        # beyond the reference: the viscous dissipation of the Stokes solution heats the material (added to the scattered H before the heat
+        # solve; needs do_heatdiff), and / or the step keeps the fields strainrate, stress, dissipation (strain_fields).  Both off: the
+        # step is bit for bit what it is without them
+        self.shear_heating = False
+        self.strain_fields = False
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
@@ -1048,6 +1096,9 @@ class Simulation3:
                             "tracer leaves the box and there is nothing to delete)")
         if o.surface_stabilization:
             raise Exception("Simulation3: surface stabilisation is not supported in 3-D")
+        self.shear_heating, self.strain_fields = bool(o.shear_heating), bool(o.strain_fields)
+        if self.shear_heating and not o.do_heatdiff:
+            raise Exception("Simulation3: Options3.shear_heating = True needs the heat solve, Options3.do_heatdiff = True")
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
         self.bcstokesflow = self._checked_flow(o.bcstokesflow, "Simulation3: Options3.bcstokesflow")
         wall_materials(o.bcinflow, self.nx, "Simulation3: Options3.bcinflow")
@@ -1066,6 +1117,10 @@ class Simulation3:
         self.warm_start = warm_start_setting(o.stokes_warm_start, "Simulation3: Options3.stokes_warm_start")
         if self.warm_start[0]:
             self.ctx.set_warm_start(*self.warm_start)
+        if o.resident and self.shear_heating:
+            self.ctx.set_shear_heating(True)
+        if o.resident and self.strain_fields:
+            self.ctx.set_strain_fields(True)
         self._inflow = False
         if o.bcinflow is not None:
             self.set_inflow_material(o.bcinflow)
@@ -1159,7 +1214,9 @@ class Simulation3:
         return cnt
 
     def field(self, name):
-        """A grid field of the last step: rho, etas, etan, cp, T, H, mat, kz, kx, ky, velz, velx, vely, pres, temp."""
+        """A grid field of the last step: rho, etas, etan, cp, T, H, mat, kz, kx, ky, velz, velx, vely, pres, temp; with
+        Options3.shear_heating or Options3.strain_fields also strainrate, stress, dissipation (H then includes the dissipation if
+        shear_heating is on)."""
         if self.opt.resident and name not in self.fields:
             out = np.empty(self.nx)
             self._lib_call("pl3_get_field", name.encode(), _lib.dptr(out))
@@ -1300,6 +1357,8 @@ class Simulation3:
             rep["ninflow"] = self.ctx.inflow_count()[0]
         if self.warm_start[0]:
             rep["stokes_start"] = self.ctx.history_info()["start"]
+        if self.shear_heating or self.strain_fields:
+            rep["dissipation_total"] = self.ctx.dissipation_total()
         self.fields = {}
         self._stepped = True
         self.last = rep
@@ -1342,6 +1401,12 @@ class Simulation3:
         if self.warm_start[0]:
             self.ctx.commit_solution(tstep)      # (as pl3_resident_step does: both paths keep the same history)
         f.update(velz=newvel[0], velx=newvel[1], vely=newvel[2], pres=pres)
+        if self.shear_heating or self.strain_fields:
+            sf = strain_fields(A)                # (of the solution on the device: the kernel of the resident step)
+            dissipation_total = sf.pop("dissipation_total")
+            f.update(sf)
+            if self.shear_heating:
+                f["H"] = f["H"] + f["dissipation"]
         if o.do_heatdiff:
             H, _ = makeDiffusionMatrix(self.nx, self.grid, self.gridmp, f["T"], [f["kz"], f["kx"], f["ky"]], f["cp"], f["rho"], f["H"],
                                        o.bcheat, o.bcheatvals, tstep, ctx=self.ctx)
@@ -1360,6 +1425,8 @@ class Simulation3:
         rep["time"] = self.totaltime; rep["ntrac"] = self.count()
         if self.warm_start[0]:
             rep["stokes_start"] = self.ctx.history_info()["start"]
+        if self.shear_heating or self.strain_fields:
+            rep["dissipation_total"] = dissipation_total
         self.fields = f
         self.last = rep
         return rep
@@ -1371,13 +1438,16 @@ class Simulation3:
             f = {k: self.field(k) for k in ("velz", "velx", "vely", "pres", "rho")}
             if self.opt.do_heatdiff:
                 f["temp"] = self.field("temp")
+            if self.shear_heating or self.strain_fields:
+                f.update({k: self.field(k) for k in STRAIN_FIELDS})
         else:
             f = self.fields
+        extra = {k: f[k] for k in STRAIN_FIELDS} if self.shear_heating or self.strain_fields else {}
         temp = f["temp"] if "temp" in f else f["velx"] * 0.0
         tr_x, tr_f = self.tracers(); tr_v = self.tracer_velocity()
         os.makedirs(outdir, exist_ok=True)
         np.savez(os.path.join(outdir, "griddata.{:06d}.npz".format(self.it)), gridz=self.grid[0], gridx=self.grid[1], gridy=self.grid[2],
-                 velz=f["velz"], velx=f["velx"], vely=f["vely"], pres=f["pres"], rho=f["rho"], temp=temp, tstep=self.it, time=self.totaltime)
+                 velz=f["velz"], velx=f["velx"], vely=f["vely"], pres=f["pres"], rho=f["rho"], temp=temp, tstep=self.it, time=self.totaltime, **extra)
         np.savez(os.path.join(outdir, "tracs.{:06d}.npz".format(self.it)), tr_x=tr_x, tr_f=tr_f, tr_v=tr_v, tstep=self.it, time=self.totaltime)
 
     def close(self):

@@ -42,6 +42,8 @@ otherwise.  --resident selects Options3.resident (one pl3_resident_step call per
 --warm switches Options3.stokes_warm_start on (three solutions kept, quadratic extrapolation) and adds how the timed solves started
 and the guard's residuals; writes profiles/mic3_step_129_warm.json unless --out says otherwise (profiles/stokes3_warm.json holds the
 medians of three such processes alternating with three without --warm).
+--shear-heating switches Options3.shear_heating on (the dissipation of the Stokes solution is added to H before the heat solve; --out is
+wanted: profiles/strain3.json holds the medians of three such processes next to three without).
 --tree DIR imports pylamp_amd from another checkout: the host-staged yardstick is run on the parent commit's library, in
 separate processes alternating with the resident runs of this one.
 """
@@ -225,6 +227,8 @@ def step_bench(a):
     kw = dict(resident=True) if a.resident else {}
     if a.warm:
         kw["stokes_warm_start"] = True
+    if a.shear_heating:
+        kw["shear_heating"] = True
     sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**kw, **_delete_kw(a)))
     del tr_x, tr_f
     wall, stages, its, starts, guard = [], {}, [], [], []
@@ -247,6 +251,8 @@ def step_bench(a):
                reps=a.reps, warmup=a.warmup, step_ms=round(float(np.median(wall)), 2), step_ms_min=round(float(np.min(wall)), 2),
                step_ms_max=round(float(np.max(wall)), 2), stokes_iterations=its,
                stage_ms={k: round(float(np.median(v)), 3) for k, v in stages.items()})
+    if a.shear_heating:
+        out.update(shear_heating=True, dissipation_total=r["dissipation_total"])
     if a.warm:          # r0_over_ref: the guard's |r0| / ref of every timed solve (below 1: the extrapolated start was taken)
         out.update(warm_start=list(sim.warm_start), stokes_start=starts, r0_over_ref=[None if g is None else float("%.3e" % g) for g in guard])
     # what the stage times do not cover: host work and copies (staged: "scatter" is the LAST of the step's five scatters alone)
@@ -266,7 +272,7 @@ def main():
     ap.add_argument("--sort-only", action="store_true"); ap.add_argument("--refill-reps", type=int, default=7)
     ap.add_argument("--parent", nargs="*", default=[])
     ap.add_argument("--step", action="store_true"); ap.add_argument("--resident", action="store_true"); ap.add_argument("--tree", default=None)
-    ap.add_argument("--warm", action="store_true")
+    ap.add_argument("--warm", action="store_true"); ap.add_argument("--shear-heating", action="store_true")
     ap.add_argument("--search", action="store_true"); ap.add_argument("--graded", type=float, default=0.0)
     ap.add_argument("--delete", action="store_true"); ap.add_argument("--off", nargs="*", default=[])
     ap.add_argument("--inflow", action="store_true")
