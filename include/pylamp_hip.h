@@ -534,6 +534,42 @@ int  pl3_heat_rhs(pl3_ctx* ctx, double* rhs);
 int  pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double rtol, int maxit, pl_solve_stats* stats);
 /* solution of the last solve of this context: which = 0 Stokes (nz, nx, ny, 4), 1 heat (nz, nx, ny) */
 int  pl3_get_solution(pl3_ctx* ctx, int which, double* out);
+/* Heat walls with a profile (one rank).  For wall w of [z0, x0, y0, zL, xL, yL] with axis a, let p < q be the two other axes in z, x, y
+ * order.  values[w] is a plane over the wall's NODES, n_p x n_q doubles in C order -- (nx, ny) on z-walls, (nz, ny) on x-walls, (nz, nx)
+ * on y-walls -- entry i n_q + j belonging to the node with index i along p and j along q.  values[w] == NULL: the wall keeps the one
+ * value bcvalue[w] of pl3_heat_set_coeffs; values == NULL or six NULL pointers clear the setting and free the planes, the state at
+ * creation.  The state belongs to the context, survives pl3_heat_set_coeffs and is read whenever the right-hand side is formed:
+ * pl3_heat_rhs, pl3_heat_solve and the heat solve of pl3_resident_step, which ignores cfg->bcheatvals[w] for a wall that has a plane.
+ *  - Meaning: that of the scalar, by the wall's kind at the time the right-hand side is formed.  FIXTEMP: the temperature of the node.
+ *    FIXFLOW: k dT/dx_a at the node, the derivative taken along +a on the low AND on the high wall.  So a positive entry is heat LEAVING
+ *    through z0, x0, y0 (the temperature rises into the box) and heat ENTERING through zL, xL, yL: the heat flow into the box per area
+ *    is -v on a low wall and +v on a high wall.  The row scaling of the solve is unchanged.
+ *  - Ownership is that of the rows: z-walls own their edges, then x-walls, then y-walls.  Entries of a plane at nodes another wall owns
+ *    are never read and not checked: rows i = 0 and i = nz - 1 of an x- or y-wall's plane, and columns j = 0 and j = nx - 1 of a
+ *    y-wall's plane as well.
+ *  - Without planes the right-hand side is formed by the kernel it was formed by before.
+ * Errors, a rejected call changing nothing: a NULL context; a non-finite entry that is read (names the wall and the indices); a context
+ * with pl3_set_comm attached. */
+int  pl3_heat_set_wall_values(pl3_ctx* ctx, const double* const values[6]);
+/* *mask: bit w set = wall w has a plane; values[w] != NULL receives the plane of such a wall, downloaded from the device (either
+ * argument may be NULL) */
+int  pl3_heat_get_wall_values(pl3_ctx* ctx, int* mask, double* const values[6]);
+/* Heat budget of a temperature field under the operator of the last pl3_heat_set_coeffs / resident step (one rank).  T: a host
+ * (nz, nx, ny) field, or NULL for the solution of the last pl3_heat_solve of this context, still on the device (whether or not it was
+ * downloaded).  Every term is a sum over the INTERIOR nodes of the terms of their rows times the control volume.  With w_a[i] =
+ * mp_a[i] - mp_a[i-1] for the midpoints mp given to pl3_heat_set_coeffs, V = w_z w_x w_y, rd_a[i] = 1 / (c_a[i+1] - c_a[i]), and k_a[i]
+ * the conductivity on the face between the nodes i and i + 1 along a:
+ *  - out[0 .. 5]: the heat flow INTO the box through z0, x0, y0, zL, xL, yL [W].  For a wall of axis a, summed over the nodes interior
+ *    in the two other axes p, q:  low wall  - k_a[0] (T[1] - T[0]) rd_a[0] w_p w_q,  high wall  + k_a[n-2] (T[n-1] - T[n-2]) rd_a[n-2]
+ *    w_p w_q -- the face fluxes the FIXFLOW rows prescribe.  The sums cover the control areas of the interior nodes: on a uniform grid
+ *    (n_p - 2)(n_q - 2) faces of the wall, not the half cells along its rim.
+ *  - out[6]: the storage rate  sum (T - T_old) / cdt V  with cdt = tstep / (rho Cp), that is rho Cp (T - T_old) / tstep V.
+ *  - out[7]: the source  sum H V.
+ * The wall terms telescope, so for any T that satisfies the interior rows  out[6] - out[7] - (out[0] + .. + out[5]) = 0  whatever the
+ * kinds of the walls; for the result of a solve what remains is its residual.  One pass over the nodes, summed in a fixed order: two
+ * calls give the same bits.
+ * Errors name the entry: no heat operator set; T == NULL before any heat solve; a context with pl3_set_comm attached. */
+int  pl3_heat_budget(pl3_ctx* ctx, const double* T, double out[8]);
 /* Strain rate, deviatoric stress and viscous dissipation of a velocity field, as the operator's own rows define them (one rank).
  * vz, vx, vy: host (nz, nx, ny) arrays on the staggered positions of the solution vector; all three NULL: the solution of the last
  * pl3_stokes_solve of this context, still on the device.  strainrate, stress, dissipation: host (nz, nx, ny) node fields, total: the

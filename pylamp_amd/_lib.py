@@ -111,6 +111,9 @@ SIGNATURES = {
     "pl3_heat_rhs": (C.c_int, [C.c_void_p, c_double_p]),
     "pl3_heat_solve": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_int, C.POINTER(SolveStats)]),
     "pl3_get_solution": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "pl3_heat_set_wall_values": (C.c_int, [C.c_void_p, C.POINTER(c_double_p)]),
+    "pl3_heat_get_wall_values": (C.c_int, [C.c_void_p, c_int_p, C.POINTER(c_double_p)]),
+    "pl3_heat_budget": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "pl3_trac2grid": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int, c_int_p, c_double_p, C.c_int,
                                 c_double_p, C.c_int, c_double_p, C.c_int, C.POINTER(c_double_p)]),
     "pl3_grid2trac": (C.c_int, [C.c_void_p, C.c_int64, c_double_p, C.c_int, C.POINTER(c_double_p), C.c_int, C.c_int, C.c_int,

@@ -1088,8 +1088,12 @@ template <bool SCALED> __global__ __launch_bounds__(256) void k3_heat_apply(Heat
     }
     y[c] = SCALED ? r / dg : r;
 }
-__global__ __launch_bounds__(256) void k3_heat_rhs(Heat3 op, const double* __restrict__ Told, const double* __restrict__ H, const double* bcv,
-                                                   double* __restrict__ rhs, int scaled) {
+// pl3_heat_set_wall_values: v[w] is the plane of wall w over its nodes, C-order (n_p, n_q) with p < q the two other axes in z, x, y order,
+// or NULL where the wall keeps its one value bcv[w]
+struct Heat3Planes { const double* v[6]; };
+// PLANES = false: what a context without planes launches (pl is not read)
+template <bool PLANES> __global__ __launch_bounds__(256) void k3_heat_rhs(Heat3 op, const double* __restrict__ Told, const double* __restrict__ H,
+                                                                          const double* bcv, Heat3Planes pl, double* __restrict__ rhs, int scaled) {
     K3_PROLOGUE(op.g)
     const G3& g = op.g;
     int wall = -1, ax = 0, hi = 0;
@@ -1100,6 +1104,10 @@ __global__ __launch_bounds__(256) void k3_heat_rhs(Heat3 op, const double* __res
     double r, dg = 1.0;
     if (wall >= 0) {
         r = bcv[wall];
+        if (PLANES && pl.v[wall]) {
+            const int p = ax == 0 ? 1 : 0, q = ax == 2 ? 1 : 2;
+            r = pl.v[wall][(long long)idx[p] * g.gn[q] + idx[q]];
+        }
         if (op.bc[wall] != PL_BC_FIXTEMP) dg = hi ? op.kk[ax][c - g.s[ax]] * TB(g.rd[ax], g.gn[ax] - 2) : -op.kk[ax][c] * TB(g.rd[ax], 0);
     } else {
         r = -Told[c] - op.cdt[c] * H[c];
@@ -1115,6 +1123,31 @@ __global__ __launch_bounds__(256) void k3_heat_rhs(Heat3 op, const double* __res
 __global__ __launch_bounds__(256) void k3_heat_coef(G3 g, const double* __restrict__ rho, const double* __restrict__ cp, double dt, double* __restrict__ out) {
     K3_PROLOGUE(g)
     out[c] = dt / (rho[c] * cp[c]);
+}
+// pl3_heat_budget (one rank): part[8 b + ..] = workgroup b's share of the heat flow into the box through z0, x0, y0, zL, xL, yL | the
+// storage rate | the source, all sums over the INTERIOR nodes with the widths w_a = 1 / rdb_a of their control volumes -- the terms of the
+// interior rows of k3_heat_apply times the volume, so that storage - source - the six wall flows telescopes to the rows' residual.  A node
+// next to a wall (idx[a] == 1 or gn[a] - 2) carries that wall's face flux over its own w_p w_q.
+__global__ __launch_bounds__(256) void k3_heat_budget(Heat3 op, const double* __restrict__ T, const double* __restrict__ Told, const double* __restrict__ H,
+                                                      double* __restrict__ part) {
+    const G3& g = op.g;
+    const long long N = (long long)g.n[0] * g.n[1] * g.n[2];
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < N; t += (long long)gridDim.x * 256) {
+        const int idx[3] = {(int)(t / ((long long)g.n[2] * g.n[1])), (int)((t / g.n[2]) % g.n[1]), (int)(t % g.n[2])};
+        if (idx[0] == 0 || idx[0] == g.gn[0] - 1 || idx[1] == 0 || idx[1] == g.gn[1] - 1 || idx[2] == 0 || idx[2] == g.gn[2] - 1) continue;
+        const long long c = i3(g, idx[0], idx[1], idx[2]);
+        const double w[3] = {1.0 / TB(op.rdb[0], idx[0]), 1.0 / TB(op.rdb[1], idx[1]), 1.0 / TB(op.rdb[2], idx[2])};
+        const double tc = T[c], V = w[0] * w[1] * w[2];
+        acc[6] += (tc - Told[c]) / op.cdt[c] * V;
+        acc[7] += H[c] * V;
+        for (int a = 0; a < 3; a++) {
+            const double area = w[a == 0 ? 1 : 0] * w[a == 2 ? 1 : 2];
+            if (idx[a] == 1) acc[a] -= op.kk[a][c - g.s[a]] * (tc - T[c - g.s[a]]) * TB(g.rd[a], 0) * area;
+            if (idx[a] == g.gn[a] - 2) acc[a + 3] += op.kk[a][c] * (T[c + g.s[a]] - tc) * TB(g.rd[a], g.gn[a] - 2) * area;
+        }
+    }
+    block_sums3<8>(acc, part);
 }
 
 // ---- host <-> device layout ------------------------------------------------------------------------------------------
@@ -1220,6 +1253,9 @@ struct pl3_ctx {
     // heat
     Heat3 hop{}; bool hop_ready = false; double* hk[3] = {nullptr}; double *hT = nullptr, *hH = nullptr, *hcdt = nullptr, *hrho = nullptr, *hcp = nullptr;
     double* hbcv = nullptr; double* htab = nullptr; double* hvec[12] = {nullptr}; double hbcv_host[6] = {0};
+    // pl3_heat_set_wall_values: the planes of the heat walls, one device buffer (hwall_dev) that hwall.v points into, and the mask of the
+    // walls that have one; kept across pl3_heat_set_coeffs
+    Heat3Planes hwall{}; double* hwall_dev = nullptr; int hwall_mask = 0;
     int nu = 2, nu_fine = 0; bool nu_set = false; int coarse_sweeps = 12; double cheb_ratio = 6.0;      // nu_fine: sweeps on the finest level (0 = nu)
     // deflation of the pressure-anchor mode (see pl_solver.hip): the vector w = A^-1 u lives in vec[13], kept between solves
     double *dfl_y = nullptr, *dfl_t = nullptr; bool dfl_valid = false;
@@ -1345,7 +1381,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     pl3_step_free(&ctx->step3);
     pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
-    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow_dev}) if (q) (void)hipFree(q);
+    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow_dev, ctx->hwall_dev}) if (q) (void)hipFree(q);
     for (double* q : ctx->vec) if (q) (void)hipFree(q);
     for (double* q : ctx->hist) if (q) (void)hipFree(q);
     for (double* q : ctx->hk) if (q) (void)hipFree(q);
@@ -2626,6 +2662,72 @@ int pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const doub
     if (ctx->nranks > 1) return p3_fail(ctx, "device-source heat coefficients run on one rank");
     return heat_set3(ctx, mp, src, true, bc, bcvalue, tstep);
 }
+// Values or fluxes of the heat walls as profiles: values[w] is the plane of wall w of [z0, x0, y0, zL, xL, yL] over the wall's NODES, C-order
+// (n_p, n_q) (flow_axes3), or NULL for a wall that keeps its one value bcvalue[w]; all NULL clears the setting and frees the planes.  Kept
+// on the context like the Stokes wall settings; a rejected call changes nothing.  Entries at nodes another wall owns (z-walls own their
+// edges, then x-walls, then y-walls) are never read and are not looked at here.
+extern "C" int pl3_heat_set_wall_values(pl3_ctx* ctx, const double* const values[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_heat_set_wall_values: NULL context");
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_heat_set_wall_values: profiles over the heat walls run on one rank (this context has pl3_set_comm attached)");
+    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
+    size_t off[7] = {0};
+    int mask = 0;
+    for (int w = 0; w < 6; w++) {
+        int p, q;
+        flow_axes3(w, p, q);
+        const int np = ctx->gn[p], nq = ctx->gn[q], a = w % 3;
+        off[w + 1] = off[w] + (size_t)np * nq;
+        if (!values || !values[w]) continue;
+        mask |= 1 << w;
+        // the nodes of the plane that wall w owns: the walls of an axis before a in the order z, x, y own the first and last line along it
+        const int i0 = p < a ? 1 : 0, i1 = p < a ? np - 1 : np, j0 = q < a ? 1 : 0, j1 = q < a ? nq - 1 : nq;
+        for (int i = i0; i < i1; i++)
+            for (int j = j0; j < j1; j++) {
+                const double u = values[w][(size_t)i * nq + j];
+                if (!std::isfinite(u))
+                    return p3_fail(ctx, std::string("pl3_heat_set_wall_values: wall ") + names[w] + " has a non-finite entry [" + std::to_string(i) + ", " +
+                                            std::to_string(j) + "] = " + num_str3(u));
+            }
+    }
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (kernels in flight may still read the planes)
+    if (!mask) {
+        if (ctx->hwall_dev) { (void)hipFree(ctx->hwall_dev); ctx->hwall_dev = nullptr; }
+        ctx->hwall = Heat3Planes{}; ctx->hwall_mask = 0;
+        return 0;
+    }
+    if (!ctx->hwall_dev) P3_HIP(ctx, hipMalloc((void**)&ctx->hwall_dev, off[6] * sizeof(double)));
+    std::vector<double> all(off[6], 0.0);
+    for (int w = 0; w < 6; w++) if ((mask >> w) & 1) std::copy(values[w], values[w] + (off[w + 1] - off[w]), all.begin() + off[w]);
+    pl3_count_copy(ctx, off[6] * sizeof(double));
+    P3_HIP(ctx, hipMemcpy(ctx->hwall_dev, all.data(), off[6] * sizeof(double), hipMemcpyHostToDevice));
+    for (int w = 0; w < 6; w++) ctx->hwall.v[w] = (mask >> w) & 1 ? ctx->hwall_dev + off[w] : nullptr;
+    ctx->hwall_mask = mask;
+    return 0;
+}
+// mask: bit w set = wall w has a plane; values[w] (NULL: not wanted) receives that wall's plane as the device holds it
+extern "C" int pl3_heat_get_wall_values(pl3_ctx* ctx, int* mask, double* const values[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_heat_get_wall_values: NULL context");
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_heat_get_wall_values: profiles over the heat walls run on one rank (this context has pl3_set_comm attached)");
+    if (mask) *mask = ctx->hwall_mask;
+    if (!values || !ctx->hwall_mask) return 0;
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int w = 0; w < 6; w++) {
+        if (!values[w] || !((ctx->hwall_mask >> w) & 1)) continue;
+        int p, q;
+        flow_axes3(w, p, q);
+        const size_t bytes = (size_t)ctx->gn[p] * ctx->gn[q] * sizeof(double);
+        pl3_count_copy(ctx, bytes);
+        P3_HIP(ctx, hipMemcpy(values[w], ctx->hwall.v[w], bytes, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+// the right-hand side of the heat rows into rhs: the kernel without planes unless the context holds some
+static void heat_rhs3(pl3_ctx* ctx, double* rhs, int scaled) {
+    if (ctx->hwall_mask) launch3(ctx, ctx->hop.g, k3_heat_rhs<true>, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, ctx->hwall, rhs, scaled);
+    else launch3(ctx, ctx->hop.g, k3_heat_rhs<false>, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, Heat3Planes{}, rhs, scaled);
+}
 static int need_hvecs(pl3_ctx* ctx) {
     for (int v = 0; v < 12; v++) if (!ctx->hvec[v]) P3_TRY(dmal(ctx, &ctx->hvec[v], ctx->geom.d.vol));
     if (!ctx->part) { P3_TRY(dmal(ctx, &ctx->part, 11 * D3_BLOCKS)); P3_HIP(ctx, hipHostMalloc((void**)&ctx->hpart, 11 * D3_BLOCKS * sizeof(double))); }
@@ -2644,7 +2746,7 @@ extern "C" int pl3_heat_rhs(pl3_ctx* ctx, double* rhs) {
     if (!ctx->hop_ready) return p3_fail(ctx, "heat operator not set");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_TRY(need_hvecs(ctx));
-    launch3(ctx, ctx->hop.g, k3_heat_rhs, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, ctx->hvec[1], 0);
+    heat_rhs3(ctx, ctx->hvec[1], 0);
     P3_HIP(ctx, hipGetLastError());
     return download3(ctx, &ctx->hvec[1], 1, rhs);
 }
@@ -2660,11 +2762,10 @@ extern "C" int pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double
     P3_TRY(need_hvecs(ctx));
     if (rtol <= 0) rtol = 1e-12;
     if (maxit <= 0) maxit = 2000;
-    const G3& g = ctx->geom.d;
     P3_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     const Vec3 B = hvec(ctx, 10), X = hvec(ctx, 11);
     if (rhs) return p3_fail(ctx, "pl3_heat_solve: rhs must be NULL -- the system is solved for the operator's own right-hand side (pl3_heat_rhs)");
-    launch3(ctx, g, k3_heat_rhs, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, B.p, 1);
+    heat_rhs3(ctx, B.p, 1);
     ctx->napply = 0;
     Vec3 w[K_NW];
     for (int q = 0; q < K_NW; q++) w[q] = hvec(ctx, q);
@@ -2690,6 +2791,23 @@ extern "C" int pl3_get_solution(pl3_ctx* ctx, int which, double* out) {
     }
     if (!ctx->have_T) return p3_fail(ctx, "pl3_get_solution: no heat solution yet");
     return download3(ctx, &ctx->hvec[11], 1, out);
+}
+// The heat budget of a temperature field with the coefficients heat_set3 left on the device (include/pylamp_hip.h): out[0 .. 5] the heat
+// flow into the box through z0, x0, y0, zL, xL, yL, out[6] the storage rate, out[7] the source.  T == NULL: the solution of the last
+// pl3_heat_solve, still on the device.  One pass, fixed summation order.
+extern "C" int pl3_heat_budget(pl3_ctx* ctx, const double* T, double out[8]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_heat_budget: NULL context");
+    if (!out) return p3_fail(ctx, "pl3_heat_budget: NULL argument");
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_heat_budget: the heat budget runs on one rank (this context has pl3_set_comm attached)");
+    if (!ctx->hop_ready) return p3_fail(ctx, "pl3_heat_budget: heat operator not set (pl3_heat_set_coeffs)");
+    if (!T && !ctx->have_T) return p3_fail(ctx, "pl3_heat_budget: NULL T means the solution of the last heat solve, and no heat solve has run on this context");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_hvecs(ctx));
+    const double* field = ctx->hvec[11];
+    if (T) { P3_TRY(upload3(ctx, T, 1, &ctx->hvec[0])); field = ctx->hvec[0]; }
+    hipLaunchKernelGGL(k3_heat_budget, dim3(D3_BLOCKS), dim3(256), 0, ctx->stream, ctx->hop, field, (const double*)ctx->hT, (const double*)ctx->hH, ctx->part);
+    P3_HIP(ctx, hipGetLastError());
+    return sum_partials3(ctx, 8, 8, out);
 }
 
 // ---- strain rate, deviatoric stress and viscous dissipation (pl3_stokes_strain_fields; include/pylamp_hip.h) ------------

@@ -133,6 +133,55 @@ def wall_flows(flow, nx, who="3-D Stokes"):
     return out
 
 
+def wall_heat_values(values, nx, who="3-D heat"):
+    """values: the boundary values of the six heat walls [z0, x0, y0, zL, xL, yL] as profiles -- a list of six entries (or a dict by
+    wall name), each None (the wall keeps its one value of bcvalue), a scalar (the constant plane) or an array of shape (n_p, n_q) over
+    the wall's NODES, p < q the two other axes in z, x, y order: (nx, ny) on z-walls, (nz, ny) on x-walls, (nz, nx) on y-walls.  An
+    entry is the node's temperature on a FIXTEMP wall and k dT/dx_a along +a on a FIXFLOW wall, low or high (so the heat flow into the
+    box per area is -v on z0, x0, y0 and +v on zL, xL, yL).  None: no planes.  Returns six entries, None or a contiguous float64
+    array.  z-walls own their edges, then x-walls, then y-walls: entries at nodes another wall owns (rows 0 and nz - 1 of an x- or
+    y-wall's plane, also columns 0 and nx - 1 of a y-wall's) are never read and not checked; a non-finite entry that is read and a
+    wrong shape are rejected by name (the rule is in include/pylamp_hip.h at pl3_heat_set_wall_values)."""
+    if values is None:
+        return [None] * 6
+    if isinstance(values, dict):
+        for k in values:
+            if k not in WALL_NAMES:
+                raise Exception("%s: the heat wall values name a wall '%s' (the walls are %s)" % (who, k, ", ".join(WALL_NAMES)))
+        values = [values.get(k) for k in WALL_NAMES]
+    if not hasattr(values, "__len__") or len(values) != 6:
+        raise Exception("%s: the heat wall values need six entries [z0, x0, y0, zL, xL, yL] (got %s)"
+                        % (who, "%d" % len(values) if hasattr(values, "__len__") else type(values).__name__))
+    out = []
+    for w, f in enumerate(values):
+        if f is None:
+            out.append(None)
+            continue
+        a = w % 3
+        p, q = FLOW_AXES[a]
+        shp = (int(nx[p]), int(nx[q]))
+        try:
+            v = np.array(f, dtype=np.float64)
+        except (TypeError, ValueError):
+            v = None
+        if v is not None and v.ndim == 0:
+            v = np.full(shp, float(v))
+        if v is None or v.shape != shp:
+            raise Exception("%s: the values of heat wall %s need the shape (%s, %s) = %r or a scalar (got %s)"
+                            % (who, WALL_NAMES[w], _AXIS_N[p], _AXIS_N[q], shp, "an object that is no array" if v is None else v.shape))
+        read = np.ones(shp, dtype=bool)              # the nodes of the plane that this wall owns
+        if p < a:
+            read[0, :] = read[-1, :] = False
+        if q < a:
+            read[:, 0] = read[:, -1] = False
+        bad = np.argwhere(~np.isfinite(v) & read)
+        if bad.size:
+            i, j = (int(u) for u in bad[0])
+            raise Exception("%s: heat wall %s has a non-finite entry [%d, %d] = %r" % (who, WALL_NAMES[w], i, j, float(v[i, j])))
+        out.append(np.ascontiguousarray(v))
+    return out
+
+
 def wall_materials(material, nx, who="3-D markers"):
     """material: what the new tracers of the refill carry where a wall flow brings material into the box (the rule is in
     include/pylamp_hip.h at pl3_mic_set_inflow) -- None, or six entries [z0, x0, y0, zL, xL, yL], each None or a dict {column: value}
@@ -411,6 +460,23 @@ class Context3:
         self.check(self.lib.pl3_stokes_get_wall_flow(self.handle(), None, ptr))
         return out
 
+    def set_heat_wall_values(self, values):
+        """Profiles over the six heat walls of this context (wall_heat_values: six entries, each None, a scalar or the plane over the
+        wall's nodes; None or six None clear them); kept until set again, across makeDiffusionMatrix and the steps.  A wall with a plane
+        ignores its entry of bcvalue (include/pylamp_hip.h at pl3_heat_set_wall_values).  One rank."""
+        V = wall_heat_values(values, self.nx)
+        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in V])
+        self.check(self.lib.pl3_heat_set_wall_values(self.handle(), ptr))
+
+    def heat_wall_values(self):
+        """Six entries, None or the plane of the wall as the device holds it."""
+        mask = C.c_int()
+        self.check(self.lib.pl3_heat_get_wall_values(self.handle(), C.byref(mask), None))
+        out = [np.zeros((self.nx[FLOW_AXES[w % 3][0]], self.nx[FLOW_AXES[w % 3][1]])) if (mask.value >> w) & 1 else None for w in range(6)]
+        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in out])
+        self.check(self.lib.pl3_heat_get_wall_values(self.handle(), None, ptr))
+        return out
+
     def close(self):
         if self.h is not None:
             self._fin()
@@ -651,10 +717,14 @@ class HeatOperator3:
         return r
 
 
-def makeDiffusionMatrix(nx, grid, gridmp, f_T, f_k, f_Cp, f_rho, f_H, bc, bcvalue, tstep, device=0, ctx=None):
+def makeDiffusionMatrix(nx, grid, gridmp, f_T, f_k, f_Cp, f_rho, f_H, bc, bcvalue, tstep, device=0, ctx=None, wallvalues=None):
     """3-D counterpart of pylamp_diff.makeDiffusionMatrix: f_k = [kz, kx, ky] on the faces normal to z, x, y;
-    bc / bcvalue = [z0, x0, y0, zL, xL, yL]."""
+    bc / bcvalue = [z0, x0, y0, zL, xL, yL].  wallvalues (wall_heat_values): profiles over the walls, set on the context before the
+    right-hand side is formed -- per wall a plane (or a scalar) replaces bcvalue[w], None keeps it, six None clear the context's planes;
+    wallvalues=None leaves the context's planes as they are."""
     ctx = ctx or Context3(nx, grid, device)
+    if wallvalues is not None:
+        ctx.set_heat_wall_values(wallvalues)
     shp = ctx.nx
     arrs = [_f3(a, shp) for a in (f_T, f_k[0], f_k[1], f_k[2], f_Cp, f_rho, f_H)]
     mp = [np.ascontiguousarray(m, dtype=np.float64) for m in gridmp]
@@ -684,6 +754,28 @@ def solve_heat(A, rtol=1e-12, maxit=2000, resident=False):
     ctx.check(ctx.lib.pl3_heat_solve(ctx.handle(), None, _lib.dptr(x), float(rtol), int(maxit), C.byref(st)))
     A.last_stats = st.as_dict()
     return x
+
+
+def _budget(ctx, T):
+    out = np.zeros(8)
+    ctx.check(ctx.lib.pl3_heat_budget(ctx.handle(), None if T is None else _lib.dptr(T), _lib.dptr(out)))
+    wall = [float(v) for v in out[:6]]
+    storage, source = float(out[6]), float(out[7])
+    return dict(wall_flow=wall, storage=storage, source=source, imbalance=storage - source - sum(wall))
+
+
+def heat_budget(A, T=None):
+    """The heat budget [W] of the temperature field T (nz nx ny values) under the operator A: wall_flow, the heat flow INTO the box
+    through [z0, x0, y0, zL, xL, yL]; storage, rho Cp (T - T_old) / tstep summed over the control volumes of the interior nodes;
+    source, H summed likewise; imbalance = storage - source - sum(wall_flow), which vanishes for a T that satisfies the interior rows.
+    T=None: the solution of the last solve_heat(A), still on the device.  The sums are those of the discrete rows (include/pylamp_hip.h
+    at pl3_heat_budget); the wall sums cover the control areas of the interior nodes, not the rim of the wall.  One rank."""
+    ctx = A._ctx
+    if T is not None:
+        T = _lib.f64(T).reshape(-1)
+        if T.size != A.shape[0]:
+            raise Exception("dimension mismatch")
+    return _budget(ctx, T)
 
 
 class VirtualCluster3:
@@ -1002,6 +1094,10 @@ class Options3:
         self.bcinflow = None
         self.bcheat = [BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW, BC_TYPE_FIXTEMP, BC_TYPE_FIXFLOW, BC_TYPE_FIXFLOW]
         self.bcheatvals = [273.0, 0.0, 0.0, 1623.0, 0.0, 0.0]
+        # beyond the reference: the heat boundary values as profiles over the walls (wall_heat_values: per wall None, a scalar or the
+        # plane over the wall's nodes -- temperatures on a FIXTEMP wall, k dT/dx_a along +a on a FIXFLOW wall); a wall with a plane
+        # ignores its entry of bcheatvals (None: every wall takes its entry of bcheatvals)
+        self.bcheatprofile = None
         self.stokes_rtol, self.stokes_maxit = DEFAULT_RTOL, DEFAULT_MAXIT
         self.heat_rtol, self.heat_maxit = 1e-12, 2000
         self.grav = None
@@ -1057,7 +1153,9 @@ class Simulation3:
     lie between the wall and every resident of their cell take the wall's values in the columns it names, step() / advect() / refill()
     report them as ninflow, and an inflow cell that ran empty gets finite values in those columns (a scattered column the material
     leaves out is still NaN there and step() raises its NaN error); a prescribed TR_TMP is a tracer temperature like any other, so
-    with heat diffusion on it enters the next step's temperature scatter, while the heat solve keeps its one boundary value per wall;
+    with heat diffusion on it enters the next step's temperature scatter, and the heat solve of the same step can hold the matching patch of the wall hot: Options3.bcheatprofile /
+    set_heat_profile give its boundary values as profiles over the walls (wall_heat_values states the format), heat_budget() the heat
+    flow through the six walls, the storage rate and the source of the last step's heat solve;
     the net flux must vanish (wall_fluxes); Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default,
     move them by 2/3 of that).  Not built: surface stabilisation, several ranks -- each is rejected with an error that names it."""
 
@@ -1102,7 +1200,10 @@ class Simulation3:
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
         self.bcstokesflow = self._checked_flow(o.bcstokesflow, "Simulation3: Options3.bcstokesflow")
         wall_materials(o.bcinflow, self.nx, "Simulation3: Options3.bcinflow")
+        self.bcheatprofile = self._checked_heat_profile(o.bcheatprofile, "Simulation3: Options3.bcheatprofile")
         self.ctx = Context3(self.nx, self.grid, device)
+        if self.bcheatprofile is not None:
+            self.ctx.set_heat_wall_values(self.bcheatprofile)      # once: the context keeps the planes for both step paths
         self.bcstokesvel = wall_velocities(o.bcstokesvel, self.bcstokes, "Simulation3: Options3.bcstokesvel")
         self.ctx.set_stokes_walls(self.bcstokes)        # the resident step and the device advection velocity read them from the context
         self.ctx.set_wall_velocity(self.bcstokesvel)
@@ -1168,6 +1269,32 @@ class Simulation3:
         ms = wall_materials(material, self.nx, "Simulation3.set_inflow_material")
         self.ctx.set_inflow_material(material)
         self._inflow = any(m is not None for m in ms)
+
+    def _checked_heat_profile(self, values, who):
+        """wall_heat_values, or None where no wall has a plane; a profile needs the heat solve."""
+        V = wall_heat_values(values, self.nx, who)
+        if all(a is None for a in V):
+            return None
+        if not self.opt.do_heatdiff:
+            raise Exception("%s: a profile over the heat walls needs the heat solve, Options3.do_heatdiff = True" % who)
+        return V
+
+    def set_heat_profile(self, values):
+        """New profiles over the six heat walls (wall_heat_values; None: every wall takes its entry of Options3.bcheatvals again) from the next
+        step on: a hot patch can move or switch on.  The kinds stay those of Options3.bcheat."""
+        V = self._checked_heat_profile(values, "Simulation3.set_heat_profile")
+        if V is not None or self.bcheatprofile is not None:
+            self.ctx.set_heat_wall_values(V)
+        self.bcheatprofile = V
+
+    def heat_budget(self):
+        """The heat budget of the last step's heat solve (heat_budget: wall_flow into the box through the six walls, storage, source
+        and imbalance, in watts), from the temperature and the coefficients the step left on the device."""
+        if not self.opt.do_heatdiff:
+            raise Exception("Simulation3.heat_budget: the heat solve is off (Options3.do_heatdiff = False)")
+        if self.last is None:
+            raise Exception("Simulation3.heat_budget: no step has run yet")
+        return _budget(self.ctx, None)
 
     # -- tracer state ------------------------------------------------------------------------------------------------
     def _lib_call(self, name, *args):
