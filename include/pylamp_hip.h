@@ -413,10 +413,10 @@ int  pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]);
  *  - identity rows, pressure rows and all coarse levels are unchanged: corrections are homogeneous. */
 int  pl3_stokes_set_wall_velocity(pl3_ctx* ctx, const double vel[18]);
 int  pl3_stokes_get_wall_velocity(pl3_ctx* ctx, double vel[18]);
-/* Flow through walls.  For wall w of [z0, x0, y0, zL, xL, yL] with axis a, let p < q be the two other axes in z, x, y order.  flow[w]
- * is an array Un_w of (n_p - 1) x (n_q - 1) doubles, entry i (n_q - 1) + j the wall-normal velocity on the wall face between the nodes
- * i, i + 1 along p and j, j + 1 along q -- where v_a lives on that wall plane -- as the component along +a (the convention of
- * pl3_stokes_set_wall_velocity): positive is inflow on z0, x0, y0 and outflow on zL, xL, yL.  flow[w] == NULL: no flow through wall w;
+/* Flow through walls.  flow[w] is the plane Un_w of wall w over its FACES (the layout of every wall plane -- wall order, the axes p < q,
+ * faces and nodes, C order, who owns the edges -- is in DESIGN.md section 6c, "Wall planes"): the wall-normal velocity on each face --
+ * where v_a lives on that wall plane -- as the component along +a (the convention of pl3_stokes_set_wall_velocity): positive is inflow
+ * on z0, x0, y0 and outflow on zL, xL, yL.  flow[w] == NULL: no flow through wall w;
  * all NULL (or flow == NULL) clears the setting, the state at creation.  A wall of either kind may carry a flow; a NOSLIP wall keeps
  * its tangential velocity, possibly zero.  The indices are GLOBAL: every rank of a pl3_set_comm decomposition is given the same six
  * planes.  The state belongs to the context, survives pl3_stokes_set_coeffs and pl3_stokes_set_walls, and is read by
@@ -534,9 +534,8 @@ int  pl3_heat_rhs(pl3_ctx* ctx, double* rhs);
 int  pl3_heat_solve(pl3_ctx* ctx, const double* rhs, double* x, double rtol, int maxit, pl_solve_stats* stats);
 /* solution of the last solve of this context: which = 0 Stokes (nz, nx, ny, 4), 1 heat (nz, nx, ny) */
 int  pl3_get_solution(pl3_ctx* ctx, int which, double* out);
-/* Heat walls with a profile (one rank).  For wall w of [z0, x0, y0, zL, xL, yL] with axis a, let p < q be the two other axes in z, x, y
- * order.  values[w] is a plane over the wall's NODES, n_p x n_q doubles in C order -- (nx, ny) on z-walls, (nz, ny) on x-walls, (nz, nx)
- * on y-walls -- entry i n_q + j belonging to the node with index i along p and j along q.  values[w] == NULL: the wall keeps the one
+/* Heat walls with a profile (one rank).  values[w] is the plane of wall w over its NODES ("Wall planes").
+ * values[w] == NULL: the wall keeps the one
  * value bcvalue[w] of pl3_heat_set_coeffs; values == NULL or six NULL pointers clear the setting and free the planes, the state at
  * creation.  The state belongs to the context, survives pl3_heat_set_coeffs and is read whenever the right-hand side is formed:
  * pl3_heat_rhs, pl3_heat_solve and the heat solve of pl3_resident_step, which ignores cfg->bcheatvals[w] for a wall that has a plane.
@@ -544,9 +543,7 @@ int  pl3_get_solution(pl3_ctx* ctx, int which, double* out);
  *    FIXFLOW: k dT/dx_a at the node, the derivative taken along +a on the low AND on the high wall.  So a positive entry is heat LEAVING
  *    through z0, x0, y0 (the temperature rises into the box) and heat ENTERING through zL, xL, yL: the heat flow into the box per area
  *    is -v on a low wall and +v on a high wall.  The row scaling of the solve is unchanged.
- *  - Ownership is that of the rows: z-walls own their edges, then x-walls, then y-walls.  Entries of a plane at nodes another wall owns
- *    are never read and not checked: rows i = 0 and i = nz - 1 of an x- or y-wall's plane, and columns j = 0 and j = nx - 1 of a
- *    y-wall's plane as well.
+ *  - Entries of a plane at nodes another wall owns (the ownership of the rows, as in "Wall planes") are never read and not checked.
  *  - Without planes the right-hand side is formed by the kernel it was formed by before.
  * Errors, a rejected call changing nothing: a NULL context; a non-finite entry that is read (names the wall and the indices); a context
  * with pl3_set_comm attached. */
@@ -701,9 +698,8 @@ int  pl3_resident_times(pl3_ctx* ctx, double ms[4]);
  * Opt-in per wall, default none = every kernel and result as without it.  An overlay on the refill above: positions, IDs, stored
  * velocities, counts, the sort, the census and the deletion are bit for bit what they are without a material; only field values of
  * new tracers change.  Per wall w of [z0, x0, y0, zL, xL, yL] (axis a = w mod 3, p < q the two other axes in z, x, y order) a context
- * may hold a set of tracer columns -- bits 0 ... 11 of `columns`; TR__ID, column 12, is never allowed -- and one plane per column,
- * (n_p - 1) x (n_q - 1) doubles over the wall's faces, entry i (n_q - 1) + j: the layout and the indices of the planes of
- * pl3_stokes_set_wall_flow.  `values` holds popcount(columns) planes in ascending column order.
+ * may hold a set of tracer columns -- bits 0 ... 11 of `columns`; TR__ID, column 12, is never allowed -- and one plane per column over
+ * the wall's faces: the planes of pl3_stokes_set_wall_flow ("Wall planes").  `values` holds popcount(columns) planes in ascending column order.
  * In every sort that refills (pl3_resident_refill, pl3_resident_advect, pl3_resident_step) a refilled cell c = (i_z, i_x, i_y) is an
  * INFLOW CELL of wall w when (a) w has a material, (b) the cell touches w: its index along a is 0 for z0, x0, y0 and n_a - 2 for zL,
  * xL, yL, and (c) the context's wall flow at the time of the sort is non-zero and inward at the cell's own face (i_p, i_q) of w:

@@ -16,6 +16,7 @@
 #include "pl_internal.h"
 #include "pl_mic3.h"
 #include "pl_step3.h"
+#include "pl_walls3.h"
 #include "pl_x0.h"
 #include <algorithm>
 #include <cmath>
@@ -1243,9 +1244,8 @@ struct pl3_ctx {
     double *es = nullptr, *en = nullptr, *rho = nullptr; Op3 op{}; bool op_ready = false;
     int noslip = 0;                 // pl3_stokes_set_walls: bit w of [z0, x0, y0, zL, xL, yL] set = no-slip; kept across pl3_stokes_set_coeffs
     Pl3WallVel wallvel{};           // pl3_stokes_set_wall_velocity: U_w = (Uz, Ux, Uy) per wall and the mask of the moving ones; kept likewise
-    // pl3_stokes_set_wall_flow: the six wall planes of the through-flow, one device buffer (flow_dev) that wallflow.un points into, and
-    // their host copies; kept likewise
-    Pl3WallFlow wallflow{}; double* flow_dev = nullptr; std::vector<double> flow_host[6];
+    // pl3_stokes_set_wall_flow: the six wall planes of the through-flow (over faces) and what the kernels take of them; kept likewise
+    Walls3Planes flow; Pl3WallFlow wallflow{};
     std::vector<Lev3*> levels;
     double* vec[14] = {nullptr};                // BiCGStab work vectors: 4 consecutive arrays each (svec)
     double* part = nullptr; double* hpart = nullptr;
@@ -1253,9 +1253,8 @@ struct pl3_ctx {
     // heat
     Heat3 hop{}; bool hop_ready = false; double* hk[3] = {nullptr}; double *hT = nullptr, *hH = nullptr, *hcdt = nullptr, *hrho = nullptr, *hcp = nullptr;
     double* hbcv = nullptr; double* htab = nullptr; double* hvec[12] = {nullptr}; double hbcv_host[6] = {0};
-    // pl3_heat_set_wall_values: the planes of the heat walls, one device buffer (hwall_dev) that hwall.v points into, and the mask of the
-    // walls that have one; kept across pl3_heat_set_coeffs
-    Heat3Planes hwall{}; double* hwall_dev = nullptr; int hwall_mask = 0;
+    // pl3_heat_set_wall_values: the planes of the heat walls (over nodes) and what the kernels take of them; kept across pl3_heat_set_coeffs
+    Walls3Planes hplanes; Heat3Planes hwall{};
     int nu = 2, nu_fine = 0; bool nu_set = false; int coarse_sweeps = 12; double cheb_ratio = 6.0;      // nu_fine: sweeps on the finest level (0 = nu)
     // deflation of the pressure-anchor mode (see pl_solver.hip): the vector w = A^-1 u lives in vec[13], kept between solves
     double *dfl_y = nullptr, *dfl_t = nullptr; bool dfl_valid = false;
@@ -1281,6 +1280,66 @@ static int p3_fail(pl3_ctx* ctx, const std::string& m) { if (ctx) ctx->err = m; 
 void pl3_count_copy(pl3_ctx* ctx, size_t bytes) {
     const int c = bytes >= sizeof(double) * (size_t)ctx->gn[0] * ctx->gn[1] * ctx->gn[2] ? 0 : 2;
     ctx->xfer[c]++; ctx->xfer[c + 1] += (int64_t)bytes;
+}
+static std::string num_str3(double v) {          // the shortest decimal that reads back as v
+    char b[40];
+    for (int p = 15; p <= 17; p++) { snprintf(b, sizeof b, "%.*g", p, v); if (strtod(b, nullptr) == v) break; }
+    return b;
+}
+// The one path of the planes over the walls (pl_walls3.h).  in[w]: the plane of wall w over its nodes or its faces, C-order, or NULL for
+// none.  Every plane is checked first -- all entries, or with `owned` only those at nodes that wall w owns (the walls of an axis before a
+// in the order z, x, y own the first and last line along it) -- then `also` (NULL: nothing) has its say; only then the stream is
+// synchronised (kernels in flight may still read the planes), all six planes go up in one copy, and mask and offsets are committed: a
+// rejected call changes nothing.  No plane at all clears: the buffer is freed.
+static int planes3_set(pl3_ctx* ctx, Walls3Planes& P, const char* entry, const char* noun, bool nodes, bool owned, const double* const in[6],
+                       int (*also)(pl3_ctx*, const double* const[6]) = nullptr) {
+    Walls3Planes N;
+    for (int w = 0; w < 6; w++) {
+        N.off[w + 1] = N.off[w] + walls3_count(ctx->gn, w, nodes);
+        if (!in || !in[w]) continue;
+        N.mask |= 1 << w;
+        int p, q;
+        const int a = w % 3;
+        walls3_axes(a, p, q);
+        const int np = ctx->gn[p] - (nodes ? 0 : 1), nq = ctx->gn[q] - (nodes ? 0 : 1);
+        const int i0 = owned && p < a ? 1 : 0, j0 = owned && q < a ? 1 : 0;
+        for (int i = i0; i < np - i0; i++)
+            for (int j = j0; j < nq - j0; j++) {
+                const double u = in[w][(size_t)i * nq + j];
+                if (!std::isfinite(u))
+                    return p3_fail(ctx, std::string(entry) + ": wall " + walls3_names[w] + " has a non-finite " + noun + " [" + std::to_string(i) + ", " +
+                                            std::to_string(j) + "] = " + num_str3(u));
+            }
+    }
+    if (also) P3_TRY(also(ctx, in));
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (!N.mask) {
+        if (P.dev) (void)hipFree(P.dev);
+        P = Walls3Planes{};
+        return 0;
+    }
+    if (!P.dev) P3_HIP(ctx, hipMalloc((void**)&P.dev, N.off[6] * sizeof(double)));      // (P.mask is 0 here: nothing points into it yet)
+    N.dev = P.dev;
+    std::vector<double> all(N.off[6], 0.0);
+    for (int w = 0; w < 6; w++) if ((N.mask >> w) & 1) std::copy(in[w], in[w] + N.count(w), all.begin() + N.off[w]);
+    pl3_count_copy(ctx, N.off[6] * sizeof(double));
+    P3_HIP(ctx, hipMemcpy(N.dev, all.data(), N.off[6] * sizeof(double), hipMemcpyHostToDevice));
+    P = N;
+    return 0;
+}
+// mask: bit w set = wall w has a plane; out[w] (NULL: not wanted) receives that wall's plane as the device holds it
+static int planes3_get(pl3_ctx* ctx, const Walls3Planes& P, int* mask, double* const out[6]) {
+    if (mask) *mask = P.mask;
+    if (!out || !P.mask) return 0;
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int w = 0; w < 6; w++) {
+        if (!out[w] || !P.plane(w)) continue;
+        pl3_count_copy(ctx, P.count(w) * sizeof(double));
+        P3_HIP(ctx, hipMemcpy(out[w], P.plane(w), P.count(w) * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 static Vec3 svec(pl3_ctx* ctx, int v) { return Vec3{ctx->vec[v], 4, &ctx->geom.d}; }          // Stokes work vector v
 static Vec3 hvec(pl3_ctx* ctx, int v) { return Vec3{ctx->hvec[v], 1, &ctx->geom.d}; }         // heat work vector v
@@ -1381,7 +1440,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     pl3_step_free(&ctx->step3);
     pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
-    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow_dev, ctx->hwall_dev}) if (q) (void)hipFree(q);
+    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow.dev, ctx->hplanes.dev}) if (q) (void)hipFree(q);
     for (double* q : ctx->vec) if (q) (void)hipFree(q);
     for (double* q : ctx->hist) if (q) (void)hipFree(q);
     for (double* q : ctx->hk) if (q) (void)hipFree(q);
@@ -1434,7 +1493,8 @@ static int halo3(pl3_ctx* ctx, const G3& g, double* const* arr, int na) {
     ctx->halo_calls++;
     for (int a = 0; a < 3; a++) {
         if (ctx->P[a] == 1) continue;
-        const int A1 = a == 0 ? 1 : 0, A2 = a == 2 ? 1 : 2;
+        int A1, A2;
+        walls3_axes(a, A1, A2);
         const long long cnt = (long long)na * (g.n[A1] + 2) * (g.n[A2] + 2);
         if (ctx->hbuf_n < (size_t)(4 * cnt)) {
             if (ctx->hbuf) { P3_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->hbuf); ctx->hbuf = nullptr; }
@@ -1564,27 +1624,21 @@ extern "C" int pl3_stokes_set_wall_rows(pl3_ctx* ctx, int slaved) {
 static void history_clear3(pl3_ctx* ctx) { ctx->warm_held = 0; for (double& d : ctx->dt_hist) d = 0.0; }
 // bc = [z0, x0, y0, zL, xL, yL], each PL_BC_FREESLIP or PL_BC_NOSLIP.  A change of a wall's kind clears the warm-start history.  Kept on the context (which starts all free-slip) across
 // pl3_stokes_set_coeffs; read by the solves, pl3_resident_step and pl3_advection_velocity.
-static std::string num_str3(double v) {          // the shortest decimal that reads back as v
-    char b[40];
-    for (int p = 15; p <= 17; p++) { snprintf(b, sizeof b, "%.*g", p, v); if (strtod(b, nullptr) == v) break; }
-    return b;
-}
 static std::string wallvel_str3(const double* u) { return "(" + num_str3(u[0]) + ", " + num_str3(u[1]) + ", " + num_str3(u[2]) + ")"; }
 extern "C" int pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]) {
     if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_walls: NULL context");
     if (!bc) return p3_fail(ctx, "pl3_stokes_set_walls: NULL argument");
-    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
     int m = 0;
     for (int w = 0; w < 6; w++) {
         if (bc[w] == PL_BC_NOSLIP) m |= 1 << w;
         else if (bc[w] != PL_BC_FREESLIP)
-            return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + names[w] + " has kind " + std::to_string(bc[w]) +
+            return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + walls3_names[w] + " has kind " + std::to_string(bc[w]) +
                                     ": a 3-D Stokes wall is FREESLIP (1) or NOSLIP (0)");
     }
     for (int w = 0; w < 6; w++)
         if (((ctx->wallvel.moving >> w) & 1) && !((m >> w) & 1)) {
             const double* u = ctx->wallvel.u + 3 * w;
-            return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + names[w] + " moves with velocity " + wallvel_str3(u) +
+            return p3_fail(ctx, std::string("pl3_stokes_set_walls: wall ") + walls3_names[w] + " moves with velocity " + wallvel_str3(u) +
                                     " and cannot become FREESLIP: only a NOSLIP wall carries a velocity (set it to zero first)");
         }
     if (m != ctx->noslip) history_clear3(ctx);          // solutions of other wall kinds are no start for these
@@ -1598,12 +1652,11 @@ extern "C" int pl3_stokes_set_walls(pl3_ctx* ctx, const int bc[6]) {
 extern "C" int pl3_stokes_set_wall_velocity(pl3_ctx* ctx, const double vel[18]) {
     if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_wall_velocity: NULL context");
     if (!vel) return p3_fail(ctx, "pl3_stokes_set_wall_velocity: NULL argument");
-    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
     static const char* const comp[3] = {"Uz", "Ux", "Uy"};
     Pl3WallVel mv{};
     for (int w = 0; w < 6; w++) {
         const double* u = vel + 3 * w;
-        const std::string who = std::string("pl3_stokes_set_wall_velocity: wall ") + names[w];
+        const std::string who = std::string("pl3_stokes_set_wall_velocity: wall ") + walls3_names[w];
         for (int q = 0; q < 3; q++)
             if (!std::isfinite(u[q])) return p3_fail(ctx, who + " has a non-finite velocity component " + comp[q] + " = " + num_str3(u[q]));
         if (u[w % 3] != 0.0)
@@ -1624,32 +1677,19 @@ extern "C" int pl3_stokes_get_wall_velocity(pl3_ctx* ctx, double vel[18]) {
     for (int e = 0; e < 18; e++) vel[e] = ctx->wallvel.u[e];
     return 0;
 }
-// Flow through the walls: flow[w] is the plane of wall w of [z0, x0, y0, zL, xL, yL], (n_p - 1, n_q - 1) wall-normal velocities along +a on
-// the faces of the wall (p < q the two other axes in z, x, y order), or NULL for no flow; all NULL clears the setting.  All six walls are
-// set in one call because the net flux must vanish: the anchor cell would absorb it as a divergence.  Kept on the context like the kinds
-// and the velocities; a rejected call changes nothing.
-static void flow_axes3(int w, int& p, int& q) { const int a = w % 3; p = a == 0 ? 1 : 0; q = a == 2 ? 1 : 2; }
-extern "C" int pl3_stokes_set_wall_flow(pl3_ctx* ctx, const double* const flow[6]) {
-    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_wall_flow: NULL context");
-    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
-    size_t off[7] = {0};
+// the net flux of the six flow planes (finite: planes3_set has looked), summed in long double by wall, row and column
+static int flow_balance3(pl3_ctx* ctx, const double* const flow[6]) {
     long double flux[6] = {0, 0, 0, 0, 0, 0}, phi = 0.0L, tot = 0.0L;
-    int mask = 0;
     for (int w = 0; w < 6; w++) {
-        int p, q;
-        flow_axes3(w, p, q);
-        const int np = ctx->gn[p] - 1, nq = ctx->gn[q] - 1;
-        off[w + 1] = off[w] + (size_t)np * nq;
         if (!flow || !flow[w]) continue;
-        mask |= 1 << w;
+        int p, q;
+        walls3_axes(w % 3, p, q);
+        const int np = ctx->gn[p] - 1, nq = ctx->gn[q] - 1;
         const std::vector<double>&cp = ctx->gcoord[p], &cq = ctx->gcoord[q];
         long double f = 0.0L;
         for (int i = 0; i < np; i++)
             for (int j = 0; j < nq; j++) {
                 const double u = flow[w][(size_t)i * nq + j];
-                if (!std::isfinite(u))
-                    return p3_fail(ctx, std::string("pl3_stokes_set_wall_flow: wall ") + names[w] + " has a non-finite flow entry [" + std::to_string(i) +
-                                            ", " + std::to_string(j) + "] = " + num_str3(u));
                 const long double area = ((long double)cp[i + 1] - (long double)cp[i]) * ((long double)cq[j + 1] - (long double)cq[j]);
                 f += (long double)u * area;
                 tot += std::fabs((long double)u) * area;
@@ -1659,43 +1699,26 @@ extern "C" int pl3_stokes_set_wall_flow(pl3_ctx* ctx, const double* const flow[6
     }
     if (std::fabs(phi) > 1e-10L * tot) {
         std::string six;
-        for (int w = 0; w < 6; w++) six += std::string(w ? ", " : "") + names[w] + " " + num_str3((double)flux[w]);
+        for (int w = 0; w < 6; w++) six += std::string(w ? ", " : "") + walls3_names[w] + " " + num_str3((double)flux[w]);
         return p3_fail(ctx, "pl3_stokes_set_wall_flow: the net flux through the walls is " + num_str3((double)phi) + " (inflow positive), more than 1e-10 of the sum " +
                                 num_str3((double)tot) + " of |Un| over the wall faces: the walls must balance, or the pressure anchor cell absorbs the rest as a "
                                 "divergence; fluxes into the box: " + six);
     }
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    if (mask && !ctx->flow_dev) P3_HIP(ctx, hipMalloc((void**)&ctx->flow_dev, off[6] * sizeof(double)));
-    if (mask) {
-        std::vector<double> all(off[6], 0.0);
-        for (int w = 0; w < 6; w++) if ((mask >> w) & 1) std::copy(flow[w], flow[w] + (off[w + 1] - off[w]), all.begin() + off[w]);
-        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (kernels in flight may still read the planes)
-        pl3_count_copy(ctx, off[6] * sizeof(double));
-        P3_HIP(ctx, hipMemcpy(ctx->flow_dev, all.data(), off[6] * sizeof(double), hipMemcpyHostToDevice));
-    }
-    Pl3WallFlow fl{};
-    fl.mask = mask;
-    for (int w = 0; w < 6; w++) {
-        if ((mask >> w) & 1) { fl.un[w] = ctx->flow_dev + off[w]; ctx->flow_host[w].assign(flow[w], flow[w] + (off[w + 1] - off[w])); }
-        else ctx->flow_host[w].clear();
-    }
-    ctx->wallflow = fl;
     return 0;
 }
-// mask: bit w set = wall w carries a flow; flow[w] (NULL: not wanted) receives that wall's plane as the device holds it
+// Flow through the walls: flow[w] is the plane of wall w over its faces ("Wall planes"), wall-normal velocities
+// along +a, or NULL for no flow; all NULL clears the setting.  All six walls are set in one call because the net flux must vanish: the
+// anchor cell would absorb it as a divergence.  Kept on the context like the kinds and the velocities; a rejected call changes nothing.
+extern "C" int pl3_stokes_set_wall_flow(pl3_ctx* ctx, const double* const flow[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_wall_flow: NULL context");
+    P3_TRY(planes3_set(ctx, ctx->flow, "pl3_stokes_set_wall_flow", "flow entry", false, false, flow, flow_balance3));
+    ctx->wallflow.mask = ctx->flow.mask;
+    for (int w = 0; w < 6; w++) ctx->wallflow.un[w] = ctx->flow.plane(w);
+    return 0;
+}
 extern "C" int pl3_stokes_get_wall_flow(pl3_ctx* ctx, int* mask, double* const flow[6]) {
     if (!ctx) return p3_fail(nullptr, "pl3_stokes_get_wall_flow: NULL context");
-    if (mask) *mask = ctx->wallflow.mask;
-    if (!flow || !ctx->wallflow.mask) return 0;
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int w = 0; w < 6; w++) {
-        if (!flow[w] || !((ctx->wallflow.mask >> w) & 1)) continue;
-        const size_t bytes = ctx->flow_host[w].size() * sizeof(double);
-        pl3_count_copy(ctx, bytes);
-        P3_HIP(ctx, hipMemcpy(flow[w], ctx->wallflow.un[w], bytes, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return planes3_get(ctx, ctx->flow, mask, flow);
 }
 extern "C" int pl3_stokes_get_scaling(pl3_ctx* ctx, double* kc, double* kb) {
     if (!ctx->op_ready) return p3_fail(ctx, "stokes operator not set");
@@ -2662,70 +2685,24 @@ int pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const doub
     if (ctx->nranks > 1) return p3_fail(ctx, "device-source heat coefficients run on one rank");
     return heat_set3(ctx, mp, src, true, bc, bcvalue, tstep);
 }
-// Values or fluxes of the heat walls as profiles: values[w] is the plane of wall w of [z0, x0, y0, zL, xL, yL] over the wall's NODES, C-order
-// (n_p, n_q) (flow_axes3), or NULL for a wall that keeps its one value bcvalue[w]; all NULL clears the setting and frees the planes.  Kept
-// on the context like the Stokes wall settings; a rejected call changes nothing.  Entries at nodes another wall owns (z-walls own their
-// edges, then x-walls, then y-walls) are never read and are not looked at here.
+// Values or fluxes of the heat walls as profiles: values[w] is the plane of wall w over its NODES ("Wall planes"), or
+// NULL for a wall that keeps its one value bcvalue[w]; all NULL clears the setting and frees the planes.  Kept on the context like the
+// Stokes wall settings; a rejected call changes nothing.  Entries at nodes another wall owns are never read and are not looked at here.
 extern "C" int pl3_heat_set_wall_values(pl3_ctx* ctx, const double* const values[6]) {
     if (!ctx) return p3_fail(nullptr, "pl3_heat_set_wall_values: NULL context");
     if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_heat_set_wall_values: profiles over the heat walls run on one rank (this context has pl3_set_comm attached)");
-    static const char* const names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
-    size_t off[7] = {0};
-    int mask = 0;
-    for (int w = 0; w < 6; w++) {
-        int p, q;
-        flow_axes3(w, p, q);
-        const int np = ctx->gn[p], nq = ctx->gn[q], a = w % 3;
-        off[w + 1] = off[w] + (size_t)np * nq;
-        if (!values || !values[w]) continue;
-        mask |= 1 << w;
-        // the nodes of the plane that wall w owns: the walls of an axis before a in the order z, x, y own the first and last line along it
-        const int i0 = p < a ? 1 : 0, i1 = p < a ? np - 1 : np, j0 = q < a ? 1 : 0, j1 = q < a ? nq - 1 : nq;
-        for (int i = i0; i < i1; i++)
-            for (int j = j0; j < j1; j++) {
-                const double u = values[w][(size_t)i * nq + j];
-                if (!std::isfinite(u))
-                    return p3_fail(ctx, std::string("pl3_heat_set_wall_values: wall ") + names[w] + " has a non-finite entry [" + std::to_string(i) + ", " +
-                                            std::to_string(j) + "] = " + num_str3(u));
-            }
-    }
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (kernels in flight may still read the planes)
-    if (!mask) {
-        if (ctx->hwall_dev) { (void)hipFree(ctx->hwall_dev); ctx->hwall_dev = nullptr; }
-        ctx->hwall = Heat3Planes{}; ctx->hwall_mask = 0;
-        return 0;
-    }
-    if (!ctx->hwall_dev) P3_HIP(ctx, hipMalloc((void**)&ctx->hwall_dev, off[6] * sizeof(double)));
-    std::vector<double> all(off[6], 0.0);
-    for (int w = 0; w < 6; w++) if ((mask >> w) & 1) std::copy(values[w], values[w] + (off[w + 1] - off[w]), all.begin() + off[w]);
-    pl3_count_copy(ctx, off[6] * sizeof(double));
-    P3_HIP(ctx, hipMemcpy(ctx->hwall_dev, all.data(), off[6] * sizeof(double), hipMemcpyHostToDevice));
-    for (int w = 0; w < 6; w++) ctx->hwall.v[w] = (mask >> w) & 1 ? ctx->hwall_dev + off[w] : nullptr;
-    ctx->hwall_mask = mask;
+    P3_TRY(planes3_set(ctx, ctx->hplanes, "pl3_heat_set_wall_values", "entry", true, true, values));
+    for (int w = 0; w < 6; w++) ctx->hwall.v[w] = ctx->hplanes.plane(w);
     return 0;
 }
-// mask: bit w set = wall w has a plane; values[w] (NULL: not wanted) receives that wall's plane as the device holds it
 extern "C" int pl3_heat_get_wall_values(pl3_ctx* ctx, int* mask, double* const values[6]) {
     if (!ctx) return p3_fail(nullptr, "pl3_heat_get_wall_values: NULL context");
     if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_heat_get_wall_values: profiles over the heat walls run on one rank (this context has pl3_set_comm attached)");
-    if (mask) *mask = ctx->hwall_mask;
-    if (!values || !ctx->hwall_mask) return 0;
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int w = 0; w < 6; w++) {
-        if (!values[w] || !((ctx->hwall_mask >> w) & 1)) continue;
-        int p, q;
-        flow_axes3(w, p, q);
-        const size_t bytes = (size_t)ctx->gn[p] * ctx->gn[q] * sizeof(double);
-        pl3_count_copy(ctx, bytes);
-        P3_HIP(ctx, hipMemcpy(values[w], ctx->hwall.v[w], bytes, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return planes3_get(ctx, ctx->hplanes, mask, values);
 }
 // the right-hand side of the heat rows into rhs: the kernel without planes unless the context holds some
 static void heat_rhs3(pl3_ctx* ctx, double* rhs, int scaled) {
-    if (ctx->hwall_mask) launch3(ctx, ctx->hop.g, k3_heat_rhs<true>, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, ctx->hwall, rhs, scaled);
+    if (ctx->hplanes.mask) launch3(ctx, ctx->hop.g, k3_heat_rhs<true>, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, ctx->hwall, rhs, scaled);
     else launch3(ctx, ctx->hop.g, k3_heat_rhs<false>, ctx->hop, ctx->hT, ctx->hH, ctx->hbcv, Heat3Planes{}, rhs, scaled);
 }
 static int need_hvecs(pl3_ctx* ctx) {

@@ -13,6 +13,7 @@
 #include "pl_internal.h"
 #include "pl_mic3.h"
 #include "pl_step3.h"
+#include "pl_walls3.h"
 #include <algorithm>
 #include <cmath>
 
@@ -1210,16 +1211,11 @@ extern "C" int pl3_tracers_removed(pl3_ctx* ctx, int64_t out[2]) {
 
 // The inflow material is context state like the search, the deletion and the RK4 weights: read by every refilling sort, which takes the
 // flow planes from the context at that moment.  Setting it touches no resident tracer.
-static const char* const m3_wall_names[6] = {"z0", "x0", "y0", "zL", "xL", "yL"};
-static size_t m3_wall_faces(const Pl3HostView& v, int wall) {
-    const int a = wall % 3;
-    return (size_t)(v.gn[a == 0 ? 1 : 0] - 1) * (size_t)(v.gn[a == 2 ? 1 : 2] - 1);
-}
 extern "C" int pl3_mic_set_inflow(pl3_ctx* ctx, int wall, unsigned columns, const double* values) {
     Pl3HostView v; Mic3* M;
     M3_TRY(m3_open(ctx, "pl3_mic_set_inflow", v, &M));
     if (wall < 0 || wall > 5) return pl3_fail(ctx, "pl3_mic_set_inflow: wall " + std::to_string(wall) + " is not one of 0 ... 5 (z0, x0, y0, zL, xL, yL)");
-    const std::string wn = m3_wall_names[wall];
+    const std::string wn = walls3_names[wall];
     if (columns >> M3_ID) {
         int bit = M3_ID;
         while (!((columns >> bit) & 1u)) bit++;
@@ -1228,7 +1224,7 @@ extern "C" int pl3_mic_set_inflow(pl3_ctx* ctx, int wall, unsigned columns, cons
     }
     if (columns == 0u) { M->inflow_mask[wall] = 0u; return 0; }
     if (!values) return pl3_fail(ctx, "pl3_mic_set_inflow: wall " + wn + " names columns but values is NULL");
-    const size_t nface = m3_wall_faces(v, wall);
+    const size_t nface = walls3_count(v.gn, wall, false);
     const int ncol = __builtin_popcount(columns);
     for (int j = 0, r = 0; j < M3_ID; j++) {
         if (!((columns >> j) & 1u)) continue;
@@ -1254,7 +1250,7 @@ extern "C" int pl3_mic_get_inflow(pl3_ctx* ctx, int wall, unsigned* columns, dou
     if (wall < 0 || wall > 5) return pl3_fail(ctx, "pl3_mic_get_inflow: wall " + std::to_string(wall) + " is not one of 0 ... 5 (z0, x0, y0, zL, xL, yL)");
     if (columns) *columns = M->inflow_mask[wall];
     if (!values || !M->inflow_mask[wall]) return 0;
-    const size_t count = (size_t)__builtin_popcount(M->inflow_mask[wall]) * m3_wall_faces(v, wall);
+    const size_t count = (size_t)__builtin_popcount(M->inflow_mask[wall]) * walls3_count(v.gn, wall, false);
     M3_HIP(ctx, m3_copy(ctx, values, M->inflow_dev[wall], count * sizeof(double), hipMemcpyDeviceToHost, v.stream));
     M3_HIP(ctx, hipStreamSynchronize(v.stream));
     return 0;

@@ -6,10 +6,10 @@
 // Velocities of the six Stokes walls (pl3_stokes_set_wall_velocity): u[3 w + q] = component q of (Uz, Ux, Uy) of wall w of [z0, x0, y0, zL,
 // xL, yL]; bit w of `moving`: that wall has a non-zero velocity.  Passed by value to k3_rhs and k_s3_advvel, and to no other kernel.
 struct Pl3WallVel { double u[18]; int moving; };
-// Flow through the six Stokes walls (pl3_stokes_set_wall_flow): un[w] is the device plane of wall w, (n_p - 1, n_q - 1) entries over the
-// GLOBAL face indices of the two other axes p < q in z, x, y order (entry i (n_q - 1) + j), the wall-normal velocity along +a; bit w of
-// `mask`: that wall carries a flow (its pointer is NULL otherwise).  Passed by value to k3_rhs, k_s3_advvel and, inside M3Inject, to
-// k_m3_inject<true> (the inflow rule of pl3_mic_set_inflow), and to no other kernel.
+// Flow through the six Stokes walls (pl3_stokes_set_wall_flow): un[w] is the device plane of wall w over its faces, GLOBAL indices (the
+// layout is in DESIGN.md section 6c, "Wall planes"), the wall-normal velocity along +a; bit w of `mask`: that wall carries a flow (its
+// pointer is NULL otherwise).  Passed by value to k3_rhs, k_s3_advvel and, inside M3Inject, to k_m3_inject<true> (the inflow rule of
+// pl3_mic_set_inflow), and to no other kernel.
 struct Pl3WallFlow { const double* un[6]; int mask; };
 // the context's ringed device arrays: node (i, j, k) of an array sits at (i + 1) s0 + (j + 1) s1 + k + pad
 struct Pl3DevView {

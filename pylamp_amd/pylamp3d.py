@@ -93,43 +93,65 @@ FLOW_AXES = ((1, 2), (0, 2), (0, 1))        # the two axes p < q of a wall plane
 _AXIS_N = ("nz", "nx", "ny")
 
 
+def _plane_shape(nx, w, nodes=False):
+    """(shape, its two extents as text) of wall w's plane over the wall's faces, or over its nodes ("Wall planes")."""
+    p, q = FLOW_AXES[w % 3]
+    if nodes:
+        return (int(nx[p]), int(nx[q])), (_AXIS_N[p], _AXIS_N[q])
+    return (int(nx[p]) - 1, int(nx[q]) - 1), (_AXIS_N[p] + " - 1", _AXIS_N[q] + " - 1")
+
+
+def _six_entries(entries, who, needs, names=None, each=""):
+    """The six per-wall entries of a setting as a list: None gives six None, a dict by wall name is spread over the walls where the
+    caller allows it (names: its words for the error about an unknown name), anything else has to be six entries long."""
+    if entries is None:
+        return [None] * 6
+    if isinstance(entries, dict) and names is not None:
+        for k in entries:
+            if k not in WALL_NAMES:
+                raise Exception("%s: %s a wall '%s' (the walls are %s)" % (who, names, k, ", ".join(WALL_NAMES)))
+        return [entries.get(k) for k in WALL_NAMES]
+    try:
+        six = None if isinstance(entries, dict) else list(entries)
+    except TypeError:
+        six = None
+    if six is None:
+        raise Exception("%s: %s six entries [z0, x0, y0, zL, xL, yL]%s (got %s)" % (who, needs, each, type(entries).__name__))
+    if len(six) != 6:
+        raise Exception("%s: %s six entries [z0, x0, y0, zL, xL, yL] (got %d)" % (who, needs, len(six)))
+    return six
+
+
+def _checked_plane(value, shape, extents, who, needs, has, read=None):
+    """value, a scalar (broadcast) or an array of the given shape, as a contiguous float64 plane.  needs / has: the subjects of the two
+    errors, a wrong shape and the first non-finite entry; read: the mask of the entries that are checked (None: all)."""
+    try:
+        a = np.array(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is not None and a.ndim == 0:
+        a = np.full(shape, float(a))
+    if a is None or a.shape != shape:
+        raise Exception("%s: %s the shape (%s, %s) = %r or a scalar (got %s)"
+                        % (who, needs, extents[0], extents[1], shape, "an object that is no array" if a is None else a.shape))
+    bad = np.argwhere(~np.isfinite(a) if read is None else ~np.isfinite(a) & read)
+    if bad.size:
+        i, j = (int(v) for v in bad[0])
+        raise Exception("%s: %s [%d, %d] = %r" % (who, has, i, j, float(a[i, j])))
+    return np.ascontiguousarray(a)
+
+
 def wall_flows(flow, nx, who="3-D Stokes"):
     """flow: the wall-normal velocities through the six walls [z0, x0, y0, zL, xL, yL] -- a list of six entries (or a dict by wall
     name), each None (no flow), a scalar (the constant profile) or an array Un of shape (n_p - 1, n_q - 1) over the wall's faces, p < q
     the two other axes in z, x, y order; the value is the component along +a, so positive is inflow on z0, x0, y0 and outflow on zL,
     xL, yL.  None: no flow anywhere.  Returns six entries, None or a contiguous float64 array; shapes and non-finite entries are
     rejected by name (the rule is in include/pylamp_hip.h at pl3_stokes_set_wall_flow)."""
-    if flow is None:
-        return [None] * 6
-    if isinstance(flow, dict):
-        for k in flow:
-            if k not in WALL_NAMES:
-                raise Exception("%s: the wall flow names a wall '%s' (the walls are %s)" % (who, k, ", ".join(WALL_NAMES)))
-        flow = [flow.get(k) for k in WALL_NAMES]
-    flow = list(flow)
-    if len(flow) != 6:
-        raise Exception("%s: the wall flow needs six entries [z0, x0, y0, zL, xL, yL] (got %d)" % (who, len(flow)))
     out = []
-    for w, f in enumerate(flow):
-        if f is None:
-            out.append(None)
-            continue
-        p, q = FLOW_AXES[w % 3]
-        shp = (int(nx[p]) - 1, int(nx[q]) - 1)
-        try:
-            a = np.array(f, dtype=np.float64)
-        except (TypeError, ValueError):
-            a = None
-        if a is not None and a.ndim == 0:
-            a = np.full(shp, float(a))
-        if a is None or a.shape != shp:
-            raise Exception("%s: the flow of wall %s needs the shape (%s - 1, %s - 1) = %r or a scalar (got %s)"
-                            % (who, WALL_NAMES[w], _AXIS_N[p], _AXIS_N[q], shp, "an object that is no array" if a is None else a.shape))
-        bad = np.argwhere(~np.isfinite(a))
-        if bad.size:
-            i, j = (int(v) for v in bad[0])
-            raise Exception("%s: wall %s has a non-finite flow entry [%d, %d] = %r" % (who, WALL_NAMES[w], i, j, float(a[i, j])))
-        out.append(np.ascontiguousarray(a))
+    for w, f in enumerate(_six_entries(flow, who, "the wall flow needs", "the wall flow names")):
+        name = WALL_NAMES[w]
+        out.append(None if f is None else _checked_plane(f, *_plane_shape(nx, w), who, "the flow of wall %s needs" % name,
+                                                         "wall %s has a non-finite flow entry" % name))
     return out
 
 
@@ -142,43 +164,19 @@ def wall_heat_values(values, nx, who="3-D heat"):
     array.  z-walls own their edges, then x-walls, then y-walls: entries at nodes another wall owns (rows 0 and nz - 1 of an x- or
     y-wall's plane, also columns 0 and nx - 1 of a y-wall's) are never read and not checked; a non-finite entry that is read and a
     wrong shape are rejected by name (the rule is in include/pylamp_hip.h at pl3_heat_set_wall_values)."""
-    if values is None:
-        return [None] * 6
-    if isinstance(values, dict):
-        for k in values:
-            if k not in WALL_NAMES:
-                raise Exception("%s: the heat wall values name a wall '%s' (the walls are %s)" % (who, k, ", ".join(WALL_NAMES)))
-        values = [values.get(k) for k in WALL_NAMES]
-    if not hasattr(values, "__len__") or len(values) != 6:
-        raise Exception("%s: the heat wall values need six entries [z0, x0, y0, zL, xL, yL] (got %s)"
-                        % (who, "%d" % len(values) if hasattr(values, "__len__") else type(values).__name__))
     out = []
-    for w, f in enumerate(values):
+    for w, f in enumerate(_six_entries(values, who, "the heat wall values need", "the heat wall values name")):
         if f is None:
             out.append(None)
             continue
-        a = w % 3
-        p, q = FLOW_AXES[a]
-        shp = (int(nx[p]), int(nx[q]))
-        try:
-            v = np.array(f, dtype=np.float64)
-        except (TypeError, ValueError):
-            v = None
-        if v is not None and v.ndim == 0:
-            v = np.full(shp, float(v))
-        if v is None or v.shape != shp:
-            raise Exception("%s: the values of heat wall %s need the shape (%s, %s) = %r or a scalar (got %s)"
-                            % (who, WALL_NAMES[w], _AXIS_N[p], _AXIS_N[q], shp, "an object that is no array" if v is None else v.shape))
+        a, name = w % 3, WALL_NAMES[w]
+        shp, extents = _plane_shape(nx, w, nodes=True)
         read = np.ones(shp, dtype=bool)              # the nodes of the plane that this wall owns
-        if p < a:
+        if FLOW_AXES[a][0] < a:
             read[0, :] = read[-1, :] = False
-        if q < a:
+        if FLOW_AXES[a][1] < a:
             read[:, 0] = read[:, -1] = False
-        bad = np.argwhere(~np.isfinite(v) & read)
-        if bad.size:
-            i, j = (int(u) for u in bad[0])
-            raise Exception("%s: heat wall %s has a non-finite entry [%d, %d] = %r" % (who, WALL_NAMES[w], i, j, float(v[i, j])))
-        out.append(np.ascontiguousarray(v))
+        out.append(_checked_plane(f, shp, extents, who, "the values of heat wall %s need" % name, "heat wall %s has a non-finite entry" % name, read))
     return out
 
 
@@ -189,22 +187,13 @@ def wall_materials(material, nx, who="3-D markers"):
     wall_flows).  Scalars are broadcast to planes.  Returns six entries, None or (mask, float64 array (ncol, n_p - 1, n_q - 1)) with
     the planes in ascending column order; a wrong length, a wrong plane shape, TR__ID, an unknown column and a non-finite value are
     rejected by name."""
-    if material is None:
-        return [None] * 6
-    if isinstance(material, dict) or not hasattr(material, "__len__"):
-        raise Exception("%s: the inflow material needs six entries [z0, x0, y0, zL, xL, yL], each None or a dict (got %s)" % (who, type(material).__name__))
-    material = list(material)
-    if len(material) != 6:
-        raise Exception("%s: the inflow material needs six entries [z0, x0, y0, zL, xL, yL] (got %d)" % (who, len(material)))
     out = []
-    for w, m in enumerate(material):
+    for w, m in enumerate(_six_entries(material, who, "the inflow material needs", each=", each None or a dict")):
         if m is None or (isinstance(m, dict) and not m):
             out.append(None)
             continue
         if not isinstance(m, dict):
             raise Exception("%s: the inflow material of wall %s needs a dict {column: value} or None (got %s)" % (who, WALL_NAMES[w], type(m).__name__))
-        p, q = FLOW_AXES[w % 3]
-        shp = (int(nx[p]) - 1, int(nx[q]) - 1)
         cols = {}
         for key, val in m.items():
             col = int(key) if isinstance(key, (int, np.integer)) and not isinstance(key, bool) else None
@@ -214,21 +203,8 @@ def wall_materials(material, nx, who="3-D markers"):
             if col is None or not 0 <= col < TR__ID:
                 raise Exception("%s: the inflow material of wall %s names an unknown column %r (the tracer columns are the TR_* constants 0 ... %d)"
                                 % (who, WALL_NAMES[w], key, TR__ID - 1))
-            try:
-                a = np.array(val, dtype=np.float64)
-            except (TypeError, ValueError):
-                a = None
-            if a is not None and a.ndim == 0:
-                a = np.full(shp, float(a))
-            if a is None or a.shape != shp:
-                raise Exception("%s: column %d of the inflow material of wall %s needs the shape (%s - 1, %s - 1) = %r or a scalar (got %s)"
-                                % (who, col, WALL_NAMES[w], _AXIS_N[p], _AXIS_N[q], shp, "an object that is no array" if a is None else a.shape))
-            bad = np.argwhere(~np.isfinite(a))
-            if bad.size:
-                i, j = (int(v) for v in bad[0])
-                raise Exception("%s: column %d of the inflow material of wall %s has a non-finite value [%d, %d] = %r"
-                                % (who, col, WALL_NAMES[w], i, j, float(a[i, j])))
-            cols[col] = a
+            subject = "column %d of the inflow material of wall %s" % (col, WALL_NAMES[w])
+            cols[col] = _checked_plane(val, *_plane_shape(nx, w), who, subject + " needs", subject + " has a non-finite value")
         order = sorted(cols)
         out.append((sum(1 << c for c in order), np.ascontiguousarray(np.stack([cols[c] for c in order]))))
     return out
@@ -414,8 +390,7 @@ class Context3:
                 out.append(None)
                 continue
             cols = [c for c in range(NFTRAC) if (mask.value >> c) & 1]
-            p, q = FLOW_AXES[w % 3]
-            planes = np.zeros((len(cols), self.nx[p] - 1, self.nx[q] - 1))
+            planes = np.zeros((len(cols),) + _plane_shape(self.nx, w)[0])
             self.check(self.lib.pl3_mic_get_inflow(self.handle(), w, None, _lib.dptr(planes)))
             out.append({c: planes[r] for r, c in enumerate(cols)})
         return out
@@ -442,40 +417,40 @@ class Context3:
         self.check(self.lib.pl3_stokes_get_wall_velocity(self.handle(), _lib.dptr(v)))
         return v
 
+    @staticmethod
+    def _plane_pointers(planes):
+        """Six planes, None or a contiguous float64 array each, as the double*[6] of the library."""
+        return (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in planes])
+
+    def _fetch_planes(self, get, nodes):
+        """The planes the device holds, by the library's getter: its mask first, then zeros for the walls that have one, filled."""
+        mask = C.c_int()
+        self.check(get(self.handle(), C.byref(mask), None))
+        out = [np.zeros(_plane_shape(self.nx, w, nodes)[0]) if (mask.value >> w) & 1 else None for w in range(6)]
+        self.check(get(self.handle(), None, self._plane_pointers(out)))
+        return out
+
     def set_wall_flow(self, flow):
         """The flow through the six Stokes walls of this context (wall_flows: six entries, each None, a scalar or the plane Un of
         the wall; None clears it); kept until set again.  All six are set at once because their net flux must vanish
         (include/pylamp_hip.h at pl3_stokes_set_wall_flow; wall_fluxes gives the figures)."""
-        fl = wall_flows(flow, self.nx)
-        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in fl])
-        self.check(self.lib.pl3_stokes_set_wall_flow(self.handle(), ptr))
+        fl = wall_flows(flow, self.nx)          # (named: the planes live until the call returns)
+        self.check(self.lib.pl3_stokes_set_wall_flow(self.handle(), self._plane_pointers(fl)))
 
     def wall_flow(self):
         """Six entries, None or the plane of the wall as the device holds it."""
-        mask = C.c_int()
-        self.check(self.lib.pl3_stokes_get_wall_flow(self.handle(), C.byref(mask), None))
-        out = [np.zeros((self.nx[FLOW_AXES[w % 3][0]] - 1, self.nx[FLOW_AXES[w % 3][1]] - 1)) if (mask.value >> w) & 1 else None
-               for w in range(6)]
-        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in out])
-        self.check(self.lib.pl3_stokes_get_wall_flow(self.handle(), None, ptr))
-        return out
+        return self._fetch_planes(self.lib.pl3_stokes_get_wall_flow, nodes=False)
 
     def set_heat_wall_values(self, values):
         """Profiles over the six heat walls of this context (wall_heat_values: six entries, each None, a scalar or the plane over the
         wall's nodes; None or six None clear them); kept until set again, across makeDiffusionMatrix and the steps.  A wall with a plane
         ignores its entry of bcvalue (include/pylamp_hip.h at pl3_heat_set_wall_values).  One rank."""
         V = wall_heat_values(values, self.nx)
-        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in V])
-        self.check(self.lib.pl3_heat_set_wall_values(self.handle(), ptr))
+        self.check(self.lib.pl3_heat_set_wall_values(self.handle(), self._plane_pointers(V)))
 
     def heat_wall_values(self):
         """Six entries, None or the plane of the wall as the device holds it."""
-        mask = C.c_int()
-        self.check(self.lib.pl3_heat_get_wall_values(self.handle(), C.byref(mask), None))
-        out = [np.zeros((self.nx[FLOW_AXES[w % 3][0]], self.nx[FLOW_AXES[w % 3][1]])) if (mask.value >> w) & 1 else None for w in range(6)]
-        ptr = (_lib.c_double_p * 6)(*[None if a is None else _lib.dptr(a) for a in out])
-        self.check(self.lib.pl3_heat_get_wall_values(self.handle(), None, ptr))
-        return out
+        return self._fetch_planes(self.lib.pl3_heat_get_wall_values, nodes=True)
 
     def close(self):
         if self.h is not None:
@@ -1139,25 +1114,42 @@ class Simulation3:
     third axis -- properties, tracer->grid, Stokes, time step, heat, grid->tracer (+ subgrid diffusion), RK4, fence, and the census
     + refill of depleted cells inside the end-of-step sort (Options3.tracdens / tracdens_min / inject_seed / inject_unique_ids;
     refill() does it without a step).  step() reports ninjected, nrefilled (cells) and nempty (cells that held no tracer: their new
-    tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank,
-    Stokes walls free-slip or no-slip per wall (Options3.bcstokes = [z0, x0, y0, zL, xL, yL]), a no-slip wall may move in its own plane (Options3.bcstokesvel, set_wall_velocity); a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per
-    axis strictly increasing from 0 to L[d]): the marker kernels then find cells by search in the coordinates (the rule is in
-    include/pylamp_hip.h at pl3_mic_set_search), while the time-step rules and the subgrid time scale keep the mean spacing.  Options3.resident = True runs the same sequence inside the library with every grid field
-    kept on the device (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).  Options3.tracs_fence_enabled = False together with
-    Options3.marker_deletion = True runs without the fence: a tracer that leaves the box (x_d <= 0 or x_d >= L_d) is removed by the
-    next sort, the census and the refill of that sort see the survivors, step() / advect() / refill() report nremoved and
-    Context3.tracers_removed() counts them.  On that path material may flow through the walls (Options3.bcstokesflow,
-    set_wall_flow; wall_flows states the format): the outflow is deleted, the cells along an inflow wall are kept filled by the refill
-    (tracdens_min > 0 is required), whose new tracers carry the mean of their cell's residents -- a zero-gradient inflow -- unless the
-    wall has an inflow material (Options3.bcinflow, set_inflow_material; wall_materials states the format): then the new tracers that
-    lie between the wall and every resident of their cell take the wall's values in the columns it names, step() / advect() / refill()
-    report them as ninflow, and an inflow cell that ran empty gets finite values in those columns (a scattered column the material
-    leaves out is still NaN there and step() raises its NaN error); a prescribed TR_TMP is a tracer temperature like any other, so
-    with heat diffusion on it enters the next step's temperature scatter, and the heat solve of the same step can hold the matching patch of the wall hot: Options3.bcheatprofile /
-    set_heat_profile give its boundary values as profiles over the walls (wall_heat_values states the format), heat_budget() the heat
-    flow through the six walls, the storage rate and the source of the last step's heat solve;
-    the net flux must vanish (wall_fluxes); Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default,
-    move them by 2/3 of that).  Not built: surface stabilisation, several ranks -- each is rejected with an error that names it."""
+    tracers carry NaN fields, as in the reference) and raises before the Stokes solve when a scattered field holds a NaN.  One rank.
+
+    Walls: the Stokes walls are free-slip or no-slip per wall (Options3.bcstokes = [z0, x0, y0, zL, xL, yL]); a no-slip wall may
+    move in its own plane (Options3.bcstokesvel, set_wall_velocity).
+
+    Grid: a regular grid unless Options3.marker_search = True, with which grid= may be any rectilinear grid (per axis strictly
+    increasing from 0 to L[d]): the marker kernels then find cells by search in the coordinates (the rule is in
+    include/pylamp_hip.h at pl3_mic_set_search), while the time-step rules and the subgrid time scale keep the mean spacing.
+
+    Resident step: Options3.resident = True runs the same sequence inside the library with every grid field kept on the device
+    (pl3_resident_step; field() then downloads on demand, transfer_stats() counts what crosses the bus).
+
+    Deletion: Options3.tracs_fence_enabled = False together with Options3.marker_deletion = True runs without the fence: a tracer
+    that leaves the box (x_d <= 0 or x_d >= L_d) is removed by the next sort, the census and the refill of that sort see the
+    survivors, step() / advect() / refill() report nremoved and Context3.tracers_removed() counts them.
+
+    Through-flow: on that path material may flow through the walls (Options3.bcstokesflow, set_wall_flow; wall_flows states the
+    format); the net flux must vanish (wall_fluxes).  The outflow is deleted, the cells along an inflow wall are kept filled by the
+    refill (tracdens_min > 0 is required), whose new tracers carry the mean of their cell's residents -- a zero-gradient inflow --
+    unless the wall has an inflow material.
+
+    Inflow material (Options3.bcinflow, set_inflow_material; wall_materials states the format): the new tracers that lie between
+    the wall and every resident of their cell take the wall's values in the columns it names, step() / advect() / refill() report
+    them as ninflow, and an inflow cell that ran empty gets finite values in those columns (a scattered column the material leaves
+    out is still NaN there and step() raises its NaN error).  A prescribed TR_TMP is a tracer temperature like any other, so with
+    heat diffusion on it enters the next step's temperature scatter, and the heat solve of the same step can hold the matching
+    patch of the wall hot (next paragraph).
+
+    Heat walls: Options3.bcheatprofile / set_heat_profile give the boundary values of the heat solve as profiles over the walls
+    (wall_heat_values states the format); heat_budget() gives the heat flow through the six walls, the storage rate and the source
+    of the last step's heat solve.
+
+    RK4: Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default, move them by 2/3
+    of that).
+
+    Not built: surface stabilisation, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
         self.nx = [int(v) for v in nx]
