@@ -2,7 +2,7 @@
 griddata.NNNNNN.npz / tracs.NNNNNN.npz in the style of the 2-D example, with a third axis (gridy, vely, tr_x (n, 3)).
 Cells that run below tracdens_min markers are refilled to tracdens inside the end-of-step sort (0 0 switches that off).
 
-    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R] [--noslip=z] [--fence-off] [--warm] [--strain]
+    python examples/falling_sphere3d.py [n=65] [steps=20] [outdir=out] [tracdens=8] [tracdens_min=4] [--resident] [--refine=R] [--noslip=z] [--fence-off] [--warm] [--strain] [--yield=TAU[,DTAU]]
 
 --resident runs the device-resident step (Options3.resident): the grid fields stay on the GPU and are downloaded for the snapshots only.
 --refine=R (e.g. 3) makes the cells R times finer around the sphere's path than far from it (pylamp3d.refined_grid) and switches
@@ -18,6 +18,8 @@ census and refill inside the same sort restore the density behind them.  Every s
 (Options3.stokes_warm_start); every step then prints how its solve started (cold, warm, or rejected by the guard).
 --strain keeps the second invariants of the strain rate and of the stress and the viscous dissipation of every step
 (Options3.strain_fields): the snapshots gain strainrate, stress and dissipation, and every step prints the total dissipation.
+--yield=TAU[,DTAU] limits the viscosity by the yield stress TAU + DTAU z [Pa, Pa/m] (Options3.yield_stress; e.g. --yield=2e6): every step
+runs a Picard loop of Stokes solves and prints its figures, and the snapshots gain the effective viscosities etas_eff, etan_eff.
 """
 import os
 import sys
@@ -33,6 +35,8 @@ refine = refine[0] if refine else 0.0
 fence_off = "--fence-off" in sys.argv[1:]
 warm = "--warm" in sys.argv[1:]
 strain = "--strain" in sys.argv[1:]
+yield_stress = [tuple(float(v) for v in a.split("=", 1)[1].split(",")) for a in sys.argv[1:] if a.startswith("--yield=")]
+yield_stress = (yield_stress[0] + (0.0,))[:2] if yield_stress else None
 noslip = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--noslip=")]
 noslip = noslip[0] if noslip else ""
 if noslip not in ("", "z", "zx", "zxy"):
@@ -54,7 +58,7 @@ if refine > 1.0:                                                                
 tr_x, tr_f = P3.falling_sphere_tracers(nx, L, np.random.default_rng(1), per_axis=per_axis)
 opt = P3.Options3(do_heatdiff=False, tdep_rho=False, tdep_eta=False,             # isothermal, constant properties
                   tracdens=tracdens, tracdens_min=tracdens_min, inject_unique_ids=True, resident=resident, marker_search=grid is not None,
-                  bcstokes=bcstokes, tracs_fence_enabled=not fence_off, marker_deletion=fence_off, stokes_warm_start=warm, strain_fields=strain)
+                  bcstokes=bcstokes, tracs_fence_enabled=not fence_off, marker_deletion=fence_off, stokes_warm_start=warm, strain_fields=strain, yield_stress=yield_stress)
 sim = P3.Simulation3(nx, L, tr_x, tr_f, opt, grid=grid)
 sphere = None
 for it in range(1, steps + 1):
@@ -66,6 +70,11 @@ for it in range(1, steps + 1):
            rep["nrefilled"]), flush=True)
     if strain:
         print("          dissipation %.4e W, largest strain rate %.3e 1/s" % (rep["dissipation_total"], sim.field("strainrate").max()), flush=True)
+    if yield_stress:
+        p = rep["picard"]
+        print("          Picard %d solves%s: change %s, yielded nodes %s, cells %s, Stokes iterations %s" %
+              (p["iterations"], "" if p["converged"] else " (not converged)", " ".join("%.2e" % c for c in p["change"]), p["yielded_nodes"], p["yielded_cells"],
+               p["stokes_iterations"]), flush=True)
     if it % 10 == 0 or it == steps:
         sim.write_snapshot(outdir)
 sim.close()

@@ -594,6 +594,38 @@ int  pl3_heat_budget(pl3_ctx* ctx, const double* T, double out[8]);
  * vz, vx, vy given. */
 int  pl3_stokes_strain_fields(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* strainrate, double* stress,
                               double* dissipation, double* total);
+/* Yield stress (opt-in, off at creation; one rank): the viscosities the operator solves with are limited by a yield stress, from the strain
+ * rates of a velocity field.
+ * Symbols.  The material viscosities are etas (nodes) and etan (cell centres) as pl3_stokes_set_coeffs receives them.  eps_DD (centres) and
+ * eps_DE (edges) are exactly the strain rates of pl3_stokes_strain_fields above, wall rules, moving walls and through-flow included.
+ * Yield stress:      tau_y(z) = tau0 + dtau_dz (z - z[0]), z the coordinate along axis 0 (depth); evaluated at z_i for node i and at the
+ *                    cell's mid-point (z[i] + z[i+1]) / 2 for the centres.
+ * Node invariant:    e_n = the strainrate field of pl3_stokes_strain_fields (the same device function and order of summation: bit for bit).
+ * Centre invariant:  e_c = sqrt(1/2 (sum_D eps_DD^2 + 2 sum_pairs m_p)), m_p the plain mean of eps_DE^2 over the cell's four edges of pair
+ *                    p = (D, E): nodes i_D, i_D + 1 x i_E, i_E + 1, cell i_F.  Summation: pairs 0, 1, 2 ((z, x), (x, y), (y, z)); within a
+ *                    pair D outermost, the lower index first.
+ * Effective viscosity, nodes and centres alike:   eta_eff = min(eta_mat, max(tau_y / (2 e), eta_floor)).
+ * It never raises a viscosity, is continuous in e, and is eta_mat where e = 0.  An entry is "yielded" when eta_eff < eta_mat.  Entries of
+ * etan beyond the cells (the last index of an axis) keep the material value; nothing is written to the ring.
+ * The effective viscosities are stateless: always derived from the material ones, never from the previous effective ones.  The context
+ * keeps the material arrays next to the operator's once a yield stress is set; pl3_stokes_set_coeffs resets both to the material ones.
+ *
+ * pl3_stokes_set_yield(on, tau0, dtau_dz, eta_floor): on = 0 switches off (the operator takes the material viscosities again, the other
+ * arguments are ignored).  Rejected by name: a context with pl3_set_comm attached; tau_y <= 0 anywhere between z[0] and z[n - 1];
+ * eta_floor <= 0; non-finite values.  A change of the setting clears the warm-start history and makes the effective viscosities the
+ * material ones.
+ * pl3_stokes_yield_update(vz, vx, vy, out): the update for host velocities ((nz, nx, ny) each; all three NULL: the resident solution of
+ * the last solve, with the rule and the errors of pl3_stokes_strain_fields).  Needs coefficients and a yield stress set.  It replaces the
+ * operator's viscosities; out = { min eta_eff over nodes and centres (NaN rule of pl3_stokes_set_coeffs), change = max |ln(eta_new /
+ * eta_prev)| over nodes and centres (eta_prev: the effective viscosities before the call), yielded nodes, yielded centres, max e_n,
+ * max e_c }.  Unless the change is exactly 0 the operator's scaling follows the new minimum (Kcont, Kbond as in pl3_stokes_set_coeffs),
+ * the next solve rebuilds the hierarchy, and the resident solution's Kcont-scaled pressure is rescaled to stay the same pressure.  One
+ * pass of the strain kernel and one per-node kernel with a fixed-order reduction, no atomics: a call repeats bit for bit.
+ * pl3_stokes_get_coeffs(which, etas, etan): which = 0 the effective, 1 the material viscosities, (nz, nx, ny) each, either may be NULL. */
+int  pl3_stokes_set_yield(pl3_ctx* ctx, int on, double tau0, double dtau_dz, double eta_floor);
+int  pl3_stokes_get_yield(pl3_ctx* ctx, int* on, double* tau0, double* dtau_dz, double* eta_floor);
+int  pl3_stokes_yield_update(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double out[6]);
+int  pl3_stokes_get_coeffs(pl3_ctx* ctx, int which, double* etas, double* etan);
 
 /* ---- 3-D marker-in-cell (one rank; every entry point fails on a context that has pl3_set_comm attached) -------------
  * The dimension-by-dimension extension of pylamp_trac.py:30-388.  tr_x is (n, 3) in [z, x, y] order, tr_f is (n, ld_f) with the
@@ -773,7 +805,9 @@ int  pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_ste
 /* A grid field of the last resident step, downloaded on demand into out (nz, nx, ny): rho, etas, etan, cp, T, H, mat, kz, kx, ky,
  * velz, velx, vely, pres (Kcont-scaled, ghosts retained), temp; after a step with pl3_step_set_shear_heating or
  * pl3_step_set_strain_fields on also strainrate, stress, dissipation (they live in a Stokes work vector: until the next call that uses
- * the work vectors).  An unknown or not-yet-computed name is an error that lists the available ones. */
+ * the work vectors); with a yield stress set (pl3_stokes_set_yield) also etas_eff, etan_eff, the effective viscosities the operator holds
+ * after the step's Picard loop, while etas and etan stay the scattered material fields.  An unknown or not-yet-computed name is an error
+ * that lists the available ones. */
 int  pl3_get_field(pl3_ctx* ctx, const char* name, double* out);
 /* Opt-in switches of pl3_resident_step, context state, both off at creation; with both off the step is bit for bit what it is without
  * them.  Shear heating: after the Stokes solve the dissipation of the solution (pl3_stokes_strain_fields) is added to the scattered H,
@@ -785,6 +819,20 @@ int  pl3_step_set_shear_heating(pl3_ctx* ctx, int on);
 int  pl3_step_shear_heating(pl3_ctx* ctx, int* on);
 int  pl3_step_set_strain_fields(pl3_ctx* ctx, int on);
 int  pl3_step_dissipation_total(pl3_ctx* ctx, double* total);
+/* The Picard loop of pl3_resident_step, run only with a yield stress set (pl3_stokes_set_yield); the settings are context state, maxit = 10
+ * and tol = 1e-2 at creation.  Step 4 of the resident step then is: solve 1 with the material viscosities (cold, or warm with
+ * pl3_stokes_set_warm_start); update the viscosities (pl3_stokes_yield_update on the resident solution); while the change of the update is
+ * above tol and fewer than maxit solves have run: solve again from the resident solution (use_x0; the reference norm is the one the solve
+ * computes from the hydrostatic state), update again.  As many updates as solves; the step is converged when the last change is <= tol.
+ * Reaching maxit is no error: the step goes on with the last solution.  The time-step rule, the strain fields and shear heating, the heat
+ * solve, the advection velocity and the one history commit of the warm start use the last solution, with the last effective viscosities
+ * where they need any; report->stokes holds the statistics of the last solve.  When nothing yields the first update returns change 0 and
+ * the step is, array for array, the step without a yield stress.
+ * pl3_step_set_picard: maxit 1 .. 32, tol >= 0, else an error by name.
+ * pl3_step_picard_report: out[0] iterations of the last resident step's loop (0: no yield stress was set), out[1] converged, then per
+ * iteration { change, yielded nodes, yielded centres, iterations of its Stokes solve }; n = capacity of out (2 + 4 x 32 holds it all). */
+int  pl3_step_set_picard(pl3_ctx* ctx, int maxit, double tol);
+int  pl3_step_picard_report(pl3_ctx* ctx, double* out, int n);
 /* The step's advection-velocity kernel on host arrays: vz, vx, vy (nz, nx, ny) -> Vz, Vx, Vy on the padded (nz+1, nx+1, ny+1)
  * centre grid: every component averaged along its own axis, then the ghosts wall by wall in the order z0, x0, y0, zL, xL, yL: a
  * FREESLIP wall mirrors the normal component with a sign flip and copies the tangential ones, the pass of a NOSLIP wall

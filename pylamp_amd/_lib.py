@@ -148,6 +148,12 @@ SIGNATURES = {
     "pl3_resident_step": (C.c_int, [C.c_void_p, C.POINTER(Step3Config), C.c_int, C.POINTER(Step3Report)]),
     "pl3_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p]),
     "pl3_stokes_strain_fields": (C.c_int, [C.c_void_p] + [c_double_p] * 7),
+    "pl3_stokes_set_yield": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "pl3_stokes_get_yield": (C.c_int, [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p]),
+    "pl3_stokes_yield_update": (C.c_int, [C.c_void_p] + [c_double_p] * 4),
+    "pl3_stokes_get_coeffs": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+    "pl3_step_set_picard": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "pl3_step_picard_report": (C.c_int, [C.c_void_p, c_double_p, C.c_int]),
     "pl3_step_set_shear_heating": (C.c_int, [C.c_void_p, C.c_int]),
     "pl3_step_shear_heating": (C.c_int, [C.c_void_p, c_int_p]),
     "pl3_step_set_strain_fields": (C.c_int, [C.c_void_p, C.c_int]),

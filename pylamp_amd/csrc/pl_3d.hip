@@ -1270,6 +1270,11 @@ struct pl3_ctx {
     double etol = 3e-8;                     // bound on the velocity-error estimate of a converged Stokes solve (PYLAMP_STOKES_ETOL)
     void* mic3 = nullptr;                   // pl_mic3.hip: resident tracers and the work buffers of the 3-D marker kernels
     void* step3 = nullptr;                  // pl_step3.hip: state of the device-resident time step
+    // yield stress (pl3_stokes_set_yield; off at creation): es / en are then the EFFECTIVE viscosities of the operator, ms / mn the material
+    // ones next to them (allocated once a yield stress is set); ytau: tau_y at the nodes z_i [0, nz) and at the cell mid-points [nz, 2 nz);
+    // ypart: the per-workgroup partials of k3_yield_visc and, behind them, those of the first finishing launch.  mat_mineta: min(eta) of the material arrays as the last set_coeffs had it
+    bool yield_on = false; double ytau0 = 0.0, ydtau = 0.0, yfloor = 0.0, mat_mineta = 0.0;
+    double *ms = nullptr, *mn = nullptr, *ytau = nullptr, *ypart = nullptr;
     bool strain_kept = false;               // Stokes work vector 2 still holds the fields of the last pl3_stokes_strain_fields / resident step
     int64_t xfer[4] = {0, 0, 0, 0};         // host <-> device copies (pl3_transfer_stats): count and bytes of those of at least one node field, of the smaller ones
 };
@@ -1440,7 +1445,7 @@ extern "C" void pl3_destroy(pl3_ctx* ctx) {
     pl3_step_free(&ctx->step3);
     pl3_mic_free(&ctx->mic3);
     free_levels3(ctx);
-    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow.dev, ctx->hplanes.dev}) if (q) (void)hipFree(q);
+    for (double* q : {ctx->es, ctx->en, ctx->rho, ctx->part, ctx->stage, ctx->hT, ctx->hH, ctx->hcdt, ctx->hrho, ctx->hcp, ctx->hbcv, ctx->htab, ctx->hbuf, ctx->flow.dev, ctx->hplanes.dev, ctx->ms, ctx->mn, ctx->ytau, ctx->ypart}) if (q) (void)hipFree(q);
     for (double* q : ctx->vec) if (q) (void)hipFree(q);
     for (double* q : ctx->hist) if (q) (void)hipFree(q);
     for (double* q : ctx->hk) if (q) (void)hipFree(q);
@@ -1545,6 +1550,7 @@ extern "C" int pl3_set_comm(pl3_ctx* ctx, pl_ctx* comm, int Pz, int Px, int Py) 
     if (Pz < 1 || Px < 1 || Py < 1 || Pz * Px * Py != comm->nranks) return p3_fail(ctx, "pl3_set_comm: Pz * Px * Py must equal the number of ranks of the communicator");
     if (ctx->op_ready || ctx->hop_ready || !ctx->levels.empty()) return p3_fail(ctx, "pl3_set_comm: call it right after pl3_create");
     if (ctx->warm_points) return p3_fail(ctx, "pl3_set_comm: the warm start of the Stokes solve (pl3_stokes_set_warm_start) runs on one rank; switch it off first");
+    if (ctx->yield_on) return p3_fail(ctx, "pl3_set_comm: the yield stress (pl3_stokes_set_yield) runs on one rank; switch it off first");
     if (comm->device != ctx->device) return p3_fail(ctx, "pl3_set_comm: the communicator context lives on another device");
     P3_HIP(ctx, hipSetDevice(ctx->device));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1578,6 +1584,16 @@ static int ring3(pl3_ctx* ctx, const double* src, double* dst) {
     P3_HIP(ctx, hipGetLastError());
     return 0;
 }
+// with a yield stress set: the arrays just written to es / en are the material viscosities, kept next to them (the effective ones start
+// as the material ones)
+static int yield_keep_material3(pl3_ctx* ctx, double mineta) {
+    ctx->mat_mineta = mineta;
+    if (!ctx->yield_on) return 0;
+    const size_t bytes = (size_t)ctx->geom.d.vol * sizeof(double);
+    P3_HIP(ctx, hipMemcpyAsync(ctx->ms, ctx->es, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    P3_HIP(ctx, hipMemcpyAsync(ctx->mn, ctx->en, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
 static void stokes_op3(pl3_ctx* ctx, double mineta, const double grav[3]) {
     const G3& g = ctx->geom.d;
     double sum = 0.0;
@@ -1601,6 +1617,7 @@ extern "C" int pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const dou
     for (size_t t = 0; t < N; t++) { if (etas[t] != etas[t]) nes = true; else mes = std::min(mes, etas[t]); if (etan[t] != etan[t]) nen = true; else men = std::min(men, etan[t]); }
     if (nes) mes = NAN; if (nen) men = NAN;
     const double mineta = (men < mes) ? men : mes;                  // python's min(a, b), pylamp_stokes.py:116-118
+    P3_TRY(yield_keep_material3(ctx, mineta));
     stokes_op3(ctx, mineta, grav);
     return 0;
 }
@@ -1610,6 +1627,7 @@ int pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* e
     P3_HIP(ctx, hipSetDevice(ctx->device));
     for (double** q : {&ctx->es, &ctx->en, &ctx->rho}) if (!*q) P3_TRY(dmal(ctx, q, ctx->geom.d.vol));
     P3_TRY(ring3(ctx, etas, ctx->es)); P3_TRY(ring3(ctx, etan, ctx->en)); P3_TRY(ring3(ctx, rho, ctx->rho));
+    P3_TRY(yield_keep_material3(ctx, mineta));
     stokes_op3(ctx, mineta, grav);
     return 0;
 }
@@ -2849,12 +2867,13 @@ template <int D> __device__ inline void edges_node3(const Op3& op, const double*
 }
 // e2 / t2 / phi: ringed arrays (NULL: not wanted); H: a plain (nz, nx, ny) array that gains phi, one IEEE addition per node (NULL: none)
 struct Strain3Out { double* e2; double* t2; double* phi; double* H; };
-__global__ __launch_bounds__(256) void k3_strain_node(Op3 op, V4 ce, Strain3Out o) {
-    K3_PROLOGUE(op.g)
+// the weighted means Y, T, P of eps_ij eps_ij, tau_ij tau_ij and 2 eta eps_ij eps_ij around node (i, j, k) (element c) from the arrays of
+// k3_strain_ce: the one order of summation of the node fields and of the node invariant of the yield stress (k3_yield_visc)
+__device__ inline void node_sums3(const Op3& op, const V4& ce, long long c, int i, int j, int k, double& Y, double& T, double& P) {
     const G3& g = op.g;
     double wl[3], wh[3], h[3];
     node_w3<0>(g, i, wl[0], wh[0], h[0]); node_w3<1>(g, j, wl[1], wh[1], h[1]); node_w3<2>(g, k, wl[2], wh[2], h[2]);
-    double Y = 0.0, T = 0.0, P = 0.0;              // the weighted means of eps_ij eps_ij, tau_ij tau_ij and 2 eta eps_ij eps_ij
+    Y = 0.0; T = 0.0; P = 0.0;
     for (int dz = 0; dz < 2; dz++) {               // the eight cells: z outermost, the lower one first; t = 2 eta_n
         const double wz = dz ? wh[0] : wl[0];
         if (wz == 0.0) continue;
@@ -2873,6 +2892,12 @@ __global__ __launch_bounds__(256) void k3_strain_node(Op3 op, V4 ce, Strain3Out 
     edges_node3<0>(op, ce.p[1], c, wl, wh, Y, T, P);
     edges_node3<1>(op, ce.p[2], c, wl, wh, Y, T, P);
     edges_node3<2>(op, ce.p[3], c, wl, wh, Y, T, P);
+}
+__global__ __launch_bounds__(256) void k3_strain_node(Op3 op, V4 ce, Strain3Out o) {
+    K3_PROLOGUE(op.g)
+    const G3& g = op.g;
+    double Y, T, P;
+    node_sums3(op, ce, c, i, j, k, Y, T, P);
     if (o.e2) o.e2[c] = sqrt(0.5 * Y);
     if (o.t2) o.t2[c] = sqrt(0.5 * T);
     o.phi[c] = P;
@@ -2939,6 +2964,242 @@ int pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total) {
     return strain_run3(ctx, svec(ctx, 11).vel(), Hplain, total);
 }
 
+// ---- yield stress: effective viscosities from the strain rates of a velocity field (pl3_stokes_set_yield / pl3_stokes_yield_update;
+// include/pylamp_hip.h, DESIGN.md 6c "Yield stress") -------------------------------------------------------------------------------------
+// k3_strain_ce (unchanged) leaves the cell sums and the edge squares in work vector 1; k3_yield_visc then handles, per thread, the eta_s of
+// its node and the eta_n of the cell whose lowest corner the node is: eta_eff = min(eta_mat, max(tau_y / (2 e), eta_floor)) from the
+// MATERIAL arrays, written over the previous effective ones (a thread reads and writes its own two entries only).  Its epilogue reduces
+// nine quantities per workgroup -- a shuffle tree per wave, then the four waves in order -- into ypart, which k3_yield_finish combines in a
+// fixed order: no atomics, a call repeats bit for bit.  (block_sums3 adds, and takes 256 threads in a row with
+// at most D3_BLOCKS workgroups; minima, maxima and the 64 x 4 workgroups of the per-node grid need this epilogue of their own.)
+enum { YQ_MIN_S = 0, YQ_NAN_S, YQ_MIN_N, YQ_NAN_N, YQ_CHANGE, YQ_YIELD_S, YQ_YIELD_N, YQ_MAX_ES, YQ_MAX_EC, YQ_N };
+__device__ inline double yq_comb(int q, double a, double b) {
+    if (q == YQ_MIN_S || q == YQ_MIN_N) return fmin(a, b);
+    if (q == YQ_YIELD_S || q == YQ_YIELD_N) return a + b;            // (counts: exact in any order)
+    return fmax(a, b);
+}
+__device__ inline double yq_unit(int q) { return (q == YQ_MIN_S || q == YQ_MIN_N) ? INFINITY : 0.0; }
+// acc of the 256 threads of a workgroup (wave w of 64 lanes) -> part[YQ_N b + q]
+__device__ inline void yq_block(const double (&acc)[YQ_N], int lane, int wave, double* __restrict__ part) {
+    __shared__ double sh[YQ_N][4];
+#pragma unroll
+    for (int q = 0; q < YQ_N; q++) {
+        double a = acc[q];
+        for (int o = 32; o > 0; o >>= 1) a = yq_comb(q, a, __shfl_down(a, o, 64));
+        if (lane == 0) sh[q][wave] = a;
+    }
+    __syncthreads();
+    const int t = wave * 64 + lane;
+    if (t < YQ_N) part[(size_t)YQ_N * ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) + t] =
+        yq_comb(t, yq_comb(t, yq_comb(t, sh[t][0], sh[t][1]), sh[t][2]), sh[t][3]);
+}
+// ms / mn: material viscosities; es / en: effective ones (in: the previous, out: the new); tau: tau_y at the nodes z_i, then at the cell
+// mid-points; floor: eta_floor
+struct Yield3 { const double* ms; const double* mn; double* es; double* en; const double* tau; double floor; };
+__device__ inline double yield_eta3(double mat, double tau, double e, double floor) {
+    double lim = tau / (2.0 * e);                   // e = 0: +inf, the material value stands
+    lim = lim > floor ? lim : floor;
+    return lim < mat ? lim : mat;
+}
+__global__ __launch_bounds__(256) void k3_yield_visc(Op3 op, V4 ce, Yield3 y, double* __restrict__ part) {
+    const G3& g = op.g;                             // one rank: local and global indices coincide
+    const int k = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, i = blockIdx.z;
+    double acc[YQ_N];
+#pragma unroll
+    for (int q = 0; q < YQ_N; q++) acc[q] = yq_unit(q);
+    if (k < g.n[2] && j < g.n[1]) {                 // (no early return: every thread takes part in the reduction)
+        const long long c = i3(g, i, j, k);
+        double Y, T, P;
+        node_sums3(op, ce, c, i, j, k, Y, T, P);
+        const double e_s = sqrt(0.5 * Y);           // the strainrate field of k3_strain_node, bit for bit
+        const double mat_s = y.ms[c], prev_s = y.es[c];
+        const double new_s = yield_eta3(mat_s, y.tau[i], e_s, y.floor);
+        y.es[c] = new_s;
+        double mat_n = y.mn[c], prev_n = y.en[c], new_n = mat_n, e_c = 0.0;       // beyond the cells eta_n keeps the material value
+        if (i < g.n[0] - 1 && j < g.n[1] - 1 && k < g.n[2] - 1) {
+            double a = ce.p[0][c];
+#pragma unroll
+            for (int p = 0; p < 3; p++) {           // pair p = (D, E): the four edges at the nodes i_D, i_D + 1 x i_E, i_E + 1 of cell i_F
+                const long long sD = g.s[p], sE = g.s[(p + 1) % 3];
+                const double* __restrict__ q = ce.p[1 + p];
+                const double m = 0.25 * (((q[c] + q[c + sE]) + q[c + sD]) + q[c + sD + sE]);
+                a += 2.0 * m;
+            }
+            e_c = sqrt(0.5 * a);
+            new_n = yield_eta3(mat_n, y.tau[g.n[0] + i], e_c, y.floor);
+        }
+        y.en[c] = new_n;
+        if (new_s != new_s) acc[YQ_NAN_S] = 1.0; else acc[YQ_MIN_S] = new_s;
+        if (new_n != new_n) acc[YQ_NAN_N] = 1.0; else acc[YQ_MIN_N] = new_n;
+        acc[YQ_CHANGE] = fmax(fabs(log(new_s / prev_s)), fabs(log(new_n / prev_n)));
+        acc[YQ_YIELD_S] = new_s < mat_s ? 1.0 : 0.0;
+        acc[YQ_YIELD_N] = new_n < mat_n ? 1.0 : 0.0;
+        acc[YQ_MAX_ES] = e_s; acc[YQ_MAX_EC] = e_c;
+    }
+    yq_block(acc, threadIdx.x, threadIdx.y, part);
+}
+// workgroup g combines the partials [g chunk, (g + 1) chunk) of nb: thread t those at t, t + 256, ... of its chunk in that order, then the
+// 256 threads as above -> out[YQ_N g + q].  Two launches finish: YQ_GROUPS workgroups over the kernel's partials, one over theirs (one
+// workgroup alone walks 83 525 partials at 257^3 in 0.86 ms, longer than the kernel that wrote them).
+#define YQ_GROUPS 128
+__global__ __launch_bounds__(256) void k3_yield_finish(long long nb, long long chunk, const double* __restrict__ part, double* __restrict__ out) {
+    const long long b0 = blockIdx.x * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
+    double acc[YQ_N];
+#pragma unroll
+    for (int q = 0; q < YQ_N; q++) acc[q] = yq_unit(q);
+    for (long long b = b0 + threadIdx.x; b < b1; b += 256) {
+#pragma unroll
+        for (int q = 0; q < YQ_N; q++) acc[q] = yq_comb(q, acc[q], part[(size_t)YQ_N * b + q]);
+    }
+    yq_block(acc, threadIdx.x & 63, threadIdx.x >> 6, out);
+}
+static int yield_free3(pl3_ctx* ctx) {
+    for (double** q : {&ctx->ms, &ctx->mn, &ctx->ytau, &ctx->ypart}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    return 0;
+}
+// the effective viscosities become the material ones again, and the operator theirs
+static int yield_reset3(pl3_ctx* ctx) {
+    if (!ctx->yield_on || !ctx->op_ready) return 0;
+    const size_t bytes = (size_t)ctx->geom.d.vol * sizeof(double);
+    P3_HIP(ctx, hipMemcpyAsync(ctx->es, ctx->ms, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    P3_HIP(ctx, hipMemcpyAsync(ctx->en, ctx->mn, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    const double grav[3] = {ctx->op.grav[0], ctx->op.grav[1], ctx->op.grav[2]};
+    const int slave = ctx->op.slave;
+    stokes_op3(ctx, ctx->mat_mineta, grav);
+    ctx->op.slave = slave;
+    return 0;
+}
+extern "C" int pl3_stokes_set_yield(pl3_ctx* ctx, int on, double tau0, double dtau_dz, double eta_floor) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_set_yield: NULL context");
+    if (on) {
+        if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, "pl3_stokes_set_yield: the yield stress runs on one rank (this context has pl3_set_comm attached)");
+        if (!std::isfinite(tau0) || !std::isfinite(dtau_dz) || !std::isfinite(eta_floor))
+            return p3_fail(ctx, "pl3_stokes_set_yield: tau0 = " + num_str3(tau0) + ", dtau_dz = " + num_str3(dtau_dz) + ", eta_floor = " + num_str3(eta_floor) + " must all be finite");
+        const double depth = ctx->gcoord[0].back() - ctx->gcoord[0].front(), low = tau0 + dtau_dz * depth;
+        if (!(tau0 > 0.0) || !(low > 0.0))
+            return p3_fail(ctx, "pl3_stokes_set_yield: the yield stress tau_y = tau0 + dtau_dz (z - z[0]) must be positive throughout the box, got " + num_str3(tau0) +
+                                    " at z[0] and " + num_str3(low) + " at z[n - 1]");
+        if (!(eta_floor > 0.0)) return p3_fail(ctx, "pl3_stokes_set_yield: eta_floor = " + num_str3(eta_floor) + " must be positive");
+    }
+    if ((on != 0) == ctx->yield_on && (!on || (tau0 == ctx->ytau0 && dtau_dz == ctx->ydtau && eta_floor == ctx->yfloor))) return 0;
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    history_clear3(ctx);                            // solutions of another rheology are no start for this one
+    P3_TRY(yield_reset3(ctx));
+    if (!on) {
+        P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->yield_on = false; ctx->ytau0 = ctx->ydtau = ctx->yfloor = 0.0;
+        return yield_free3(ctx);
+    }
+    const G3& g = ctx->geom.d;
+    const int nz = g.gn[0];
+    if (!ctx->ms) {
+        const dim3 gr = grid3(g);
+        int rc = dmal(ctx, &ctx->ms, g.vol) || dmal(ctx, &ctx->mn, g.vol) || dmal(ctx, &ctx->ytau, 2 * nz) ||
+                 dmal(ctx, &ctx->ypart, (long long)YQ_N * ((long long)gr.x * gr.y * gr.z + YQ_GROUPS));
+        if (rc) { const std::string m = ctx->err; yield_free3(ctx); return p3_fail(ctx, "pl3_stokes_set_yield: " + m); }
+        if (ctx->op_ready) {                        // the coefficients set so far are the material ones
+            P3_HIP(ctx, hipMemcpyAsync(ctx->ms, ctx->es, (size_t)g.vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+            P3_HIP(ctx, hipMemcpyAsync(ctx->mn, ctx->en, (size_t)g.vol * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        }
+    }
+    const std::vector<double>& z = ctx->gcoord[0];
+    std::vector<double> tau(2 * (size_t)nz, 0.0);
+    for (int i = 0; i < nz; i++) tau[i] = tau0 + dtau_dz * (z[i] - z[0]);
+    for (int i = 0; i + 1 < nz; i++) tau[nz + i] = tau0 + dtau_dz * ((z[i + 1] + z[i]) / 2 - z[0]);
+    pl3_count_copy(ctx, tau.size() * sizeof(double));
+    P3_HIP(ctx, hipMemcpyAsync(ctx->ytau, tau.data(), tau.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->yield_on = true; ctx->ytau0 = tau0; ctx->ydtau = dtau_dz; ctx->yfloor = eta_floor;
+    return 0;
+}
+extern "C" int pl3_stokes_get_yield(pl3_ctx* ctx, int* on, double* tau0, double* dtau_dz, double* eta_floor) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_get_yield: NULL context");
+    if (on) *on = ctx->yield_on ? 1 : 0;
+    if (tau0) *tau0 = ctx->ytau0;
+    if (dtau_dz) *dtau_dz = ctx->ydtau;
+    if (eta_floor) *eta_floor = ctx->yfloor;
+    return 0;
+}
+// which = 0: the effective viscosities the operator holds; 1: the material ones (the same arrays unless a yield stress is set)
+extern "C" int pl3_stokes_get_coeffs(pl3_ctx* ctx, int which, double* etas, double* etan) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_get_coeffs: NULL context");
+    if (which != 0 && which != 1) return p3_fail(ctx, "pl3_stokes_get_coeffs: which = " + std::to_string(which) + " must be 0 (effective) or 1 (material)");
+    if (!ctx->op_ready) return p3_fail(ctx, "pl3_stokes_get_coeffs: no Stokes coefficients set (pl3_stokes_set_coeffs)");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    double* src[2] = {which && ctx->yield_on ? ctx->ms : ctx->es, which && ctx->yield_on ? ctx->mn : ctx->en};
+    if (etas) P3_TRY(download3(ctx, &src[0], 1, etas));
+    if (etan) P3_TRY(download3(ctx, &src[1], 1, etan));
+    return 0;
+}
+// the update for the velocities vel (three ringed arrays; not work vector 1): out = min eta_eff, change, yielded nodes, yielded cells,
+// max e_n, max e_c.  A change other than exactly 0 rebuilds the operator from the new coefficients (stokes_op3; the next solve rebuilds
+// the hierarchy) and, since the pressure unknown is scaled by Kcont, keeps the resident solution the same physical pressure.
+static int yield_run3(pl3_ctx* ctx, const Vec3& vel, double out[6]) {
+    const G3& g = ctx->geom.d;
+    const Vec3 ce = svec(ctx, 1);
+    const dim3 gr = grid3(g);
+    launch3(ctx, g, k3_strain_ce, ctx->op, cv3(vel), ctx->wallvel, wv4(ce));
+    launch3(ctx, g, k3_yield_visc, ctx->op, cv4(ce), Yield3{ctx->ms, ctx->mn, ctx->es, ctx->en, ctx->ytau, ctx->yfloor}, ctx->ypart);
+    const long long nb = (long long)gr.x * gr.y * gr.z, chunk = (nb + YQ_GROUPS - 1) / YQ_GROUPS;
+    double* groups = ctx->ypart + YQ_N * nb;           // the YQ_GROUPS partials of the first finishing launch
+    hipLaunchKernelGGL(k3_yield_finish, dim3(YQ_GROUPS), dim3(256), 0, ctx->stream, nb, chunk, (const double*)ctx->ypart, groups);
+    hipLaunchKernelGGL(k3_yield_finish, dim3(1), dim3(256), 0, ctx->stream, (long long)YQ_GROUPS, (long long)YQ_GROUPS, (const double*)groups, ctx->part);
+    P3_HIP(ctx, hipGetLastError());
+    pl3_count_copy(ctx, YQ_N * sizeof(double));
+    P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, YQ_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double* r = ctx->hpart;
+    const double mes = r[YQ_NAN_S] > 0.0 ? NAN : r[YQ_MIN_S], men = r[YQ_NAN_N] > 0.0 ? NAN : r[YQ_MIN_N];
+    const double mineta = (men < mes) ? men : mes;                  // the rule of pl3_stokes_set_coeffs
+    out[0] = mineta; out[1] = r[YQ_CHANGE]; out[2] = r[YQ_YIELD_S]; out[3] = r[YQ_YIELD_N]; out[4] = r[YQ_MAX_ES]; out[5] = r[YQ_MAX_EC];
+    if (out[1] != 0.0) {
+        const double kc_old = ctx->op.Kc;
+        const double grav[3] = {ctx->op.grav[0], ctx->op.grav[1], ctx->op.grav[2]};
+        const int slave = ctx->op.slave;
+        stokes_op3(ctx, mineta, grav);
+        ctx->op.slave = slave;
+        if (ctx->have_x && ctx->vec[11] && ctx->op.Kc != kc_old && std::isfinite(kc_old / ctx->op.Kc)) {
+            const Vec3 P = svec(ctx, 11).prs();
+            axpby3(ctx, P, kc_old / ctx->op.Kc, P, 0.0, P);
+            P3_HIP(ctx, hipGetLastError());
+        }
+    }
+    return 0;
+}
+static int yield_check3(pl3_ctx* ctx, const char* who, bool resident) {
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, std::string(who) + ": the yield stress runs on one rank (this context has pl3_set_comm attached)");
+    if (!ctx->op_ready) return p3_fail(ctx, std::string(who) + ": no Stokes coefficients set (pl3_stokes_set_coeffs)");
+    if (!ctx->yield_on) return p3_fail(ctx, std::string(who) + ": no yield stress set (pl3_stokes_set_yield)");
+    if (resident && !ctx->have_x) return p3_fail(ctx, std::string(who) + ": NULL velocities mean the solution of the last Stokes solve, and no solve has run on this context");
+    return 0;
+}
+extern "C" int pl3_stokes_yield_update(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double out[6]) {
+    if (!ctx) return p3_fail(nullptr, "pl3_stokes_yield_update: NULL context");
+    const bool given = vz || vx || vy;
+    if (given && !(vz && vx && vy)) return p3_fail(ctx, "pl3_stokes_yield_update: vz, vx, vy must be given all three or all NULL");
+    P3_TRY(yield_check3(ctx, "pl3_stokes_yield_update", !given));
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, given ? 3 : 14));
+    Vec3 vel = svec(ctx, 11).vel();
+    if (given) {
+        vel = svec(ctx, 0).vel();
+        const double* in[3] = {vz, vx, vy};
+        for (int q = 0; q < 3; q++) { double* d = vel[q]; P3_TRY(upload3(ctx, in[q], 1, &d)); }
+    }
+    double o[6];
+    P3_TRY(yield_run3(ctx, vel, o));
+    if (out) for (int q = 0; q < 6; q++) out[q] = o[q];
+    return 0;
+}
+// the same for the resident solution, for pl_step3.hip
+int pl3i_yield_update_dev(pl3_ctx* ctx, double out[6]) {
+    P3_TRY(yield_check3(ctx, "pl3_resident_step", true));
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, 14));
+    return yield_run3(ctx, svec(ctx, 11).vel(), out);
+}
+
 // ---- what the device-resident step (pl_step3.hip) needs of a context ----------------------------------------------------------
 int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     P3_HIP(ctx, hipSetDevice(ctx->device));
@@ -2953,6 +3214,7 @@ int pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v) {
     for (int q = 0; q < 4; q++) { v->X[q] = svec(ctx, 11)[q]; v->scratch[q] = svec(ctx, 0)[q]; }
     v->T = ctx->hvec[11]; v->have_x = ctx->have_x; v->have_T = ctx->have_T; v->noslip = ctx->noslip; v->wallvel = ctx->wallvel;
     v->wallflow = ctx->wallflow;
+    v->eta_eff[0] = ctx->es; v->eta_eff[1] = ctx->en; v->yield_on = ctx->yield_on;
     return 0;
 }
 // counts and bytes of the host <-> device copies of this context's pl3_* calls since the last reset: out = { copies of at least one

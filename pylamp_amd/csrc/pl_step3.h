@@ -23,6 +23,8 @@ struct Pl3DevView {
     Pl3WallFlow wallflow;                   // ... and the flow through them
     double* strain[3];                      // strainrate, stress, dissipation of the last pl3i_strain_fields_dev (Stokes work vector 2) ...
     bool have_strain;                       // ... and whether nothing has asked for the work vectors since
+    double* eta_eff[2];                     // the operator's (effective) viscosities etas, etan, ringed ...
+    bool yield_on;                          // ... and whether a yield stress is set (pl3_stokes_set_yield): they may then differ from the scattered ones
     void** slot;                            // opaque state owned by pl_step3.hip, released by pl3_step_free
 };
 // pl_3d.hip
@@ -30,6 +32,7 @@ int  pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v);
 int  pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3], double mineta);
 int  pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const double* const src[7], const int bc[6], const double bcvalue[6], double tstep);
 int  pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total);     // the fields of the resident solution; Hplain (NULL: none) += dissipation
+int  pl3i_yield_update_dev(pl3_ctx* ctx, double out[6]);     // pl3_stokes_yield_update for the resident solution
 void pl3_count_copy(pl3_ctx* ctx, size_t bytes);          // every host <-> device copy of a pl3_* entry point reports here
 // pl_mic3.hip (plain (nz, nx, ny) device arrays in and out)
 int  pl3i_mic_scatter(pl3_ctx* ctx, int nf, const int* columns, const int* avgscheme, const double* const tc[3], const int tn[3], double* dout);

@@ -18,6 +18,7 @@
 #define S3_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return pl3_fail(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 #define S3_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 #define S3_MAXPART 1024
+#define PL3_PICARD_CAP 32
 enum { S3_SUM = 0, S3_MIN = 1, S3_MAX = 2 };
 enum { S3_RHO = 0, S3_ETAS, S3_CP, S3_T, S3_H, S3_MAT, S3_ETAN, S3_KZ, S3_KX, S3_KY, S3_NPLAIN };       // slots of the scattered fields
 
@@ -195,13 +196,16 @@ struct Step3 {
     // that ran with one of them on
     bool shear_heating = false, strain_fields = false, have_strain = false;
     double dissipation_total = 0.0;
+    // pl3_step_set_picard, and what the Picard loop of the last step did (pl3_step_picard_report); it runs only with a yield stress set
+    int picard_maxit = 10; double picard_tol = 1e-2;
+    int picard_its = 0, picard_converged = 0; double picard_log[4 * PL3_PICARD_CAP] = {0};      // per iteration: change, yielded nodes, yielded cells, Stokes iterations
 };
 void pl3_step_free(void** slot) {
     delete (Step3*)*slot;
     *slot = nullptr;
 }
-static const char* const S3_NAMES[18] = {"rho", "etas", "cp", "T", "H", "mat", "etan", "kz", "kx", "ky", "velz", "velx", "vely", "pres", "temp",
-                                         "strainrate", "stress", "dissipation"};
+static const char* const S3_NAMES[20] = {"rho", "etas", "cp", "T", "H", "mat", "etan", "kz", "kx", "ky", "velz", "velx", "vely", "pres", "temp",
+                                         "strainrate", "stress", "dissipation", "etas_eff", "etan_eff"};
 
 struct S3Open { Pl3HostView h; Pl3DevView d; Step3* S; S3Dims dims; size_t N; };
 static int s3_open(pl3_ctx* ctx, const char* who, S3Open& o) {
@@ -328,6 +332,20 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     S3_TRY(pl3i_stokes_set_coeffs_dev(ctx, F + S3_ETAS * N, F + S3_ETAN * N, F + S3_RHO * N, cfg->use_grav ? cfg->grav : nullptr, mineta));
     S3_TRY(pl3_stokes_solve(ctx, nullptr, nullptr, 0, cfg->stokes_rtol, cfg->stokes_maxit, &rep->stokes));
     o.S->have_vel = true;
+    // 4a. yield stress (opt-in, pl3_stokes_set_yield): the Picard loop -- update the viscosities from the solution, solve again from it
+    // while the change is above the tolerance; as many updates as solves, everything below uses the last solution
+    o.S->picard_its = 0; o.S->picard_converged = 0;
+    if (o.d.yield_on) {
+        for (int n = 0;; n++) {
+            double y[6];
+            S3_TRY(pl3i_yield_update_dev(ctx, y));
+            double* l = o.S->picard_log + 4 * n;
+            l[0] = y[1]; l[1] = y[2]; l[2] = y[3]; l[3] = (double)rep->stokes.iterations;
+            o.S->picard_its = n + 1; o.S->picard_converged = y[1] <= o.S->picard_tol ? 1 : 0;
+            if (!(y[1] > o.S->picard_tol) || n + 1 >= o.S->picard_maxit) break;
+            S3_TRY(pl3_stokes_solve(ctx, nullptr, nullptr, 1, cfg->stokes_rtol, cfg->stokes_maxit, &rep->stokes));
+        }
+    }
     // 4b. strain rate, stress and dissipation of that solution (opt-in); with shear heating H += dissipation, one addition per node,
     // before the heat coefficients are taken from it
     if (o.S->shear_heating || o.S->strain_fields) {
@@ -389,9 +407,9 @@ extern "C" int pl3_get_field(pl3_ctx* ctx, const char* name, double* out) {
     const Step3& S = *o.S;
     int id = -1;
     std::string have;
-    for (int q = 0; q < 18; q++) {
+    for (int q = 0; q < 20; q++) {
         const bool ok = q < 10 ? S.have_scattered && (S.have_heat_fields || q == S3_RHO || q == S3_ETAS || q == S3_ETAN)
-                               : (q < 14 ? S.have_vel : (q == 14 ? S.have_temp : S.have_strain && o.d.have_strain));
+                               : (q < 14 ? S.have_vel : (q == 14 ? S.have_temp : (q < 18 ? S.have_strain && o.d.have_strain : S.have_vel && o.d.yield_on)));
         if (ok) have += std::string(have.empty() ? "" : ", ") + S3_NAMES[q];
         if (ok && !std::strcmp(name, S3_NAMES[q])) id = q;
     }
@@ -402,7 +420,7 @@ extern "C" int pl3_get_field(pl3_ctx* ctx, const char* name, double* out) {
     else if (id == 14) S3_TRY(pl3i_mic_buf(ctx, "s_temp", N, &src));
     else {
         S3_TRY(pl3i_mic_buf(ctx, "s_stage", 3 * N, &src));
-        hipLaunchKernelGGL(k_s3_layout, s3_blocks((long long)N), dim3(256), 0, o.d.stream, o.dims, id < 14 ? o.d.X[id - 10] : o.d.strain[id - 15], src, 0);
+        hipLaunchKernelGGL(k_s3_layout, s3_blocks((long long)N), dim3(256), 0, o.d.stream, o.dims, id < 14 ? o.d.X[id - 10] : (id < 18 ? o.d.strain[id - 15] : o.d.eta_eff[id - 18]), src, 0);
         S3_HIP(ctx, hipGetLastError());
     }
     pl3_count_copy(ctx, N * sizeof(double));
@@ -444,6 +462,30 @@ extern "C" int pl3_step_dissipation_total(pl3_ctx* ctx, double* total) {
     S3_TRY(s3_open(ctx, "pl3_step_dissipation_total", o));
     if (!o.S->have_strain) return pl3_fail(ctx, "pl3_step_dissipation_total: no resident step has run with shear heating or the strain fields on (pl3_step_set_shear_heating, pl3_step_set_strain_fields)");
     *total = o.S->dissipation_total;
+    return 0;
+}
+
+// The Picard loop of the resident step (it runs only with a yield stress set, pl3_stokes_set_yield): at most maxit (1 .. 32) Stokes solves
+// per step, stopped once the change max |ln(eta_new / eta_prev)| of an update is at most tol (>= 0).  10 and 1e-2 at creation.
+extern "C" int pl3_step_set_picard(pl3_ctx* ctx, int maxit, double tol) {
+    if (!ctx) return pl3_fail(nullptr, "pl3_step_set_picard: NULL context");
+    if (maxit < 1 || maxit > PL3_PICARD_CAP)
+        return pl3_fail(ctx, "pl3_step_set_picard: maxit = " + std::to_string(maxit) + " must be 1 .. " + std::to_string(PL3_PICARD_CAP));
+    if (!(tol >= 0.0)) return pl3_fail(ctx, "pl3_step_set_picard: tol = " + std::to_string(tol) + " must be >= 0");
+    S3Open o;
+    S3_TRY(s3_open(ctx, "pl3_step_set_picard", o));
+    o.S->picard_maxit = maxit; o.S->picard_tol = tol;
+    return 0;
+}
+// out[0] iterations of the last resident step's Picard loop (0: it did not run), out[1] converged, then per iteration change, yielded
+// nodes, yielded cells, Stokes iterations; n: the capacity of out (2 + 4 x 32 holds everything), entries beyond it are not written
+extern "C" int pl3_step_picard_report(pl3_ctx* ctx, double* out, int n) {
+    if (!ctx) return pl3_fail(nullptr, "pl3_step_picard_report: NULL context");
+    if (!out || n < 2) return pl3_fail(ctx, "pl3_step_picard_report: out needs room for at least 2 entries");
+    S3Open o;
+    S3_TRY(s3_open(ctx, "pl3_step_picard_report", o));
+    out[0] = o.S->picard_its; out[1] = o.S->picard_converged;
+    for (int q = 0; q < 4 * o.S->picard_its && 2 + q < n; q++) out[2 + q] = o.S->picard_log[q];
     return 0;
 }
 

@@ -329,6 +329,38 @@ class Context3:
         self.check(self.lib.pl3_step_dissipation_total(self.handle(), C.byref(t)))
         return t.value
 
+    def set_yield(self, tau0, dtau_dz=0.0, eta_floor=None, on=True):
+        """Yield stress of the Stokes operator of this context (off at creation): tau_y = tau0 + dtau_dz (z - z[0]) [Pa], and the floor
+        eta_floor [Pa s] of the effective viscosity (None: the smallest positive float64, no floor).  on=False (or tau0 None)
+        switches it off.  yield_update then limits the viscosities; the definition is in include/pylamp_hip.h at
+        pl3_stokes_set_yield.  One rank."""
+        if not on or tau0 is None:
+            self.check(self.lib.pl3_stokes_set_yield(self.handle(), 0, 0.0, 0.0, 0.0))
+            return
+        floor = np.finfo(np.float64).tiny if eta_floor is None else float(eta_floor)
+        self.check(self.lib.pl3_stokes_set_yield(self.handle(), 1, float(tau0), float(dtau_dz), floor))
+
+    def yield_setting(self):
+        """(tau0, dtau_dz, eta_floor) of set_yield, or None: off."""
+        on = C.c_int(); v = [C.c_double() for _ in range(3)]
+        self.check(self.lib.pl3_stokes_get_yield(self.handle(), C.byref(on), *[C.byref(a) for a in v]))
+        return tuple(a.value for a in v) if on.value else None
+
+    def set_picard(self, maxit, tol):
+        """The Picard loop of the resident step of this context (it runs with a yield stress set): at most maxit (1 .. 32) Stokes solves,
+        stopped once the change of a viscosity update is at most tol (>= 0)."""
+        self.check(self.lib.pl3_step_set_picard(self.handle(), int(maxit), float(tol)))
+
+    def picard_report(self):
+        """What the Picard loop of the last resident step did: iterations (0: no yield stress was set), converged, and per iteration the
+        change, the yielded nodes and cells and the iterations of its Stokes solve."""
+        o = np.zeros(2 + 4 * PICARD_MAXIT_CAP)
+        self.check(self.lib.pl3_step_picard_report(self.handle(), _lib.dptr(o), o.size))
+        n = int(o[0])
+        rows = o[2:2 + 4 * n].reshape(n, 4)
+        return dict(iterations=n, converged=bool(o[1]), change=[float(v) for v in rows[:, 0]], yielded_nodes=[int(v) for v in rows[:, 1]],
+                    yielded_cells=[int(v) for v in rows[:, 2]], stokes_iterations=[int(v) for v in rows[:, 3]])
+
     def set_marker_search(self, on):
         """Per-axis cell search for the 3-D marker kernels of this context (rectilinear grids; default off = the regular-grid
         formula).  Resident tracers are re-sorted by the new rule."""
@@ -590,7 +622,7 @@ class StokesOperator3:
 
 
 def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device=0, ctx=None, strict_reference=True, wallvel=None,
-                     wallflow=None):
+                     wallflow=None, yield_stress=None):
     """3-D counterpart of pylamp_stokes.makeStokesMatrix: f_etas at the NODES (averaged onto the edges by the kernels),
     f_etan at the cell centres, f_rho at the nodes; bc = [z0, x0, y0, zL, xL, yL], each BC_TYPE_FREESLIP or BC_TYPE_NOSLIP.
     bc=None leaves the walls of the context as they are: all free-slip on a new context, or what Context3.set_stokes_walls /
@@ -605,7 +637,10 @@ def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device
     of the context as they are (at rest on a new context).  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_velocity.
     wallflow: the flow through the six walls (wall_flows: six entries, each None, a scalar or the plane Un of the wall-normal
     velocity); it enters the returned right-hand side likewise, and its net flux must vanish.  None leaves the flow of the context as
-    it is (none on a new context); six None clear it.  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_flow."""
+    it is (none on a new context); six None clear it.  The rule is in include/pylamp_hip.h at pl3_stokes_set_wall_flow.
+    yield_stress: tau0 [Pa], (tau0, dtau_dz) or (tau0, dtau_dz, eta_floor) sets the yield stress of the context (Context3.set_yield), False
+    switches it off, None leaves it as it is (off on a new context).  The operator starts with the material viscosities either way;
+    yield_update(A, x) limits them."""
     walls = None if bc is None else stokes_walls(bc)
     vel = None if wallvel is None else wall_velocities(wallvel, walls)
     flows = None if wallflow is None else wall_flows(wallflow, nx)
@@ -618,6 +653,13 @@ def makeStokesMatrix(nx, grid, f_etas, f_etan, f_rho, bc=None, grav=None, device
         ctx.set_stokes_walls(walls)
     if vel is not None:
         ctx.set_wall_velocity(vel)
+    if yield_stress is False:
+        ctx.set_yield(None)
+    elif yield_stress is not None:
+        ys = (float(yield_stress),) if np.ndim(yield_stress) == 0 else tuple(yield_stress)
+        if not 1 <= len(ys) <= 3:
+            raise Exception("3-D Stokes: yield_stress needs tau0, (tau0, dtau_dz) or (tau0, dtau_dz, eta_floor), got %r" % (yield_stress,))
+        ctx.set_yield(*ys)
     shp = ctx.nx
     es, en, rho = _f3(f_etas, shp), _f3(f_etan, shp), _f3(f_rho, shp)
     g = None if grav is None else (C.c_double * 3)(*[float(v) for v in grav])
@@ -668,6 +710,75 @@ def strain_fields(A, x=None):
     ctx.check(ctx.lib.pl3_stokes_strain_fields(ctx.handle(), v[0], v[1], v[2], *[_lib.dptr(out[k]) for k in STRAIN_FIELDS], C.byref(tot)))
     out["dissipation_total"] = tot.value
     return out
+
+
+PICARD_MAXIT_CAP = 32               # most Stokes solves of one step's Picard loop (pl3_step_set_picard)
+YIELD_UPDATE_KEYS = ("min_eta", "change", "yielded_nodes", "yielded_cells", "max_strainrate_nodes", "max_strainrate_cells")
+
+
+def yield_setting(value, who="yield_stress"):
+    """(tau0, dtau_dz) of a yield_stress value: None / False -> None, off; a number tau0 -> (tau0, 0.0); a pair (tau0, dtau_dz)."""
+    if value is None or value is False:
+        return None
+    try:
+        pair = (float(value), 0.0) if np.ndim(value) == 0 else tuple(float(v) for v in value)
+    except (TypeError, ValueError):
+        pair = ()
+    if len(pair) != 2 or isinstance(value, (bool, np.bool_)):
+        raise Exception("%s: expected None, a yield stress tau0 [Pa] or a pair (tau0, dtau_dz), got %r" % (who, value))
+    return pair
+
+
+def yield_update(A, x=None):
+    """Limit the viscosities of A's operator by the yield stress of its context (Context3.set_yield) for the velocities of the solution
+    vector x (nz nx ny 4), or with x=None for the solution of the last solve(A), still on the device:
+    eta_eff = min(eta_mat, max(tau_y / (2 e), eta_floor)) at the nodes and the cell centres, always from the material viscosities.
+    Returns min_eta, change = max |ln(eta_new / eta_prev)|, yielded_nodes, yielded_cells and the largest node and centre strain-rate
+    invariants; coefficients(A) fetches the arrays.  The definition is in include/pylamp_hip.h at pl3_stokes_set_yield.  One rank."""
+    ctx = A._ctx
+    if x is None:
+        v = [None, None, None]
+    else:
+        x = _lib.f64(x).reshape(-1)
+        if x.size != A.shape[0]:
+            raise Exception("dimension mismatch")
+        v = [_lib.dptr(np.ascontiguousarray(c)) for c in x2vp(x, ctx.nx)[0]]
+    o = np.zeros(6)
+    ctx.check(ctx.lib.pl3_stokes_yield_update(ctx.handle(), v[0], v[1], v[2], _lib.dptr(o)))
+    out = dict(zip(YIELD_UPDATE_KEYS, (float(a) for a in o)))
+    out["yielded_nodes"], out["yielded_cells"] = int(o[2]), int(o[3])
+    return out
+
+
+def picard_loop(A, picard_maxit, picard_tol, rtol=DEFAULT_RTOL, maxit=DEFAULT_MAXIT):
+    """The Picard loop of a step with a yield stress, after the first solve(A) (with the material viscosities) has left its solution on
+    the device: update the viscosities (yield_update); while the change is above picard_tol and fewer than picard_maxit solves have run,
+    solve again from the resident solution and update again.  As many updates as solves; reaching picard_maxit is no error.  Returns
+    iterations, converged (the last change <= picard_tol) and per iteration change, yielded_nodes, yielded_cells and the iterations of its
+    Stokes solve; solution(A) and coefficients(A) fetch the last solution and the last effective viscosities."""
+    if isinstance(picard_maxit, (bool, np.bool_)) or not isinstance(picard_maxit, (int, np.integer)) or not 1 <= picard_maxit <= PICARD_MAXIT_CAP:
+        raise Exception("picard_loop: picard_maxit = %r must be an integer 1 .. %d" % (picard_maxit, PICARD_MAXIT_CAP))
+    if not float(picard_tol) >= 0:
+        raise Exception("picard_loop: picard_tol = %r must be >= 0" % (picard_tol,))
+    rep = dict(iterations=0, converged=False, change=[], yielded_nodes=[], yielded_cells=[], stokes_iterations=[])
+    while True:
+        u = yield_update(A)                      # (of the solution on the device)
+        rep["iterations"] += 1
+        rep["change"].append(u["change"]); rep["yielded_nodes"].append(u["yielded_nodes"]); rep["yielded_cells"].append(u["yielded_cells"])
+        rep["stokes_iterations"].append(int(A.last_stats["iterations"]))
+        rep["converged"] = bool(u["change"] <= picard_tol)
+        if not u["change"] > picard_tol or rep["iterations"] >= picard_maxit:
+            return rep
+        solve(A, rtol=rtol, maxit=maxit, resident=True, warm=True)
+
+
+def coefficients(A, material=False):
+    """(etas, etan) of A's operator, (nz, nx, ny) each: the effective viscosities it solves with, or with material=True the material
+    ones it was given (the same arrays unless a yield stress is set and yield_update has run)."""
+    ctx = A._ctx
+    es, en = np.empty(ctx.nx), np.empty(ctx.nx)
+    ctx.check(ctx.lib.pl3_stokes_get_coeffs(ctx.handle(), 1 if material else 0, _lib.dptr(es), _lib.dptr(en)))
+    return es, en
 
 
 class HeatOperator3:
@@ -1102,11 +1213,20 @@ class Options3:
         # step is bit for bit what it is without them
         self.shear_heating = False
         self.strain_fields = False
+        # beyond the reference: a yield stress limits the viscosity of the Stokes solve, eta_eff = min(eta, max(tau_y / (2 e), floor)) with
+        # e the second invariant of the strain rate and tau_y = tau0 + dtau_dz z (Context3.set_yield).  None: off; tau0 [Pa]; or
+        # (tau0, dtau_dz).  yield_eta_floor: the floor [Pa s], None = etamin.  Every step then runs a Picard loop of Stokes solves;
+        # picard_maxit (1 .. 32) and picard_tol (the change max |ln(eta_new / eta_prev)| at which it stops) are user settings, and these
+        # defaults a choice: ten solves bound the cost of a step, 1e-2 is a 1 % change of the viscosity
+        self.yield_stress = None
+        self.yield_eta_floor = None
+        self.picard_maxit, self.picard_tol = 10, 1e-2
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise Exception("unknown option " + k)
             setattr(self, k, v)
         warm_start_setting(self.stokes_warm_start)
+        yield_setting(self.yield_stress, "Options3.yield_stress")
 
 
 class Simulation3:
@@ -1149,6 +1269,11 @@ class Simulation3:
     RK4: Options3.rk4_classic = True makes the tracers move by U tstep (the reference's RK4 weights, the default, move them by 2/3
     of that).
 
+    Yield stress: Options3.yield_stress = tau0 or (tau0, dtau_dz) limits the viscosity of the Stokes solve, eta_eff = min(eta,
+    max(tau_y / (2 e), floor)) (Context3.set_yield), and every step runs a Picard loop of at most Options3.picard_maxit Stokes solves
+    until the change of the viscosities is at most Options3.picard_tol (picard_loop); step() reports it as rep["picard"], field()
+    knows etas_eff and etan_eff.
+
     Not built: surface stabilisation, several ranks -- each is rejected with an error that names it."""
 
     def __init__(self, nx, L, tr_x=None, tr_f=None, options=None, device=0, grid=None):
@@ -1189,6 +1314,12 @@ class Simulation3:
         self.shear_heating, self.strain_fields = bool(o.shear_heating), bool(o.strain_fields)
         if self.shear_heating and not o.do_heatdiff:
             raise Exception("Simulation3: Options3.shear_heating = True needs the heat solve, Options3.do_heatdiff = True")
+        self.yield_stress = yield_setting(o.yield_stress, "Simulation3: Options3.yield_stress")
+        if self.yield_stress is not None:
+            if isinstance(o.picard_maxit, (bool, np.bool_)) or not isinstance(o.picard_maxit, (int, np.integer)) or not 1 <= o.picard_maxit <= PICARD_MAXIT_CAP:
+                raise Exception("Simulation3: Options3.picard_maxit = %r must be an integer 1 .. %d" % (o.picard_maxit, PICARD_MAXIT_CAP))
+            if not float(o.picard_tol) >= 0:
+                raise Exception("Simulation3: Options3.picard_tol = %r must be >= 0" % (o.picard_tol,))
         self.bcstokes = stokes_walls(o.bcstokes, "Simulation3: Options3.bcstokes")
         self.bcstokesflow = self._checked_flow(o.bcstokesflow, "Simulation3: Options3.bcstokesflow")
         wall_materials(o.bcinflow, self.nx, "Simulation3: Options3.bcinflow")
@@ -1210,6 +1341,9 @@ class Simulation3:
         self.warm_start = warm_start_setting(o.stokes_warm_start, "Simulation3: Options3.stokes_warm_start")
         if self.warm_start[0]:
             self.ctx.set_warm_start(*self.warm_start)
+        if self.yield_stress is not None:
+            self.ctx.set_yield(*self.yield_stress, eta_floor=o.etamin if o.yield_eta_floor is None else o.yield_eta_floor)
+            self.ctx.set_picard(o.picard_maxit, o.picard_tol)        # (read by the resident step; the staged one runs the same loop below)
         if o.resident and self.shear_heating:
             self.ctx.set_shear_heating(True)
         if o.resident and self.strain_fields:
@@ -1335,7 +1469,8 @@ class Simulation3:
     def field(self, name):
         """A grid field of the last step: rho, etas, etan, cp, T, H, mat, kz, kx, ky, velz, velx, vely, pres, temp; with
         Options3.shear_heating or Options3.strain_fields also strainrate, stress, dissipation (H then includes the dissipation if
-        shear_heating is on)."""
+        shear_heating is on); with Options3.yield_stress also etas_eff, etan_eff, the effective viscosities after the step's Picard loop
+        (etas, etan stay the scattered material fields)."""
         if self.opt.resident and name not in self.fields:
             out = np.empty(self.nx)
             self._lib_call("pl3_get_field", name.encode(), _lib.dptr(out))
@@ -1478,6 +1613,8 @@ class Simulation3:
             rep["stokes_start"] = self.ctx.history_info()["start"]
         if self.shear_heating or self.strain_fields:
             rep["dissipation_total"] = self.ctx.dissipation_total()
+        if self.yield_stress is not None:
+            rep["picard"] = self.ctx.picard_report()
         self.fields = {}
         self._stepped = True
         self.last = rep
@@ -1507,6 +1644,11 @@ class Simulation3:
         A, _ = makeStokesMatrix(self.nx, self.grid, f["etas"], f["etan"], f["rho"], bc=self.bcstokes, grav=o.grav, ctx=self.ctx,
                                 wallvel=self.bcstokesvel)
         x = solve(A, rtol=o.stokes_rtol, maxit=o.stokes_maxit)
+        picard = None
+        if self.yield_stress is not None:        # the Picard loop of pl3_resident_step
+            picard = picard_loop(A, o.picard_maxit, o.picard_tol, rtol=o.stokes_rtol, maxit=o.stokes_maxit)
+            x = solution(A)                      # (the last update keeps its Kcont-scaled pressure in step with the operator's new scaling)
+            f["etas_eff"], f["etan_eff"] = coefficients(A)
         newvel, pres = x2vp(x, self.nx)
         with np.errstate(divide="ignore"):       # (a fluid at rest: the clamp below takes tstep_adv_max)
             tstep_stokes = o.tstep_modifier * np.min(dx) / max(np.max(v) for v in newvel)
@@ -1546,6 +1688,8 @@ class Simulation3:
             rep["stokes_start"] = self.ctx.history_info()["start"]
         if self.shear_heating or self.strain_fields:
             rep["dissipation_total"] = dissipation_total
+        if picard is not None:
+            rep["picard"] = picard
         self.fields = f
         self.last = rep
         return rep
@@ -1559,9 +1703,13 @@ class Simulation3:
                 f["temp"] = self.field("temp")
             if self.shear_heating or self.strain_fields:
                 f.update({k: self.field(k) for k in STRAIN_FIELDS})
+            if self.yield_stress is not None:
+                f.update({k: self.field(k) for k in ("etas_eff", "etan_eff")})
         else:
             f = self.fields
         extra = {k: f[k] for k in STRAIN_FIELDS} if self.shear_heating or self.strain_fields else {}
+        if self.yield_stress is not None:
+            extra.update(etas_eff=f["etas_eff"], etan_eff=f["etan_eff"])
         temp = f["temp"] if "temp" in f else f["velx"] * 0.0
         tr_x, tr_f = self.tracers(); tr_v = self.tracer_velocity()
         os.makedirs(outdir, exist_ok=True)

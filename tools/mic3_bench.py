@@ -42,6 +42,7 @@ otherwise.  --resident selects Options3.resident (one pl3_resident_step call per
 --warm switches Options3.stokes_warm_start on (three solutions kept, quadratic extrapolation) and adds how the timed solves started
 and the guard's residuals; writes profiles/mic3_step_129_warm.json unless --out says otherwise (profiles/stokes3_warm.json holds the
 medians of three such processes alternating with three without --warm).
+--yield TAU switches Options3.yield_stress on (with --picard-maxit / --picard-tol) and adds every timed step's Picard figures.
 --shear-heating switches Options3.shear_heating on (the dissipation of the Stokes solution is added to H before the heat solve; --out is
 wanted: profiles/strain3.json holds the medians of three such processes next to three without).
 --tree DIR imports pylamp_amd from another checkout: the host-staged yardstick is run on the parent commit's library, in
@@ -229,9 +230,11 @@ def step_bench(a):
         kw["stokes_warm_start"] = True
     if a.shear_heating:
         kw["shear_heating"] = True
+    if a.yield_stress is not None:
+        kw.update(yield_stress=a.yield_stress, picard_maxit=a.picard_maxit, picard_tol=a.picard_tol)
     sim = P3.Simulation3(nx, L, tr_x, tr_f, P3.Options3(**kw, **_delete_kw(a)))
     del tr_x, tr_f
-    wall, stages, its, starts, guard = [], {}, [], [], []
+    wall, stages, its, starts, guard, picard = [], {}, [], [], [], []
     for rep in range(a.warmup + a.reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -241,6 +244,8 @@ def step_bench(a):
         assert r["stokes"]["converged"] == 1 and r["heat"]["converged"] == 1, r
         if rep >= a.warmup:
             wall.append(ms); its.append(r["stokes"]["iterations"])
+            if "picard" in r:
+                picard.append(r["picard"])
             if a.warm:
                 h = sim.ctx.history_info()
                 starts.append(r["stokes_start"]); guard.append(h["r0"] / h["ref"] if h["ref"] > 0 else None)
@@ -253,6 +258,8 @@ def step_bench(a):
                stage_ms={k: round(float(np.median(v)), 3) for k, v in stages.items()})
     if a.shear_heating:
         out.update(shear_heating=True, dissipation_total=r["dissipation_total"])
+    if picard:          # (stage_ms["stokes"] is the LAST solve of a step's Picard loop)
+        out.update(yield_stress=a.yield_stress, picard_maxit=a.picard_maxit, picard_tol=a.picard_tol, picard=picard)
     if a.warm:          # r0_over_ref: the guard's |r0| / ref of every timed solve (below 1: the extrapolated start was taken)
         out.update(warm_start=list(sim.warm_start), stokes_start=starts, r0_over_ref=[None if g is None else float("%.3e" % g) for g in guard])
     # what the stage times do not cover: host work and copies (staged: "scatter" is the LAST of the step's five scatters alone)
@@ -276,6 +283,8 @@ def main():
     ap.add_argument("--search", action="store_true"); ap.add_argument("--graded", type=float, default=0.0)
     ap.add_argument("--delete", action="store_true"); ap.add_argument("--off", nargs="*", default=[])
     ap.add_argument("--inflow", action="store_true")
+    ap.add_argument("--yield", dest="yield_stress", type=float, default=None); ap.add_argument("--picard-maxit", type=int, default=10)
+    ap.add_argument("--picard-tol", type=float, default=1e-2)
     for name in ("--parent-sort", "--this-sort", "--parent-step", "--this-step"):
         ap.add_argument(name, nargs="*", default=[])
     a = ap.parse_args()
