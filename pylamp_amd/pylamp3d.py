@@ -1606,9 +1606,10 @@ class Simulation3:
         self.totaltime += r.tstep
         rep = dict(it=self.it, tstep=r.tstep, limiter="H" if r.limiter else "S", stokes=r.stokes.as_dict(),
                    heat=r.heat.as_dict() if o.do_heatdiff else None, ninjected=int(r.ninjected), nrefilled=int(r.nrefilled),
-                   nempty=int(r.nempty), mincount=int(r.mincount), nremoved=int(r.nremoved), time=self.totaltime, ntrac=self.ntrac)
-        if self._inflow:
+                   nempty=int(r.nempty), mincount=int(r.mincount), nremoved=int(r.nremoved))
+        if self._inflow:                         # (the staged step's key order: the counters of the sort, then time and ntrac)
             rep["ninflow"] = self.ctx.inflow_count()[0]
+        rep.update(time=self.totaltime, ntrac=self.ntrac)
         if self.warm_start[0]:
             rep["stokes_start"] = self.ctx.history_info()["start"]
         if self.shear_heating or self.strain_fields:

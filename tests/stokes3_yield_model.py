@@ -16,6 +16,7 @@ the entry is ambiguous: |eta_mat - max(tau_y / (2 e), eta_floor)| <= B, which th
 """
 import numpy as np
 
+import stokes3_flow_model as F
 import stokes3_model as M
 import stokes3_moving_model as V
 import stokes3_strain_model as S
@@ -92,15 +93,19 @@ def node_stress(nx, grid, etas, etan, v, bc=None, wallvel=None):
     return S.strain_fields(nx, grid, etas, etan, v, bc=bc, wallvel=wallvel)["stress"]
 
 
-def direct(nx, grid, etas, etan, rho, bc=None, wallvel=None, grav=None, strict=True, reuse=None, keep=None):
+def direct(nx, grid, etas, etan, rho, bc=None, wallvel=None, grav=None, strict=True, reuse=None, keep=None, wallflow=None):
     """The model's direct solve of the operator's own right-hand side with the viscosities (etas, etan): the flat float64 solution, the
-    pressure Kcont-scaled.  reuse: a solver of a nearby operator (one `keep` has received) whose factors precondition the refinement
+    pressure Kcont-scaled.  wallflow (None: no flow): the flow through the six walls, which enters the right-hand side alone
+    (stokes3_flow_model.stokes_rhs).  reuse: a solver of a nearby operator (one `keep` has received) whose factors precondition the refinement
     with THIS operator's longdouble residual -- the same solution to the same tolerance, without a factorisation of its own; if the
     refinement does not get there, the operator is factorised after all.  keep (a list): gains the solver used."""
     n = [int(k) for k in nx]
     es, en = np.asarray(etas, dtype=np.float64), np.asarray(etan, dtype=np.float64)
     ap = lambda x, rounded=True: W.stokes_apply(n, grid, es, en, x, bc=bc, strict=strict, rounded=rounded)
-    b = V.stokes_rhs(n, grid, es, en, rho, grav=grav, bc=bc, wallvel=wallvel, strict=strict)
+    if wallflow is None:
+        b = V.stokes_rhs(n, grid, es, en, rho, grav=grav, bc=bc, wallvel=wallvel, strict=strict)
+    else:
+        b = F.stokes_rhs(n, grid, es, en, rho, grav=grav, bc=bc, wallvel=wallvel, wallflow=wallflow, strict=strict)
     if reuse is not None:
         near = M.DirectSolver.__new__(M.DirectSolver)
         near.apply, near.dr, near.dc, near.lu = ap, reuse.dr, reuse.dc, reuse.lu
@@ -115,10 +120,10 @@ def direct(nx, grid, etas, etan, rho, bc=None, wallvel=None, grav=None, strict=T
 
 
 def picard(nx, grid, etas, etan, rho, tau0, dtau_dz, eta_floor, maxit, tol=0.0, bc=None, wallvel=None, grav=None, strict=True, perturb=None,
-           reuse=None):
+           reuse=None, wallflow=None):
     """The loop of the step: solve with the material viscosities, update, and while the change is above tol and fewer than maxit solves
     have run solve with the effective ones and update again.  perturb (None: nothing) is called as perturb(x) on every direct solution and
-    returns the vector the loop goes on with.  reuse: the `solvers` of an earlier, nearby run (see direct).  Returns a dict: solvers (one per
+    returns the vector the loop goes on with.  wallflow: as in direct.  reuse: the `solvers` of an earlier, nearby run (see direct).  Returns a dict: solvers (one per
     iteration), x (the last solution), etas_eff, etan_eff (after the last update), change
     (per iteration), yielded_nodes, yielded_cells, converged."""
     n = [int(k) for k in nx]
@@ -127,7 +132,7 @@ def picard(nx, grid, etas, etan, rho, tau0, dtau_dz, eta_floor, maxit, tol=0.0, 
     prev = None
     while True:
         k = len(out["change"])
-        x = direct(n, grid, es, en, rho, bc=bc, wallvel=wallvel, grav=grav, strict=strict, keep=out["solvers"],
+        x = direct(n, grid, es, en, rho, bc=bc, wallvel=wallvel, grav=grav, strict=strict, keep=out["solvers"], wallflow=wallflow,
                    reuse=reuse[k] if reuse is not None and k < len(reuse) else None)
         if perturb is not None:
             x = perturb(x)
