@@ -15,6 +15,7 @@
 // coarse operators with natural wall rows, arithmetic viscosity coarsening) for A_vv.  One GPU per problem.
 #include "pl_internal.h"
 #include "pl_mic3.h"
+#include "pl_reduce3.h"
 #include "pl_step3.h"
 #include "pl_walls3.h"
 #include "pl_x0.h"
@@ -996,25 +997,14 @@ __global__ void k3_x0_start(long long n, X0Start3 a, double* __restrict__ x) {
     }
 }
 #define D3_BLOCKS 1024
-// the end of every reduction kernel (256 threads): part[NQ b + q] = the sum of acc[q] over workgroup b -- a shuffle tree per wave, then
-// the four wave sums in order
-template <int NQ> __device__ inline void block_sums3(const double (&acc)[NQ], double* __restrict__ part) {
-    __shared__ double sh[NQ][4];
-    for (int q = 0; q < NQ; q++) {
-        double a = acc[q];
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < NQ) part[NQ * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
-}
+// (every reduction kernel below ends in r3_block of pl_reduce3.h with all-sum slots: part[NQ b + q] = the sum of acc[q] over workgroup b)
 // up to five dot products in one pass: part[5 b + q] = sum a_q[t] b_q[t]
 struct Dot5 { const double* a[5]; const double* b[5]; int n; };
 __global__ __launch_bounds__(256) void k3_dots(long long n, Dot5 d, double* __restrict__ part) {
     double acc[5] = {0, 0, 0, 0, 0};
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256)
         for (int q = 0; q < d.n; q++) acc[q] += d.a[q][t] * d.b[q][t];
-    block_sums3<5>(acc, part);
+    r3_block<R3All<R3_SUM, 5>>(acc, threadIdx.x, blockIdx.x, part);
 }
 // The second reduction point of BiCGStab with everything the velocity-error estimate needs, in ONE pass (one rank; vectors of 4 consecutive
 // arrays of `vol` elements, the pressure array last): part[11 b + ..] = t.s, t.t, r~.s, r~.t, s.s | the same three of the pressure array
@@ -1032,7 +1022,7 @@ __global__ __launch_bounds__(256) void k3_dots11(Fuse11 a, double* __restrict__ 
             if (a.yw) { const double Y = a.yw[e - np]; acc[9] += Y * S; acc[10] += Y * T; }
         } else if (a.x) { const double X = a.x[e] + (a.dx ? a.dx[e] : 0.0); acc[8] += X * X; }
     }
-    block_sums3<11>(acc, part);
+    r3_block<R3All<R3_SUM, 11>>(acc, threadIdx.x, blockIdx.x, part);
 }
 // x += alpha y + omega z, r = s - omega t, and the NEXT direction p = r + beta (p - omega v) in the same pass
 __global__ void k3_xrp_update(long long n, double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z, double* __restrict__ r,
@@ -1148,7 +1138,7 @@ __global__ __launch_bounds__(256) void k3_heat_budget(Heat3 op, const double* __
             if (idx[a] == g.gn[a] - 2) acc[a + 3] += op.kk[a][c] * (T[c + g.s[a]] - tc) * TB(g.rd[a], g.gn[a] - 2) * area;
         }
     }
-    block_sums3<8>(acc, part);
+    r3_block<R3All<R3_SUM, 8>>(acc, threadIdx.x, blockIdx.x, part);
 }
 
 // ---- host <-> device layout ------------------------------------------------------------------------------------------
@@ -1189,7 +1179,7 @@ __global__ __launch_bounds__(256) void k3_dots_own(G3 g, int na, Dot5 d, double*
         for (int kk = threadIdx.x; kk < g.n[2]; kk += 256)
             for (int u = 0; u < d.n; u++) acc[u] += d.a[u][base + kk] * d.b[u][base + kk];
     }
-    block_sums3<5>(acc, part);
+    r3_block<R3All<R3_SUM, 5>>(acc, threadIdx.x, blockIdx.x, part);
 }
 // sum |v| over the entries of na consecutive arrays that lie OUTSIDE the owned block (the ring of nodes in z and x, the padding of the
 // y-lines): part[5 b] -- what the flat kernels above rely on being zero on one rank (pl3_stokes_ring_sum)
@@ -1200,7 +1190,7 @@ __global__ __launch_bounds__(256) void k3_ring_abs(G3 g, int na, const double* _
         if (li >= 0 && li < g.n[0] && lj >= 0 && lj < g.n[1] && lk >= 0 && lk < g.n[2]) continue;
         for (int q = 0; q < na; q++) acc[0] += fabs(v[q * g.vol + e]);
     }
-    block_sums3<5>(acc, part);
+    r3_block<R3All<R3_SUM, 5>>(acc, threadIdx.x, blockIdx.x, part);
 }
 
 // =====================================================================================================================
@@ -1606,6 +1596,20 @@ static void stokes_op3(pl3_ctx* ctx, double mineta, const double grav[3]) {
     op.anchor[0] = 3; op.anchor[1] = 2; op.anchor[2] = 2;
     ctx->op_ready = true;
 }
+// the operator again for another min(eta): gravity and the wall-row mode stay as they are
+static void stokes_reop3(pl3_ctx* ctx, double mineta) {
+    const double grav[3] = {ctx->op.grav[0], ctx->op.grav[1], ctx->op.grav[2]};
+    const int slave = ctx->op.slave;
+    stokes_op3(ctx, mineta, grav);
+    ctx->op.slave = slave;
+}
+// python's min(etas.min(), etan.min()), pylamp_stokes.py:116-118, from the two minima over the non-NaN entries and whether each field holds
+// a NaN: the minimum of such a field is NaN, and min(a, b) is a unless b is smaller
+double nan_min3(double mes, double men, bool nan_s, bool nan_n) {
+    if (nan_s) mes = NAN;
+    if (nan_n) men = NAN;
+    return (men < mes) ? men : mes;
+}
 extern "C" int pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3]) {
     if (!etas || !etan || !rho) return p3_fail(ctx, "pl3_stokes_set_coeffs: NULL argument");
     P3_HIP(ctx, hipSetDevice(ctx->device));
@@ -1615,8 +1619,7 @@ extern "C" int pl3_stokes_set_coeffs(pl3_ctx* ctx, const double* etas, const dou
     const size_t N = (size_t)g.gn[0] * g.gn[1] * g.gn[2];
     double mes = INFINITY, men = INFINITY; bool nes = false, nen = false;
     for (size_t t = 0; t < N; t++) { if (etas[t] != etas[t]) nes = true; else mes = std::min(mes, etas[t]); if (etan[t] != etan[t]) nen = true; else men = std::min(men, etan[t]); }
-    if (nes) mes = NAN; if (nen) men = NAN;
-    const double mineta = (men < mes) ? men : mes;                  // python's min(a, b), pylamp_stokes.py:116-118
+    const double mineta = nan_min3(mes, men, nes, nen);
     P3_TRY(yield_keep_material3(ctx, mineta));
     stokes_op3(ctx, mineta, grav);
     return 0;
@@ -2913,7 +2916,7 @@ __global__ __launch_bounds__(256) void k3_strain_total(G3 g, const double* __res
         node_w3<0>(g, i, wl, wh, hz); node_w3<1>(g, j, wl, wh, hx); node_w3<2>(g, k, wl, wh, hy);
         acc[0] += phi[i3(g, i, j, k)] * (hz * hx * hy);
     }
-    block_sums3<1>(acc, part);
+    r3_block<R3All<R3_SUM, 1>>(acc, threadIdx.x, blockIdx.x, part);
 }
 static Vec3 strain_out3(pl3_ctx* ctx) { return svec(ctx, 2); }      // strainrate, stress, dissipation (ringed)
 // the three node fields of the velocities vel (three ringed arrays; not work vector 1 or 2) into strain_out3; Hplain (NULL: none) gains the
@@ -2931,26 +2934,27 @@ static int strain_run3(pl3_ctx* ctx, const Vec3& vel, double* Hplain, double* to
     }
     return 0;
 }
-static int strain_check3(pl3_ctx* ctx, const char* who, bool resident) {
-    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, std::string(who) + ": the strain-rate, stress and dissipation fields run on one rank (this context has pl3_set_comm attached)");
+// The velocities of the post-solve entry point `who`: the host arrays vz, vx, vy, uploaded to work vector 0, or, with all three NULL, the
+// solution of the last Stokes solve (work vector 11).  what: the feature, as the one-rank message names it.
+static int post_vel3(pl3_ctx* ctx, const char* who, const char* what, const double* vz, const double* vx, const double* vy, Vec3* vel) {
+    const bool given = vz || vx || vy;
+    if (given && !(vz && vx && vy)) return p3_fail(ctx, std::string(who) + ": vz, vx, vy must be given all three or all NULL");
+    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, std::string(who) + ": " + what + " on one rank (this context has pl3_set_comm attached)");
     if (!ctx->op_ready) return p3_fail(ctx, std::string(who) + ": no Stokes coefficients set (pl3_stokes_set_coeffs)");
-    if (resident && !ctx->have_x) return p3_fail(ctx, std::string(who) + ": NULL velocities mean the solution of the last Stokes solve, and no solve has run on this context");
+    if (!given && !ctx->have_x) return p3_fail(ctx, std::string(who) + ": NULL velocities mean the solution of the last Stokes solve, and no solve has run on this context");
+    P3_HIP(ctx, hipSetDevice(ctx->device));
+    P3_TRY(need_vecs(ctx, given ? 3 : 14));
+    *vel = svec(ctx, given ? 0 : 11).vel();
+    const double* in[3] = {vz, vx, vy};
+    for (int q = 0; given && q < 3; q++) { double* d = (*vel)[q]; P3_TRY(upload3(ctx, in[q], 1, &d)); }
     return 0;
 }
+#define STRAIN3_WHAT "the strain-rate, stress and dissipation fields run"
 extern "C" int pl3_stokes_strain_fields(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double* strainrate, double* stress,
                                         double* dissipation, double* total) {
     if (!ctx) return p3_fail(nullptr, "pl3_stokes_strain_fields: NULL context");
-    const bool given = vz || vx || vy;
-    if (given && !(vz && vx && vy)) return p3_fail(ctx, "pl3_stokes_strain_fields: vz, vx, vy must be given all three or all NULL");
-    P3_TRY(strain_check3(ctx, "pl3_stokes_strain_fields", !given));
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_TRY(need_vecs(ctx, given ? 3 : 14));
-    Vec3 vel = svec(ctx, 11).vel();
-    if (given) {
-        vel = svec(ctx, 0).vel();
-        const double* in[3] = {vz, vx, vy};
-        for (int q = 0; q < 3; q++) { double* d = vel[q]; P3_TRY(upload3(ctx, in[q], 1, &d)); }
-    }
+    Vec3 vel;
+    P3_TRY(post_vel3(ctx, "pl3_stokes_strain_fields", STRAIN3_WHAT, vz, vx, vy, &vel));
     P3_TRY(strain_run3(ctx, vel, nullptr, total));
     double* host[3] = {strainrate, stress, dissipation};
     for (int q = 0; q < 3; q++) if (host[q]) { double* d = strain_out3(ctx)[q]; P3_TRY(download3(ctx, &d, 1, host[q])); }
@@ -2958,10 +2962,9 @@ extern "C" int pl3_stokes_strain_fields(pl3_ctx* ctx, const double* vz, const do
 }
 // the same for the resident solution, for pl_step3.hip: nothing but the total crosses the bus
 int pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total) {
-    P3_TRY(strain_check3(ctx, "pl3_resident_step", true));
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_TRY(need_vecs(ctx, 14));
-    return strain_run3(ctx, svec(ctx, 11).vel(), Hplain, total);
+    Vec3 vel;
+    P3_TRY(post_vel3(ctx, "pl3_resident_step", STRAIN3_WHAT, nullptr, nullptr, nullptr, &vel));
+    return strain_run3(ctx, vel, Hplain, total);
 }
 
 // ---- yield stress: effective viscosities from the strain rates of a velocity field (pl3_stokes_set_yield / pl3_stokes_yield_update;
@@ -2969,30 +2972,10 @@ int pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total) {
 // k3_strain_ce (unchanged) leaves the cell sums and the edge squares in work vector 1; k3_yield_visc then handles, per thread, the eta_s of
 // its node and the eta_n of the cell whose lowest corner the node is: eta_eff = min(eta_mat, max(tau_y / (2 e), eta_floor)) from the
 // MATERIAL arrays, written over the previous effective ones (a thread reads and writes its own two entries only).  Its epilogue reduces
-// nine quantities per workgroup -- a shuffle tree per wave, then the four waves in order -- into ypart, which k3_yield_finish combines in a
-// fixed order: no atomics, a call repeats bit for bit.  (block_sums3 adds, and takes 256 threads in a row with
-// at most D3_BLOCKS workgroups; minima, maxima and the 64 x 4 workgroups of the per-node grid need this epilogue of their own.)
+// nine quantities per workgroup (r3_block, pl_reduce3.h) into ypart, which k_r3_finish combines in a fixed order: no atomics, a call
+// repeats bit for bit.
 enum { YQ_MIN_S = 0, YQ_NAN_S, YQ_MIN_N, YQ_NAN_N, YQ_CHANGE, YQ_YIELD_S, YQ_YIELD_N, YQ_MAX_ES, YQ_MAX_EC, YQ_N };
-__device__ inline double yq_comb(int q, double a, double b) {
-    if (q == YQ_MIN_S || q == YQ_MIN_N) return fmin(a, b);
-    if (q == YQ_YIELD_S || q == YQ_YIELD_N) return a + b;            // (counts: exact in any order)
-    return fmax(a, b);
-}
-__device__ inline double yq_unit(int q) { return (q == YQ_MIN_S || q == YQ_MIN_N) ? INFINITY : 0.0; }
-// acc of the 256 threads of a workgroup (wave w of 64 lanes) -> part[YQ_N b + q]
-__device__ inline void yq_block(const double (&acc)[YQ_N], int lane, int wave, double* __restrict__ part) {
-    __shared__ double sh[YQ_N][4];
-#pragma unroll
-    for (int q = 0; q < YQ_N; q++) {
-        double a = acc[q];
-        for (int o = 32; o > 0; o >>= 1) a = yq_comb(q, a, __shfl_down(a, o, 64));
-        if (lane == 0) sh[q][wave] = a;
-    }
-    __syncthreads();
-    const int t = wave * 64 + lane;
-    if (t < YQ_N) part[(size_t)YQ_N * ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) + t] =
-        yq_comb(t, yq_comb(t, yq_comb(t, sh[t][0], sh[t][1]), sh[t][2]), sh[t][3]);
-}
+using YieldOps = R3Ops<R3_MIN, R3_MAX, R3_MIN, R3_MAX, R3_MAX, R3_SUM, R3_SUM, R3_MAX, R3_MAX>;       // (the two sums are counts)
 // ms / mn: material viscosities; es / en: effective ones (in: the previous, out: the new); tau: tau_y at the nodes z_i, then at the cell
 // mid-points; floor: eta_floor
 struct Yield3 { const double* ms; const double* mn; double* es; double* en; const double* tau; double floor; };
@@ -3004,9 +2987,7 @@ __device__ inline double yield_eta3(double mat, double tau, double e, double flo
 __global__ __launch_bounds__(256) void k3_yield_visc(Op3 op, V4 ce, Yield3 y, double* __restrict__ part) {
     const G3& g = op.g;                             // one rank: local and global indices coincide
     const int k = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, i = blockIdx.z;
-    double acc[YQ_N];
-#pragma unroll
-    for (int q = 0; q < YQ_N; q++) acc[q] = yq_unit(q);
+    double acc[YQ_N] = {INFINITY, 0.0, INFINITY, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};        // (every maximum is of figures >= 0)
     if (k < g.n[2] && j < g.n[1]) {                 // (no early return: every thread takes part in the reduction)
         const long long c = i3(g, i, j, k);
         double Y, T, P;
@@ -3036,23 +3017,11 @@ __global__ __launch_bounds__(256) void k3_yield_visc(Op3 op, V4 ce, Yield3 y, do
         acc[YQ_YIELD_N] = new_n < mat_n ? 1.0 : 0.0;
         acc[YQ_MAX_ES] = e_s; acc[YQ_MAX_EC] = e_c;
     }
-    yq_block(acc, threadIdx.x, threadIdx.y, part);
+    r3_block<YieldOps>(acc, 64 * threadIdx.y + threadIdx.x, (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, part);
 }
-// workgroup g combines the partials [g chunk, (g + 1) chunk) of nb: thread t those at t, t + 256, ... of its chunk in that order, then the
-// 256 threads as above -> out[YQ_N g + q].  Two launches finish: YQ_GROUPS workgroups over the kernel's partials, one over theirs (one
-// workgroup alone walks 83 525 partials at 257^3 in 0.86 ms, longer than the kernel that wrote them).
+// Two launches of k_r3_finish combine the partials: YQ_GROUPS workgroups over the kernel's, one over theirs (one workgroup alone walks
+// 83 525 partials at 257^3 in 0.86 ms, longer than the kernel that wrote them).
 #define YQ_GROUPS 128
-__global__ __launch_bounds__(256) void k3_yield_finish(long long nb, long long chunk, const double* __restrict__ part, double* __restrict__ out) {
-    const long long b0 = blockIdx.x * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
-    double acc[YQ_N];
-#pragma unroll
-    for (int q = 0; q < YQ_N; q++) acc[q] = yq_unit(q);
-    for (long long b = b0 + threadIdx.x; b < b1; b += 256) {
-#pragma unroll
-        for (int q = 0; q < YQ_N; q++) acc[q] = yq_comb(q, acc[q], part[(size_t)YQ_N * b + q]);
-    }
-    yq_block(acc, threadIdx.x & 63, threadIdx.x >> 6, out);
-}
 static int yield_free3(pl3_ctx* ctx) {
     for (double** q : {&ctx->ms, &ctx->mn, &ctx->ytau, &ctx->ypart}) { if (*q) (void)hipFree(*q); *q = nullptr; }
     return 0;
@@ -3063,10 +3032,7 @@ static int yield_reset3(pl3_ctx* ctx) {
     const size_t bytes = (size_t)ctx->geom.d.vol * sizeof(double);
     P3_HIP(ctx, hipMemcpyAsync(ctx->es, ctx->ms, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     P3_HIP(ctx, hipMemcpyAsync(ctx->en, ctx->mn, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    const double grav[3] = {ctx->op.grav[0], ctx->op.grav[1], ctx->op.grav[2]};
-    const int slave = ctx->op.slave;
-    stokes_op3(ctx, ctx->mat_mineta, grav);
-    ctx->op.slave = slave;
+    stokes_reop3(ctx, ctx->mat_mineta);
     return 0;
 }
 extern "C" int pl3_stokes_set_yield(pl3_ctx* ctx, int on, double tau0, double dtau_dz, double eta_floor) {
@@ -3143,22 +3109,20 @@ static int yield_run3(pl3_ctx* ctx, const Vec3& vel, double out[6]) {
     launch3(ctx, g, k3_yield_visc, ctx->op, cv4(ce), Yield3{ctx->ms, ctx->mn, ctx->es, ctx->en, ctx->ytau, ctx->yfloor}, ctx->ypart);
     const long long nb = (long long)gr.x * gr.y * gr.z, chunk = (nb + YQ_GROUPS - 1) / YQ_GROUPS;
     double* groups = ctx->ypart + YQ_N * nb;           // the YQ_GROUPS partials of the first finishing launch
-    hipLaunchKernelGGL(k3_yield_finish, dim3(YQ_GROUPS), dim3(256), 0, ctx->stream, nb, chunk, (const double*)ctx->ypart, groups);
-    hipLaunchKernelGGL(k3_yield_finish, dim3(1), dim3(256), 0, ctx->stream, (long long)YQ_GROUPS, (long long)YQ_GROUPS, (const double*)groups, ctx->part);
+    hipLaunchKernelGGL(k_r3_finish<YieldOps>, dim3(YQ_GROUPS), dim3(256), 0, ctx->stream, nb, chunk, (const double*)ctx->ypart, groups);
+    hipLaunchKernelGGL(k_r3_finish<YieldOps>, dim3(1), dim3(256), 0, ctx->stream, (long long)YQ_GROUPS, (long long)YQ_GROUPS, (const double*)groups, ctx->part);
     P3_HIP(ctx, hipGetLastError());
     pl3_count_copy(ctx, YQ_N * sizeof(double));
     P3_HIP(ctx, hipMemcpyAsync(ctx->hpart, ctx->part, YQ_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     P3_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const double* r = ctx->hpart;
-    const double mes = r[YQ_NAN_S] > 0.0 ? NAN : r[YQ_MIN_S], men = r[YQ_NAN_N] > 0.0 ? NAN : r[YQ_MIN_N];
-    const double mineta = (men < mes) ? men : mes;                  // the rule of pl3_stokes_set_coeffs
-    out[0] = mineta; out[1] = r[YQ_CHANGE]; out[2] = r[YQ_YIELD_S]; out[3] = r[YQ_YIELD_N]; out[4] = r[YQ_MAX_ES]; out[5] = r[YQ_MAX_EC];
+    const double mineta = nan_min3(r[YQ_MIN_S], r[YQ_MIN_N], r[YQ_NAN_S] > 0.0, r[YQ_NAN_N] > 0.0);
+    // (the three maxima are of figures >= 0 and the fmax of the reduction drops a NaN: 0, not the unit -inf, where every entry is a NaN)
+    out[0] = mineta; out[1] = fmax(r[YQ_CHANGE], 0.0); out[2] = r[YQ_YIELD_S]; out[3] = r[YQ_YIELD_N];
+    out[4] = fmax(r[YQ_MAX_ES], 0.0); out[5] = fmax(r[YQ_MAX_EC], 0.0);
     if (out[1] != 0.0) {
         const double kc_old = ctx->op.Kc;
-        const double grav[3] = {ctx->op.grav[0], ctx->op.grav[1], ctx->op.grav[2]};
-        const int slave = ctx->op.slave;
-        stokes_op3(ctx, mineta, grav);
-        ctx->op.slave = slave;
+        stokes_reop3(ctx, mineta);
         if (ctx->have_x && ctx->vec[11] && ctx->op.Kc != kc_old && std::isfinite(kc_old / ctx->op.Kc)) {
             const Vec3 P = svec(ctx, 11).prs();
             axpby3(ctx, P, kc_old / ctx->op.Kc, P, 0.0, P);
@@ -3167,26 +3131,16 @@ static int yield_run3(pl3_ctx* ctx, const Vec3& vel, double out[6]) {
     }
     return 0;
 }
-static int yield_check3(pl3_ctx* ctx, const char* who, bool resident) {
-    if (ctx->nranks > 1 || ctx->comm) return p3_fail(ctx, std::string(who) + ": the yield stress runs on one rank (this context has pl3_set_comm attached)");
-    if (!ctx->op_ready) return p3_fail(ctx, std::string(who) + ": no Stokes coefficients set (pl3_stokes_set_coeffs)");
+// who's velocities (post_vel3) on a context with a yield stress set
+static int yield_vel3(pl3_ctx* ctx, const char* who, const double* vz, const double* vx, const double* vy, Vec3* vel) {
+    P3_TRY(post_vel3(ctx, who, "the yield stress runs", vz, vx, vy, vel));
     if (!ctx->yield_on) return p3_fail(ctx, std::string(who) + ": no yield stress set (pl3_stokes_set_yield)");
-    if (resident && !ctx->have_x) return p3_fail(ctx, std::string(who) + ": NULL velocities mean the solution of the last Stokes solve, and no solve has run on this context");
     return 0;
 }
 extern "C" int pl3_stokes_yield_update(pl3_ctx* ctx, const double* vz, const double* vx, const double* vy, double out[6]) {
     if (!ctx) return p3_fail(nullptr, "pl3_stokes_yield_update: NULL context");
-    const bool given = vz || vx || vy;
-    if (given && !(vz && vx && vy)) return p3_fail(ctx, "pl3_stokes_yield_update: vz, vx, vy must be given all three or all NULL");
-    P3_TRY(yield_check3(ctx, "pl3_stokes_yield_update", !given));
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_TRY(need_vecs(ctx, given ? 3 : 14));
-    Vec3 vel = svec(ctx, 11).vel();
-    if (given) {
-        vel = svec(ctx, 0).vel();
-        const double* in[3] = {vz, vx, vy};
-        for (int q = 0; q < 3; q++) { double* d = vel[q]; P3_TRY(upload3(ctx, in[q], 1, &d)); }
-    }
+    Vec3 vel;
+    P3_TRY(yield_vel3(ctx, "pl3_stokes_yield_update", vz, vx, vy, &vel));
     double o[6];
     P3_TRY(yield_run3(ctx, vel, o));
     if (out) for (int q = 0; q < 6; q++) out[q] = o[q];
@@ -3194,10 +3148,9 @@ extern "C" int pl3_stokes_yield_update(pl3_ctx* ctx, const double* vz, const dou
 }
 // the same for the resident solution, for pl_step3.hip
 int pl3i_yield_update_dev(pl3_ctx* ctx, double out[6]) {
-    P3_TRY(yield_check3(ctx, "pl3_resident_step", true));
-    P3_HIP(ctx, hipSetDevice(ctx->device));
-    P3_TRY(need_vecs(ctx, 14));
-    return yield_run3(ctx, svec(ctx, 11).vel(), out);
+    Vec3 vel;
+    P3_TRY(yield_vel3(ctx, "pl3_resident_step", nullptr, nullptr, nullptr, &vel));
+    return yield_run3(ctx, vel, out);
 }
 
 // ---- what the device-resident step (pl_step3.hip) needs of a context ----------------------------------------------------------

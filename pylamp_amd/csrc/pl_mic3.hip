@@ -12,6 +12,7 @@
 // pylamp_trac.py:83-156 (which leaves vz extrapolated under VELDIV): it has no meaning with three components.
 #include "pl_internal.h"
 #include "pl_mic3.h"
+#include "pl_reduce3.h"
 #include "pl_step3.h"
 #include "pl_walls3.h"
 #include <algorithm>
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(1024) void k_m3_scan_sums(int nb, int* __restrict__
     if (idpart) {
         double mx = -INFINITY;
         for (int i = tid; i < nid; i += 1024) mx = fmax(mx, idpart[i]);
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o, 64));
+        r3_wave(R3_MAX, mx);
         if ((tid & 63) == 0) dpart[tid >> 6] = mx;
         __syncthreads();
         if (tid == 0) { for (int q = 1; q < 16; q++) mx = fmax(mx, dpart[q]); tot->maxid = mx; }
@@ -333,14 +334,10 @@ __global__ __launch_bounds__(256) void k_m3_census(int m, const int* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------
 // block partials of the largest tracer ID (NaN ignored); with key, over the survivors of this sort only (key == trash: the tracer leaves)
 __global__ __launch_bounds__(256) void k_m3_max(long long n, const double* __restrict__ x, const int* __restrict__ key, int trash, double* __restrict__ part) {
-    __shared__ double sh[4];
-    double m = -INFINITY;
+    double m[1] = {-INFINITY};
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256)
-        if (!key || key[t] != trash) m = fmax(m, x[t]);
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+        if (!key || key[t] != trash) m[0] = fmax(m[0], x[t]);
+    r3_block<R3All<R3_MAX, 1>>(m, threadIdx.x, blockIdx.x, part);
 }
 // The new tracers of the deficient cells, written into the room the sort left behind the residents of each cell.  One wave per
 // deficient cell, taken from the compacted list (in a typical step a few cells in a million are deficient: a thread per cell would

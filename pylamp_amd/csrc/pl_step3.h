@@ -30,6 +30,7 @@ struct Pl3DevView {
 // pl_3d.hip
 int  pl3i_dev_view(pl3_ctx* ctx, Pl3DevView* v);
 int  pl3i_stokes_set_coeffs_dev(pl3_ctx* ctx, const double* etas, const double* etan, const double* rho, const double grav[3], double mineta);
+double nan_min3(double mes, double men, bool nan_s, bool nan_n);     // min(etas.min(), etan.min()) as NumPy has it: NaN where a field holds one
 int  pl3i_heat_set_coeffs_dev(pl3_ctx* ctx, const double* const mp[3], const double* const src[7], const int bc[6], const double bcvalue[6], double tstep);
 int  pl3i_strain_fields_dev(pl3_ctx* ctx, double* Hplain, double* total);     // the fields of the resident solution; Hplain (NULL: none) += dissipation
 int  pl3i_yield_update_dev(pl3_ctx* ctx, double out[6]);     // pl3_stokes_yield_update for the resident solution

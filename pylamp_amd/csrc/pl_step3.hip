@@ -9,6 +9,7 @@
 // workgroup), so no workgroup waits on another and the order of every combination is fixed.
 #include "pl_internal.h"
 #include "pl_mic3.h"
+#include "pl_reduce3.h"
 #include "pl_step3.h"
 #include <algorithm>
 #include <chrono>
@@ -19,53 +20,23 @@
 #define S3_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 #define S3_MAXPART 1024
 #define PL3_PICARD_CAP 32
-enum { S3_SUM = 0, S3_MIN = 1, S3_MAX = 2 };
 enum { S3_RHO = 0, S3_ETAS, S3_CP, S3_T, S3_H, S3_MAT, S3_ETAN, S3_KZ, S3_KX, S3_KY, S3_NPLAIN };       // slots of the scattered fields
 
 struct S3Dims { int n[3]; long long s0, s1; int pad; };
 __device__ inline long long s3_ring(const S3Dims& d, int i, int j, int k) { return (long long)(i + 1) * d.s0 + (long long)(j + 1) * d.s1 + k + d.pad; }
-__device__ inline double s3_comb(int op, double a, double b) { return op == S3_SUM ? a + b : (op == S3_MIN ? fmin(a, b) : fmax(a, b)); }
-__device__ inline double s3_unit(int op) { return op == S3_SUM ? 0.0 : (op == S3_MIN ? INFINITY : -INFINITY); }
-struct S3Ops { int op[8]; };
-
-// acc[0..K) of every thread -> one value per slot in part[blockIdx.x * K + slot]: lanes by shuffles, then the four waves in order
-template <int K>
-__device__ inline void s3_block_reduce(const S3Ops& ops, double acc[K], double* __restrict__ part) {
-    __shared__ double sh[K][4];
-#pragma unroll
-    for (int q = 0; q < K; q++) {
-        double x = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x = s3_comb(ops.op[q], x, __shfl_down(x, o, 64));
-        if ((threadIdx.x & 63) == 0) sh[q][threadIdx.x >> 6] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        const int q = threadIdx.x;
-        double x = sh[q][0];
-        for (int w = 1; w < 4; w++) x = s3_comb(ops.op[q], x, sh[q][w]);
-        part[(size_t)blockIdx.x * K + q] = x;
-    }
+// node t of the plain (nz, nx, ny) order -> its indices, and its element in a ringed array
+__device__ inline void s3_ijk(const S3Dims& d, long long t, int& i, int& j, int& k) {
+    k = (int)(t % d.n[2]); j = (int)((t / d.n[2]) % d.n[1]); i = (int)(t / ((long long)d.n[2] * d.n[1]));
 }
-// one workgroup finishes the nb partials of K slots
-template <int K>
-__global__ __launch_bounds__(256) void k_s3_finish(int nb, S3Ops ops, const double* __restrict__ part, double* __restrict__ out) {
-    double acc[K];
-#pragma unroll
-    for (int q = 0; q < K; q++) {
-        double x = s3_unit(ops.op[q]);
-        for (int b = threadIdx.x; b < nb; b += 256) x = s3_comb(ops.op[q], x, part[(size_t)b * K + q]);
-        acc[q] = x;
-    }
-    s3_block_reduce<K>(ops, acc, out);
-}
+__device__ inline long long s3_ring(const S3Dims& d, long long t) { int i, j, k; s3_ijk(d, t, i, j, k); return s3_ring(d, i, j, k); }
 
 // One pass over the scattered fields: slot 0 / 1 the NaN counts of rho / etas; 2, 3 the smallest non-NaN etas and whether it holds a NaN;
 // 4, 5 the same for etan; 6, 7 the largest 2 kz / (rho cp) -- every operation rounded on its own, as NumPy evaluates it -- and its NaN flag
 // (kz == NULL: heat is off, 6 and 7 stay empty)
+using S3FieldOps = R3Ops<R3_SUM, R3_SUM, R3_MIN, R3_MAX, R3_MIN, R3_MAX, R3_MAX, R3_MAX>;
 __global__ __launch_bounds__(256) void k_s3_reduce_fields(long long N, const double* __restrict__ rho, const double* __restrict__ etas,
                                                          const double* __restrict__ etan, const double* __restrict__ kz, const double* __restrict__ cp,
-                                                         S3Ops ops, double* __restrict__ part) {
+                                                         double* __restrict__ part) {
     double acc[8] = {0.0, 0.0, INFINITY, 0.0, INFINITY, 0.0, -INFINITY, 0.0};
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < N; t += (long long)gridDim.x * 256) {
         const double r = rho[t], es = etas[t], en = etan[t];
@@ -77,21 +48,21 @@ __global__ __launch_bounds__(256) void k_s3_reduce_fields(long long N, const dou
             if (d != d) acc[7] = 1.0; else acc[6] = fmax(acc[6], d);
         }
     }
-    s3_block_reduce<8>(ops, acc, part);
+    r3_block<S3FieldOps>(acc, threadIdx.x, blockIdx.x, part);
 }
 // largest vz, vx, vy over all nodes of the ringed solution (the plain maximum, as step() has it): slots 2 q the maximum of the non-NaN
 // entries, 2 q + 1 whether the component holds a NaN
 struct S3Vel { const double* v[3]; };
-__global__ __launch_bounds__(256) void k_s3_velmax(S3Dims d, S3Vel x, S3Ops ops, double* __restrict__ part) {
+using S3VelOps = R3All<R3_MAX, 6>;
+__global__ __launch_bounds__(256) void k_s3_velmax(S3Dims d, S3Vel x, double* __restrict__ part) {
     const long long N = (long long)d.n[0] * d.n[1] * d.n[2];
     double acc[6] = {-INFINITY, 0.0, -INFINITY, 0.0, -INFINITY, 0.0};
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < N; t += (long long)gridDim.x * 256) {
-        const int k = (int)(t % d.n[2]), j = (int)((t / d.n[2]) % d.n[1]), i = (int)(t / ((long long)d.n[2] * d.n[1]));
-        const long long c = s3_ring(d, i, j, k);
+        const long long c = s3_ring(d, t);
 #pragma unroll
         for (int q = 0; q < 3; q++) { const double u = x.v[q][c]; if (u != u) acc[2 * q + 1] = 1.0; else acc[2 * q] = fmax(acc[2 * q], u); }
     }
-    s3_block_reduce<6>(ops, acc, part);
+    r3_block<S3VelOps>(acc, threadIdx.x, blockIdx.x, part);
 }
 
 // Cell-centred velocities on the padded (nz+1, nx+1, ny+1) grid (pylamp2.py:491-545 with a third axis; advection_velocity in
@@ -164,7 +135,8 @@ __global__ __launch_bounds__(256) void k_s3_wall_carry(S3Dims d, const double* _
     const long long N = (long long)d.n[0] * d.n[1] * d.n[2];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= N) return;
-    const int k = (int)(t % d.n[2]), j = (int)((t / d.n[2]) % d.n[1]), i = (int)(t / ((long long)d.n[2] * d.n[1]));
+    int i, j, k;
+    s3_ijk(d, t, i, j, k);
     if (i == 0 || i == d.n[0] - 1 || j == 0 || j == d.n[1] - 1 || k == 0 || k == d.n[2] - 1) T[t] = prev[t];
 }
 // the solved temperature (ringed) -> plain, and the increment newtemp - T that the gather interpolates to the tracers
@@ -173,8 +145,7 @@ __global__ __launch_bounds__(256) void k_s3_increment(S3Dims d, const double* __
     const long long N = (long long)d.n[0] * d.n[1] * d.n[2];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= N) return;
-    const int k = (int)(t % d.n[2]), j = (int)((t / d.n[2]) % d.n[1]), i = (int)(t / ((long long)d.n[2] * d.n[1]));
-    const double u = sol[s3_ring(d, i, j, k)];
+    const double u = sol[s3_ring(d, t)];
     newtemp[t] = u;
     dT[t] = u - T[t];
 }
@@ -183,8 +154,8 @@ __global__ __launch_bounds__(256) void k_s3_layout(S3Dims d, double* __restrict_
     const long long N = (long long)d.n[0] * d.n[1] * d.n[2];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= N) return;
-    const int k = (int)(t % d.n[2]), j = (int)((t / d.n[2]) % d.n[1]), i = (int)(t / ((long long)d.n[2] * d.n[1]));
-    if (to_ring) ringed[s3_ring(d, i, j, k)] = plain[t]; else plain[t] = ringed[s3_ring(d, i, j, k)];
+    const long long c = s3_ring(d, t);
+    if (to_ring) ringed[c] = plain[t]; else plain[t] = ringed[c];
 }
 
 // =====================================================================================================================
@@ -207,7 +178,7 @@ void pl3_step_free(void** slot) {
 static const char* const S3_NAMES[20] = {"rho", "etas", "cp", "T", "H", "mat", "etan", "kz", "kx", "ky", "velz", "velx", "vely", "pres", "temp",
                                          "strainrate", "stress", "dissipation", "etas_eff", "etan_eff"};
 
-struct S3Open { Pl3HostView h; Pl3DevView d; Step3* S; S3Dims dims; size_t N; };
+struct S3Open { Pl3HostView h; Pl3DevView d; Step3* S; S3Dims dims; size_t N, GNp; };        // N nodes; GNp points of the padded centre grid
 static int s3_open(pl3_ctx* ctx, const char* who, S3Open& o) {
     S3_TRY(pl3_host_view(ctx, &o.h));
     if (o.h.nranks > 1) return pl3_fail(ctx, std::string(who) + ": the device-resident 3-D step runs on one rank (this context has pl3_set_comm attached)");
@@ -217,6 +188,7 @@ static int s3_open(pl3_ctx* ctx, const char* who, S3Open& o) {
     for (int a = 0; a < 3; a++) o.dims.n[a] = o.h.gn[a];
     o.dims.s0 = o.d.s0; o.dims.s1 = o.d.s1; o.dims.pad = o.d.pad;
     o.N = (size_t)o.h.gn[0] * o.h.gn[1] * o.h.gn[2];
+    o.GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
     return 0;
 }
 static inline dim3 s3_blocks(long long n) { return dim3((unsigned)((std::max<long long>(n, 1) + 255) / 256)); }
@@ -226,9 +198,10 @@ static inline double py_min(double a, double b) { return b < a ? b : a; }
 static inline double py_max(double a, double b) { return b > a ? b : a; }
 
 // partials -> K values on the host: one launch of one workgroup and one small read-back
-template <int K>
-static int s3_finish(pl3_ctx* ctx, S3Open& o, int nb, const S3Ops& ops, const double* part, double* red, double host[K]) {
-    hipLaunchKernelGGL(k_s3_finish<K>, dim3(1), dim3(256), 0, o.d.stream, nb, ops, part, red);
+template <class OPS>
+static int s3_finish(pl3_ctx* ctx, S3Open& o, int nb, const double* part, double* red, double host[OPS::K]) {
+    constexpr int K = OPS::K;
+    hipLaunchKernelGGL(k_r3_finish<OPS>, dim3(1), dim3(256), 0, o.d.stream, (long long)nb, (long long)nb, part, red);
     S3_HIP(ctx, hipGetLastError());
     pl3_count_copy(ctx, K * sizeof(double));
     S3_HIP(ctx, hipMemcpyAsync(host, red, K * sizeof(double), hipMemcpyDeviceToHost, o.d.stream));
@@ -236,9 +209,8 @@ static int s3_finish(pl3_ctx* ctx, S3Open& o, int nb, const S3Ops& ops, const do
     return 0;
 }
 static void s3_advvel(S3Open& o, double* const X[3], double* adv) {
-    const size_t GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
-    S3Vel x{{X[0], X[1], X[2]}}; S3Adv a{{adv, adv + GNp, adv + 2 * GNp}};
-    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip, o.d.wallvel, o.d.wallflow);
+    S3Vel x{{X[0], X[1], X[2]}}; S3Adv a{{adv, adv + o.GNp, adv + 2 * o.GNp}};
+    hipLaunchKernelGGL(k_s3_advvel, s3_blocks((long long)o.GNp), dim3(256), 0, o.d.stream, o.dims, x, a, o.d.noslip, o.d.wallvel, o.d.wallflow);
 }
 
 extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int it, pl3_step_report* rep) {
@@ -251,7 +223,7 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     if (it < 1) return pl3_fail(ctx, "pl3_resident_step: steps count from 1");
     const bool heat = cfg->do_heatdiff != 0;
     if (heat && it > 1 && !o.S->have_temp) return pl3_fail(ctx, "pl3_resident_step: step > 1 with heat needs the temperature of the previous resident step");
-    const size_t N = o.N, GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
+    const size_t N = o.N, GNp = o.GNp;
     const int nb = s3_nparts((long long)N);
     double *F, *temp, *dT, *adv, *part, *red;
     S3_TRY(pl3i_mic_buf(ctx, "s_fields", N * S3_NPLAIN, &F));
@@ -300,11 +272,10 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     o.S->have_scattered = true; o.S->have_heat_fields = heat;
 
     // 2. NaN check, min(eta) and the largest diffusivity in one pass
-    const S3Ops fops{{S3_SUM, S3_SUM, S3_MIN, S3_MAX, S3_MIN, S3_MAX, S3_MAX, S3_MAX}};
     hipLaunchKernelGGL(k_s3_reduce_fields, dim3(nb), dim3(256), 0, o.d.stream, (long long)N, (const double*)(F + S3_RHO * N), (const double*)(F + S3_ETAS * N),
-                       (const double*)(F + S3_ETAN * N), (const double*)(heat ? F + S3_KZ * N : nullptr), (const double*)(heat ? F + S3_CP * N : nullptr), fops, part);
+                       (const double*)(F + S3_ETAN * N), (const double*)(heat ? F + S3_KZ * N : nullptr), (const double*)(heat ? F + S3_CP * N : nullptr), part);
     double r8[8];
-    S3_TRY(s3_finish<8>(ctx, o, nb, fops, part, red, r8));
+    S3_TRY(s3_finish<S3FieldOps>(ctx, o, nb, part, red, r8));
     rep->nan_rho = (int64_t)r8[0]; rep->nan_etas = (int64_t)r8[1];
     if (rep->nan_rho > 0 || rep->nan_etas > 0) {
         const bool rho_bad = rep->nan_rho > 0;
@@ -313,8 +284,7 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
         return pl3_fail(ctx, std::string("pl3_resident_step: the scattered field '") + (rho_bad ? "rho" : "etas") + "' holds NaN at " +
                                  std::to_string((long long)(rho_bad ? rep->nan_rho : rep->nan_etas)) + " nodes (tracers and temperature are left as they were)");
     }
-    const double mes = r8[3] > 0.0 ? NAN : r8[2], men = r8[5] > 0.0 ? NAN : r8[4];
-    const double mineta = (men < mes) ? men : mes;                  // python's min(etas.min(), etan.min()), pylamp_stokes.py:116-118
+    const double mineta = nan_min3(r8[2], r8[4], r8[3] > 0.0, r8[5] > 0.0);
 
     // 3. the heat time-step rule (after the wall carry, which touches T alone)
     double dxmin = INFINITY;
@@ -354,10 +324,9 @@ extern "C" int pl3_resident_step(pl3_ctx* ctx, const pl3_step_config* cfg, int i
     }
 
     // 5. the Stokes time-step rule, the limiter and the clamps
-    const S3Ops vops{{S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX, S3_MAX}};
-    hipLaunchKernelGGL(k_s3_velmax, dim3(nb), dim3(256), 0, o.d.stream, o.dims, S3Vel{{o.d.X[0], o.d.X[1], o.d.X[2]}}, vops, part);
+    hipLaunchKernelGGL(k_s3_velmax, dim3(nb), dim3(256), 0, o.d.stream, o.dims, S3Vel{{o.d.X[0], o.d.X[1], o.d.X[2]}}, part);
     double r6[6];
-    S3_TRY(s3_finish<6>(ctx, o, nb, vops, part, red, r6));
+    S3_TRY(s3_finish<S3VelOps>(ctx, o, nb, part, red, r6));
     double vmax = r6[1] > 0.0 ? NAN : r6[0];
     for (int q = 1; q < 3; q++) vmax = py_max(vmax, r6[2 * q + 1] > 0.0 ? NAN : r6[2 * q]);
     double tstep_stokes = cfg->tstep_modifier * dxmin / vmax;
@@ -495,7 +464,7 @@ extern "C" int pl3_advection_velocity(pl3_ctx* ctx, const double* vz, const doub
     if (!vz || !vx || !vy || !Vz || !Vx || !Vy) return pl3_fail(ctx, "pl3_advection_velocity: NULL argument");
     S3Open o;
     S3_TRY(s3_open(ctx, "pl3_advection_velocity", o));
-    const size_t N = o.N, GNp = (size_t)(o.h.gn[0] + 1) * (o.h.gn[1] + 1) * (o.h.gn[2] + 1);
+    const size_t N = o.N, GNp = o.GNp;
     double *stage, *adv;
     S3_TRY(pl3i_mic_buf(ctx, "s_stage", 3 * N, &stage));
     S3_TRY(pl3i_mic_buf(ctx, "s_advtest", 3 * GNp, &adv));

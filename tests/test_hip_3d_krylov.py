@@ -1,7 +1,7 @@
 """The 3-D Stokes Krylov loop, its deflation and its error estimate against tests/stokes3_krylov_model.py:
 what lies in pl_3d.hip between the preconditioner and the numbers a solve hands back, kernel by kernel and then as a loop.
 
-a. k3_dots / k3_dots_own / k3_dots11 with block_sums3 and sum_partials3, k3_axpby, k3_p_update, k3_xr_update, k3_xrp_update and
+a. k3_dots / k3_dots_own / k3_dots11 with r3_block (pl_reduce3.h) and sum_partials3, k3_axpby, k3_p_update, k3_xr_update, k3_xrp_update and
    k3_random, one launch each through pl3_krylov_probe.  Sums against longdouble sums: |got - want| <= 5 (trips + 10 + 1024) eps
    sum |terms|, trips = ceil(n / (1024 x 256)) -- the longest accumulation chain (per-thread trips, six shuffle steps, four wave sums,
    1024 partials on the host), the 5 of the 2-D twin's SUM_TOL.  Updates element by element: 4 eps sum |terms of the element|.
@@ -172,7 +172,7 @@ def _dot_pairs(v, nd):
 @pytest.mark.parametrize("kind", ["spread", "cancel"])
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 def test_dots_match_longdouble_sums(shape, kind):
-    """k3_dots with 1 ... 5 products, block_sums3 and sum_partials3."""
+    """k3_dots with 1 ... 5 products, r3_block and sum_partials3."""
     n, v = SHAPES[shape], operands(shape, kind)
     with _one_rank(n) as (P3, A):
         for nd in range(1, 6):

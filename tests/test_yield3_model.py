@@ -16,7 +16,9 @@ LD = np.longdouble
 EPS = np.finfo(np.float64).eps
 N_, F_ = W.NOSLIP, W.FREESLIP
 LEN = [1.0e5, 1.3e5, 0.9e5]
-SHAPES = ([17, 13, 21], [7, 9, 67], [5, 5, 5], [6, 70, 5])          # the shapes of tests/test_hip_3d_strain.py
+# the shapes of tests/test_hip_3d_strain.py, and one whose per-node grid has 1 x 6 x 33 = 198 workgroups: more than the 128 groups of the
+# first finishing launch of the yield reduction, so that a group combines two partials and 29 groups hold none
+SHAPES = ([17, 13, 21], [7, 9, 67], [5, 5, 5], [6, 70, 5], [33, 21, 5])
 KINDS = ("regular", "graded")
 WALLS = ("freeslip strict", "noslip all", "moving z0", "through-flow x")
 

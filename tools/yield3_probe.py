@@ -3,7 +3,7 @@
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/yield3_probe.py [--n 129] [--updates 25] [--applies 250]
 
 A dense, stiff blob in a box with no-slip z walls: one resident solve, `--applies` scaled operator applications (pl3_stokes_apply_bench)
-and `--updates` calls of yield_update on the resident solution (k3_strain_ce + k3_yield_visc + k3_yield_finish; each call derives the
+and `--updates` calls of yield_update on the resident solution (k3_strain_ce + k3_yield_visc + two k_r3_finish; each call derives the
 viscosities from the material ones, so every call does the same work).  tau0 is the median of the node stress of the solve.  Prints one
 JSON line with the host times per call; tools/kernel_stats.py turns the trace's database into the per-kernel averages."""
 import argparse
